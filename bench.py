@@ -2,7 +2,7 @@
 """Headline benchmark: training images/sec of the ResNet-50 directional 3D-RetinaNet at 1920x1080
 (BASELINE.json metric; workload = configs[1]: batch 8 per GPU, fp32, synthetic frames + 10 random GT boxes).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,29 @@ zero_grad, forward + loss, sum of the three losses, backward, clip_grad_norm_(0.
 all on inputs already resident in HBM.  With N > 1 every rank trains on its own 8 images (weak scaling) and
 gradients are averaged over RCCL inside backward (retinanet_mi355x.ddp).  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, the outputs of the last
+timed step (--dump-outputs DIR) and the line.  Everything else it measures -- the per-kernel timing pass, the eager
+label-check pass, the other product modes and precisions, the loss kernel and forward-only passes, the CPU baseline --
+runs only with --full (where --sections / --no-kernel-timing / --no-cpu-baseline narrow it as before).
+
+--dump-outputs DIR: rank 0 writes what the last timed step computed, as float32 .npy files:
+  loss, cls_loss, reg_loss, vp_loss   the step's summed loss and the model's three loss outputs
+  weights_sample, grads_sample        the trainable parameters after the optimizer step, and the gradients of that step as
+                                      the optimizer reads them before clipping (with N > 1 ranks: the all-reduced sum times
+                                      1/N, i.e. the mean), flattened in net.parameters() order and sampled at the same fixed
+                                      seeded positions
+The last timed step of such a run starts from the seeded starting state again: the weights are copied back to their seeded
+values and Adam's moments and step number to zero, outside the timed interval (the clock stops after step K-1 and runs
+again for step K).  Without it the arrays would not repeat: the default weight-gradient reductions use fp32 atomics whose
+last bits vary from run to run, and carried from step to step through Adam they grow into trajectories that end far apart.
+Restarted, the step computes from the same inputs in every run with the same arguments, so two builds can be compared
+array by array; two runs of one build differ only by the rounding of that step's atomic reductions
+(profiles/dump_outputs_repeat.txt; with RN_DETERMINISTIC=1, fixed-order reductions and slower steps, not at all).  A run
+without --dump-outputs times K steps that train on from one another, as it always did.  No extra step runs in either case:
+a kernel trace of the command holds exactly W + K training steps (plus the --full passes, and with --dump-outputs the
+copies back in front of step K).
+
+Extra objects in the line (--full only):
   roofline      the dominant kernel family (implicit-GEMM conv, 128x128 tile): algorithmic (fp32) FLOPs and algorithmic bytes (every
                 operand once) of its launches inside the timed steps / their HIP-event durations.  Which roof prices it is the roofline
                 model's own rule: arithmetic intensity against the ridge peak / 8 TB/s, where peak is that of the instruction the kernels
@@ -73,7 +95,7 @@ def parse():
                          "fp8 = configs[4]'s arithmetic (e4m3 activations / weights), INFERENCE forward only: a different metric "
                          "(forward images/sec), e.g. --arch resnet101 --dtype fp8 --batch 16")
     ap.add_argument("--sections", default="all", choices=["all", "headline"],
-                    help="headline: ONLY the benchmark's own steps (warm-up, timed steps, the same steps with per-kernel events) -- no "
+                    help="with --full -- headline: ONLY the benchmark's own steps (warm-up, timed steps, the same steps with per-kernel events) -- no "
                          "native-MFMA / bf16 / fp8 sections, no forward-only passes, no loss micro-benchmark -- so that a rocprofv3 "
                          "--kernel-trace --stats of this command divides by (warmup + 2 * steps) into the line's kernels.*.ms_per_step")
     ap.add_argument("--fp32-mfma", default="", choices=["", "split", "split3", "native"],
@@ -82,11 +104,49 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="capture the whole step (forward, loss, backward, clip + Adam) into one hipGraph after the warm-up and "
                          "replay it in the timed region (single GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: leave out the per-kernel timing pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline steps (per-kernel timing, eager label check, other product modes "
+                         "and precisions, loss kernel and forward-only passes, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses and a fixed sample of the updated weights and their gradients to "
+                         "DIR/<name>.npy (float32); that step starts from the seeded starting state again (module docstring)")
     ap.add_argument("--ddp-timeline", action="store_true",
                     help="N > 1: rank 0 also prints the per-bucket all-reduce timeline of the last step (stderr)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_SAMPLE = 1 << 20             # parameter / gradient positions written by --dump-outputs (4 MB per array)
+
+
+def dump_positions(n):
+    """The sorted positions (of n flattened parameters) --dump-outputs samples: drawn from a fixed seed, the same in every run."""
+    import numpy as np
+    return np.unique(np.random.default_rng(0).integers(0, n, size=min(n, DUMP_SAMPLE)))
+
+
+def dump_outputs(out_dir, net, losses, grad_scale=1.0):
+    """--dump-outputs: the arrays the timed step hands its caller -- the losses, the updated weights and the gradients of the
+    step -- as float32 .npy files.  Weights and gradients are flattened in net.parameters() order and sampled at the same
+    dump_positions.  grad_scale: what the optimizer multiplies the gradient buffer by before it uses it (1/N where the
+    data-parallel reducer leaves the all-reduced sum there)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cls_l, reg_l, vp_l, loss = losses
+    arrays = {"loss": loss, "cls_loss": cls_l, "reg_loss": reg_l, "vp_loss": vp_l}
+    params = [p for p in net.parameters() if p.requires_grad]
+    idx = torch.from_numpy(dump_positions(sum(p.numel() for p in params))).to(params[0].device)
+    arrays["weights_sample"] = torch.cat([p.detach().reshape(-1).float() for p in params])[idx]
+    if all(p.grad is not None for p in params):
+        arrays["grads_sample"] = torch.cat([p.grad.detach().reshape(-1).float() for p in params])[idx] * grad_scale
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def loss_kernel_roofline(dev, B, H, W, C=8, N=10, iters=20):
@@ -558,6 +618,17 @@ def main():
     img = frames(B, H, W, 0 + rank, dev)                          # the frames the parity tests and cpu_baseline use, resident in HBM
     ann = synth.labels_dir(B, 10, H, W, 8, seed=1 + rank).to(dev)
 
+    last = {}                                                                  # the latest step's losses (--dump-outputs)
+
+    start = [p.detach().clone() for p in params] if args.dump_outputs else None     # the seeded starting state (docstring)
+
+    def restart():
+        with torch.no_grad():
+            torch._foreach_copy_([p.detach() for p in params], start)
+            torch._foreach_zero_(list(opt.m) + list(opt.v))
+            opt.step_dev.zero_()
+        opt.step_count = 0
+
     def step():
         opt.zero_grad(set_to_none=True)
         cls_l, reg_l, vp_l = net([img, ann])
@@ -568,6 +639,7 @@ def main():
             # all-reduce per step, result left on the device
             ddp.mean_losses(cls_l, reg_l, vp_l)
         opt.step()                                                             # clip (:385) + Adam step (:387)
+        last["losses"] = (cls_l, reg_l, vp_l, loss)
         return loss
 
     def barrier():
@@ -598,15 +670,25 @@ def main():
             run_step, graph_note = step, "capture failed, eager launches measured: %s" % str(e)[:200]
             torch.cuda.synchronize()
     t0 = time.time()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1 if args.dump_outputs else args.steps):
         loss = run_step()
     barrier()
     dt = time.time() - t0
+    if args.dump_outputs:
+        # the last timed step from the seeded starting state (module docstring); the copy back stays outside the clock
+        restart()
+        barrier()
+        t0 = time.time()
+        loss = run_step()
+        barrier()
+        dt += time.time() - t0
+        if rank == 0:
+            dump_outputs(args.dump_outputs, net, last["losses"], grad_scale=opt.grad_scale)
     # Kernel roofline: the SAME K steps again, every launch of the conv / transform kernels bracketed by HIP events on the
     # launch stream (prof.KernelTimer).  Kept out of the throughput region above because ~1 400 event records per step
     # cost 2.4 % of it (74.8 vs 76.5 images/s measured); the kernels, shapes and order are identical.
     timer = None
-    if not args.no_kernel_timing:                              # every rank (the steps contain the all-reduce); rank 0 reports
+    if args.full and not args.no_kernel_timing:                # every rank (the steps contain the all-reduce); rank 0 reports
         timer = prof.ACTIVE = prof.KernelTimer()
         for _ in range(args.steps):
             step()
@@ -624,7 +706,7 @@ def main():
     # The library's DEFAULT mode checks the labels eagerly (one host read per step, as the reference's FocalLoss raises inside the
     # forward); the loop above defers that check (RN_DEFERRED_LABEL_CHECK, set in main).  The same K steps in the default mode:
     eager = None
-    if world == 1 and args.sections == "all" and not (args.graph and graph_note and "replayed" in graph_note):
+    if args.full and world == 1 and args.sections == "all" and not (args.graph and graph_note and "replayed" in graph_note):
         os.environ["RN_EAGER_LABEL_CHECK"] = "1"
         try:
             step()
@@ -794,7 +876,7 @@ def main():
                 line["fp8"] = fp8_section(dev, args, B, H, W)
             except Exception as e:
                 line["fp8"] = {"error": str(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.arch, H, W)
             except Exception as e:

@@ -83,7 +83,7 @@ CROP_HW = (112, 112)         # the tracker's crop detector input (train_crop_det
 
 # architecture -> (golden file, input size, batch) of the whole-model fixtures (tools/make_golden.py gen_model / gen_model_deep)
 MODEL_CASES = {"resnet18": ("model", None, None), "resnet50": ("model", None, None),
-               "resnet34": ("model_deep", CROP_HW, 2), "resnet101": ("model_deep", MODEL_HW, 1)}
+               "resnet34": ("model_deep", CROP_HW, 2), "resnet101": ("model_deep101", MODEL_HW, 1)}
 
 
 def model_case(arch, directional=True):

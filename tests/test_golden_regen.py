@@ -26,7 +26,7 @@ FLOAT_TOL = 1e-6            # relative to the array's largest magnitude; only fo
 
 
 def _thread_order_dependent(fname, key):
-    return fname in ("model.npz", "model_deep.npz") and ("_gsum_" in key or "_g_" in key or key.endswith("_losses"))
+    return fname in ("model.npz", "model_deep.npz", "model_deep101.npz") and ("_gsum_" in key or "_g_" in key or key.endswith("_losses"))
 
 
 @pytest.fixture(scope="module")

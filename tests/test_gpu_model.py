@@ -1,5 +1,5 @@
 """GPU parity of the whole detector (drop-in ResNet on the HIP engine) against the golden vectors the
-REFERENCE produced on CPU (tests/golden/model.npz, model_deep.npz) and against the oracle.
+REFERENCE produced on CPU (tests/golden/model.npz, model_deep.npz, model_deep101.npz) and against the oracle.
 
 Tolerances: fp32 losses / boxes / scores within 1e-4 relative (north_star).  Parameter gradients are compared tensor by
 tensor (L2-relative error, and the largest element error relative to the gradient's max magnitude).  Measured on the

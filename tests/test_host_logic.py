@@ -56,6 +56,36 @@ def test_bench_refuses_to_report_fewer_gpus_than_asked():
     assert '"metric"' not in r.stdout
 
 
+def test_bench_dump_outputs_are_float32_at_fixed_positions(tmp_path):
+    """bench.py --dump-outputs: the losses, each under its own name, and the updated weights and their gradients sampled at the
+    SAME fixed positions of the flattened parameters, float32 .npy files; the gradients times the optimizer's grad_scale (1/N
+    where the data-parallel reducer leaves the sum in the buffer)."""
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.Linear(200, 5))
+    net(torch.randn(4, 300)).sum().backward()
+    losses = (torch.tensor([1.0, 2.0]), torch.tensor([3.0, 4.0]), torch.tensor([5.0, 6.0]), torch.tensor(7.0, dtype=torch.float64))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), net, losses, grad_scale=0.5)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["cls_loss.npy", "grads_sample.npy", "loss.npy", "reg_loss.npy", "vp_loss.npy", "weights_sample.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.tobytes() == b.tobytes(), n
+    load = lambda n: np.load(tmp_path / "a" / (n + ".npy"))
+    assert load("cls_loss").tolist() == [1.0, 2.0] and load("reg_loss").tolist() == [3.0, 4.0]
+    assert load("vp_loss").tolist() == [5.0, 6.0] and float(load("loss")) == 7.0
+    flat_w = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy()
+    flat_g = torch.cat([p.grad.reshape(-1) for p in net.parameters()]).numpy()
+    pos = bench.dump_positions(flat_w.size)
+    assert 0 < pos.size <= min(flat_w.size, bench.DUMP_SAMPLE) and np.all(np.diff(pos) > 0)
+    assert np.array_equal(bench.dump_positions(flat_w.size), pos)
+    assert np.array_equal(load("weights_sample"), flat_w[pos])
+    assert np.array_equal(load("grads_sample"), flat_g[pos] * np.float32(0.5))
+
+
 @pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (build container only)")
 def test_util_track_merges_with_the_reference_namespace():
     """with 3d-playground_amd first on sys.path, util_track.kf is the drop-in while the tracker's

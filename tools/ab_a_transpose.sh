@@ -10,7 +10,7 @@ for r in 1 2; do for lib in preT new; do
 done; done
 for r in 1 2; do for lib in preT new; do
   if [ $lib = preT ]; then export RN_LIB_PATH=3d-playground_amd/retinanet_mi355x/lib/ab/libpreT.so; else unset RN_LIB_PATH; fi
-  python bench.py --steps 10 --warmup 3 --sections headline --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 3 --sections headline --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.readline()); k=l['kernels']
 print('$lib', l['value'], l['ms_per_step'], {n:(k[n]['ms_per_step'],k[n]['frac']) for n in ('conv_igemm_2x2','conv_igemm_4x1','conv_wgrad','wino_input','wino_output') if n in k})" >> gpurun_out/r4g/step.log

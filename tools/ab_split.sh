@@ -20,7 +20,7 @@ for cfg in "A 0" "D 0" "D 1"; do
   set -- $cfg
   lib=$LIB/ab/lib$1.so; [ "$1" = "D" ] && lib=$LIB/libretinanet_mi355x.so
   echo "=== step: lib $1 RN_SPLIT_A_ONCE=$2" | tee -a $out/step.log
-  RN_LIB_PATH=$lib RN_SPLIT_A_ONCE=$2 python bench.py --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  RN_LIB_PATH=$lib RN_SPLIT_A_ONCE=$2 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.readline()); k=l['kernels']
 print(l['value'], l['ms_per_step'], {n:(k[n]['ms_per_step'],k[n]['frac']) for n in ('conv_igemm_2x2','conv_igemm_4x1','conv_wgrad','wino_input','wino_output') if n in k}, l.get('fp32_native_mfma',{}).get('value'))" | tee -a $out/step.log

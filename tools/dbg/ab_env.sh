@@ -4,7 +4,7 @@ mkdir -p gpurun_out/ab
 for rep in $(seq $reps); do
 for v in $a $b; do
   echo "== $name=$v" | tee -a gpurun_out/ab/$name.txt
-  env $name=$v timeout -k 10 300 python bench.py --steps 10 --warmup 3 --sections headline --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  env $name=$v timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --sections headline --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ for rep in 1 2; do
 for v in mfstg0 product; do
   if [ $v = product ]; then unset RN_LIB_PATH; else export RN_LIB_PATH=3d-playground_amd/retinanet_mi355x/lib/ab/lib$v.so; fi
   echo "== $v" | tee -a gpurun_out/r6b/stg_step.txt
-  timeout -k 10 200 python bench.py --steps 10 --warmup 3 --sections headline --no-cpu-baseline 2>/dev/null | python -c "
+  timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --sections headline --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,20 +10,20 @@ part=${1:-1}
 if [ "$part" = 1 ]; then
   RN_TEST_MEASURE=0 timeout -k 10 900 python3 -m pytest tests -q -s -m gpu > "$O/gpu_tests.log" 2>&1
   echo "tests done" && tail -1 "$O/gpu_tests.log"
-  timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > "$O/bench.log" 2>&1
+  timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > "$O/bench.log" 2>&1
   echo "bench done"
 fi
 if [ "$part" = 2 ]; then
   # the headline's own steps only, towers and weight gradients on ONE stream (a kernel's duration in the trace means something only when nothing else
   # shares the GPU): Sum(duration) / (warmup + 2 * steps) of a family = kernels.<family>.ms_per_step of the line it prints
-  RN_TOWER_STREAMS=0 RN_WGRAD_STREAMS=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 bench.py --steps 5 --warmup 2 --sections headline --no-cpu-baseline > "$O/bench_headline_under_rocprof.log" 2>&1
+  RN_TOWER_STREAMS=0 RN_WGRAD_STREAMS=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 bench.py --full --steps 5 --warmup 2 --sections headline --no-cpu-baseline > "$O/bench_headline_under_rocprof.log" 2>&1
   cp "$(ls $O/stats/*/*kernel_stats.csv | head -1)" "$O/kernel_stats_headline.csv"
   echo "stats done"
   bash tools/collect_traffic.sh
   python3 tools/summarize_traffic.py gpurun_out/traffic > "$O/pmc_traffic.json"
   echo "traffic done"
-  timeout -k 10 600 python3 bench.py --steps 10 --warmup 3 --dtype bf16 --no-cpu-baseline > "$O/bench_bf16.log" 2>&1
-  timeout -k 10 600 python3 bench.py --arch resnet101 --dtype fp8 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > "$O/bench_fp8_train_resnet101_b16.log" 2>&1
+  timeout -k 10 600 python3 bench.py --full --steps 10 --warmup 3 --dtype bf16 --no-cpu-baseline > "$O/bench_bf16.log" 2>&1
+  timeout -k 10 600 python3 bench.py --full --arch resnet101 --dtype fp8 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > "$O/bench_fp8_train_resnet101_b16.log" 2>&1
   timeout -k 10 400 python3 tools/fp8_error_budget.py > "$O/fp8_error_budget.txt" 2>&1
   timeout -k 10 300 python3 tools/bench_loss.py > "$O/loss_microbench.txt" 2>&1
   echo "part 2 done"

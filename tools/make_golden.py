@@ -247,9 +247,10 @@ def gen_model(model_dir, model_2d):
 
 def gen_model_deep(model_dir):
     """The other two architectures callers build: resnet34 = the tracker's crop detector (MC3D_crop_tracker.py:1535, at its
-    112x112 crop size, batch 2) and resnet101 (BASELINE configs[4]).  Own file so that model.npz stays as it was."""
-    out = {}
+    112x112 crop size, batch 2) and resnet101 (BASELINE configs[4]).  Own files so that model.npz stays as it was, one per
+    architecture so that each stays under the size limit of a committed file."""
     for arch, hw, batch in (("resnet34", gc.CROP_HW, 2), ("resnet101", gc.MODEL_HW, 1)):
+        out = {}
         sd, img, ann = gc.model_inputs(arch, directional=True, hw=hw, batch=batch)
         net = getattr(model_dir, arch)(num_classes=4)
         net.load_state_dict(sd)
@@ -264,7 +265,7 @@ def gen_model_deep(model_dir):
             boxes, cls = net(img, LOCALIZE=True)
         out["%s_dir_boxes" % arch] = t2n(boxes)
         out["%s_dir_cls" % arch] = t2n(cls)
-    np.savez_compressed(os.path.join(OUT, "model_deep.npz"), **out)
+        np.savez_compressed(os.path.join(OUT, gc.MODEL_CASES[arch][0] + ".npz"), **out)
 
 
 def gen_homography():

@@ -27,7 +27,7 @@ done
 for r in $(seq 1 $rounds); do
   for cfg in off on; do
     echo "=== step round $r $cfg" | tee -a $out/step.log
-    env $(run $cfg) python bench.py --steps 8 --warmup 3 --sections headline --no-cpu-baseline 2>/dev/null | python -c "
+    env $(run $cfg) python bench.py --full --steps 8 --warmup 3 --sections headline --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.readline()); k=l['kernels']
 print(l['value'], l['ms_per_step'], {n:(k[n]['ms_per_step'],k[n]['frac']) for n in ('conv_igemm_2x2','conv_igemm_4x1','conv_wgrad','wino_input','wino_output') if n in k})" | tee -a $out/step.log
