@@ -81,3 +81,17 @@ extern "C" int rn_set_option(int option, int value) {
     g_opt[option].store(value, std::memory_order_relaxed);
     return RN_OK;
 }
+
+// Identity of the graph capture a stream is in (0: not capturing).  torch exposes whether a stream captures, not which capture: the
+// amax-table allocator (retinanet_mi355x/conv.py) keys its zeroed chunks by it, so that no two captures -- and no capture and eager
+// work -- ever hand out slices of one chunk.
+extern "C" int rn_stream_capture_id(void *stream, unsigned long long *id) {
+    if (!id) return RN_EINVAL;
+    *id = 0;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    unsigned long long cid = 0;
+    const hipError_t e = hipStreamGetCaptureInfo((hipStream_t)stream, &st, &cid);
+    if (e != hipSuccess) return (int)e;
+    if (st == hipStreamCaptureStatusActive) *id = cid;
+    return RN_OK;
+}

@@ -137,7 +137,10 @@ struct SplitH8 { f16x8 h, l; };
 // The scale of a tensor whose largest magnitude has the fp32 bit pattern `amax_bits` (sign cleared): 2^(14 - floor(log2 amax)), so that
 // amax * scale is in [2^14, 2^15); 1 for an all-zero tensor.  Returned as the biased exponent field: scale = bits(se << 23), its inverse
 // bits((254 - se) << 23); both stay normal numbers for every amax (tensors below 2^-112 are scaled by 2^126 and simply use less of fp16's
-// range).  A NaN / infinite amax gives a finite scale: the non-finite elements themselves make the result NaN.
+// range).  A NaN / infinite amax gives a finite scale (2^-114): the non-finite elements themselves make their rows NaN, and every FINITE
+// element of that image falls below fp16's range at that scale -- the rest of the image keeps only the epilogue's value.  A finite amax
+// near fp32's maximum gives finite terms, but the epilogues apply the row's inverse scale before the weight row's, and that product can
+// overflow to inf (tests/test_gpu_amax.py pins both).
 __host__ __device__ __forceinline__ int rn_f16_scale_exp(unsigned amax_bits) {
     const int e = (int)((amax_bits >> 23) & 0xffu);
     if (e == 0) return 127;
@@ -204,9 +207,11 @@ __device__ __forceinline__ void split_store_chunk_h(const float *__restrict__ sr
         ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16((A).h, (B).h, ACC, 0, 0, 0);         \
     } while (0)
 
-// AMAX TABLES of a tensor (rn_conv_desc.x_amax / y_amax): per IMAGE, which binary exponents its elements have -- 256 bytes, byte e != 0
-// iff some element's fp32 exponent field is e.  That is all a consumer needs (rn_f16_scale_exp takes the LARGEST exponent: the scale is
-// a power of two), and it makes the producer side free of atomics and of read-backs:
+// AMAX TABLES of a tensor (rn_conv_desc.x_amax / y_amax): per IMAGE 256 bytes, one per fp32 exponent field.  What is guaranteed: the
+// HIGHEST set byte is the exponent field of the image's largest |value|, and no byte above it is set.  A lower byte e set only means that
+// some lane's largest stored |value| had exponent e; most exponents present in the image leave no byte (not "byte e != 0 iff some
+// element has exponent e").  That is all a consumer needs (rn_f16_scale_exp takes the LARGEST exponent: the scale is a power of two),
+// and it makes the producer side free of atomics and of read-backs:
 //   * a producer lane that has stored values with largest magnitude v writes the byte  table[image][exponent(v)] = 1  -- a plain store,
 //     idempotent, no ordering between lanes, waves or launches needed (the parity classes of a stride-2 data gradient, an accumulation
 //     in place: later launches just add bytes); lines written on several XCDs merge byte-wise when the kernel ends;

@@ -27,6 +27,7 @@ SIGNATURES = {
     "rn_split_weights": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "rn_split_weights_f16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "rn_amax": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "rn_stream_capture_id": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_ulonglong)]),
     "rn_anchor_count": (c_i64, [c_i32, c_i32]),
     "rn_anchor_base_boxes": (None, [c_vp]),
     "rn_anchors_fwd": (c_i32, [c_vp, c_i32, c_i32, c_vp]),

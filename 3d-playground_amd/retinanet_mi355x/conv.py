@@ -102,6 +102,7 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
     d = ConvDesc(N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, a, b, p_h, p_w, ds, act, add_mode, add_hw[0], add_hw[1],
                  mask_mode, int(in_relu), os_, oo_h, oo_w, Hy, Wy,
                  a2[0], a2[1], a2[2], a2[3], Hi * Wi * Cin, ybs, add_batch_stride, w_batch_stride)
+    amax_drop(y)                                         # a reused destination: the words of what it held before are stale
     bits = _sign_words(y, sign and y_batch_stride is None and out_map is None)
     d.sign_out = None if bits is None else bits.data_ptr()
     yam = None
@@ -254,17 +255,41 @@ def _w_operand(w_packed, d=None):
 # (words, tensor._version at that time) as ._rn_amax.  A consumer takes the words if the version still matches (an in-place torch
 # operation since then invalidates them; this module's own in-place kernels drop the attribute), else one rn_amax pass computes them.
 # Words are views of zeroed chunks that are never reused.  Per image, so that an image's scales -- and every bit of its results -- do not
-# depend on what else is in the batch.
+# depend on what else is in the batch.  A chunk made during a graph capture is zeroed by a fill the graph itself replays, so it serves
+# that capture only; an eager chunk is zeroed once, so it never serves a capture (_amax_chunk_key).
 _AMAX_CHUNK = {}
 
 
 AMAX_SUB = 64                                    # int32 words of one image's exponent table (csrc/mfma_split.h: RN_AMAX_BYTES = 256)
 
 
+def capture_id(stream):
+    """The graph capture the raw stream handle `stream` is in (rn_stream_capture_id): a per-process identity, 0 when not capturing."""
+    cid = ctypes.c_ulonglong(0)
+    _hip.check(_hip.load().rn_stream_capture_id(stream, ctypes.byref(cid)), "rn_stream_capture_id")
+    return cid.value
+
+
+def _amax_chunk_key(device):
+    """Which zeroed chunk the next amax words on `device` come from: one per (device, stream, capture).  The capture matters because
+    torch.cuda.graph captures every graph on one shared stream: keyed by the stream alone, a second capture (or a capture on a stream
+    that ran eagerly before) would slice the first one's chunk, whose zero fill belongs to another graph or to no graph at all -- and
+    the exponent bytes of replay after replay would pile up in it.  The capture is asked of the stream itself, so it is the one of
+    `device` whatever the current device; the legacy default stream (handle 0) cannot capture and is not asked."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    return (device, stream, capture_id(stream) if stream else 0)
+
+
 def _amax_alloc(device, nwords):
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    key = _amax_chunk_key(device)
     nwords = (nwords + 7) // 8 * 8                    # blocks start on 32-byte boundaries
     c = _AMAX_CHUNK.get(key)
+    if c is None:
+        # A stream is in one capture at a time: the chunks of its earlier captures belong to finished graphs, whose own fills zero them
+        # on every replay.  This table lets go of them (capture ids never come back) -- the tensors that carry their words keep them,
+        # and the rest of their memory stays with the graph's pool instead of outliving the graph here.
+        for k in [k for k in _AMAX_CHUNK if k[:2] == key[:2] and k[2] not in (0, key[2])]:
+            del _AMAX_CHUNK[k]
     if c is None or c[1] + nwords > c[0].numel():
         c = _AMAX_CHUNK[key] = [torch.zeros(max(1 << 18, nwords), dtype=torch.int32, device=device), 0]     # 1 MB: ~500 tensors of 8 images
     c[1] += nwords
@@ -307,7 +332,8 @@ def amax_carry(view, src):
 
 
 def amax_drop(t):
-    """After an in-place kernel of this module rewrote t."""
+    """Before a kernel of this module rewrites t -- in place, or as a caller's destination reused through a path that leaves no words of
+    its own (y_batch_stride, out_map): kernel writes do not bump t._version, so old words would otherwise survive (_sign_words' twin)."""
     if hasattr(t, "_rn_amax"):
         del t._rn_amax
 
@@ -483,6 +509,8 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
         has_mask = pm is not None and pm[0] is not None
         # sign bits: read instead of the fp32 masks when every mask of the launch carries them; written for dense results on request
         mbits = has_mask and BITMASKS and all(getattr(m, "_rn_sign", None) is not None for m in pm)
+        for o in outs[sl]:
+            amax_drop(o)
         signs = [_sign_words(o, sign and not y_batch_stride) for o in outs[sl]]
         yams = [amax_slot(dev, o.shape[0]) for o in outs[sl]] if want_amax() and not y_batch_stride else None
         g = _wino_group(part, dsts=outs[sl], adds=pa, masks=pm, mask_bits=mbits, signs=signs, amaxs=yams)
@@ -616,6 +644,7 @@ def conv_igemm_grouped(problems, w_packed, scale=None, shift=None, act=ACT_NONE,
         d.w_format, d.w_unscale = wfmt, wus
         if wfmt == 3:
             d.x_amax, d.x_amax_img_stride, d.x_amax_row_stride = amax_words(x).data_ptr(), 1, 0
+        amax_drop(pr["y"])
         bits = _sign_words(pr["y"], pr.get("sign", False) and pr.get("y_batch_stride") is None)
         d.sign_out = None if bits is None else bits.data_ptr()
         yam = amax_slot(x.device, x.shape[0]) if want_amax() and pr.get("y_batch_stride") is None else None
@@ -899,6 +928,7 @@ def conv_igemm_bf16(x, w_packed, y, geom, scale=None, shift=None, add=None, add_
     assert x.dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16 and y.dtype in (torch.bfloat16, torch.float32)
     mask_ptr, mask_mode = _mask_operand(mask, mask_mode)
     d = _make_desc(x, geom, act, add_mode, add_hw, mask_mode, False, out_map, y_batch_stride, add_batch_stride, None)
+    amax_drop(y)
     bits = _sign_words(y, sign and y_batch_stride is None and out_map is None and y.dtype == torch.bfloat16)
     d.sign_out = None if bits is None else bits.data_ptr()
     kind = "conv_igemm_bf16"
@@ -1036,6 +1066,7 @@ def conv_igemm_bf16_grouped(problems, w_packed, scale=None, shift=None, act=ACT_
         assert x.dtype == torch.bfloat16 and (pr["y"].dtype == torch.float32) == yf32
         mask_ptr, mmode = _mask_operand(mask, pr.get("mask_mode", 2))
         d = _make_desc(x, geom, act, 1 if add is not None else 0, (0, 0), mmode, False, None, pr.get("y_batch_stride"), None, None)
+        amax_drop(pr["y"])
         bits = _sign_words(pr["y"], pr.get("sign", False) and pr.get("y_batch_stride") is None and not yf32)
         d.sign_out = None if bits is None else bits.data_ptr()
         g.d[i] = d
@@ -1131,6 +1162,7 @@ def conv_igemm_fp8(xq, wq, y, geom, scale, shift=None, add=None, add_mode=0, add
     lib = _hip.load()
     assert xq.dtype == torch.uint8 and wq.dtype == torch.uint8 and y.dtype in (torch.uint8, torch.float32)
     d = _make_desc(xq, geom, act, add_mode, add_hw, 0, False, None, y_batch_stride, None, None)
+    amax_drop(y)
     kind = "conv_igemm_fp8"
     if prof.ACTIVE is not None:
         kind += _p8_suffix("rn_conv_igemm_fp8_tile", d, y.dtype == torch.float32)
@@ -1157,6 +1189,7 @@ def conv_igemm_fp8_grouped(problems, wq, scale, shift=None, act=ACT_NONE, out_sc
         x = pr["x"]
         assert x.dtype == torch.uint8 and (pr["y"].dtype == torch.float32) == yf32
         g.d[i] = _make_desc(x, pr["geom"], act, 0, (0, 0), 0, False, None, pr.get("y_batch_stride"), None, None)
+        amax_drop(pr["y"])
         g.x[i], g.y[i], g.add[i], g.mask[i] = x.data_ptr(), pr["y"].data_ptr(), None, None
     trm, trn = divmod(lib.rn_conv_igemm_fp8_tile_rows(ctypes.byref(g), int(yf32)), 1000)    # the launcher's tile for this group
     for i in range(g.n):

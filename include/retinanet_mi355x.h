@@ -269,8 +269,10 @@ typedef struct rn_conv_desc {
                                       = (y[e] > 0) for every stored element at float offset e -- what the backward pass needs of a ReLU
                                       output (D/utils.py:60-80), at 1/32 of the bytes.  Needs Cout % 32 == 0 and y_batch_stride % 32
                                       == 0.  mask_mode | RN_MASK_BITS (4): `mask` points to such words (the consumer's side). */
-    const void *x_amax;            /* RN_FP32_SPLIT3 (round 5): the AMAX TABLES of x: per image 256 bytes, byte e != 0 iff some element of the
-                                      image has fp32 exponent field e (what a producer's y_amax left, or rn_amax) -- the kernel takes the
+    const void *x_amax;            /* RN_FP32_SPLIT3 (round 5): the AMAX TABLES of x: per image 256 bytes whose HIGHEST set byte is the fp32
+                                      exponent field of the image's largest |value|; a lower byte e set means only that some lane's
+                                      largest stored |value| had exponent e, and most exponents present leave no byte (what a
+                                      producer's y_amax left, or rn_amax) -- the kernel takes the
                                       largest exponent present as the image's power-of-two scale for its fp16 split, row by row: GEMM
                                       row (image n, pixel r) uses table n * x_amax_img_stride when x_amax_row_stride == 0 (the usual
                                       form, img stride 1: an image's result then does not depend on what else is in the batch), or the
@@ -347,9 +349,12 @@ int rn_split_weights(const float *w_packed, void *w_split, int64_t rows, int Kpa
  * the inverse scales.  Pass as w_packed with rn_conv_desc.w_format = 3 and w_unscale = row_unscale.  (rn_prep_batched: job kind 5.) */
 int rn_split_weights_f16(const float *w_packed, void *w_split, float *row_unscale, int64_t rows, int Kpad, void *stream);
 /* The amax tables of a tensor (rn_conv_desc.x_amax) for tensors no producer left them for: x = n_images images of per_image floats,
- * amax = [n_images][256] bytes, byte e of table i set when an element of image i has exponent field e (only the largest matters; the
- * kernel sets the largest per thread); zero the tables first.  One pass over x. */
+ * amax = [n_images][256] bytes: every thread sets the byte of the exponent field of the largest |value| it read, so the highest set
+ * byte of table i is the exponent field of image i's largest |value| (lower bytes: some thread's maximum); zero the tables first.
+ * One pass over x. */
 int rn_amax(const float *x, int64_t per_image, int n_images, void *amax, void *stream);
+/* *id = the identity of the graph capture `stream` is in (hipStreamGetCaptureInfo), 0 when it is not capturing.  Host only. */
+int rn_stream_capture_id(void *stream, unsigned long long *id);
 /* 1 when rn_conv_igemm would run this problem on an fp16-split kernel (so: wants w_format 3, x_amax, w_unscale): in RN_FP32_SPLIT3 mode,
  * every problem (the 16x16x32 kernel for the wide layers with Cin % 32 == 0, the two-term form of the 128 x 128 / 256 x 64 tile for the
  * rest); 0 in the other modes. */
