@@ -61,6 +61,9 @@ SIGNATURES = {
     "rn_kf_view": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "rn_kf_predict": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_i32, c_vp]),
     "rn_kf_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "rn_track_cost": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "rn_lsap_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rn_linear_sum_assignment": (c_i32, [c_vp, c_i64, c_i64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rn_frame_ingest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp]),
 }
 

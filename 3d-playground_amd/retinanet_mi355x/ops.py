@@ -583,6 +583,80 @@ def md_iou(a, b):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ track association
+LSAP_MAX_MIN = 4096                # RN_LSAP_MAX_MIN: min(rows, cols)
+LSAP_MAX = PARSE_MAX               # max(rows, cols)
+LSAP_OK, LSAP_INVALID, LSAP_INFEASIBLE = 0, 1, 2
+
+
+def track_cost(pre, det):
+    """The cost of MC_Crop_Tracker.match_hungarian (MC3D_crop_tracker.py:680-701): priors [n, >=6] and detections
+    [m, >=6] fp32 states (direction at column 5) -> [n,m] fp64 ``1 - md_iou`` of their road-plane footprints."""
+    lib = _hip.load()
+    _hip.need_gpu(pre, det)
+    if pre.dim() != 2 or det.dim() != 2 or pre.shape[1] < 6 or det.shape[1] < 6:
+        raise RuntimeError("track_cost: states are [n, >= 6], got %s and %s" % (tuple(pre.shape), tuple(det.shape)))
+    pre, det = _hip.f32c(pre), _hip.f32c(det)
+    n, m = pre.shape[0], det.shape[0]
+    cost = torch.empty((n, m), dtype=torch.float64, device=pre.device)
+    if n and m:
+        with torch.cuda.device(pre.device):
+            _hip.check(lib.rn_track_cost(pre.data_ptr(), pre.shape[1], det.data_ptr(), det.shape[1], n, m, cost.data_ptr(),
+                                         _hip.stream()), "rn_track_cost")
+    return cost
+
+
+def _lsap(cost, max_cost):
+    """-> (row_match int32 [nr], info int32 [2] = (pairs kept, status)), device tensors, no synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(cost)
+    if cost.dim() != 2:
+        raise ValueError("expected a matrix (2-D array), got a %d array" % cost.dim())
+    nr, nc = cost.shape
+    dev = cost.device
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    row_match = torch.full((nr,), -1, dtype=torch.int32, device=dev)
+    if nr == 0 or nc == 0:
+        return row_match, info
+    if min(nr, nc) > LSAP_MAX_MIN or max(nr, nc) > LSAP_MAX:
+        raise RuntimeError("linear_sum_assignment takes at most %d x %d (either orientation), got %d x %d"
+                           % (LSAP_MAX_MIN, LSAP_MAX, nr, nc))
+    c = cost.double().contiguous()
+    ws = torch.empty(lib.rn_lsap_workspace_bytes(nr, nc), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_linear_sum_assignment(c.data_ptr(), nr, nc, float(max_cost), ws.data_ptr(), row_match.data_ptr(),
+                                                info[0:1].data_ptr(), info[1:2].data_ptr(), _hip.stream()),
+                   "rn_linear_sum_assignment")
+    return row_match, info
+
+
+def _matched_rows(row_match, k):
+    """The k rows with a match, in increasing order, without a synchronisation (a stable sort of the 'unmatched' flag)."""
+    return torch.argsort((row_match < 0).to(torch.int8), stable=True)[:k]
+
+
+def match(cost, max_cost, info=False):
+    """linear_sum_assignment + match_hungarian's gate (MC3D_crop_tracker.py:706-723) in one launch, without a
+    synchronisation: -> row_match int32 [nr] (matched column or -1; all -1 on invalid / infeasible input, which is the
+    reference's ``except ValueError: return []``).  info=True also returns the device int32 [2] (pairs kept, status)."""
+    row_match, inf = _lsap(cost, max_cost)
+    return (row_match, inf) if info else row_match
+
+
+def linear_sum_assignment(cost):
+    """scipy.optimize.linear_sum_assignment(cost) on the device, same result: (row_ind, col_ind) int64 device tensors
+    sorted by row.  Copies one word pair (count, status) to the host; raises ValueError with scipy's wording on a NaN or
+    -inf entry or when no finite complete assignment exists."""
+    row_match, inf = _lsap(cost, float("inf"))
+    k, status = (int(x) for x in inf.cpu())
+    if status == LSAP_INVALID:
+        raise ValueError("matrix contains invalid numeric entries")
+    if status == LSAP_INFEASIBLE:
+        raise ValueError("cost matrix is infeasible")
+    rows = _matched_rows(row_match, k)
+    return rows, row_match[rows].long()
+
+
 # ------------------------------------------------------------------------------------------------ frame ingest
 IMAGENET_MEAN = (0.485, 0.456, 0.406)     # util_track/mp_loader.py:241
 IMAGENET_STD = (0.229, 0.224, 0.225)

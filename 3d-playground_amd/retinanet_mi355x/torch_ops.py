@@ -16,6 +16,7 @@ Operator                                         reference code it stands for
   decode_dir(anchors, reg) / decode_2d(...)      BBoxTransform.forward                 D/utils.py:102-149, R/utils.py:102-126
   clip_boxes_(boxes, H, W)                       ClipBoxes.forward (in place)          R/utils.py:134-144
   nms(boxes, scores, thr)                        torchvision.ops.nms as the path uses it   D/model.py:383
+  linear_sum_assignment(cost)                    scipy.optimize.linear_sum_assignment  MC3D_crop_tracker.py:706
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
   frame_ingest(frames_u8, swap_rb, nhwc4)        to_tensor + normalize of the loaders  util_track/mp_loader.py:239-243
 
@@ -135,6 +136,17 @@ def _(boxes, scores, iou_threshold):
     return boxes.new_empty((n,), dtype=torch.int64)
 
 
+@_lib.custom_op(NS + "::linear_sum_assignment", mutates_args=(), device_types="cuda")
+def linear_sum_assignment(cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.linear_sum_assignment(cost)
+
+
+@linear_sum_assignment.register_fake
+def _(cost):
+    n = torch.library.get_ctx().new_dynamic_size()
+    return cost.new_empty((n,), dtype=torch.int64), cost.new_empty((n,), dtype=torch.int64)
+
+
 # ---- homography
 @_lib.custom_op(NS + "::state_to_space", mutates_args=(), device_types="cuda")
 def state_to_space(state: torch.Tensor) -> torch.Tensor:
@@ -180,4 +192,4 @@ def _(frames_u8, swap_rb, nhwc4):
 
 
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "state_to_space", "state_to_im", "im_to_state", "frame_ingest")
+             "linear_sum_assignment", "state_to_space", "state_to_im", "im_to_state", "frame_ingest")

@@ -197,6 +197,26 @@ int rn_kf_predict(float *X, float *P, const float *D, double *T, const float *F,
 int rn_kf_update(float *X, float *P, const int32_t *rows, const double *z, const float *H, const float *R,
                  const float *mu_R, int m, void *stream);
 
+/* ---------------------------------------------------------------- tracker: association --------------------
+ * The middle of MC_Crop_Tracker.match_hungarian (MC3D_crop_tracker.py:637-731) without leaving the device.
+ * rn_track_cost: pre [n, pre_stride] / det [m, det_stride] fp32 states, direction at column 5 (Torch_KF.view with
+ *   with_direction gives 7 columns, parse_detections 6) -> cost [n,m] fp64 = 1 - md_iou of the fp32 road-plane
+ *   footprints (min / max of the four bottom corners of state_to_space), md_iou's operation order (:1030-1049), the
+ *   union not clamped (0/0 -> NaN, which the assignment reports as invalid, as scipy raises).
+ * rn_linear_sum_assignment: scipy.optimize.linear_sum_assignment (its rectangular_lsap: Crouse 2016, shortest
+ *   augmenting path, scipy's column order and tie rule) on cost [nr,nc] fp64 row-major, transposed by strides when
+ *   nr > nc; then the gate of match_hungarian (:719-723): a pair whose cost is > max_cost is dropped (+inf: no gate).
+ *   row_match [nr] i32 = matched column or -1; n_matched[0] = pairs kept; status[0] = 0 ok, 1 invalid (a NaN or -inf
+ *   entry), 2 infeasible (no finite complete assignment) -- both with no matches, what match_hungarian's
+ *   `except ValueError: return []` gives.  No synchronisation.  min(nr,nc) <= RN_LSAP_MAX_MIN, max(nr,nc) <=
+ *   RN_PARSE_MAX.  workspace: rn_lsap_workspace_bytes(nr, nc) bytes. */
+#define RN_LSAP_MAX_MIN 4096
+int rn_track_cost(const float *pre, int64_t pre_stride, const float *det, int64_t det_stride, int64_t n, int64_t m,
+                  double *cost, void *stream);
+int64_t rn_lsap_workspace_bytes(int64_t nr, int64_t nc);
+int rn_linear_sum_assignment(const double *cost, int64_t nr, int64_t nc, double max_cost, void *workspace,
+                             int32_t *row_match, int32_t *n_matched, int32_t *status, void *stream);
+
 /* ---------------------------------------------------------------- frame ingest ----------------------------
  * Replaces F.to_tensor + F.normalize of the reference's loaders (util_track/mp_loader.py:239-243,
  * perform_3D_detection_on_video_sequences.py:51-58) on device: frames uint8 [B,H,W,3] (as the decoder / cv2.resize

@@ -528,6 +528,107 @@ def gen_kf():
     np.savez_compressed(os.path.join(OUT, "kf.npz"), **out)
 
 
+def gen_tracker_assoc():
+    """scipy.optimize.linear_sum_assignment on the matrices of tests/track_cases.py (indices only: both sides rebuild the
+    matrices from seeds); MC_Crop_Tracker.match_hungarian run unbound on a stand-in ``self`` (hg, md_iou, phi_match);
+    and a scripted 8-frame run of match_hungarian / manage_tracks / increment_fslds / remove_overlaps /
+    remove_anomalies in track()'s order (MC3D_crop_tracker.py:1100-1137, 1259-1261) on the reference's own Torch_KF."""
+    import track_cases as tc
+    from scipy.optimize import linear_sum_assignment
+    trk, hgmod = import_reference_tracker()
+    T = trk.MC_Crop_Tracker
+    kfmod = ref_module_from_file("_reference_util_track_kf", "util_track/kf.py")
+    out = {}
+    for name, c in tc.lsap_cases():
+        r, k = linear_sum_assignment(c)
+        out["lsap_%s_row" % name], out["lsap_%s_col" % name] = r.astype(np.int64), k.astype(np.int64)
+    hg = hgmod.Homography()                                # state_to_space needs no camera: a bare wrapper
+    me = types.SimpleNamespace(phi_match=tc.PHI_MATCH, hg=hgmod.Homography_Wrapper(hg1=hg, hg2=hgmod.Homography()))
+    me.md_iou = types.MethodType(T.md_iou, me)
+    for name, pre, det in tc.hungarian_cases():
+        p, d = torch.from_numpy(pre), torch.from_numpy(det)
+        if len(pre) and len(det):
+            fp = me.hg.state_to_space(p.clone())
+            fd = me.hg.state_to_space(d.clone())
+
+            def env(s):
+                b = torch.zeros([s.shape[0], 4])
+                b[:, 0], b[:, 2] = torch.min(s[:, 0:4, 0], dim=1)[0], torch.max(s[:, 0:4, 0], dim=1)[0]
+                b[:, 1], b[:, 3] = torch.min(s[:, 0:4, 1], dim=1)[0], torch.max(s[:, 0:4, 1], dim=1)[0]
+                return b
+            a, b = env(fp), env(fd)
+            f, s = a.shape[0], b.shape[0]
+            out["hung_%s_dist" % name] = t2n(1.0 - T.md_iou(me, a.unsqueeze(1).repeat(1, s, 1).double(),
+                                                               b.unsqueeze(0).repeat(f, 1, 1).double()))
+        m = T.match_hungarian(me, p.clone(), d.clone())
+        out["hung_%s_is_list" % name] = np.array(isinstance(m, list))
+        out["hung_%s_match" % name] = np.asarray(m, dtype=np.int64).reshape(-1, 2)
+    # the 8-frame sequence
+    trkr = types.SimpleNamespace(**{k: v for k, v in tc.PARAMS.items()})
+    trkr.hg = me.hg
+    trkr.class_dict = tc.class_dict()
+    trkr.filter = kfmod.Torch_KF(torch.device("cpu"), INIT=tc.kf_init())
+    trkr.fsld, trkr.all_classes, trkr.all_confs, trkr.all_cameras = {}, {}, {}, {}
+    trkr.next_obj_id, trkr.updated_this_frame = 0, []
+    trkr.time_metrics = {"add and remove": 0.0}
+    trkr.ts_bias = list(tc.TS_BIAS)
+    for meth in ("match_hungarian", "manage_tracks", "increment_fslds", "remove_overlaps", "remove_anomalies", "md_iou"):
+        setattr(trkr, meth, types.MethodType(getattr(T, meth), trkr))
+    log = {}
+    phase = ["none"]
+    remove = trkr.filter.remove
+
+    def logged_remove(ids):
+        log[phase[0]] = sorted(int(i) for i in ids)
+        remove(ids)
+    trkr.filter.remove = logged_remove
+    for f, fr in enumerate(tc.sequence()):
+        log.clear()
+        trkr.timestamps = list(fr["timestamps"])
+        detections = torch.from_numpy(fr["detections"])
+        labels, scores = torch.from_numpy(fr["labels"]), torch.from_numpy(fr["scores"])
+        camera_idxs = torch.from_numpy(fr["cameras"])
+        # MC3D_crop_tracker.py:1100-1137, verbatim in substance
+        trkr.updated_this_frame = []
+        avg_time = sum(trkr.timestamps) / len(trkr.timestamps)
+        dts = trkr.filter.get_dt(avg_time)
+        pre_ids, pre_loc = trkr.filter.view(with_direction=True, dt=dts)
+        matchings = trkr.match_hungarian(pre_loc, detections)
+        if len(matchings) > 0:
+            assert len(trkr.filter.X) != 6, "see tests/track_cases.py:sequence (Q broadcast at 6 rows)"
+            filter_idxs = [match[0] for match in matchings]
+            match_times = [trkr.timestamps[camera_idxs[match[1]]] + trkr.ts_bias[camera_idxs[match[1]]] for match in matchings]
+            dts = trkr.filter.get_dt(match_times, idxs=filter_idxs)
+            trkr.filter.predict(dt=dts)
+        detection_times = [trkr.timestamps[cam_idx] + trkr.ts_bias[cam_idx] for cam_idx in camera_idxs]
+        trkr.manage_tracks(detections, matchings, pre_ids, labels, scores, camera_idxs, detection_times)
+        updated = list(set(trkr.updated_this_frame))
+        undetected = [i for i in pre_ids if i not in updated]
+        phase[0] = "fsld"
+        trkr.increment_fslds(pre_ids, undetected)
+        phase[0] = "over"
+        trkr.remove_overlaps()
+        phase[0] = "anom"
+        trkr.remove_anomalies(x_bounds=trkr.x_range)
+        phase[0] = "none"
+        key = "seq%d_" % f
+        out[key + "pre_ids"] = np.array(pre_ids, dtype=np.int64)
+        out[key + "match"] = np.asarray(matchings, dtype=np.int64).reshape(-1, 2)
+        fk = sorted(trkr.fsld)
+        out[key + "fsld"] = np.array([[k, trkr.fsld[k]] for k in fk], dtype=np.int64).reshape(-1, 2)
+        out[key + "next_obj_id"] = np.array(trkr.next_obj_id, dtype=np.int64)
+        ids, _ = trkr.filter.view()
+        out[key + "ids"] = np.array(ids, dtype=np.int64)
+        out[key + "X"], out[key + "P"], out[key + "T"] = (t2n(trkr.filter.X.clone()), t2n(trkr.filter.P.clone()),
+                                                            t2n(trkr.filter.T.clone()))     # predict works in place
+        ck = sorted(trkr.all_classes)
+        out[key + "classes"] = np.array([trkr.all_classes[k] for k in ck], dtype=np.float64).reshape(-1, 8)
+        out[key + "class_ids"] = np.array(ck, dtype=np.int64)
+        for ph in ("fsld", "over", "anom"):
+            out[key + "rm_" + ph] = np.array(log.get(ph, []), dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, "tracker_assoc.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -544,7 +645,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -561,7 +662,7 @@ def main():
         gen_csv_kat()
     if "csv_rows" in which:
         gen_csv_rows()
-    if "tracker_post" in which or "crop_refine" in which:
+    if "tracker_post" in which or "crop_refine" in which or "tracker_assoc" in which:
         tracker_import_shims()
     if "tracker_post" in which:
         gen_tracker_post()
@@ -569,6 +670,8 @@ def main():
         gen_crop_refine()
     if "kf" in which:
         gen_kf()
+    if "tracker_assoc" in which:
+        gen_tracker_assoc()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
