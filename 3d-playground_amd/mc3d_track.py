@@ -1,10 +1,12 @@
 """Drop-in for the association step of the reference's multi-camera tracker (``MC3D_crop_tracker.py``):
 ``match_hungarian`` (:637-731), ``manage_tracks`` (:385-461), ``increment_fslds`` (:463-479), ``remove_overlaps``
 (:482-518) and ``remove_anomalies`` (:520-557), plus ``associate``, the detection-frame block of ``track``
-(:1100-1137) in one call, and ``prune``, the pruning at the end of every frame (:1259-1261).
+(:1100-1137) in one call, ``prune``, the pruning at the end of every frame (:1259-1261), and ``estimate_ts_bias``
+(:237-315), which parse_detections calls between the transforms and the space NMS when ``est_ts`` is set (the
+reference's default).
 
 The functions take ``self`` exactly like the methods they replace and read the same attributes (``filter`` = a
-``Torch_KF``, ``timestamps``, ``ts_bias``, ``phi_match``, ``phi_over``, ``f_max``, ``max_size``, ``x_range``,
+``Torch_KF``, ``timestamps``, ``ts_bias``, ``ts_alpha``, ``phi_nms_space``, ``phi_match``, ``phi_over``, ``f_max``, ``max_size``, ``x_range``,
 ``class_dict``, ``fsld``, ``all_classes``, ``all_confs``, ``all_cameras``, ``next_obj_id``, ``updated_this_frame``),
 so a maintainer binds them into the reference class unchanged::
 
@@ -14,12 +16,14 @@ so a maintainer binds them into the reference class unchanged::
     MC_Crop_Tracker.increment_fslds = mc3d_track.increment_fslds
     MC_Crop_Tracker.remove_overlaps = mc3d_track.remove_overlaps
     MC_Crop_Tracker.remove_anomalies = mc3d_track.remove_anomalies
+    MC_Crop_Tracker.estimate_ts_bias = mc3d_track.estimate_ts_bias
 
 or inherits ``TrackManager``.  With the filter on the GPU (``util_track/kf.py``) and the detections from
 ``mc3d_post.parse_detections`` left on the device, the cost matrix, the assignment and the gate run in
 libretinanet_mi355x.so (``rn_track_cost``, ``rn_linear_sum_assignment``); the host sees one copy per frame of the
 matchings with the labels, scores and cameras of the detections (the bookkeeping dictionaries are host Python), and
-the ids of the tracks that pruning removes.
+the ids of the tracks that pruning removes; ``estimate_ts_bias`` (``rn_estimate_ts_bias``) costs one more small copy,
+the biases with the pair count.
 
 Reference behaviour kept on purpose:
   * ``associate`` calls ``increment_fslds(pre_ids, undetected)`` with the arguments swapped against the signature
@@ -231,6 +235,47 @@ def associate(self, detections, labels, scores, camera_idxs):
     return pre_ids, matchings
 
 
+def estimate_ts_bias(self, boxes, camera_idxs):
+    """MC3D_crop_tracker.py:237-315 on the device: ``boxes`` [d,6] states and ``camera_idxs`` [d] as parse_detections
+    holds them before the space NMS.  Reads ``filter``, ``timestamps``, ``ts_bias``, ``phi_nms_space``, ``ts_alpha``;
+    the footprints and md_iou are the kernel's own (``hg`` / ``md_iou`` of the host class are not called).  Uploads the
+    time stamps and biases (a few doubles), runs ``rn_estimate_ts_bias`` and replaces ``self.ts_bias`` by a list of
+    Python floats from one device -> host copy (biases and the (pairs, status) word together).  When the pair buffer
+    was too small the call is repeated once with a buffer sized from the count.  Returns None, as the reference."""
+    if len(camera_idxs) == 0:
+        return
+    _, objs = self.filter.view(with_direction=True)
+    if len(objs) == 0:
+        return
+    dev = _device(self, boxes, camera_idxs, objs)
+    if not isinstance(boxes, torch.Tensor):
+        boxes = torch.as_tensor(np.asarray(boxes, dtype=np.float32))
+    if not isinstance(camera_idxs, torch.Tensor):
+        camera_idxs = torch.as_tensor(np.asarray(camera_idxs, dtype=np.int64))
+    n_cam = len(self.ts_bias)
+    host = torch.tensor([[float(t) for t in self.timestamps], [float(b) for b in self.ts_bias]], dtype=torch.float64)
+    if host.shape[1] != n_cam:
+        raise RuntimeError("estimate_ts_bias: %d timestamps for %d biases" % (len(self.timestamps), n_cam))
+    state = host.to(dev)                                                  # row 0 time stamps, row 1 biases
+    boxes, camera_idxs, objs = boxes.to(dev), camera_idxs.to(dev), objs.to(dev)
+    mu_v = float(self.filter.mu_v)
+    max_pairs = None
+    for attempt in range(2):
+        info = _ops.estimate_ts_bias(boxes, camera_idxs, objs, state[0], state[1], self.phi_nms_space, self.ts_alpha, mu_v,
+                                     max_pairs=max_pairs)
+        flat = torch.cat((state[1], info.double())).cpu().tolist()        # the one device -> host copy
+        count, status = int(flat[n_cam]), int(flat[n_cam + 1])
+        if status != _ops.TS_OVERFLOW:
+            break
+        max_pairs = count                                                 # ts_bias was left untouched: run again
+    if status == _ops.TS_BAD_CAMERA:
+        raise IndexError("estimate_ts_bias: a camera index is outside the %d cameras of ts_bias" % n_cam)
+    if status != _ops.TS_OK:
+        raise RuntimeError("estimate_ts_bias: %d pairs did not fit the pair buffer" % count)
+    if count > 0:                                                         # no pair: the reference writes nothing
+        self.ts_bias = [float(b) for b in flat[:n_cam]]
+
+
 def prune(self):
     """remove_overlaps, then remove_anomalies(x_bounds=self.x_range) (MC3D_crop_tracker.py:1259-1261).
     -> (overlap removals, anomaly removals)."""
@@ -245,4 +290,5 @@ class TrackManager:
     remove_overlaps = remove_overlaps
     remove_anomalies = remove_anomalies
     associate = associate
+    estimate_ts_bias = estimate_ts_bias
     prune = prune

@@ -64,6 +64,9 @@ SIGNATURES = {
     "rn_track_cost": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "rn_lsap_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rn_linear_sum_assignment": (c_i32, [c_vp, c_i64, c_i64, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rn_ts_bias_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rn_estimate_ts_bias": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f64, c_f64, c_f32,
+                                    c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rn_frame_ingest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp]),
 }
 

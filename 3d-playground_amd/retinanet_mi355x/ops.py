@@ -657,6 +657,57 @@ def linear_sum_assignment(cost):
     return rows, row_match[rows].long()
 
 
+# ------------------------------------------------------------------------------------------------ time stamp bias
+TS_MAX_CAMS = 1024                 # RN_TS_MAX_CAMS
+TS_OK, TS_OVERFLOW, TS_BAD_CAMERA = 0, 1, 2
+
+
+def estimate_ts_bias(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, mu_v, count=None, max_pairs=None,
+                     details=False):
+    """MC_Crop_Tracker.estimate_ts_bias (MC3D_crop_tracker.py:237-315) on the device, see include/retinanet_mi355x.h.
+    boxes [d, >=6] fp32 states and camera_idxs [d] as the parser leaves them before the space NMS; objs [n, >=7] =
+    Torch_KF.view(with_direction=True); timestamps [n_cam] fp64; ts_bias [n_cam] fp64 contiguous, UPDATED IN PLACE;
+    count = the parser's device int32 count (rows valid) or None.  max_pairs sizes the pair buffer (default max(256, d)).
+    -> info int32 [2] = (number of pairs, status) on the device, no synchronisation; status TS_OVERFLOW (more pairs than
+    max_pairs) and TS_BAD_CAMERA leave ts_bias untouched.  details=True -> (info, pairs [max_pairs,2] int32 (i, j),
+    time_error [max_pairs,2] fp32 of each pair's two entries)."""
+    lib = _hip.load()
+    _hip.need_gpu(boxes, camera_idxs, objs, timestamps, ts_bias, count)
+    if boxes.dim() != 2 or boxes.shape[1] < 6 or camera_idxs.shape[0] != boxes.shape[0]:
+        raise RuntimeError("estimate_ts_bias: boxes are [d, >= 6] with one camera index each, got %s and %s"
+                           % (tuple(boxes.shape), tuple(camera_idxs.shape)))
+    d = boxes.shape[0]
+    n = 0 if objs is None else objs.shape[0]
+    if n and (objs.dim() != 2 or objs.shape[1] < 7):
+        raise RuntimeError("estimate_ts_bias: the filter view is [n, >= 7] (direction at 5, speed at 6), got %s" % (tuple(objs.shape),))
+    if d > PARSE_MAX:
+        raise RuntimeError("estimate_ts_bias takes at most %d detections, got %d" % (PARSE_MAX, d))
+    n_cam = ts_bias.shape[0]
+    if ts_bias.dtype != torch.float64 or not ts_bias.is_contiguous() or ts_bias.dim() != 1:
+        raise RuntimeError("estimate_ts_bias updates ts_bias in place: it has to be a contiguous 1-D float64 tensor")
+    if timestamps.shape[0] != n_cam or n_cam == 0 or n_cam > TS_MAX_CAMS:
+        raise RuntimeError("estimate_ts_bias: %d timestamps for %d biases (1 .. %d cameras)" % (timestamps.shape[0], n_cam, TS_MAX_CAMS))
+    dev = boxes.device
+    mp = max(256, d) if max_pairs is None else int(max_pairs)
+    if mp <= 0:
+        raise RuntimeError("estimate_ts_bias: max_pairs has to be positive")
+    info = torch.zeros(2, dtype=torch.int32, device=dev)
+    pairs = torch.full((mp, 2), -1, dtype=torch.int32, device=dev) if details else None
+    te = torch.zeros((mp, 2), dtype=torch.float32, device=dev) if details else None
+    if d and n:
+        boxes, objs = _hip.f32c(boxes), _hip.f32c(objs)
+        cams = camera_idxs.long().contiguous()
+        ts = timestamps.double().contiguous()
+        cnt = None if count is None else count.to(torch.int32).contiguous()
+        ws = torch.empty(lib.rn_ts_bias_workspace_bytes(d, mp), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _hip.check(lib.rn_estimate_ts_bias(boxes.data_ptr(), boxes.shape[1], cams.data_ptr(), d, _hip.ptr(cnt),
+                                               objs.data_ptr(), objs.shape[1], n, ts.data_ptr(), ts_bias.data_ptr(), n_cam,
+                                               float(phi), float(alpha), float(mu_v), ws.data_ptr(), mp, _hip.ptr(pairs),
+                                               _hip.ptr(te), info.data_ptr(), _hip.stream()), "rn_estimate_ts_bias")
+    return (info, pairs, te) if details else info
+
+
 # ------------------------------------------------------------------------------------------------ frame ingest
 IMAGENET_MEAN = (0.485, 0.456, 0.406)     # util_track/mp_loader.py:241
 IMAGENET_STD = (0.229, 0.224, 0.225)

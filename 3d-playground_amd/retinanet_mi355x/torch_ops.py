@@ -17,6 +17,7 @@ Operator                                         reference code it stands for
   clip_boxes_(boxes, H, W)                       ClipBoxes.forward (in place)          R/utils.py:134-144
   nms(boxes, scores, thr)                        torchvision.ops.nms as the path uses it   D/model.py:383
   linear_sum_assignment(cost)                    scipy.optimize.linear_sum_assignment  MC3D_crop_tracker.py:706
+  estimate_ts_bias(boxes, cams, objs, ts, bias..) MC_Crop_Tracker.estimate_ts_bias      MC3D_crop_tracker.py:237-315
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
   frame_ingest(frames_u8, swap_rb, nhwc4)        to_tensor + normalize of the loaders  util_track/mp_loader.py:239-243
 
@@ -147,6 +148,17 @@ def _(cost):
     return cost.new_empty((n,), dtype=torch.int64), cost.new_empty((n,), dtype=torch.int64)
 
 
+@_lib.custom_op(NS + "::estimate_ts_bias", mutates_args=("ts_bias",), device_types="cuda")
+def estimate_ts_bias(boxes: torch.Tensor, camera_idxs: torch.Tensor, objs: torch.Tensor, timestamps: torch.Tensor,
+                     ts_bias: torch.Tensor, phi: float, alpha: float, mu_v: float, max_pairs: int) -> torch.Tensor:
+    return ops.estimate_ts_bias(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, mu_v, max_pairs=max_pairs)
+
+
+@estimate_ts_bias.register_fake
+def _(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, mu_v, max_pairs):
+    return boxes.new_empty((2,), dtype=torch.int32)
+
+
 # ---- homography
 @_lib.custom_op(NS + "::state_to_space", mutates_args=(), device_types="cuda")
 def state_to_space(state: torch.Tensor) -> torch.Tensor:
@@ -192,4 +204,4 @@ def _(frames_u8, swap_rb, nhwc4):
 
 
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "linear_sum_assignment", "state_to_space", "state_to_im", "im_to_state", "frame_ingest")
+             "linear_sum_assignment", "estimate_ts_bias", "state_to_space", "state_to_im", "im_to_state", "frame_ingest")

@@ -217,6 +217,33 @@ int64_t rn_lsap_workspace_bytes(int64_t nr, int64_t nc);
 int rn_linear_sum_assignment(const double *cost, int64_t nr, int64_t nc, double max_cost, void *workspace,
                              int32_t *row_match, int32_t *n_matched, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------- tracker: time stamp bias ----------------
+ * MC_Crop_Tracker.estimate_ts_bias (MC3D_crop_tracker.py:237-315), the step between the transforms and the space NMS
+ * of parse_detections when est_ts is set (:373-374, the reference's default), without leaving the device.
+ * rn_estimate_ts_bias: boxes [d, box_stride] fp32 states (x,y,l,w,h,direction) and camera_idxs [d] i64 as the parser
+ *   leaves them before the space NMS; d_count (may be NULL) = a device word holding the rows valid (the parser's
+ *   out_count), clamped to d, so the call needs no host copy of it.  objs [n, obj_stride] = Torch_KF.view with
+ *   with_direction (direction at column 5, speed at column 6).  timestamps / ts_bias [n_cam] fp64 on the device; ts_bias
+ *   is updated in place.  Steps: mean speed per direction (:258-265, an empty direction takes +-mu_v); fp32 road-plane
+ *   footprints and md_iou in fp64 (:1030-1049) for every i < j; the pairs from different cameras with iou > phi in the
+ *   order i ascending, j ascending (:284-289); per pair the two entries (cam_i, cam_j, x_j - x_i) and (cam_j, cam_i,
+ *   x_i - x_j), both with the direction of detection i; time_error = dx / vel - fp32(ts[cam2] - ts[cam1]) in fp32
+ *   (:292-303); then serially, in list order, for cam1 != 0 (:311-315):
+ *     ts_bias[cam1] = fp32(fp32((1 - alpha) * ts_bias[cam1]) + fp32(alpha) * (-time_error + fp32(ts_bias[cam2])))
+ *   which is what torch's promotion makes of the reference's mix of Python floats and a 0-d fp32 tensor.
+ *   info[0] = number of pairs, info[1] = status: 0 ok; 1 more pairs than max_pairs; 2 a camera index outside
+ *   [0, n_cam) -- with 1 and 2 ts_bias is left untouched.  pairs_out [max_pairs,2] i32 (i, j) and te_out [max_pairs,2]
+ *   fp32 (the time_error of the pair's two entries) may be NULL.  d == 0 or n == 0: info = (0, 0), nothing else (the
+ *   reference's early returns).  No synchronisation.  d <= RN_PARSE_MAX, n_cam <= RN_TS_MAX_CAMS.
+ *   workspace: rn_ts_bias_workspace_bytes(d, max_pairs) bytes. */
+#define RN_TS_MAX_CAMS 1024
+int64_t rn_ts_bias_workspace_bytes(int64_t d, int64_t max_pairs);
+int rn_estimate_ts_bias(const float *boxes, int64_t box_stride, const int64_t *camera_idxs, int64_t d,
+                        const int32_t *d_count, const float *objs, int64_t obj_stride, int64_t n,
+                        const double *timestamps, double *ts_bias, int n_cam, double phi, double alpha, float mu_v,
+                        void *workspace, int64_t max_pairs, int32_t *pairs_out, float *te_out, int32_t *info,
+                        void *stream);
+
 /* ---------------------------------------------------------------- frame ingest ----------------------------
  * Replaces F.to_tensor + F.normalize of the reference's loaders (util_track/mp_loader.py:239-243,
  * perform_3D_detection_on_video_sequences.py:51-58) on device: frames uint8 [B,H,W,3] (as the decoder / cv2.resize

@@ -528,6 +528,78 @@ def gen_kf():
     np.savez_compressed(os.path.join(OUT, "kf.npz"), **out)
 
 
+def _run_sequence(T, kfmod, tc, hg, frames, ts_bias, out, before_frame=None, attrs=None, methods=()):
+    """Detection frames through match_hungarian / manage_tracks / increment_fslds / remove_overlaps / remove_anomalies in
+    track()'s order (MC3D_crop_tracker.py:1100-1137, 1259-1261, verbatim in substance) on a stand-in tracker with the
+    reference's own Torch_KF; the state after every frame goes to out["seq<f>_*"].  ``before_frame(trkr, key, detections,
+    labels, scores, camera_idxs)`` -> the four tensors to associate (the parse stage of the frame)."""
+    trkr = types.SimpleNamespace(**{k: v for k, v in tc.PARAMS.items()})
+    trkr.hg = hg
+    trkr.class_dict = tc.class_dict()
+    trkr.filter = kfmod.Torch_KF(torch.device("cpu"), INIT=tc.kf_init())
+    trkr.fsld, trkr.all_classes, trkr.all_confs, trkr.all_cameras = {}, {}, {}, {}
+    trkr.next_obj_id, trkr.updated_this_frame = 0, []
+    trkr.time_metrics = {"add and remove": 0.0}
+    trkr.ts_bias = list(ts_bias)
+    for k, v in (attrs or {}).items():
+        setattr(trkr, k, v)
+    for meth in ("match_hungarian", "manage_tracks", "increment_fslds", "remove_overlaps", "remove_anomalies", "md_iou") + tuple(methods):
+        setattr(trkr, meth, types.MethodType(getattr(T, meth), trkr))
+    log = {}
+    phase = ["none"]
+    remove = trkr.filter.remove
+
+    def logged_remove(ids):
+        log[phase[0]] = sorted(int(i) for i in ids)
+        remove(ids)
+    trkr.filter.remove = logged_remove
+    for f, fr in enumerate(frames):
+        log.clear()
+        key = "seq%d_" % f
+        trkr.timestamps = list(fr["timestamps"])
+        detections = torch.from_numpy(fr["detections"])
+        labels, scores = torch.from_numpy(fr["labels"]), torch.from_numpy(fr["scores"])
+        camera_idxs = torch.from_numpy(fr["cameras"])
+        if before_frame is not None:
+            detections, labels, scores, camera_idxs = before_frame(trkr, key, detections, labels, scores, camera_idxs)
+        trkr.updated_this_frame = []
+        avg_time = sum(trkr.timestamps) / len(trkr.timestamps)
+        dts = trkr.filter.get_dt(avg_time)
+        pre_ids, pre_loc = trkr.filter.view(with_direction=True, dt=dts)
+        matchings = trkr.match_hungarian(pre_loc, detections)
+        if len(matchings) > 0:
+            assert len(trkr.filter.X) != 6, "see tests/track_cases.py:sequence (Q broadcast at 6 rows)"
+            filter_idxs = [match[0] for match in matchings]
+            match_times = [trkr.timestamps[camera_idxs[match[1]]] + trkr.ts_bias[camera_idxs[match[1]]] for match in matchings]
+            dts = trkr.filter.get_dt(match_times, idxs=filter_idxs)
+            trkr.filter.predict(dt=dts)
+        detection_times = [trkr.timestamps[cam_idx] + trkr.ts_bias[cam_idx] for cam_idx in camera_idxs]
+        trkr.manage_tracks(detections, matchings, pre_ids, labels, scores, camera_idxs, detection_times)
+        updated = list(set(trkr.updated_this_frame))
+        undetected = [i for i in pre_ids if i not in updated]
+        phase[0] = "fsld"
+        trkr.increment_fslds(pre_ids, undetected)
+        phase[0] = "over"
+        trkr.remove_overlaps()
+        phase[0] = "anom"
+        trkr.remove_anomalies(x_bounds=trkr.x_range)
+        phase[0] = "none"
+        out[key + "pre_ids"] = np.array(pre_ids, dtype=np.int64)
+        out[key + "match"] = np.asarray(matchings, dtype=np.int64).reshape(-1, 2)
+        fk = sorted(trkr.fsld)
+        out[key + "fsld"] = np.array([[k, trkr.fsld[k]] for k in fk], dtype=np.int64).reshape(-1, 2)
+        out[key + "next_obj_id"] = np.array(trkr.next_obj_id, dtype=np.int64)
+        ids, _ = trkr.filter.view()
+        out[key + "ids"] = np.array(ids, dtype=np.int64)
+        out[key + "X"], out[key + "P"], out[key + "T"] = (t2n(trkr.filter.X.clone()), t2n(trkr.filter.P.clone()),
+                                                            t2n(trkr.filter.T.clone()))     # predict works in place
+        ck = sorted(trkr.all_classes)
+        out[key + "classes"] = np.array([trkr.all_classes[k] for k in ck], dtype=np.float64).reshape(-1, 8)
+        out[key + "class_ids"] = np.array(ck, dtype=np.int64)
+        for ph in ("fsld", "over", "anom"):
+            out[key + "rm_" + ph] = np.array(log.get(ph, []), dtype=np.int64)
+
+
 def gen_tracker_assoc():
     """scipy.optimize.linear_sum_assignment on the matrices of tests/track_cases.py (indices only: both sides rebuild the
     matrices from seeds); MC_Crop_Tracker.match_hungarian run unbound on a stand-in ``self`` (hg, md_iou, phi_match);
@@ -563,70 +635,141 @@ def gen_tracker_assoc():
         m = T.match_hungarian(me, p.clone(), d.clone())
         out["hung_%s_is_list" % name] = np.array(isinstance(m, list))
         out["hung_%s_match" % name] = np.asarray(m, dtype=np.int64).reshape(-1, 2)
-    # the 8-frame sequence
-    trkr = types.SimpleNamespace(**{k: v for k, v in tc.PARAMS.items()})
-    trkr.hg = me.hg
-    trkr.class_dict = tc.class_dict()
-    trkr.filter = kfmod.Torch_KF(torch.device("cpu"), INIT=tc.kf_init())
-    trkr.fsld, trkr.all_classes, trkr.all_confs, trkr.all_cameras = {}, {}, {}, {}
-    trkr.next_obj_id, trkr.updated_this_frame = 0, []
-    trkr.time_metrics = {"add and remove": 0.0}
-    trkr.ts_bias = list(tc.TS_BIAS)
-    for meth in ("match_hungarian", "manage_tracks", "increment_fslds", "remove_overlaps", "remove_anomalies", "md_iou"):
-        setattr(trkr, meth, types.MethodType(getattr(T, meth), trkr))
-    log = {}
-    phase = ["none"]
-    remove = trkr.filter.remove
-
-    def logged_remove(ids):
-        log[phase[0]] = sorted(int(i) for i in ids)
-        remove(ids)
-    trkr.filter.remove = logged_remove
-    for f, fr in enumerate(tc.sequence()):
-        log.clear()
-        trkr.timestamps = list(fr["timestamps"])
-        detections = torch.from_numpy(fr["detections"])
-        labels, scores = torch.from_numpy(fr["labels"]), torch.from_numpy(fr["scores"])
-        camera_idxs = torch.from_numpy(fr["cameras"])
-        # MC3D_crop_tracker.py:1100-1137, verbatim in substance
-        trkr.updated_this_frame = []
-        avg_time = sum(trkr.timestamps) / len(trkr.timestamps)
-        dts = trkr.filter.get_dt(avg_time)
-        pre_ids, pre_loc = trkr.filter.view(with_direction=True, dt=dts)
-        matchings = trkr.match_hungarian(pre_loc, detections)
-        if len(matchings) > 0:
-            assert len(trkr.filter.X) != 6, "see tests/track_cases.py:sequence (Q broadcast at 6 rows)"
-            filter_idxs = [match[0] for match in matchings]
-            match_times = [trkr.timestamps[camera_idxs[match[1]]] + trkr.ts_bias[camera_idxs[match[1]]] for match in matchings]
-            dts = trkr.filter.get_dt(match_times, idxs=filter_idxs)
-            trkr.filter.predict(dt=dts)
-        detection_times = [trkr.timestamps[cam_idx] + trkr.ts_bias[cam_idx] for cam_idx in camera_idxs]
-        trkr.manage_tracks(detections, matchings, pre_ids, labels, scores, camera_idxs, detection_times)
-        updated = list(set(trkr.updated_this_frame))
-        undetected = [i for i in pre_ids if i not in updated]
-        phase[0] = "fsld"
-        trkr.increment_fslds(pre_ids, undetected)
-        phase[0] = "over"
-        trkr.remove_overlaps()
-        phase[0] = "anom"
-        trkr.remove_anomalies(x_bounds=trkr.x_range)
-        phase[0] = "none"
-        key = "seq%d_" % f
-        out[key + "pre_ids"] = np.array(pre_ids, dtype=np.int64)
-        out[key + "match"] = np.asarray(matchings, dtype=np.int64).reshape(-1, 2)
-        fk = sorted(trkr.fsld)
-        out[key + "fsld"] = np.array([[k, trkr.fsld[k]] for k in fk], dtype=np.int64).reshape(-1, 2)
-        out[key + "next_obj_id"] = np.array(trkr.next_obj_id, dtype=np.int64)
-        ids, _ = trkr.filter.view()
-        out[key + "ids"] = np.array(ids, dtype=np.int64)
-        out[key + "X"], out[key + "P"], out[key + "T"] = (t2n(trkr.filter.X.clone()), t2n(trkr.filter.P.clone()),
-                                                            t2n(trkr.filter.T.clone()))     # predict works in place
-        ck = sorted(trkr.all_classes)
-        out[key + "classes"] = np.array([trkr.all_classes[k] for k in ck], dtype=np.float64).reshape(-1, 8)
-        out[key + "class_ids"] = np.array(ck, dtype=np.int64)
-        for ph in ("fsld", "over", "anom"):
-            out[key + "rm_" + ph] = np.array(log.get(ph, []), dtype=np.int64)
+    _run_sequence(T, kfmod, tc, me.hg, tc.sequence(), tc.TS_BIAS, out)
     np.savez_compressed(os.path.join(OUT, "tracker_assoc.npz"), **out)
+
+
+def _traced_ts_bias(T, me, boxes, cams):
+    """The reference's estimate_ts_bias, unbound on ``me``, under a line tracer that reads its locals: the method keeps
+    the entry list and time_error to itself.  It depends on the reference's local names x_offsets, i, j, time_error,
+    EB_vel and WB_vel (MC3D_crop_tracker.py:260-303): if they are renamed there, rename them here.  -> (entries [e,4] i64 (cam1, cam2, i, j), time_error [e] f32, vel [2] f32)."""
+    code = T.estimate_ts_bias.__code__
+    got = {"ij": [], "te": np.zeros(0, np.float32), "vel": np.zeros(2, np.float32), "cams": []}
+
+    def local(frame, event, arg):
+        loc = frame.f_locals
+        xo = loc.get("x_offsets")
+        if xo is not None:
+            while len(got["ij"]) < len(xo):                      # an append ran since the last line: i, j are still its own
+                got["ij"].append((loc["i"], loc["j"]))
+            if event == "return":
+                got["cams"] = [(int(e[0]), int(e[1])) for e in xo]
+                if "time_error" in loc:
+                    got["te"] = t2n(loc["time_error"].float().reshape(-1))
+                got["vel"] = np.array([float(loc["EB_vel"]), float(loc["WB_vel"])], dtype=np.float32)
+        return local
+
+    def tracer(frame, event, arg):
+        return local if frame.f_code is code else None
+    sys.settrace(tracer)
+    try:
+        T.estimate_ts_bias(me, boxes, cams)
+    finally:
+        sys.settrace(None)
+    ent = np.array([(c1, c2, i, j) for (c1, c2), (i, j) in zip(got["cams"], got["ij"])], dtype=np.int64).reshape(-1, 4)
+    assert len(ent) == len(got["te"]) and len(got["cams"]) == len(got["ij"])
+    return ent, got["te"], got["vel"]
+
+
+def _ref_filter(kfmod, tc, objs):
+    """The reference's Torch_KF holding the tracks objs [n,7] (x y l w h dir v)."""
+    kf = kfmod.Torch_KF(torch.device("cpu"), INIT=tc.kf_init())
+    if len(objs):
+        o = torch.from_numpy(np.ascontiguousarray(objs))
+        kf.add(o[:, :5].clone(), list(range(len(o))), o[:, 5].clone(), torch.zeros(len(o), dtype=torch.float64))
+        kf.X[:, 5] = o[:, 6]
+        assert np.array_equal(t2n(kf.view(with_direction=True)[1]), objs)
+    return kf
+
+
+def gen_ts_bias():
+    """MC_Crop_Tracker.estimate_ts_bias (MC3D_crop_tracker.py:237-315) run unbound on a stand-in ``self`` (the reference's
+    Torch_KF, a bare Homography_Wrapper, md_iou, timestamps, ts_bias, phi_nms_space, ts_alpha) on the scenes of
+    tests/ts_bias_cases.py; the reference's parse_detections with est_ts=True and that method bound; and 8 frames of
+    estimate_ts_bias -> space_nms -> association -> pruning in track()'s order on the reference's own filter.  Every
+    case is checked here for the behaviour it is named after.  Outputs only."""
+    import track_cases as tc
+    import ts_bias_cases as tb
+    trk, hgmod = import_reference_tracker()
+    T = trk.MC_Crop_Tracker
+    kfmod = ref_module_from_file("_reference_util_track_kf", "util_track/kf.py")
+    bare = hgmod.Homography_Wrapper(hg1=hgmod.Homography(), hg2=hgmod.Homography())
+    out = {}
+
+    def stand_in(objs, timestamps, ts_bias, phi, hg=bare):
+        me = types.SimpleNamespace(filter=_ref_filter(kfmod, tc, objs), hg=hg, timestamps=list(timestamps),
+                                   ts_bias=list(ts_bias), phi_nms_space=phi, ts_alpha=tb.ALPHA)
+        me.md_iou = types.MethodType(T.md_iou, me)
+        return me
+    for name, c in tb.cases().items():
+        me = stand_in(c["objs"], c["timestamps"], c["ts_bias"], c["phi"])
+        ent, te, vel = _traced_ts_bias(T, me, torch.from_numpy(c["boxes"]).clone(), torch.from_numpy(c["cams"]).clone())
+        out[name + "_entries"], out[name + "_time_error"], out[name + "_vel"] = ent, te, vel
+        out[name + "_ts_bias"] = np.array(me.ts_bias, dtype=np.float64)
+        start = list(c["ts_bias"])
+        assert all(float(np.float32(b)) == b for b, b0 in zip(me.ts_bias, start) if b != b0), name   # written biases are fp32 values
+        if name == "overlap3":
+            written, dependent = set(), False
+            for c1, c2, _, _ in ent:
+                dependent |= c1 != 0 and c2 in written
+                written |= {c1} - {0}
+            assert len(ent) >= 12 and dependent and set(ent[:, 0]) == {0, 1, 2} and me.ts_bias[0] == start[0]
+            dirs = c["boxes"][ent[:, 2], 5]
+            assert (dirs == 1).any() and (dirs == -1).any()
+        elif name == "cam0_only":
+            assert len(ent) >= 4 and all(0 in (c1, c2) for c1, c2, _, _ in ent) and me.ts_bias[0] == 0.0
+            assert (ent[0::2, 0] == 0).any() and (ent[1::2, 0] == 0).any() and me.ts_bias[1] != start[1]
+        elif name == "one_direction":
+            assert vel[1] == -tb.MU_V and (c["boxes"][ent[:, 2], 5] == -1).any()
+        elif name in ("same_camera", "no_tracks", "no_detections", "threshold_equal", "threshold_ulps_above"):
+            assert len(ent) == 0 and me.ts_bias == start
+        elif name in ("threshold", "threshold_ulps_below"):
+            assert [tuple(e) for e in ent[:, 2:]] == [(0, 1), (0, 1)]
+    c = tb.cases()["threshold"]                            # the reference's own md_iou puts the pairs where they are meant to be
+    fp = torch.from_numpy(tb.footprints(c["boxes"])).double()
+    iou = T.md_iou(stand_in(c["objs"], c["timestamps"], c["ts_bias"], c["phi"]), fp[[0, 2]][None], fp[[1, 3]][None]).reshape(-1)
+    assert float(iou[0]) > tb.PHI > float(iou[1]) and float(iou[0]) - float(iou[1]) < 1e-5
+    assert float(iou[0]) == tb.cases()["threshold_equal"]["phi"]
+    # parse_detections with est_ts = True and the reference's own estimate_ts_bias bound
+    scores, labels, boxes, cams, names, (Ps, Hs), (Ps2, Hs2) = gc.tracker_post_inputs()
+
+    def make_hg(P, H):
+        hg = hgmod.Homography()
+        hg.correspondence = {n: {"P": P[i], "H": H[i], "H_inv": np.linalg.inv(H[i])} for i, n in enumerate(names)}
+        hg.default_correspondence = names[0]
+        return hg
+    objs, ts, bias = tb.parse_scene()
+    me = stand_in(objs, ts, bias, tb.PHI, hg=hgmod.Homography_Wrapper(hg1=make_hg(Ps, Hs), hg2=make_hg(Ps2, Hs2)))
+    me.sigma_d, me.phi_nms_im, me.cameras, me.est_ts = 0.1, 0.3, list(names), True
+    me.im_nms, me.space_nms = types.MethodType(T.im_nms, me), types.MethodType(T.space_nms, me)
+    seen = {}
+
+    def est(boxes_, cams_):
+        seen["ent"], seen["te"], seen["vel"] = _traced_ts_bias(T, me, boxes_, cams_)
+    me.estimate_ts_bias = est
+    st, lb, sc, cm = T.parse_detections(me, scores.clone(), labels.clone(), boxes.clone(), cams.clone(), refine_height=True)
+    k = "parse_est_ts_"
+    out[k + "state"], out[k + "labels"], out[k + "scores"], out[k + "cams"] = t2n(st), t2n(lb), t2n(sc), t2n(cm)
+    out[k + "entries"], out[k + "time_error"], out[k + "vel"] = seen["ent"], seen["te"], seen["vel"]
+    out[k + "ts_bias"] = np.array(me.ts_bias, dtype=np.float64)
+    assert len(seen["ent"]) >= 20 and me.ts_bias != list(bias)
+    # the 8-frame sequence: MC3D_crop_tracker.py:373-381 in front of every frame of _run_sequence
+    moved = [0]
+
+    def parse_stage(trkr, key, detections, labels, scores, camera_idxs):
+        before = list(trkr.ts_bias)
+        ent, te, vel = _traced_ts_bias(T, trkr, detections.clone(), camera_idxs)
+        moved[0] += trkr.ts_bias != before
+        idxs = trkr.space_nms(detections, scores, threshold=trkr.phi_nms_space)
+        out[key + "entries"], out[key + "time_error"], out[key + "vel"] = ent, te, vel
+        out[key + "ts_bias"] = np.array(trkr.ts_bias, dtype=np.float64)
+        out[key + "nms_idx"] = t2n(idxs).astype(np.int64)
+        return detections[idxs], labels[idxs], scores[idxs], camera_idxs[idxs]
+    _run_sequence(T, kfmod, tc, bare, tb.sequence(), tb.SEQ_TS_BIAS, out, before_frame=parse_stage,
+                  attrs=dict(phi_nms_space=tb.PHI, ts_alpha=tb.ALPHA), methods=("space_nms",))
+    moved = moved[0]
+    assert moved >= 6, moved                                # the biases move from frame to frame
+    np.savez_compressed(os.path.join(OUT, "ts_bias.npz"), **out)
 
 
 def main():
@@ -645,7 +788,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -662,7 +805,7 @@ def main():
         gen_csv_kat()
     if "csv_rows" in which:
         gen_csv_rows()
-    if "tracker_post" in which or "crop_refine" in which or "tracker_assoc" in which:
+    if "tracker_post" in which or "crop_refine" in which or "tracker_assoc" in which or "ts_bias" in which:
         tracker_import_shims()
     if "tracker_post" in which:
         gen_tracker_post()
@@ -672,6 +815,8 @@ def main():
         gen_kf()
     if "tracker_assoc" in which:
         gen_tracker_assoc()
+    if "ts_bias" in which:
+        gen_ts_bias()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
