@@ -708,6 +708,72 @@ def estimate_ts_bias(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, 
     return (info, pairs, te) if details else info
 
 
+# ------------------------------------------------------------------------------------------------ fitting the filter
+FIT_MAX = 1 << 24                  # RN_FIT_MAX
+MOMENTS_MAX_K, MOMENTS_MAX_G = 8, 16
+
+
+def fit_nearest(gt, det, offsets):
+    """The nearest-box search of fit_filter_3D.py:356-375 on the device, see include/retinanet_mi355x.h.  gt [B, >=6]
+    fp32 ground-truth states, one per frame; det [D, >=6] fp32 detection states; offsets [B+1] the CSR bounds of each
+    frame's detections.  -> (rows int32 [B]: the chosen row of det or -1, resid fp32 [B,5]: det[row,:5] - gt[:, :5] of
+    the matched frames compacted in frame order (the caller slices with info[0]; the rest is zero), info int32 [3] =
+    (matched, empty frames, frames without a comparable distance)).  Device tensors, no synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(gt, det, offsets)
+    if gt.dim() != 2 or gt.shape[1] < 6 or det.dim() != 2 or det.shape[1] < 6:
+        raise RuntimeError("fit_nearest: states are [n, >= 6], got %s and %s" % (tuple(gt.shape), tuple(det.shape)))
+    B, D = gt.shape[0], det.shape[0]
+    if offsets.dim() != 1 or offsets.shape[0] != B + 1:
+        raise RuntimeError("fit_nearest: %d offsets for %d frames (B + 1 expected)" % (offsets.numel(), B))
+    if B > FIT_MAX or D > FIT_MAX:
+        raise RuntimeError("fit_nearest takes at most %d frames and detections, got %d and %d" % (FIT_MAX, B, D))
+    dev = gt.device
+    gt, det = _state6(gt), _state6(det)
+    off = offsets.to(torch.int32).contiguous()
+    rows = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    resid = torch.zeros((B, 5), dtype=torch.float32, device=dev)
+    info = torch.zeros(3, dtype=torch.int32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            _hip.check(lib.rn_fit_nearest(gt.data_ptr(), det.data_ptr() if D else None, off.data_ptr(), B, D, rows.data_ptr(),
+                                          resid.data_ptr(), info.data_ptr(), _hip.stream()), "rn_fit_nearest")
+    return rows, resid, info
+
+
+def residual_moments(E, group=None, groups=None):
+    """Mean and population covariance of residual rows (fit_filter_3D.py:292-299 and its three repeats) on the device,
+    see include/retinanet_mi355x.h.  E [N,k] fp32, k <= 8.  Without ``group``: -> (mean [k], cov [k,k], count int32 [1]).
+    With ``group`` [N] integer ids in [0, groups), groups <= 16: -> (mean [G,k], cov [G,k,k], count int32 [G]); a group
+    without rows has count 0 and zeros.  fp64 sums in a fixed order, rounded once: two runs give the same bits."""
+    lib = _hip.load()
+    _hip.need_gpu(E, group)
+    if E.dim() != 2 or not 1 <= E.shape[1] <= MOMENTS_MAX_K:
+        raise RuntimeError("residual_moments: E is [N, k] with 1 <= k <= %d, got %s" % (MOMENTS_MAX_K, tuple(E.shape)))
+    N, k = E.shape
+    if group is None:
+        if groups not in (None, 1):
+            raise RuntimeError("residual_moments: groups = %r without group ids" % (groups,))
+        G = 1
+    else:
+        G = int(groups) if groups is not None else 0
+        if not 1 <= G <= MOMENTS_MAX_G or group.dim() != 1 or group.shape[0] != N:
+            raise RuntimeError("residual_moments: one group id per row and 1 <= groups <= %d, got %s ids for %d rows, groups = %r"
+                               % (MOMENTS_MAX_G, tuple(group.shape), N, groups))
+        group = group.to(torch.int32).contiguous()
+    dev = E.device
+    E = _hip.f32c(E)
+    mean = torch.empty((G, k), dtype=torch.float32, device=dev)
+    cov = torch.empty((G, k, k), dtype=torch.float32, device=dev)
+    count = torch.empty(G, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_residual_moments(E.data_ptr() if N else None, N, k, _hip.ptr(group), G, mean.data_ptr(),
+                                           cov.data_ptr(), count.data_ptr(), _hip.stream()), "rn_residual_moments")
+    if group is None:
+        return mean[0], cov[0], count
+    return mean, cov, count
+
+
 # ------------------------------------------------------------------------------------------------ frame ingest
 IMAGENET_MEAN = (0.485, 0.456, 0.406)     # util_track/mp_loader.py:241
 IMAGENET_STD = (0.229, 0.224, 0.225)

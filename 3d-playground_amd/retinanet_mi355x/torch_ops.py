@@ -18,6 +18,8 @@ Operator                                         reference code it stands for
   nms(boxes, scores, thr)                        torchvision.ops.nms as the path uses it   D/model.py:383
   linear_sum_assignment(cost)                    scipy.optimize.linear_sum_assignment  MC3D_crop_tracker.py:706
   estimate_ts_bias(boxes, cams, objs, ts, bias..) MC_Crop_Tracker.estimate_ts_bias      MC3D_crop_tracker.py:237-315
+  fit_nearest(gt, det, offsets)                  nearest-box search of the R fit       fit_filter_3D.py:356-375
+  residual_moments(E, group, groups)             mean / covariance loops               fit_filter_3D.py:292-299, 377-384, 426-434
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
   frame_ingest(frames_u8, swap_rb, nhwc4)        to_tensor + normalize of the loaders  util_track/mp_loader.py:239-243
 
@@ -159,6 +161,34 @@ def _(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, mu_v, max_pairs
     return boxes.new_empty((2,), dtype=torch.int32)
 
 
+# ---- fitting the filter
+@_lib.custom_op(NS + "::fit_nearest", mutates_args=(), device_types="cuda")
+def fit_nearest(gt: torch.Tensor, det: torch.Tensor, offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.fit_nearest(gt, det, offsets)
+
+
+@fit_nearest.register_fake
+def _(gt, det, offsets):
+    B = gt.shape[0]
+    return gt.new_empty((B,), dtype=torch.int32), gt.new_empty((B, 5), dtype=torch.float32), gt.new_empty((3,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::residual_moments", mutates_args=(), device_types="cuda")
+def residual_moments(E: torch.Tensor, group: Optional[torch.Tensor], groups: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Always the grouped layout (mean [G,k], cov [G,k,k], count [G]); group None = one group."""
+    if group is None:
+        mean, cov, count = ops.residual_moments(E)
+        return mean[None].clone(), cov[None].clone(), count
+    return ops.residual_moments(E, group, groups)
+
+
+@residual_moments.register_fake
+def _(E, group, groups):
+    G, k = (1 if group is None else groups), E.shape[1]
+    return (E.new_empty((G, k), dtype=torch.float32), E.new_empty((G, k, k), dtype=torch.float32),
+            E.new_empty((G,), dtype=torch.int32))
+
+
 # ---- homography
 @_lib.custom_op(NS + "::state_to_space", mutates_args=(), device_types="cuda")
 def state_to_space(state: torch.Tensor) -> torch.Tensor:
@@ -204,4 +234,4 @@ def _(frames_u8, swap_rb, nhwc4):
 
 
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "linear_sum_assignment", "estimate_ts_bias", "state_to_space", "state_to_im", "im_to_state", "frame_ingest")
+             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest")

@@ -244,6 +244,31 @@ int rn_estimate_ts_bias(const float *boxes, int64_t box_stride, const int64_t *c
                         void *workspace, int64_t max_pairs, int32_t *pairs_out, float *te_out, int32_t *info,
                         void *stream);
 
+/* ---------------------------------------------------------------- fitting the filter ----------------------
+ * The two pieces of fit_filter_3D.py that the transforms and the filter kernels above do not cover.
+ * rn_fit_nearest (fit_filter_3D.py:356-375): B frames, each with one ground-truth state gt [B,6] fp32 and the
+ *   detections det [offsets[b], offsets[b+1]) of det [D,6] fp32 states (offsets [B+1] i32, clamped into [0, D]).  Per
+ *   frame: the fp32 road-plane footprints (min / max of corners 0..3 of i24_state_to_space, :331-336 and :357-361), the
+ *   script's own iou (:30-61; no epsilon, max(0, .) per factor) in fp32, distance 1.0 - iou, and the first detection
+ *   whose distance is strictly below the running minimum (:363-372): ties go to the lowest index, a NaN distance (0/0)
+ *   never wins.  rows [B] i32 = the chosen row of det, or -1 for an empty frame (the script's `continue`, :343-344) and
+ *   for a frame in which no distance compared below infinity (the script would fail on None - gt_state; the frame is
+ *   skipped and counted).  resid [B,5] fp32: det[row,:5] - gt[b,:5] (:374-375) of the frames with a match, compacted in
+ *   frame order; the rows behind the count are not written.  info[0] = frames with a match, info[1] = empty frames,
+ *   info[2] = frames without a comparable distance.  No synchronisation.  B, D <= RN_FIT_MAX.
+ * rn_residual_moments (:292-299, :377-384, :426-434, :471-478): E [N,k] fp32, k <= RN_MOMENTS_MAX_K; group (may be
+ *   NULL: one group) [N] i32 in [0, G), G <= RN_MOMENTS_MAX_G, rows with another id are left out.  Per group: count,
+ *   mean [G,k] fp32 and the population covariance [G,k,k] fp32 (divided by the count), centred on the fp32 mean with the
+ *   differences rounded to fp32 (the script's `vec - mean`); the sums run in fp64 in a fixed order (no atomics: the
+ *   same bits every run) and are rounded to fp32 once.  A group without rows gets count 0 and zeros. */
+#define RN_FIT_MAX (1 << 24)
+#define RN_MOMENTS_MAX_K 8
+#define RN_MOMENTS_MAX_G 16
+int rn_fit_nearest(const float *gt, const float *det, const int32_t *offsets, int64_t B, int64_t D, int32_t *rows,
+                   float *resid, int32_t *info, void *stream);
+int rn_residual_moments(const float *E, int64_t N, int k, const int32_t *group, int G, float *mean, float *cov,
+                        int32_t *count, void *stream);
+
 /* ---------------------------------------------------------------- frame ingest ----------------------------
  * Replaces F.to_tensor + F.normalize of the reference's loaders (util_track/mp_loader.py:239-243,
  * perform_3D_detection_on_video_sequences.py:51-58) on device: frames uint8 [B,H,W,3] (as the decoder / cv2.resize

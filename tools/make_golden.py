@@ -772,6 +772,196 @@ def gen_ts_bias():
     np.savez_compressed(os.path.join(OUT, "ts_bias.npz"), **out)
 
 
+def _script_iou(a, b):
+    """The script's own iou (fit_filter_3D.py:30-61), restated: the file cannot be imported (it opens its dataset, its
+    homography pickle and its checkpoint at import, :166-181)."""
+    area_a = (a[2] - a[0]) * (a[3] - a[1])
+    area_b = (b[2] - b[0]) * (b[3] - b[1])
+    minx, maxx = max(a[0], b[0]), min(a[2], b[2])
+    miny, maxy = max(a[1], b[1]), min(a[3], b[3])
+    intersection = max(0, maxx - minx) * max(0, maxy - miny)
+    union = area_a + area_b - intersection
+    return intersection / union
+
+
+def _script_moments(error_vectors):
+    """:292-299 (and :377-384, :426-434, :471-478): torch.mean, then the serial fp32 sum of outer products."""
+    k = error_vectors.shape[1]
+    mean = torch.mean(error_vectors, dim=0)
+    covariance = torch.zeros((k, k))
+    for vec in error_vectors:
+        covariance += torch.mm((vec - mean).unsqueeze(1), (vec - mean).unsqueeze(1).transpose(0, 1))
+    return mean, covariance / error_vectors.shape[0]
+
+
+def _script_footprint(hg, states):
+    space = hg.state_to_space(states)
+    box = torch.zeros([space.shape[0], 4])
+    box[:, 0] = torch.min(space[:, 0:4, 0], dim=1)[0]
+    box[:, 2] = torch.max(space[:, 0:4, 0], dim=1)[0]
+    box[:, 1] = torch.min(space[:, 0:4, 1], dim=1)[0]
+    box[:, 3] = torch.max(space[:, 0:4, 1], dim=1)[0]
+    return box
+
+
+def _script_nearest(hg, gt_state, detections):
+    """:331-337 and :356-372 -> the chosen row or None."""
+    gt_box = _script_footprint(hg, gt_state).squeeze(0)
+    boxes_new = _script_footprint(hg, detections)
+    min_dist, min_idx = np.inf, None
+    for d_idx in range(len(boxes_new)):
+        dist = 1.0 - _script_iou(boxes_new[d_idx], gt_box)
+        if dist < min_dist:
+            min_dist, min_idx = dist, d_idx
+    return min_idx
+
+
+def gen_fit_filter():
+    """fit_filter_3D.py restated cell by cell (Q :242-304, R :306-389, class sizes :394-441, speed and P :444-485) around
+    the reference's own Homography_Wrapper and Torch_KF, in the script's order and with its incremental add / predict
+    loop, on the inputs of tests/fit_filter_cases.py.  The script's kf.add has no time argument and its kf.objs() is a
+    dict by id (an older util_track/kf.py): here add gets zero times and the newest rows are read through obj_idxs, the
+    rows the script's ids 0..3 name.  Arrays only."""
+    import fit_filter_cases as fc
+    matplotlib_stub()
+    hgmod = ref_module_from_file("_reference_homography", "homography.py")
+    kfmod = ref_module_from_file("_reference_util_track_kf", "util_track/kf.py")
+    names, (Ps, Hs), (Ps2, Hs2) = fc.cameras()
+
+    def make_hg(P, H):
+        h = hgmod.Homography()
+        h.correspondence = {n: {"P": P[i], "H": H[i], "H_inv": np.linalg.inv(H[i])} for i, n in enumerate(names)}
+        h.default_correspondence = names[0]
+        return h
+    hg = hgmod.Homography_Wrapper(hg1=make_hg(Ps, Hs), hg2=make_hg(Ps2, Hs2))
+    class_dict = {i: n for i, n in enumerate(fc.CLASS_NAMES)}
+    out = {}
+
+    def to_state(gt_im, classes, camera):                                   # :262-266
+        heights = hg.guess_heights(classes)
+        temp_boxes = hg.im_to_state(gt_im, heights=heights, name=camera)
+        repro_boxes = hg.state_to_im(temp_boxes, name=camera)
+        refined_heights = hg.height_from_template(repro_boxes, heights, gt_im)
+        return hg.im_to_state(gt_im, heights=refined_heights, name=camera)
+
+    # ---- Q
+    kf_params = fc.kf_params()
+    kf = kfmod.Torch_KF(torch.device("cpu"), INIT=kf_params)
+    tr, tr_cls, tr_cam = fc.tracklets()
+    tr_t = torch.from_numpy(tr)
+    errors, preds, tgts, states = [], [], [], []
+    for idx in range(len(tr) // 4):
+        targets = []
+        for b_idx in range(4):
+            k = idx * 4 + b_idx
+            gt_im = tr_t[k]
+            classes = [class_dict[int(tr_cls[k])]] * 3
+            gt_state = to_state(gt_im, classes, names[tr_cam[k]])
+            states.append(gt_state)
+            vel = (gt_state[1, 0] - gt_state[0, 0]) * 30
+            init_state = torch.cat((gt_state[0, :5].unsqueeze(0), vel.unsqueeze(0).unsqueeze(1)), dim=1)
+            direction = gt_state[0, 5].unsqueeze(0)
+            kf.add(init_state, [b_idx], direction, torch.zeros(1, dtype=torch.float64))
+            vel = (gt_state[2, 0] - gt_state[1, 0]) * 30
+            targets.append(torch.cat((gt_state[1, :5].unsqueeze(0), vel.unsqueeze(0).unsqueeze(1)), dim=1).squeeze(0))
+        kf.predict()
+        pred = torch.stack([kf.X[kf.obj_idxs[i]].clone() for i in kf.obj_idxs.keys()])
+        targets = torch.stack(targets)
+        errors.append(pred - targets)
+        preds.append(pred)
+        tgts.append(targets)
+    error_vectors = torch.cat(errors, dim=0)
+    mean, covariance = _script_moments(error_vectors)
+    out["q_states"] = t2n(torch.stack(states))
+    out["q_pred"], out["q_target"], out["q_errors"] = t2n(torch.cat(preds)), t2n(torch.cat(tgts)), t2n(error_vectors)
+    out["mu_Q"], out["Q"] = t2n(mean), t2n(covariance)
+    kf_params["mu_Q"], kf_params["Q"] = mean, covariance
+    assert abs(float(mean[5])) > 0.05 and len(kf.X) == len(tr)
+
+    # ---- R
+    gt_im_all, gt_cls, cam, scores, labels, boxes20, offsets = fc.detector_frames()
+    errors, rows, gt_states, det_states = [], [], [], []
+    for b in range(len(gt_im_all)):
+        camera = names[cam[b]]
+        gt_state = to_state(torch.from_numpy(gt_im_all[b]), [class_dict[int(gt_cls[b])]], camera)
+        gt_states.append(gt_state[0])
+        lo, hi = int(offsets[b]), int(offsets[b + 1])
+        if hi - lo == 0:                                                      # :343-344
+            rows.append(-1)
+            continue
+        detections = torch.from_numpy(boxes20[lo:hi]).reshape(-1, 10, 2)
+        detections = detections[:, :8, :]
+        detections = to_state(detections, [class_dict[int(l)] for l in labels[lo:hi]], camera)      # :349-354
+        det_states.append(detections)
+        d_idx = _script_nearest(hg, gt_state, detections)
+        assert d_idx is not None
+        rows.append(lo + d_idx)
+        error = detections[d_idx] - gt_state
+        errors.append(error[0, :5])
+    error_vectors = torch.stack(errors)
+    mean, covariance = _script_moments(error_vectors)
+    out["r_gt_states"], out["r_det_states"] = t2n(torch.stack(gt_states)), t2n(torch.cat(det_states))
+    out["r_rows"], out["r_errors"] = np.array(rows, dtype=np.int32), t2n(error_vectors)
+    out["mu_R"], out["R"] = t2n(mean), t2n(covariance)
+    kf_params["mu_R"], kf_params["R"] = mean, covariance
+
+    # ---- class sizes (:394-441): every frame of a tracklet under the tracklet's first class
+    means = {}
+    for k in range(len(tr)):
+        means.setdefault(class_dict[int(tr_cls[k])], []).append(states[k])
+    class_sizes, class_covariances = {}, {}
+    for key in means.keys():
+        vecs = torch.cat(means[key], dim=0)[:, 2:5]
+        class_sizes[key], class_covariances[key] = _script_moments(vecs)
+    assert sorted(class_sizes) == sorted(fc.CLASS_NAMES)
+    out["class_size"] = np.stack([t2n(class_sizes[n]) for n in fc.CLASS_NAMES])
+    out["class_covariance"] = np.stack([t2n(class_covariances[n]) for n in fc.CLASS_NAMES])
+    kf_params["class_size"], kf_params["class_covariance"] = class_sizes, class_covariances
+
+    # ---- mean speed and P (:444-485)
+    vecs = []
+    for gt_state in states:
+        vel = torch.abs(gt_state[-1, 0] - gt_state[0, 0]) / ((len(gt_state) - 1) / 30.0)
+        vecs.append(vel.clone().unsqueeze(0))
+    vecs = torch.cat(vecs, dim=0).unsqueeze(1)
+    mean, covariance = _script_moments(vecs)
+    out["speeds"] = t2n(vecs)
+    kf_params["P"] = torch.zeros([6, 6]).float()
+    kf_params["mu_v"] = mean
+    kf_params["P"][:5, :5] = kf_params["R"]
+    kf_params["P"][5, 5] = covariance.item()
+    out["mu_v"], out["var_v"], out["P"] = t2n(mean), t2n(covariance), t2n(kf_params["P"])
+
+    # ---- the operator-level cases of the nearest-box search, through the script's loop
+    bare = hgmod.Homography_Wrapper(hg1=hgmod.Homography(), hg2=hgmod.Homography())
+    for name, (gt, det, off) in fc.nearest_cases().items():
+        rows, resid = [], []
+        for b in range(len(gt)):
+            lo, hi = int(off[b]), int(off[b + 1])
+            g = torch.from_numpy(gt[b:b + 1])
+            d = torch.from_numpy(det[lo:hi])
+            d_idx = _script_nearest(bare, g, d) if hi > lo else None
+            rows.append(-1 if d_idx is None else lo + d_idx)
+            if d_idx is not None:
+                resid.append((d[d_idx] - g)[0, :5])
+        out["nearest_%s_rows" % name] = np.array(rows, dtype=np.int32)
+        out["nearest_%s_resid" % name] = t2n(torch.stack(resid))
+    assert list(out["nearest_ties_rows"]) == [0, 70 + 3, 140 + 1] and list(out["nearest_nan_rows"]) == [1, -1, 4, -1]
+
+    # ---- a filter built from the fitted dict: add with class sizes and the mean speed, predict, update
+    st, classes, z = fc.filter_probe()
+    kf = kfmod.Torch_KF(torch.device("cpu"), INIT=kf_params)
+    s = torch.from_numpy(st)
+    kf.add(s[:, :5].clone(), list(range(len(s))), s[:, 5].clone(), torch.zeros(len(s), dtype=torch.float64),
+           init_speed=True, classes=classes)
+    out["probe_X0"], out["probe_P0"] = t2n(kf.X.clone()), t2n(kf.P.clone())
+    kf.predict()
+    out["probe_X1"], out["probe_P1"] = t2n(kf.X.clone()), t2n(kf.P.clone())
+    kf.update(torch.from_numpy(z), list(range(len(s))))
+    out["probe_X2"], out["probe_P2"] = t2n(kf.X.clone()), t2n(kf.P.clone())
+    np.savez_compressed(os.path.join(OUT, "fit_filter.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -788,7 +978,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -817,6 +1007,8 @@ def main():
         gen_tracker_assoc()
     if "ts_bias" in which:
         gen_ts_bias()
+    if "fit_filter" in which:
+        gen_fit_filter()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
