@@ -3,7 +3,7 @@
 // Replaces BBoxTransform.forward (D/utils.py:102-149 directional, R/utils.py:102-126 2D), ClipBoxes.forward
 // (R/utils.py:134-144), the adaptive-threshold while-loops and per-class / batched NMS of ResNet.forward
 // (D/model.py:311-397, R/model.py:283-311) and torchvision.ops.nms (third party; contract restated in
-// oracle/boxes.py, parity unpinned).
+// oracle/boxes.py and pinned by an exact integer reference, tests/post_cases.py).
 //
 // Compiled with -ffp-contract=off: decode and IoU are evaluated with one rounding per operation in the
 // reference's order, so survivors and kept indices are bit-identical to the CPU path.
@@ -349,6 +349,7 @@ extern "C" int64_t rn_post_workspace_bytes(int64_t n_scores, int64_t max_candida
 
 __device__ __forceinline__ unsigned int f32_desc_key(float f) {                // larger float -> smaller key
     unsigned int u = __float_as_uint(f);
+    if ((u << 1) == 0u) u = 0u;                                                // -0.0 ranks with +0.0: the tie goes by position
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                            // ascending in f
     return ~u;
 }

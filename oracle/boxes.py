@@ -8,8 +8,15 @@
                                                     restated from its documented contract: order by score
                                                     descending, drop a box whose IoU with an already kept box
                                                     is > thr, return kept indices in score order.
-                                                    PARITY UNPINNED: no reference test or fixture covers it.
-                                                    Ties in score are broken by lower index first.)
+                                                    Ties in score are broken by lower index first, +0.0
+                                                    and -0.0 being equal.
+                                                    Pinned by tests/test_post_cases_host.py: on every
+                                                    integer-coordinate case of tests/post_cases.py it returns
+                                                    the list of an exact integer greedy NMS, with no exception,
+                                                    and on the non-integer family that of an fp64 evaluation.
+                                                    Still unchecked: the third-party function itself.
+                                                    torchvision is not installed where these tests run, so
+                                                    nothing here compares against torchvision.ops.nms.)
   batched_nms           <- batched_nms             D/model.py:19-57 (offset trick in fp32)
   adaptive_threshold    <- the while-loops         D/model.py:322-328 (MULTI_FRAME), :368-374 (single)
   postprocess_single    <- ResNet.forward eval     D/model.py:346-397
@@ -63,7 +70,7 @@ def clip_boxes(boxes, height, width):
 
 
 def greedy_nms(boxes, scores, thr):
-    """int64 keep indices, decreasing score.  See module docstring (parity unpinned)."""
+    """int64 keep indices, decreasing score.  See module docstring (what pins it, and what does not)."""
     n = boxes.shape[0]
     if n == 0:
         return torch.empty((0,), dtype=torch.int64)

@@ -14,7 +14,8 @@ Quirks kept:
   * survivors come back in NMS order (decreasing score), twice;
   * an empty input or nothing above sigma_d returns four empty lists (MC3D_crop_tracker.py:334-348).
 ``nms`` is torchvision.ops.nms in the reference (a third-party dependency, not under /root/reference, version
-unpinned); oracle/boxes.greedy_nms restates its published contract (parity unpinned for NMS itself, see there).
+unpinned); oracle/boxes.greedy_nms restates its published contract (pinned by an exact integer reference, not by
+torchvision itself; see there).
 The timestamp-bias side effect (estimate_ts_bias, MC3D_crop_tracker.py:373-374) is tracker state, not part of the
 returned values, and is left to the caller.
 """
