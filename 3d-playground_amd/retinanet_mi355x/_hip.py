@@ -69,6 +69,10 @@ SIGNATURES = {
                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rn_fit_nearest": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rn_residual_moments": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rn_eval_select": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_i32, c_i32, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rn_eval_match": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_f64, c_vp, c_vp, c_vp, c_vp]),
+    "rn_eval_ap_workspace_bytes": (c_i64, [c_i64]),
+    "rn_eval_ap": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rn_frame_ingest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp]),
 }
 

@@ -12,6 +12,7 @@ import torch
 from . import _hip
 
 NMS_MAX = 16384
+EVAL_MAX_K = 1 << 20          # RN_EVAL_MAX_K: detections of ONE image eval_select takes (64 classes x NMS_MAX)
 KEEP = 10000                  # D/model.py:368
 
 
@@ -772,6 +773,139 @@ def residual_moments(E, group=None, groups=None):
     if group is None:
         return mean[0], cov[0], count
     return mean, cov, count
+
+
+# ------------------------------------------------------------------------------------------------ detector validation (mAP)
+EVAL_MAX_DET = 4096                # RN_EVAL_MAX_DET: max_detections per image
+EVAL_MAX_ROWS = 1 << 24            # RN_EVAL_MAX_ROWS: rows of the dataset's detection table
+EVAL_MAX_CLASSES = 256             # RN_EVAL_MAX_CLASSES
+EVAL_SORT_TILE, EVAL_SORT_SPAN = 64, 2048      # RN_EVAL_SORT_TILE / _SPAN: rows per sort step / per workgroup
+EVAL_OK, EVAL_TOO_MANY, EVAL_BAD_LABEL, EVAL_TABLE_FULL = 0, 1, 2, 4       # bits of state[1]
+EVAL_ROW_WORDS = 8                 # x1 y1 x2 y2 score (fp32 bits) | label image index (int32)
+
+
+def eval_status_text(status):
+    names = [(EVAL_TOO_MANY, "an image with more than %d detections" % EVAL_MAX_K),
+             (EVAL_BAD_LABEL, "a selected detection whose label is outside [0, num_classes)"),
+             (EVAL_TABLE_FULL, "the detection table is full")]
+    return "; ".join(t for b, t in names if status & b) or "ok"
+
+
+def eval_table(rows, num_images, device):
+    """-> (table int32 [rows, 8] -- the 32-byte rows of include/retinanet_mi355x.h, the float columns as their bits --,
+    img_rows int32 [num_images, 2] zeroed, state int32 [2] = (cursor, status) zeroed)."""
+    if not 0 <= rows <= EVAL_MAX_ROWS:
+        raise RuntimeError("the detection table takes at most %d rows, got %d" % (EVAL_MAX_ROWS, rows))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the detection table lives on the MI355X (no CPU fallback); got device %s" % device)
+    return (torch.zeros((rows, EVAL_ROW_WORDS), dtype=torch.int32, device=device),
+            torch.zeros((num_images, 2), dtype=torch.int32, device=device), torch.zeros(2, dtype=torch.int32, device=device))
+
+
+def eval_box_cols(boxes, box_cols=None):
+    """(first, one past last) column of the 2D box: (0, 4) for [K,4] boxes, (16, 20) -- the 2D envelope the model's own
+    NMS uses -- for the directional model's [K,20] rows."""
+    if box_cols is None:
+        if boxes.dim() != 2 or boxes.shape[1] not in (4, 20):
+            raise RuntimeError("eval_select: give box_cols for boxes of shape %s" % (tuple(boxes.shape),))
+        box_cols = (0, 4) if boxes.shape[1] == 4 else (16, 20)
+    c0, c1 = int(box_cols[0]), int(box_cols[1])
+    if c1 - c0 != 4 or c0 < 0 or (boxes.numel() and (boxes.dim() != 2 or c1 > boxes.shape[1])):
+        raise RuntimeError("eval_select: box_cols %r does not name four columns of boxes %s" % (box_cols, tuple(boxes.shape)))
+    return c0, c1
+
+
+def eval_select(scores, labels, boxes, table, img_rows, state, image, num_classes, score_threshold=0.05, max_detections=100,
+                box_cols=None):
+    """_get_detections' selection for ONE image (csv_eval.py:102-123) appended to the dataset's table: score >
+    float32(score_threshold), score descending (ties: lower index first), the first max_detections.  table / img_rows /
+    state from eval_table, updated in place; calls for different images are ordered by the stream.  Failures are bits in
+    state[1] (EVAL_*), and the image then appends nothing.  No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(scores, labels, boxes, table, img_rows, state)
+    K = scores.shape[0]
+    if scores.dim() != 1 or labels.shape != scores.shape or (K and boxes.shape[0] != K):
+        raise RuntimeError("eval_select: scores [K], labels [K], boxes [K, n], got %s %s %s"
+                           % (tuple(scores.shape), tuple(labels.shape), tuple(boxes.shape)))
+    if not 0 <= int(max_detections) <= EVAL_MAX_DET:
+        raise RuntimeError("eval_select: max_detections is at most %d, got %d" % (EVAL_MAX_DET, max_detections))
+    if not 0 < int(num_classes) <= EVAL_MAX_CLASSES or not 0 <= int(image) < img_rows.shape[0]:
+        raise RuntimeError("eval_select: image %d of %d, %d classes (at most %d)" % (image, img_rows.shape[0], num_classes, EVAL_MAX_CLASSES))
+    _eval_check_table(table, state)
+    c0 = 0
+    if K:
+        c0, _ = eval_box_cols(boxes, box_cols)
+        scores, boxes = _hip.f32c(scores), _hip.f32c(boxes)
+        labels = labels.long().contiguous()
+    with torch.cuda.device(table.device):
+        _hip.check(lib.rn_eval_select(scores.data_ptr() if K else None, labels.data_ptr() if K else None,
+                                      boxes.data_ptr() if K else None, boxes.shape[1] if K else 4, c0, K, float(score_threshold),
+                                      int(max_detections), int(image), img_rows.shape[0], int(num_classes),
+                                      table.data_ptr() if table.shape[0] else None, table.shape[0], state.data_ptr(),
+                                      img_rows.data_ptr(), _hip.stream()), "rn_eval_select")
+
+
+def _eval_check_table(table, state):
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous() or \
+            state.dtype != torch.int32 or state.numel() != 2 or not state.is_contiguous() or table.shape[0] > EVAL_MAX_ROWS:
+        raise RuntimeError("the detection table is a contiguous int32 [rows <= %d, %d] tensor with an int32 [2] state (ops.eval_table)"
+                           % (EVAL_MAX_ROWS, EVAL_ROW_WORDS))
+
+
+def eval_match(table, img_rows, ann_box, ann_offsets, num_classes, iou_threshold=0.5, num_annotations=None):
+    """The greedy matching of evaluate (csv_eval.py:189-213).  ann_box [M,4] fp64 and ann_offsets int32
+    [num_images * num_classes + 1] in (image, class) order.  -> (tp uint8 [rows]: 1 true positive / 0 false positive per
+    table row, num_annotations int32 [num_classes] (written into the tensor given, if one is)).  No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(table, img_rows, ann_box, ann_offsets, num_annotations)
+    I, C, M = img_rows.shape[0], int(num_classes), ann_box.shape[0]
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous():
+        raise RuntimeError("eval_match: the table comes from ops.eval_table")
+    if ann_box.dtype != torch.float64 or (M and tuple(ann_box.shape) != (M, 4)) or ann_offsets.dtype != torch.int32 or \
+            ann_offsets.numel() != I * C + 1 or not 0 < C <= EVAL_MAX_CLASSES:
+        raise RuntimeError("eval_match: ann_box [M,4] float64, ann_offsets int32 [%d * %d + 1], got %s %s and %s %s"
+                           % (I, C, ann_box.dtype, tuple(ann_box.shape), ann_offsets.dtype, tuple(ann_offsets.shape)))
+    dev = table.device
+    ann_box, ann_offsets, img_rows = ann_box.contiguous(), ann_offsets.contiguous(), img_rows.contiguous()
+    if num_annotations is None:
+        num_annotations = torch.zeros(C, dtype=torch.int32, device=dev)
+    elif num_annotations.dtype != torch.int32 or num_annotations.numel() != C or not num_annotations.is_contiguous():
+        raise RuntimeError("eval_match: num_annotations is a contiguous int32 [num_classes] tensor")
+    rows = table.shape[0]
+    tp = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    taken = torch.empty(M, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_eval_match(table.data_ptr() if rows else None, rows, img_rows.data_ptr() if I else None, I, C,
+                                     ann_box.data_ptr() if M else None, ann_offsets.data_ptr(), M, float(iou_threshold),
+                                     taken.data_ptr() if M else None, tp.data_ptr() if rows else None,
+                                     num_annotations.data_ptr(), _hip.stream()), "rn_eval_match")
+    return tp, num_annotations
+
+
+def eval_ap(table, state, tp, num_annotations, ap=None):
+    """Per-class average precision (csv_eval.py:216-235, _compute_ap :38-62).  -> (ap float64 [num_classes] (written into
+    the tensor given, if one is), order int32 [rows]: the table rows sorted stably by (label, score descending); the first
+    state[0] entries are valid, the rest -1).  Bit-identical from run to run.  No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(table, state, tp, num_annotations, ap)
+    _eval_check_table(table, state)
+    rows, C = table.shape[0], num_annotations.numel()
+    if tp.dtype != torch.uint8 or tp.numel() != rows or not tp.is_contiguous() or num_annotations.dtype != torch.int32 or \
+            not num_annotations.is_contiguous() or not 0 < C <= EVAL_MAX_CLASSES:
+        raise RuntimeError("eval_ap: tp uint8 [rows] and num_annotations int32 [classes <= %d] as eval_match returns them" % EVAL_MAX_CLASSES)
+    dev = table.device
+    if ap is None:
+        ap = torch.zeros(C, dtype=torch.float64, device=dev)
+    elif ap.dtype != torch.float64 or ap.numel() != C or not ap.is_contiguous():
+        raise RuntimeError("eval_ap: ap is a contiguous float64 [num_classes] tensor")
+    order = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.rn_eval_ap_workspace_bytes(rows), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_eval_ap(table.data_ptr() if rows else None, rows, state.data_ptr(), tp.data_ptr() if rows else None,
+                                  num_annotations.data_ptr(), C, ws.data_ptr() if rows else None, ap.data_ptr(),
+                                  order.data_ptr() if rows else None, _hip.stream()), "rn_eval_ap")
+    return ap, order
 
 
 # ------------------------------------------------------------------------------------------------ frame ingest

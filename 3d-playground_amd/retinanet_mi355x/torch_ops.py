@@ -22,6 +22,9 @@ Operator                                         reference code it stands for
   residual_moments(E, group, groups)             mean / covariance loops               fit_filter_3D.py:292-299, 377-384, 426-434
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
   frame_ingest(frames_u8, swap_rb, nhwc4)        to_tensor + normalize of the loaders  util_track/mp_loader.py:239-243
+  eval_select(scores, labels, boxes, table, ..)  _get_detections' selection (in place)  R/csv_eval.py:102-123
+  eval_match(table, img_rows, ann_box, off, ..)  evaluate's greedy matching             R/csv_eval.py:189-213, 21-35
+  eval_ap(table, state, tp, num_annotations)     per-class sort + _compute_ap           R/csv_eval.py:216-235, 38-62
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -233,5 +236,36 @@ def _(frames_u8, swap_rb, nhwc4):
     return frames_u8.new_empty((B, H, W, 4) if nhwc4 else (B, 3, H, W), dtype=torch.float32)
 
 
+# ---- detector validation (mAP)
+@_lib.custom_op(NS + "::eval_select", mutates_args=("table", "img_rows", "state"), device_types="cuda")
+def eval_select(scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor, table: torch.Tensor, img_rows: torch.Tensor,
+                state: torch.Tensor, image: int, num_classes: int, score_threshold: float, max_detections: int,
+                box_col: int) -> None:
+    ops.eval_select(scores, labels, boxes, table, img_rows, state, image, num_classes, score_threshold, max_detections,
+                    box_cols=(box_col, box_col + 4))
+
+
+@_lib.custom_op(NS + "::eval_match", mutates_args=(), device_types="cuda")
+def eval_match(table: torch.Tensor, img_rows: torch.Tensor, ann_box: torch.Tensor, ann_offsets: torch.Tensor, num_classes: int,
+               iou_threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.eval_match(table, img_rows, ann_box, ann_offsets, num_classes, iou_threshold)
+
+
+@eval_match.register_fake
+def _(table, img_rows, ann_box, ann_offsets, num_classes, iou_threshold):
+    return table.new_empty((table.shape[0],), dtype=torch.uint8), table.new_empty((num_classes,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::eval_ap", mutates_args=(), device_types="cuda")
+def eval_ap(table: torch.Tensor, state: torch.Tensor, tp: torch.Tensor, num_annotations: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.eval_ap(table, state, tp, num_annotations)
+
+
+@eval_ap.register_fake
+def _(table, state, tp, num_annotations):
+    return (table.new_empty((num_annotations.shape[0],), dtype=torch.float64), table.new_empty((table.shape[0],), dtype=torch.int32))
+
+
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest")
+             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest",
+             "eval_select", "eval_match", "eval_ap")

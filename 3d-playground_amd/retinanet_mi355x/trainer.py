@@ -57,14 +57,17 @@ def dataparallel_state_dict(sd):
 
 
 def train(net, optimizer, scheduler, batches, epochs, *, start_epoch=0, clip_norm=None, checkpoint=None, rank=0, group=None,
-          log=print, freeze_bn=True, log_every=2, skip_zero_loss=True, dataparallel_keys=False):
+          log=print, freeze_bn=True, log_every=2, skip_zero_loss=True, dataparallel_keys=False, validate=None):
     """net([im, label]) -> (cls_loss, reg_loss, vp_loss); batches(epoch) -> iterable of (im, label) already on the device (this
     rank's shard); optimizer: ``optim.ClipAdam`` (clip fused: leave clip_norm None) or any torch optimizer (clip_norm = 0.1
     reproduces :385); scheduler: ``ReduceLROnPlateau`` or None; checkpoint: a path pattern with ``{}`` for the epoch, written
     by rank 0 after every epoch: ``net.state_dict()`` with bare keys -- the format of the reference's SINGLE-GPU runs -- or, with
     ``dataparallel_keys=True``, with the ``module.`` prefix its multi-GPU trainer writes and resumes from (dataparallel_state_dict).
-    The ranks' shards may differ in length (see the module docstring).  Returns the per-epoch history
-    [{"epoch", "mean_loss", "iterations", "skipped", "lr"}]."""
+    The ranks' shards may differ in length (see the module docstring).  validate: None, or a callable ``validate(net, epoch)
+    -> dict`` (e.g. ``lambda net, epoch: csv_eval.evaluate(dataset_val, net)``, D/train.py:168) run on EVERY rank after the
+    scheduler step and before the barrier, under ``net.eval()`` and ``torch.no_grad()``; its result is kept as the epoch's
+    ``"validation"`` entry and logged by rank 0.  The scheduler still steps on the mean training loss.  Returns the per-epoch
+    history [{"epoch", "mean_loss", "iterations", "skipped", "lr"}] (+ "validation" when validate is given)."""
     params = [p for p in net.parameters() if p.requires_grad]
     device = params[0].device
     history = []
@@ -107,6 +110,11 @@ def train(net, optimizer, scheduler, batches, epochs, *, start_epoch=0, clip_nor
         if scheduler is not None and epoch_loss:
             scheduler.step(mean_loss)                          # :412 -- the same number on every rank
         lr = optimizer.param_groups[0]["lr"]
+        validation = None
+        if validate is not None:                               # the reference evaluates every epoch (D/train.py:168)
+            net.eval()
+            with torch.no_grad():
+                validation = validate(net, epoch)
         if checkpoint is not None and rank == 0:               # :415-417
             path = checkpoint.format(epoch)
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -114,6 +122,10 @@ def train(net, optimizer, scheduler, batches, epochs, *, start_epoch=0, clip_nor
         if _world(group) > 1:
             dist.barrier(group=group)                          # nobody starts the next epoch before the checkpoint is on disk
         history.append({"epoch": epoch, "mean_loss": mean_loss, "iterations": len(epoch_loss), "skipped": skipped, "lr": lr})
+        if validate is not None:
+            history[-1]["validation"] = validation
+            if rank == 0:
+                log("Epoch %d validation: %s" % (epoch, validation))
         if rank == 0:
             log("Epoch %d training complete: mean loss %.5f over %d iterations (%d skipped), lr %.3g"
                 % (epoch, mean_loss, len(epoch_loss), skipped, lr))

@@ -269,6 +269,57 @@ int rn_fit_nearest(const float *gt, const float *det, const int32_t *offsets, in
 int rn_residual_moments(const float *E, int64_t N, int k, const int32_t *group, int G, float *mean, float *cov,
                         int32_t *count, void *stream);
 
+/* ---------------------------------------------------------------- detector validation: mAP ----------------
+ * retinanet/csv_eval.py (the same file in R/ and D/): evaluate, called after every epoch by D/train.py:168.  The
+ * detections of the whole dataset stay in one device table of 32-byte rows
+ *   { f32 x1, y1, x2, y2, score; i32 label, image, index (the detection's position in its image's input) }
+ * and the host reads num_classes x (AP, annotation count) at the end.  No entry synchronises; all take any stream.
+ * state [2] i32 on the device: state[0] = rows in the table (the append cursor), state[1] = status, an OR of the
+ * RN_EVAL_* bits below; the caller zeroes both before the first image.  Ties in score keep dataset order everywhere
+ * (image ascending, then selected rank; inside an image the lower input index first; -0.0 ranks with +0.0) -- the
+ * reference's two np.argsort calls leave that order open.
+ * rn_eval_select (_get_detections, csv_eval.py:102-123), one call per image, in stream order: keeps scores [K] fp32
+ *   with score > score_threshold (fp32, strict; NaN is dropped), orders them by score descending and appends the first
+ *   max_detections as rows at the cursor.  The box is boxes[k * box_stride + box_col .. + 4) -- box_col 0 for [K,4]
+ *   boxes, 16 for the directional model's [K,20] rows (its 2D envelope).  img_rows [num_images,2] i32 receives the
+ *   image's row range [begin, end).  K > RN_EVAL_MAX_K, a selected label outside [0, num_classes), or fewer than the
+ *   selected number of free rows set RN_EVAL_TOO_MANY / RN_EVAL_BAD_LABEL / RN_EVAL_TABLE_FULL in state[1]; the image
+ *   then appends nothing (an empty range).  max_detections <= RN_EVAL_MAX_DET (RN_EINVAL above).
+ * rn_eval_match (evaluate, :189-213, with compute_overlap :21-35): annotations packed as ann_box [M,4] fp64 with
+ *   ann_offsets [num_images * num_classes + 1] i32 in (image, class) order.  Every row gets tp[row] = 1 (true positive)
+ *   or 0: rows are taken in table order; no annotation in the row's (image, class) -> 0; else the fp64 overlap with each
+ *   of them, the union (area_a + area_b) - iw*ih clamped at DBL_EPSILON, no +1; the first maximum; 1 when it is >=
+ *   iou_threshold and that annotation has not been taken, else 0 -- also when another, free annotation clears the
+ *   threshold; a NaN overlap gives 0 and takes nothing.  Any number of annotations per group.  num_annotations
+ *   [num_classes] i32 counts every image's annotations (:192).  taken: M bytes of workspace.
+ * rn_eval_ap (:216-235 and _compute_ap :38-62): order [table_rows] i32 = the rows sorted stably by (label ascending,
+ *   score descending) -- an LSD radix sort, tiles of RN_EVAL_SORT_TILE rows, RN_EVAL_SORT_SPAN rows per workgroup --
+ *   of which the first state[0] entries are written; ap [num_classes] fp64: cumulative TP / FP (integers), recall =
+ *   tp / num_annotations, precision = tp / (tp + fp), the envelope by a reverse running maximum, the sum of
+ *   (recall step) * envelope over the points where the recall changes, in a fixed order: the same bits every run.  A
+ *   class without annotations gets 0, as does one without detections.  workspace: rn_eval_ap_workspace_bytes(table_rows)
+ *   bytes, 16-byte aligned like the table.  table_rows <= RN_EVAL_MAX_ROWS, num_classes <= RN_EVAL_MAX_CLASSES. */
+#define RN_EVAL_MAX_K (1 << 20)
+#define RN_EVAL_MAX_DET 4096
+#define RN_EVAL_MAX_ROWS (1 << 24)
+#define RN_EVAL_MAX_CLASSES 256
+#define RN_EVAL_SORT_TILE 64
+#define RN_EVAL_SORT_SPAN 2048
+#define RN_EVAL_OK 0
+#define RN_EVAL_TOO_MANY 1
+#define RN_EVAL_BAD_LABEL 2
+#define RN_EVAL_TABLE_FULL 4
+int rn_eval_select(const float *scores, const int64_t *labels, const float *boxes, int64_t box_stride, int64_t box_col,
+                   int64_t K, float score_threshold, int max_detections, int image, int64_t num_images,
+                   int num_classes, void *table, int64_t table_rows, int32_t *state, int32_t *img_rows, void *stream);
+int rn_eval_match(const void *table, int64_t table_rows, const int32_t *img_rows, int64_t num_images, int num_classes,
+                  const double *ann_box, const int32_t *ann_offsets, int64_t M, double iou_threshold, void *taken,
+                  uint8_t *tp, int32_t *num_annotations, void *stream);
+int64_t rn_eval_ap_workspace_bytes(int64_t table_rows);
+int rn_eval_ap(const void *table, int64_t table_rows, const int32_t *state, const uint8_t *tp,
+               const int32_t *num_annotations, int num_classes, void *workspace, double *ap, int32_t *order,
+               void *stream);
+
 /* ---------------------------------------------------------------- frame ingest ----------------------------
  * Replaces F.to_tensor + F.normalize of the reference's loaders (util_track/mp_loader.py:239-243,
  * perform_3D_detection_on_video_sequences.py:51-58) on device: frames uint8 [B,H,W,3] (as the decoder / cv2.resize

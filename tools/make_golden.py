@@ -962,6 +962,69 @@ def gen_fit_filter():
     np.savez_compressed(os.path.join(OUT, "fit_filter.npz"), **out)
 
 
+class _EvalItem(dict):
+    """What csv_eval._get_detections reads of a dataset item: data[0] (CHW, its GPU branch) or data['img'] (HWC, its CPU
+    branch).  Pixel (0,0) of channel 0 carries the image index."""
+    def __getitem__(self, k):
+        return dict.__getitem__(self, "chw" if k == 0 else k)
+
+
+class _EvalDataset:
+    def __init__(self, anns, C):
+        self.anns, self.C = anns, C
+
+    def __len__(self):
+        return len(self.anns)
+
+    def num_classes(self):
+        return self.C
+
+    def __getitem__(self, i):
+        chw = torch.zeros(3, 2, 2)
+        chw[0, 0, 0] = float(i)
+        return _EvalItem(chw=chw, img=chw.permute(1, 2, 0))
+
+    def load_annotations(self, i):
+        return self.anns[i]
+
+    def label_to_name(self, label):
+        return "class%d" % label
+
+
+class _EvalNet:
+    """Returns the stored detections of the image whose index the input carries."""
+    def __init__(self, dets):
+        self.dets = dets
+
+    def eval(self):
+        return self
+
+    def __call__(self, x):
+        s, l, b = self.dets[int(round(float(x[0, 0, 0, 0])))]
+        return torch.from_numpy(s.copy()), torch.from_numpy(l.copy()), torch.from_numpy(b.copy())
+
+
+def gen_csv_eval():
+    """The reference's own csv_eval.evaluate (retinanet/csv_eval.py) on the stub dataset and network above."""
+    import contextlib
+    import io
+    import eval_cases as ec
+    ce = ref_module_from_file("ref_csv_eval", "retinanet/csv_eval.py")
+    out = {}
+    for name, g in ec.GOLDEN.items():
+        dets, anns = ec.golden_inputs(name)
+        C = g["classes"]
+        with contextlib.redirect_stdout(io.StringIO()):
+            res = ce.evaluate(_EvalDataset(anns, C), _EvalNet(dets), iou_threshold=g["iou"], score_threshold=g["score"],
+                              max_detections=g["max_det"])
+        for k, v in ec.pack_golden(dets, anns, C).items():
+            out[name + "_" + k] = v
+        out[name + "_params"] = np.array([g["iou"], g["score"], g["max_det"]], np.float64)
+        out[name + "_ap"] = np.array([float(res[c][0]) for c in range(C)], np.float64)
+        out[name + "_num_annotations"] = np.array([float(res[c][1]) for c in range(C)], np.float64)
+    np.savez_compressed(os.path.join(OUT, "csv_eval.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -978,7 +1041,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1009,6 +1072,8 @@ def main():
         gen_ts_bias()
     if "fit_filter" in which:
         gen_fit_filter()
+    if "csv_eval" in which:
+        gen_csv_eval()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
