@@ -911,6 +911,8 @@ def eval_ap(table, state, tp, num_annotations, ap=None):
 # ------------------------------------------------------------------------------------------------ frame ingest
 IMAGENET_MEAN = (0.485, 0.456, 0.406)     # util_track/mp_loader.py:241
 IMAGENET_STD = (0.229, 0.224, 0.225)
+AUGMENT_PARAMS_BYTES = 104                # sizeof(rn_augment_params)
+AUGMENT_TAPS = 7                          # RN_AUG_TAPS
 
 
 def frame_ingest(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, nhwc4=False):
@@ -929,6 +931,46 @@ def frame_ingest(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD,
         _hip.check(lib.rn_frame_ingest(f.data_ptr(), B, H, W, int(bool(swap_rb)), *[float(m) for m in mean],
                                        *[float(s) for s in std], int(bool(nhwc4)), out.data_ptr(), _hip.stream()),
                    "rn_frame_ingest")
+    return out
+
+
+def augment_frames(frames_u8, params, noise=None, seed=0, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The image chain of the reference's training loader on device (include/retinanet_mi355x.h, rn_augment_frames;
+    corrected_3D_dataset.py:330-478).  frames_u8: uint8 [B,H,W,3]; params: (records, table_x, table_y) as
+    ``augment.pack_params`` makes them -- numpy arrays (uploaded here) or device tensors (records as uint8 [B,104], tables
+    int32 [B,W,8] and [B,H,8]); noise: optional uint8 [B,H,W,3] pad bytes, else the device generator keyed by ``seed``.
+    -> float32 [B,3,H,W]."""
+    lib = _hip.load()
+    _hip.need_gpu(frames_u8, noise)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise RuntimeError("augment_frames takes uint8 [B,H,W,3] frames, got %s %s" % (frames_u8.dtype, tuple(frames_u8.shape)))
+    f = frames_u8.contiguous()
+    B, H, W, _ = f.shape
+    rec, tx, ty = params
+    if isinstance(rec, np.ndarray):
+        rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.uint8).reshape(len(rec), -1)).to(f.device)
+        tx, ty = torch.from_numpy(np.ascontiguousarray(tx)).to(f.device), torch.from_numpy(np.ascontiguousarray(ty)).to(f.device)
+    _hip.need_gpu(rec, tx, ty)
+    rec, tx, ty = rec.contiguous(), tx.contiguous(), ty.contiguous()
+    if rec.dtype != torch.uint8 or tuple(rec.shape) != (B, AUGMENT_PARAMS_BYTES) or rec.data_ptr() % 8:
+        raise RuntimeError("augment_frames: records must be 8-byte aligned uint8 [%d,%d], got %s %s"
+                           % (B, AUGMENT_PARAMS_BYTES, rec.dtype, tuple(rec.shape)))
+    if tx.dtype != torch.int32 or ty.dtype != torch.int32 or tuple(tx.shape) != (B, W, 1 + AUGMENT_TAPS) or \
+            tuple(ty.shape) != (B, H, 1 + AUGMENT_TAPS):
+        raise RuntimeError("augment_frames: tables must be int32 [%d,%d,%d] and [%d,%d,%d], got %s and %s"
+                           % (B, W, 1 + AUGMENT_TAPS, B, H, 1 + AUGMENT_TAPS, tuple(tx.shape), tuple(ty.shape)))
+    if noise is not None:
+        if noise.dtype != torch.uint8 or tuple(noise.shape) != (B, H, W, 3):
+            raise RuntimeError("augment_frames: noise must be uint8 %s, got %s %s" % ((B, H, W, 3), noise.dtype, tuple(noise.shape)))
+        noise = noise.contiguous()
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=f.device)
+    if B == 0:
+        return out
+    ws = torch.empty(int(lib.rn_augment_workspace_bytes(B, H, W)) // 8, dtype=torch.int64, device=f.device)
+    with torch.cuda.device(f.device):
+        _hip.check(lib.rn_augment_frames(f.data_ptr(), B, H, W, rec.data_ptr(), tx.data_ptr(), ty.data_ptr(), _hip.ptr(noise),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, *[float(m) for m in mean], *[float(s) for s in std],
+                                         ws.data_ptr(), out.data_ptr(), _hip.stream()), "rn_augment_frames")
     return out
 
 

@@ -330,6 +330,47 @@ int rn_eval_ap(const void *table, int64_t table_rows, const int32_t *state, cons
 int rn_frame_ingest(const uint8_t *frames, int B, int H, int W, int swap_rb, float mean0, float mean1, float mean2,
                     float std0, float std1, float std2, int layout, float *out, void *stream);
 
+/* ---------------------------------------------------------------- training-batch augmentation -------------
+ * The image chain of the reference's training loader (corrected_3D_dataset.py: Detection_Dataset.__getitem__, :330-478,
+ * CROP == 0) on device, byte for byte what torchvision's PIL backend computes: frames uint8 [B,H,W,3] -> fp32 NCHW
+ * [B,3,H,W].  The random draws and the label transforms stay on the host (retinanet_mi355x/augment.py); what travels per
+ * image is one rn_augment_params record and two rows of resampling coefficients.
+ *
+ * rn_augment_params (104 bytes, 8-byte aligned):
+ *   affine[6]  destination -> source matrix of Image.rotate (:369): cos / sin rounded to 15 decimals, centre (W/2, H/2),
+ *              angle % 360, computed on the host exactly as Pillow does; source (sx, sy) = (a0 (x+.5) + a1 (y+.5) + a2,
+ *              a3 (x+.5) + a4 (y+.5) + a5) in double, output 0 unless 0 <= sx < W and 0 <= sy < H, else the bilinear blend of the
+ *              four taps around (sx-.5, sy-.5) with clamped indices, truncated to a byte
+ *   rh, rw     size of the resized image (:334-335); only its top-left min(rh,H) x min(rw,W) is read (:339), the rest of
+ *              the frame is noise bytes floor(fp32(k 2^-24) 255) (:338, 342)
+ *   flip       != 0: F.hflip (:352), a mirrored column in the rotation's reads
+ *   apply      != 0: the ColorJitter of self.im_tf (:177-180) runs, in the order order[4] (0 brightness, 1 contrast,
+ *              2 saturation, 3 hue = nothing), each t = a + f (p - a) in fp32 with f = factors[op], 0 if t <= 0, 255 if
+ *              t >= 255, else truncated; a = 0, the mean of L over the image as it stands (floor(sum / N + .5)), or the pixel's L;
+ *              L = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *   dy, dx     the tile swap (:468-478) as a roll: out[:, y, x] = t[:, (y + dy) % H, (x + dx) % W], 0 <= dy < H, 0 <= dx < W
+ * table_x int32 [B,W,1+RN_AUG_TAPS], table_y int32 [B,H,1+RN_AUG_TAPS]: per output index of Pillow's bilinear resize
+ *   (horizontal pass first, uint8 between the passes) the first source index and the taps k = int(.5 + w 2^22); the output is
+ *   clip((2^21 + sum k p) >> 22, 0, 255).  Rows at and beyond min(rw, W) / min(rh, H) are not read; a pass whose size does
+ *   not change is skipped.
+ * noise: uint8 [B,H,W,3] pad bytes, or null for the device generator (splitmix64 of seed * 0x9E3779B97F4A7C15 + the element's
+ *   index in [B,H,W,3]; its top 24 bits are k).  workspace: rn_augment_workspace_bytes(B, H, W) bytes, 8-byte aligned: two uint8
+ *   images per frame and one 64-bit sum per image.  Finish: (byte / 255 - mean[c]) / std[c] as rn_frame_ingest.
+ * Five launches for the whole batch on the stream, no host synchronisation. */
+#define RN_AUG_TAPS 7
+typedef struct rn_augment_params {
+    double affine[6];
+    int32_t rh, rw, flip, apply;
+    int32_t order[4];
+    int32_t dy, dx;
+    float factors[3];
+    int32_t reserved;
+} rn_augment_params;
+int64_t rn_augment_workspace_bytes(int B, int H, int W);
+int rn_augment_frames(const uint8_t *frames, int B, int H, int W, const rn_augment_params *params, const int32_t *table_x,
+                      const int32_t *table_y, const uint8_t *noise, uint64_t seed, float mean0, float mean1, float mean2,
+                      float std0, float std1, float std2, void *workspace, float *out, void *stream);
+
 /* ---------------------------------------------------------------- convolution engine ----------------------
  * fp32 implicit-GEMM convolutions on the matrix cores (v_mfma_f32_32x32x2_f32).  Replaces nn.Conv2d +
  * BatchNorm2d(eval) + ReLU + residual add (D/utils.py:25-43, 60-80), PyramidFeatures (D/model.py:84-117) and

@@ -11,6 +11,10 @@ behind three harness-side shims:
   3. ``Tensor.cuda`` -> identity, except a leaf that requires grad returns a clone (a real ``.cuda()``
      returns a non-leaf copy; D/losses.py:310 writes into such a tensor in place).
 
+The augmentation section (gen_augment) adds a fourth: ``torchvision.transforms`` / ``functional`` as the thin Pillow
+wrappers of tools/tv_pillow_stub.py, so that the reference's own Detection_Dataset.__getitem__ and collate run; the
+colour-jitter draws are therefore "parity unpinned" as well.
+
 Inputs come from ``retinanet_mi355x.synth`` (portable integer-hash generators), so the fixtures
 hold OUTPUTS (and the few inputs built with libm/LAPACK).  This script refuses to run without
 /root/reference and is never executed on the GPU box.
@@ -1025,6 +1029,176 @@ def gen_csv_eval():
     np.savez_compressed(os.path.join(OUT, "csv_eval.npz"), **out)
 
 
+# ----------------------------------------------------------------------------- training-batch augmentation
+class _Recorder:
+    """Wraps np.random.normal / rand / randint and torch.rand for one __getitem__: what was drawn, in order."""
+    def __init__(self):
+        self.np_draws, self.randints, self.noise = [], [], []
+
+    def __enter__(self):
+        self.saved = (np.random.normal, np.random.rand, np.random.randint, torch.rand)
+
+        def wrap(fn, kind):
+            def inner(*a, **k):
+                v = fn(*a, **k)
+                self.np_draws.append(float(v))
+                if kind == "randint":
+                    self.randints.append((int(a[1]), int(v)))
+                return v
+            return inner
+
+        def rand(*a, **k):
+            v = self.saved[3](*a, **k)
+            if v.dim() == 3:
+                self.noise.append(v.clone())
+            return v
+        np.random.normal, np.random.rand = wrap(self.saved[0], "normal"), wrap(self.saved[1], "rand")
+        np.random.randint, torch.rand = wrap(self.saved[2], "randint"), rand
+        return self
+
+    def __exit__(self, *exc):
+        np.random.normal, np.random.rand, np.random.randint, torch.rand = self.saved
+
+
+def augment_reference_dataset(tmp, cases):
+    """A temporary dataset in the reference's own format (PNG frames, labels.cpkl, camera_vps.cpkl) for the cases of
+    tests/augment_cases.py (name, shape key, camera, boxes, seed), read by the reference's own Detection_Dataset.
+    -> {name: (dataset, index)}"""
+    import pickle
+    import random
+    from PIL import Image
+    import augment_cases as ac
+    import tv_pillow_stub
+    tv_pillow_stub.install()
+    ref = ref_module_from_file("_reference_corrected_3D_dataset", "corrected_3D_dataset.py")
+    os.makedirs(os.path.join(tmp, "frames"), exist_ok=True)
+    all_data, by_path = [], {}
+    for i, (name, shape, camera, kind, seed) in enumerate(cases):
+        W, H = ac.SHAPES[shape]
+        path = os.path.join(tmp, "frames", "%s_0_%d.png" % (camera, i))
+        Image.fromarray(ac.frame_bytes(name, W, H)).save(path)
+        all_data.append([path, ac.boxes_rows(name, kind, W, H)])
+        by_path[path] = (name, kind)
+    with open(os.path.join(tmp, "labels.cpkl"), "wb") as f:
+        pickle.dump(all_data, f)
+    with open(os.path.join(tmp, "camera_vps.cpkl"), "wb") as f:
+        pickle.dump(ac.VPS, f)
+    found, cwd = {}, os.getcwd()
+    os.chdir(tmp)                                             # the reference opens camera_vps.cpkl in the working directory
+    try:
+        for mode in ("train", "test"):                        # the two sides of its 90/10 split, from the same shuffle
+            random.seed(0)
+            ds = ref.Detection_Dataset(tmp, mode=mode, CROP=0)
+            for idx, path in enumerate(ds.data):
+                name, kind = by_path[path]
+                if kind == "empty":                           # a frame whose label tensor is empty: the no_labels path (:311-313)
+                    ds.labels[idx] = torch.zeros([0, 21], dtype=torch.float64)
+                found[name] = (ds, idx)
+    finally:
+        os.chdir(cwd)
+    assert len(found) == len(cases)
+    return ref, found
+
+
+def augment_reference_item(ds, idx, seed):
+    """The reference's __getitem__ under seeds, with every draw and every intermediate image recorded."""
+    import random
+    from PIL import Image
+    import augment_cases as ac
+    import tv_pillow_stub
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    random.seed(seed)
+    del tv_pillow_stub.LOG[:]
+    with _Recorder() as rec:
+        im_t, y = ds[idx]
+    log = list(tv_pillow_stub.LOG)
+    first = {}
+    for k, v in log:
+        first.setdefault(k, v)
+    H, W = im_t.shape[1:]
+    camera = ds.data[idx].split("/")[-1].split("_")[0]
+    d = rec.np_draws
+    scale, aspect, flip, angle, tile = max(1, d[0]), max(0.75, d[1]), d[2], d[3] * 40 - 20, d[4]
+    assert first["rotate"][0] == angle and len(rec.noise) == 1 and ("hflip" in first) == (flip > 0.5)
+    xs = [v for hi, v in rec.randints if hi == W]
+    ys = [v for hi, v in rec.randints if hi == H]
+    dx = xs[-1] if 0.25 < tile < 0.75 else 0
+    dy = ys[-1] if tile > 0.5 and tile != 0.75 else 0
+    (rh, rw), resized = first["resize"]
+    apply = first["apply"]
+    order, factors = first["jitter"] if apply else ([0, 1, 2, 3], [1.0, 1.0, 1.0])
+    steps = [v for k, v in log if k == "jitter_step"]
+    out = dict(frame=np.array(Image.open(ds.data[idx])), labels_in=t2n(ds.labels[idx]),
+               camera=np.array(camera), vps=np.array(ac.VPS[camera], np.float64), seed=np.array(seed),
+               np_draws=np.array(d, np.float64), xsplits=np.array(xs, np.int64), ysplits=np.array(ys, np.int64),
+               scalars=np.array([scale, aspect, angle, tile], np.float64),
+               draws=np.array([rh, rw, int(flip > 0.5), apply, dy, dx], np.int32),
+               order=np.array(order, np.int32), factors=np.array(factors, np.float64),
+               noise=ac.noise_bytes(t2n(rec.noise[0]).transpose(1, 2, 0)), resized=resized, padded=first["to_pil_image"],
+               rotated=first["rotate"][1],
+               jitter_steps=np.stack(steps) if steps else np.zeros((0, H, W, 3), np.uint8),
+               im_t=t2n(im_t), y=t2n(y))
+    assert np.array_equal(first["to_tensor"], steps[-1] if steps else out["rotated"])
+    return out
+
+
+def augment_features(name, kind, camera, o):
+    """What one golden item covers of the list the set must contain."""
+    rh, rw, flip, apply, dy, dx = (int(v) for v in o["draws"])
+    scale, aspect, angle, tile = o["scalars"]
+    f = {"flip%d" % flip, "tile_none" if tile <= 0.25 else "tile_x" if tile < 0.5 else "tile_xy" if tile < 0.75 else "tile_y",
+         "aspect_below_1" if aspect < 1 else "aspect_above_1", "jitter_applied" if apply else "jitter_skipped"}
+    if (0.25 < tile < 0.75 and dx == 0) or (tile > 0.5 and dy == 0):
+        f.add("split_at_0")
+    if scale == 1:
+        f.add("scale_1")
+    if apply:
+        f.add("order_" + "".join(str(v) for v in o["order"]))
+    if kind == "empty":
+        f.add("label_less")
+        if flip:
+            f.add("label_less_flipped")
+    if kind == "none":
+        f.add("zero_row")
+    if kind == "corner" and o["y"][0, 20] == -1:
+        f.add("rotated_out")
+    if camera == "p2c3":
+        f.add("p2c3")
+    return f
+
+
+AUGMENT_MUST_COVER = {"flip0", "flip1", "tile_none", "tile_x", "tile_xy", "tile_y", "split_at_0", "aspect_below_1",
+                      "aspect_above_1", "scale_1", "jitter_applied", "jitter_skipped", "label_less", "label_less_flipped",
+                      "zero_row", "rotated_out", "p2c3"}
+
+
+def gen_augment():
+    """The reference's own Detection_Dataset.__getitem__ and collate (corrected_3D_dataset.py:296-498, 714-741, CROP == 0) on a
+    temporary dataset, behind tools/tv_pillow_stub.py and an empty cv2; the inputs, every draw, the noise, the bytes at every
+    step, im_t and y of every case of tests/augment_cases.py."""
+    import tempfile
+    import augment_cases as ac
+    out, covered, items = {}, set(), {}
+    with tempfile.TemporaryDirectory() as tmp:
+        ref, found = augment_reference_dataset(tmp, ac.GOLDEN)
+        for name, shape, camera, kind, seed in ac.GOLDEN:
+            o = augment_reference_item(*found[name], seed)
+            covered |= augment_features(name, kind, camera, o)
+            items[name] = o
+            for k, v in o.items():
+                out["%s_%s" % (name, k)] = v
+    assert AUGMENT_MUST_COVER <= covered, AUGMENT_MUST_COVER - covered
+    assert len([c for c in covered if c.startswith("order_")]) >= 3, covered
+    for shape in ac.SHAPES:
+        names = [c[0] for c in ac.GOLDEN if c[1] == shape]
+        ims, ys = ref.collate([(torch.from_numpy(items[n]["im_t"]), torch.from_numpy(items[n]["y"])) for n in names])
+        assert len({len(items[n]["y"]) for n in names}) > 1 and np.array_equal(t2n(ims), np.stack([items[n]["im_t"] for n in names]))
+        out["collate_%s_y" % shape] = t2n(ys)
+    out["names"] = np.array([c[0] for c in ac.GOLDEN])
+    np.savez_compressed(os.path.join(OUT, "augment.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -1041,7 +1215,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1074,6 +1248,8 @@ def main():
         gen_fit_filter()
     if "csv_eval" in which:
         gen_csv_eval()
+    if "augment" in which:
+        gen_augment()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods

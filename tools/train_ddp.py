@@ -45,6 +45,9 @@ def parse():
     ap.add_argument("--resume", default=None, help="checkpoint (state_dict, with or without the DataParallel 'module.' prefix)")
     ap.add_argument("--dataparallel-keys", action="store_true",
                     help="write checkpoints with the 'module.' key prefix of the reference's multi-GPU trainer (train_detector_3D_angle.py:415-417)")
+    ap.add_argument("--augment", action="store_true",
+                    help="feed the step from augment.AugmentedBatches (the reference loader's augmentation, on the device) over "
+                         "synth.frames quantised to uint8, instead of from ready-made tensors")
     return ap.parse_args()
 
 
@@ -94,6 +97,19 @@ def main():
         for it in range(args.iters):
             seed = 1000 * epoch + 10 * it + rank                                   # rank r's shard of iteration `it`
             yield synth.frames(B, H, W, seed=seed).to(dev), synth.labels_dir(B, 10, H, W, 8, seed=seed + 5).to(dev)
+
+    if args.augment:
+        import numpy as np
+        from retinanet_mi355x import augment, ops
+        n = B * args.iters
+        mean, std = (torch.tensor(v).view(1, 3, 1, 1) for v in (ops.IMAGENET_MEAN, ops.IMAGENET_STD))
+        u8 = ((synth.frames(n, H, W, seed=100 + rank) * std + mean) * 255).round().clamp(0, 255).byte().permute(0, 2, 3, 1).contiguous().numpy()
+        lab = synth.labels_dir(n, 10, H, W, 8, seed=105 + rank)
+        labels = [l[l[:, 20] != -1][:, :21].double() for l in lab]
+        np.random.seed(rank)                                                       # every rank draws for its own shard
+        torch.manual_seed(rank)
+        batches = augment.AugmentedBatches(u8, labels, ["p1c1"] * n, {"p1c1": [[-310.5, 12.25], [2100.75, -55.5], [48.0, 3000.5]]},
+                                           B, dev, seed=rank)
 
     t0 = time.time()
     hist = trainer.train(net, opt, sched, batches, args.epochs, checkpoint=os.path.join(args.out, "corrected_data_e{}.pt"),
