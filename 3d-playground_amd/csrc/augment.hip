@@ -15,9 +15,7 @@
 // parameter record or a table is clamped before it is used, so a bad record gives wrong pixels, never an access outside the buffers.
 #include <stdint.h>
 
-#include "common.h"
-
-#define AUG_ROW (1 + RN_AUG_TAPS)            // int32 per table row: first source index, then the taps
+#include "augment_dev.h"
 
 struct AugArgs {
     const uint8_t *frames;                   // [B,H,W,3]
@@ -31,24 +29,6 @@ struct AugArgs {
     int B, H, W;
     float mean[3], stdv[3];
 };
-
-__device__ __forceinline__ int aug_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ unsigned aug_clip8(int acc) {
-    const int v = acc >> 22;
-    return (unsigned)aug_clampi(v, 0, 255);
-}
-
-// the counter-based generator: splitmix64 of (seed, element index) -> 24 bits -> floor(fp32(k 2^-24) 255)
-__device__ __forceinline__ unsigned aug_noise(uint64_t seed, uint64_t element) {
-    uint64_t z = element + seed * 0x9E3779B97F4A7C15ull;
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const float u = (float)(unsigned)(z >> 40) * 5.9604644775390625e-8f;      // k * 2^-24, exact
-    return (unsigned)(u * 255.0f);
-}
 
 __global__ __launch_bounds__(256) void aug_resize_h(const AugArgs a) {
     const int64_t hw = (int64_t)a.H * a.W;
@@ -143,34 +123,6 @@ __global__ __launch_bounds__(256) void aug_rotate(const AugArgs a) {
     }
 }
 
-__device__ __forceinline__ int aug_luma(const int px[3]) { return (19595 * px[0] + 38470 * px[1] + 7471 * px[2] + 32768) >> 16; }
-
-// Image.blend(degenerate, image, f)
-__device__ __forceinline__ int aug_blend(int d, int p, float f) {
-    const float t = (float)d + f * (float)(p - d);
-    return t <= 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t);
-}
-
-// The ImageEnhance passes in the drawn order, on one pixel.  until_contrast: stop in front of the contrast op (for its mean).
-__device__ __forceinline__ void aug_jitter(int px[3], const rn_augment_params &q, bool until_contrast, int mean) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int op = q.order[i];
-        if (op == 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) px[c] = aug_blend(0, px[c], q.factors[0]);
-        } else if (op == 1) {
-            if (until_contrast) return;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) px[c] = aug_blend(mean, px[c], q.factors[1]);
-        } else if (op == 2) {
-            const int l = aug_luma(px);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) px[c] = aug_blend(l, px[c], q.factors[2]);
-        }                                                                   // 3 = hue: draws nothing, changes nothing
-    }
-}
-
 __global__ __launch_bounds__(256) void aug_contrast_sum(const AugArgs a) {
     __shared__ int red[4];
     const int64_t hw = (int64_t)a.H * a.W;
@@ -211,8 +163,6 @@ __global__ __launch_bounds__(256) void aug_finish(const AugArgs a) {
         a.out[((int64_t)b * 3 + c) * hw + p] = (t - a.mean[c]) / a.stdv[c];  // normalize: sub_, div_
     }
 }
-
-static inline int64_t aug_align(int64_t n) { return (n + 255) / 256 * 256; }
 
 extern "C" int64_t rn_augment_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;

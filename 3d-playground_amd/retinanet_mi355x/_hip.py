@@ -76,6 +76,9 @@ SIGNATURES = {
     "rn_frame_ingest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp]),
     "rn_augment_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "rn_augment_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64] + [c_f32] * 6 + [c_vp, c_vp, c_vp]),
+    "rn_augment_crops_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "rn_augment_crops": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, ctypes.c_uint64]
+                         + [c_f32] * 6 + [c_vp, c_vp, c_vp]),
 }
 
 class ConvDesc(ctypes.Structure):

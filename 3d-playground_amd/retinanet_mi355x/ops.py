@@ -974,6 +974,65 @@ def augment_frames(frames_u8, params, noise=None, seed=0, mean=IMAGENET_MEAN, st
     return out
 
 
+AUGMENT_CROP_PARAMS_BYTES = 128           # sizeof(rn_augment_crop_params)
+AUGMENT_CROP_WIN_LIMIT = 16384            # the largest window edge and crop size rn_augment_crops takes
+
+
+def augment_crops(frames_u8, params, K, win_max, crop, noise=None, occlusion=None, seed=0, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The crop mode of the reference's training loader on device (include/retinanet_mi355x.h, rn_augment_crops;
+    corrected_3D_dataset.py:330-390, 501-594).  frames_u8: uint8 [B,H,W,3]; params: (records, table_x, table_y, table_cx,
+    table_cy) as ``augment.pack_crop_params`` makes them -- numpy arrays (uploaded here) or device tensors (records as uint8
+    [B,128], tables int32 [B,W,8], [B,H,8] and two [B,crop,1+K]); K: the taps of the second resize's tables, the batch's largest
+    ceil(max(size / crop, 1)) * 2 + 1; win_max: at least the largest window edge of the batch;
+    noise: optional uint8 [B,H,W,3] pad bytes; occlusion: optional float32 [B,3,crop,crop] values for the occluded regions; both
+    come from the device generator keyed by ``seed`` otherwise.  -> float32 [B,3,crop,crop]."""
+    lib = _hip.load()
+    _hip.need_gpu(frames_u8, noise, occlusion)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise RuntimeError("augment_crops takes uint8 [B,H,W,3] frames, got %s %s" % (frames_u8.dtype, tuple(frames_u8.shape)))
+    f = frames_u8.contiguous()
+    B, H, W, _ = f.shape
+    K, win_max, crop = int(K), int(win_max), int(crop)
+    rec, tx, ty, cx, cy = params
+    if not (0 < crop <= AUGMENT_CROP_WIN_LIMIT and 0 < win_max <= AUGMENT_CROP_WIN_LIMIT):
+        raise RuntimeError("augment_crops: crop and win_max must lie in [1, %d], got %d and %d" % (AUGMENT_CROP_WIN_LIMIT, crop, win_max))
+    if isinstance(rec, np.ndarray):
+        rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.uint8).reshape(len(rec), -1)).to(f.device)
+        tx, ty, cx, cy = (torch.from_numpy(np.ascontiguousarray(t)).to(f.device) for t in (tx, ty, cx, cy))
+    _hip.need_gpu(rec, tx, ty, cx, cy)
+    rec, tx, ty, cx, cy = rec.contiguous(), tx.contiguous(), ty.contiguous(), cx.contiguous(), cy.contiguous()
+    if rec.dtype != torch.uint8 or tuple(rec.shape) != (B, AUGMENT_CROP_PARAMS_BYTES) or rec.data_ptr() % 8:
+        raise RuntimeError("augment_crops: records must be 8-byte aligned uint8 [%d,%d], got %s %s"
+                           % (B, AUGMENT_CROP_PARAMS_BYTES, rec.dtype, tuple(rec.shape)))
+    if tx.dtype != torch.int32 or ty.dtype != torch.int32 or tuple(tx.shape) != (B, W, 1 + AUGMENT_TAPS) or \
+            tuple(ty.shape) != (B, H, 1 + AUGMENT_TAPS):
+        raise RuntimeError("augment_crops: the first resize's tables must be int32 [%d,%d,%d] and [%d,%d,%d], got %s and %s"
+                           % (B, W, 1 + AUGMENT_TAPS, B, H, 1 + AUGMENT_TAPS, tuple(tx.shape), tuple(ty.shape)))
+    if K < 3 or cx.dtype != torch.int32 or cy.dtype != torch.int32 or tuple(cx.shape) != (B, crop, 1 + K) or \
+            tuple(cy.shape) != (B, crop, 1 + K):
+        raise RuntimeError("augment_crops: the second resize's tables must both be int32 [%d,%d,%d] (K = %d >= 3), got %s %s and %s %s"
+                           % (B, crop, 1 + K, K, cx.dtype, tuple(cx.shape), cy.dtype, tuple(cy.shape)))
+    if noise is not None:
+        if noise.dtype != torch.uint8 or tuple(noise.shape) != (B, H, W, 3):
+            raise RuntimeError("augment_crops: noise must be uint8 %s, got %s %s" % ((B, H, W, 3), noise.dtype, tuple(noise.shape)))
+        noise = noise.contiguous()
+    if occlusion is not None:
+        if occlusion.dtype != torch.float32 or tuple(occlusion.shape) != (B, 3, crop, crop):
+            raise RuntimeError("augment_crops: occlusion must be float32 %s, got %s %s"
+                               % ((B, 3, crop, crop), occlusion.dtype, tuple(occlusion.shape)))
+        occlusion = occlusion.contiguous()
+    out = torch.empty((B, 3, crop, crop), dtype=torch.float32, device=f.device)
+    if B == 0:
+        return out
+    ws = torch.empty(int(lib.rn_augment_crops_workspace_bytes(B, win_max, crop)) // 8, dtype=torch.int64, device=f.device)
+    with torch.cuda.device(f.device):
+        _hip.check(lib.rn_augment_crops(f.data_ptr(), B, H, W, rec.data_ptr(), tx.data_ptr(), ty.data_ptr(), cx.data_ptr(),
+                                        cy.data_ptr(), K, win_max, crop, _hip.ptr(noise), _hip.ptr(occlusion),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, *[float(m) for m in mean], *[float(s) for s in std],
+                                        ws.data_ptr(), out.data_ptr(), _hip.stream()), "rn_augment_crops")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ tracker: crop refinement
 CROP_MAX_A, CROP_MAX_K = 4096, 256
 

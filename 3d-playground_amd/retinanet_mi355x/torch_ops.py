@@ -23,6 +23,7 @@ Operator                                         reference code it stands for
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
   frame_ingest(frames_u8, swap_rb, nhwc4)        to_tensor + normalize of the loaders  util_track/mp_loader.py:239-243
   augment_frames(frames_u8, records, tx, ty, ..) Detection_Dataset.__getitem__'s image chain  corrected_3D_dataset.py:330-478
+  augment_crops(frames_u8, records, 4 tables, ..) ... with CROP > 0 (the crop detector's)     corrected_3D_dataset.py:501-594
   eval_select(scores, labels, boxes, table, ..)  _get_detections' selection (in place)  R/csv_eval.py:102-123
   eval_match(table, img_rows, ann_box, off, ..)  evaluate's greedy matching             R/csv_eval.py:189-213, 21-35
   eval_ap(table, state, tp, num_annotations)     per-class sort + _compute_ap           R/csv_eval.py:216-235, 38-62
@@ -249,6 +250,19 @@ def _(frames_u8, records, table_x, table_y, noise, seed):
     return frames_u8.new_empty((B, 3, H, W), dtype=torch.float32)
 
 
+@_lib.custom_op(NS + "::augment_crops", mutates_args=(), device_types="cuda")
+def augment_crops(frames_u8: torch.Tensor, records: torch.Tensor, table_x: torch.Tensor, table_y: torch.Tensor,
+                  table_cx: torch.Tensor, table_cy: torch.Tensor, K: int, win_max: int, crop: int, noise: Optional[torch.Tensor],
+                  occlusion: Optional[torch.Tensor], seed: int) -> torch.Tensor:
+    return ops.augment_crops(frames_u8, (records, table_x, table_y, table_cx, table_cy), K, win_max, crop, noise=noise,
+                             occlusion=occlusion, seed=seed)
+
+
+@augment_crops.register_fake
+def _(frames_u8, records, table_x, table_y, table_cx, table_cy, K, win_max, crop, noise, occlusion, seed):
+    return frames_u8.new_empty((frames_u8.shape[0], 3, crop, crop), dtype=torch.float32)
+
+
 # ---- detector validation (mAP)
 @_lib.custom_op(NS + "::eval_select", mutates_args=("table", "img_rows", "state"), device_types="cuda")
 def eval_select(scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor, table: torch.Tensor, img_rows: torch.Tensor,
@@ -280,5 +294,5 @@ def _(table, state, tp, num_annotations):
 
 
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "augment_frames",
+             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "augment_frames", "augment_crops",
              "eval_select", "eval_match", "eval_ap")

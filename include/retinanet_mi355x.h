@@ -371,6 +371,45 @@ int rn_augment_frames(const uint8_t *frames, int B, int H, int W, const rn_augme
                       const int32_t *table_y, const uint8_t *noise, uint64_t seed, float mean0, float mean1, float mean2,
                       float std0, float std1, float std2, void *workspace, float *out, void *stream);
 
+/* ---------------------------------------------------------------- crop-detector training batches ----------
+ * The same loader with CROP > 0 (corrected_3D_dataset.py:330-390, 501-594), the crop detector's: the frame is resized, padded,
+ * flipped and rotated as above, then a window (minx, miny, cw, ch) is cut out of it (F.crop, zero outside the frame), resized
+ * to crop x crop, jittered, normalised and sometimes partly occluded.  Only the window is evaluated: device work is
+ * proportional to the window areas and crop^2, no launch is sized by the frame.  frames uint8 [B,H,W,3] -> fp32 NCHW
+ * [B,3,crop,crop].
+ *
+ * rn_augment_crop_params (128 bytes, 8-byte aligned):
+ *   affine, rh, rw, flip, apply, order, factors   as in rn_augment_params
+ *   win[4]      minx, miny, cw, ch: the window in the rotated frame's coordinates; minx / miny may be negative and the window
+ *               may lie partly or wholly outside the frame; 1 <= cw, ch <= win_max
+ *   occluded    != 0: inside occlude[4] = x0, y0, x1, y1 (0 <= x0 <= x1 <= crop, likewise y; the end is exclusive) the output
+ *               is a raw value that replaces the normalised one (:588-592)
+ * table_x, table_y: the first resize, as for rn_augment_frames.  table_cx, table_cy int32 [B,crop,1+K]: the second resize
+ *   (cw -> crop horizontally, then ch -> crop vertically, uint8 between the passes), per output index the first source index
+ *   and K taps, zero beyond a row's own; K >= the largest ceil(max(size / crop, 1)) * 2 + 1 of the batch.  A pass whose size
+ *   does not change is skipped and its table is not read.
+ * noise: uint8 [B,H,W,3] pad bytes or null (the generator of rn_augment_frames, read only where the window needs it).
+ * occlusion: fp32 [B,3,crop,crop] read at the output coordinate inside occlude, or null: then the value is
+ *   mean[c] + std[c] z, z = sqrt(-2 ln u1) cos(2 pi u2) in fp32 with u1 = (k1 + 1) 2^-24, u2 = k2 2^-24, k1 = bits 40..63 and
+ *   k2 = bits 16..39 of splitmix64 of seed * 0x9E3779B97F4A7C15 + (the element's index in [B,3,crop,crop] | 2^63).
+ * win_max: at least the largest cw and ch of the batch (a record beyond it is clamped: wrong pixels, no access outside).
+ * workspace: rn_augment_crops_workspace_bytes(B, win_max, crop) bytes, 8-byte aligned.
+ * Five launches for the whole batch on the stream (window, resize h, resize v, contrast sum, finish), no host synchronisation. */
+typedef struct rn_augment_crop_params {
+    double affine[6];
+    int32_t rh, rw, flip, apply;
+    int32_t order[4];
+    int32_t win[4];
+    float factors[3];
+    int32_t occluded;
+    int32_t occlude[4];
+} rn_augment_crop_params;
+int64_t rn_augment_crops_workspace_bytes(int B, int win_max, int crop);
+int rn_augment_crops(const uint8_t *frames, int B, int H, int W, const rn_augment_crop_params *params, const int32_t *table_x,
+                     const int32_t *table_y, const int32_t *table_cx, const int32_t *table_cy, int K, int win_max, int crop,
+                     const uint8_t *noise, const float *occlusion, uint64_t seed, float mean0, float mean1, float mean2,
+                     float std0, float std1, float std2, void *workspace, float *out, void *stream);
+
 /* ---------------------------------------------------------------- convolution engine ----------------------
  * fp32 implicit-GEMM convolutions on the matrix cores (v_mfma_f32_32x32x2_f32).  Replaces nn.Conv2d +
  * BatchNorm2d(eval) + ReLU + residual add (D/utils.py:25-43, 60-80), PyramidFeatures (D/model.py:84-117) and

@@ -1060,7 +1060,7 @@ class _Recorder:
         np.random.normal, np.random.rand, np.random.randint, torch.rand = self.saved
 
 
-def augment_reference_dataset(tmp, cases):
+def augment_reference_dataset(tmp, cases, shapes=None, crop=0):
     """A temporary dataset in the reference's own format (PNG frames, labels.cpkl, camera_vps.cpkl) for the cases of
     tests/augment_cases.py (name, shape key, camera, boxes, seed), read by the reference's own Detection_Dataset.
     -> {name: (dataset, index)}"""
@@ -1074,7 +1074,7 @@ def augment_reference_dataset(tmp, cases):
     os.makedirs(os.path.join(tmp, "frames"), exist_ok=True)
     all_data, by_path = [], {}
     for i, (name, shape, camera, kind, seed) in enumerate(cases):
-        W, H = ac.SHAPES[shape]
+        W, H = (shapes or ac.SHAPES)[shape]
         path = os.path.join(tmp, "frames", "%s_0_%d.png" % (camera, i))
         Image.fromarray(ac.frame_bytes(name, W, H)).save(path)
         all_data.append([path, ac.boxes_rows(name, kind, W, H)])
@@ -1088,7 +1088,7 @@ def augment_reference_dataset(tmp, cases):
     try:
         for mode in ("train", "test"):                        # the two sides of its 90/10 split, from the same shuffle
             random.seed(0)
-            ds = ref.Detection_Dataset(tmp, mode=mode, CROP=0)
+            ds = ref.Detection_Dataset(tmp, mode=mode, CROP=crop)
             for idx, path in enumerate(ds.data):
                 name, kind = by_path[path]
                 if kind == "empty":                           # a frame whose label tensor is empty: the no_labels path (:311-313)
@@ -1199,6 +1199,180 @@ def gen_augment():
     np.savez_compressed(os.path.join(OUT, "augment.npz"), **out)
 
 
+# ----------------------------------------------------------------------------- crop-detector training batches
+class _CropRecorder(_Recorder):
+    """... and np.random.normal(size=2) (an array: both values, in order) and torch.normal (the occlusion's values)."""
+    def __enter__(self):
+        _Recorder.__enter__(self)
+        self.normals, self.saved_normal, normal = [], torch.normal, np.random.normal
+        np_draws = self.np_draws
+
+        def np_normal(*a, **k):
+            if "size" not in k:
+                return normal(*a, **k)
+            v = self.saved[0](*a, **k)                    # the unwrapped function: the wrapper cannot take an array
+            np_draws.extend(float(x) for x in v)
+            return v
+
+        def np_randint(*a, **k):                          # one argument or two, floats among them: as they are passed
+            v = self.saved[2](*a, **k)
+            np_draws.append(float(v))
+            return v
+
+        def t_normal(*a, **k):
+            v = self.saved_normal(*a, **k)
+            self.normals.append(v.clone())
+            return v
+        np.random.normal, np.random.randint, torch.normal = np_normal, np_randint, t_normal
+        return self
+
+    def __exit__(self, *exc):
+        _Recorder.__exit__(self, *exc)
+        torch.normal = self.saved_normal
+
+
+def augment_crop_reference_item(ds, idx, seed, cs):
+    """The reference's __getitem__ with CROP = cs under seeds: every draw, the locals that place the window, every
+    intermediate image of the crop branch, the occlusion's region and values, im_t and y."""
+    import random
+    from PIL import Image
+    import augment_cases as ac
+    import tv_pillow_stub
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    random.seed(seed)
+    del tv_pillow_stub.LOG[:]
+    ds.CROP = cs
+    seen = {}
+
+    def profile(frame, event, arg):
+        if event == "return" and frame.f_code.co_name == "__getitem__" and "centx" in frame.f_locals:
+            seen.update(frame.f_locals)
+    with _CropRecorder() as rec:
+        sys.setprofile(profile)
+        try:
+            im_t, y = ds[idx]
+        finally:
+            sys.setprofile(None)
+    log = list(tv_pillow_stub.LOG)
+    first = {}
+    for k, v in log:
+        first.setdefault(k, v)
+    camera = ds.data[idx].split("/")[-1].split("_")[0]
+    frame = np.array(Image.open(ds.data[idx]))
+    H, W = frame.shape[:2]
+    d = rec.np_draws
+    scale, aspect, flip, angle = max(1, d[0]), max(0.75, d[1]), d[2], d[3] * 40 - 20
+    assert first["rotate"][0] == angle and len(rec.noise) == 1 and ("hflip" in first) == (flip > 0.5)
+    resizes = [v for k, v in log if k == "resize"]
+    assert len(resizes) == 2 and resizes[1][0] == (cs, cs)
+    (rh, rw), _ = resizes[0]
+    win, cropped = first["crop"]
+    assert win == (seen["minx"], seen["miny"], seen["maxx"] - seen["minx"], seen["maxy"] - seen["miny"])
+    apply = first["apply"]
+    order, factors = first["jitter"] if apply else ([0, 1, 2, 3], [1.0, 1.0, 1.0])
+    steps = [v for k, v in log if k == "jitter_step"]
+    occlude_draw = float(seen["OCCLUDE"])
+    occluded = occlude_draw > 0.9
+    region, values = (0, 0, 0, 0), np.zeros((3, cs, cs), np.float32)
+    assert len(rec.normals) == (3 if occluded else 0)
+    if occluded:
+        region = tuple(int(v) for v in seen["region"])
+        x0, y0, x1, y1 = region
+        values[:, y0:y1, x0:x1] = t2n(torch.stack(rec.normals))
+        assert np.array_equal(t2n(im_t)[:, y0:y1, x0:x1], values[:, y0:y1, x0:x1])
+    out = dict(frame=frame, labels_in=t2n(ds.labels[idx]), camera=np.array(camera), vps=np.array(ac.VPS[camera], np.float64),
+               seed=np.array(seed), cs=np.array(cs), np_draws=np.array(d, np.float64),
+               scalars=np.array([scale, aspect, angle, occlude_draw], np.float64),
+               draws=np.array([rh, rw, int(flip > 0.5), apply, int(occluded)], np.int32),
+               order=np.array(order, np.int32), factors=np.array(factors, np.float64),
+               noise=ac.noise_bytes(t2n(rec.noise[0]).transpose(1, 2, 0)),
+               center=np.array([float(seen["centx"]), float(seen["centy"])], np.float64), size=np.array(float(seen["size"]), np.float64),
+               win=np.array(win, np.int64), window=cropped, second=resizes[1][1],
+               jitter_steps=np.stack(steps) if steps else np.zeros((0, cs, cs, 3), np.uint8),
+               region=np.array(region, np.int64), occlusion=values, im_t=t2n(im_t), y=t2n(y))
+    assert np.array_equal(first["to_tensor"], steps[-1] if steps else out["second"])
+    return out
+
+
+def augment_crop_features(name, kind, camera, o):
+    """What one golden item covers of the list the set must contain."""
+    rh, rw, flip, apply, occluded = (int(v) for v in o["draws"])
+    H, W = o["frame"].shape[:2]
+    minx, miny, cw, ch = (int(v) for v in o["win"])
+    cs = int(o["cs"])
+    f = {"flip%d" % flip, "jitter_applied" if apply else "jitter_skipped", "occluded" if occluded else "not_occluded"}
+    overlaps = minx < W and minx + cw > 0 and miny < H and miny + ch > 0
+    if not overlaps:
+        f.add("outside")
+    elif minx >= 0 and miny >= 0 and minx + cw <= W and miny + ch <= H:
+        f.add("inside")
+    else:
+        f |= {n for n, c in (("left", minx < 0), ("top", miny < 0), ("right", minx + cw > W), ("bottom", miny + ch > H)) if c}
+    if cw != ch:
+        f.add("non_square")
+    if max(cw, ch) / cs > 3:
+        f.add("shrink_above_3")
+        if o["window"].any():
+            f.add("shrink_above_3_of_content")
+    if max(cw, ch) < cs:
+        f.add("enlargement")
+    if minx < 0 or miny < 0:
+        f.add("negative_origin")
+    if rh < H and overlaps and miny + ch > rh and o["window"].any():
+        f.add("pad_noise")
+    if kind == "empty":
+        f.add("label_less_flipped" if flip else "label_less")
+    if kind == "none":
+        f.add("zero_row")
+    n_in = len(o["labels_in"])
+    kept = 0 if o["y"][0, 0] == -1 and o["y"][0, 20] == -1 else len(o["y"])
+    if kind not in ("empty", "none") and 0 < kept < n_in:
+        f.add("box_removed")
+    if kind not in ("empty", "none") and kept == 0:
+        f.add("all_removed")
+    if o["y"].dtype == np.float64:
+        f.add("y_fp64")
+        if cw != ch:
+            f.add("kept_in_non_square")
+    else:
+        f.add("y_fp32")
+    if camera == "p2c3":
+        f.add("p2c3")
+    return f
+
+
+AUGMENT_CROP_MUST_COVER = {"flip0", "flip1", "inside", "left", "top", "right", "bottom", "outside", "non_square", "shrink_above_3",
+                           "enlargement", "pad_noise", "label_less", "label_less_flipped", "zero_row", "box_removed", "all_removed",
+                           "jitter_applied", "jitter_skipped", "occluded", "not_occluded", "p2c3", "negative_origin", "y_fp64",
+                           "y_fp32", "shrink_above_3_of_content", "kept_in_non_square"}
+
+
+def gen_augment_crop():
+    """The reference's own Detection_Dataset.__getitem__ with CROP > 0 and collate (corrected_3D_dataset.py:296-402, 501-594,
+    714-741) on a temporary dataset, behind tools/tv_pillow_stub.py: the inputs, every draw, the window, the bytes at every
+    step of the crop branch, the occlusion, im_t and y of every case of tests/augment_crop_cases.py."""
+    import tempfile
+    import augment_crop_cases as cc
+    out, covered, items = {}, set(), {}
+    with tempfile.TemporaryDirectory() as tmp:
+        ref, found = augment_reference_dataset(tmp, [cc.case_golden(c) for c in cc.GOLDEN], cc.SHAPES, crop=24)
+        for name, shape, camera, kind, seed, cs in cc.GOLDEN:
+            o = augment_crop_reference_item(*found[name], seed, cs)
+            covered |= augment_crop_features(name, kind, camera, o)
+            items[name] = o
+            for k, v in o.items():
+                out["%s_%s" % (name, k)] = v
+    assert AUGMENT_CROP_MUST_COVER <= covered, AUGMENT_CROP_MUST_COVER - covered
+    for shape, cs in sorted({(c[1], c[5]) for c in cc.GOLDEN}):
+        names = [c[0] for c in cc.GOLDEN if (c[1], c[5]) == (shape, cs)]
+        ims, ys = ref.collate([(torch.from_numpy(items[n]["im_t"]), torch.from_numpy(items[n]["y"])) for n in names])
+        assert np.array_equal(t2n(ims), np.stack([items[n]["im_t"] for n in names]))
+        out["collate_%s%d_y" % (shape, cs)] = t2n(ys)
+    out["names"] = np.array([c[0] for c in cc.GOLDEN])
+    np.savez_compressed(os.path.join(OUT, "augment_crop.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -1215,7 +1389,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1250,6 +1424,8 @@ def main():
         gen_csv_eval()
     if "augment" in which:
         gen_augment()
+    if "augment_crop" in which:
+        gen_augment_crop()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods

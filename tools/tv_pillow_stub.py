@@ -1,7 +1,7 @@
 """A stand-in for the part of ``torchvision.transforms`` that the reference's training loader uses, as thin Pillow wrappers
 (torchvision is not installed; its PIL backend is itself a thin wrapper over Pillow).  Only tools/make_golden.py installs it.
 
-Written from torchvision's published behaviour: ``resize`` / ``hflip`` / ``rotate`` / ``adjust_*`` call the Pillow method of the
+Written from torchvision's published behaviour: ``resize`` / ``crop`` / ``hflip`` / ``rotate`` / ``adjust_*`` call the Pillow method of the
 same meaning; ``to_tensor`` is uint8 / 255 in fp32; ``to_pil_image`` is ``mul(255).byte()``; ``Normalize`` is ``sub_(mean).div_(std)``;
 ``RandomApply`` skips when ``p < torch.rand(1)``; ``ColorJitter.get_params`` draws ``randperm(4)`` and then one ``uniform_`` per
 active factor (hue = 0 is inactive: no draw, no pass).  What the draws are is therefore "parity unpinned".
@@ -24,6 +24,12 @@ def _u8(img):
 def resize(img, size, interpolation=Image.BILINEAR):
     out = img.resize(tuple(size[::-1]), interpolation)
     LOG.append(("resize", (tuple(int(s) for s in size), _u8(out))))
+    return out
+
+
+def crop(img, top, left, height, width):
+    out = img.crop((left, top, left + width, top + height))
+    LOG.append(("crop", ((int(left), int(top), int(width), int(height)), _u8(out))))
     return out
 
 
@@ -136,7 +142,7 @@ def install():
     tv = sys.modules.get("torchvision") or types.ModuleType("torchvision")
     tvt = types.ModuleType("torchvision.transforms")
     tvf = types.ModuleType("torchvision.transforms.functional")
-    for n in ("resize", "to_tensor", "to_pil_image", "hflip", "rotate", "adjust_brightness", "adjust_contrast",
+    for n in ("resize", "crop", "to_tensor", "to_pil_image", "hflip", "rotate", "adjust_brightness", "adjust_contrast",
               "adjust_saturation", "normalize"):
         setattr(tvf, n, getattr(me, n))
     for n in ("Compose", "RandomApply", "ColorJitter", "ToTensor", "Normalize"):
