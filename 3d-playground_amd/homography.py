@@ -10,14 +10,32 @@ numpy matrices; inputs and outputs are CPU tensors exactly as every caller of th
 ``device`` (default cuda:0).  A device tensor input stays on its device.
 
 Out of scope here: correspondence fitting (``add_correspondence`` needs cv2.findHomography),
-vanishing-point estimation, ``scale_Z``, CSV loading and plotting -- one-off set-up code that needs OpenCV and
-data files the reference does not ship.  Populate ``correspondence`` directly, as the tracker does
-(MC3D_crop_tracker.py:1561).
+vanishing-point estimation, ``scale_Z`` and plotting -- one-off set-up code that needs OpenCV and data files the
+reference does not ship.  Populate ``correspondence`` directly, as the tracker does (MC3D_crop_tracker.py:1561).
+``load_i24_csv`` (homography.py:750-791) is here: pure ``csv``, host side.
 """
+import csv
+
 import numpy as np
 import torch
 
 from retinanet_mi355x import ops as _ops
+
+
+def load_i24_csv(file):
+    """homography.py:750-791: -> (the ``Frame #`` header row, {frame index: [row, ...]}).  Lines up to and including the row
+    whose first cell is ``Frame #`` are headers; empty rows are skipped; rows of one frame index gather under one key in
+    file order, wherever they appear."""
+    with open(file, "r") as f:
+        rows = list(csv.reader(f))
+    data, headers, in_headers = {}, None, True
+    for row in rows:
+        if in_headers:
+            headers = row
+            in_headers = not (len(row) > 0 and row[0] == "Frame #")
+        elif len(row) > 0:
+            data.setdefault(int(row[0]), []).append(row)
+    return headers, data
 
 
 class Homography():

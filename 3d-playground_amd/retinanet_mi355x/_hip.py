@@ -79,6 +79,12 @@ SIGNATURES = {
     "rn_augment_crops_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "rn_augment_crops": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, ctypes.c_uint64]
                          + [c_f32] * 6 + [c_vp, c_vp, c_vp]),
+    "rn_mot_prepare": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64] + [c_vp] * 7),
+    "rn_mot_iou": (c_i32, [c_vp] * 5 + [c_i64, c_i64, c_vp, c_vp]),
+    "rn_mot_assign": (c_i32, [c_vp] * 5 + [c_i64] * 4 + [c_vp] * 5),
+    "rn_mot_frame_metrics": (c_i32, [c_vp] * 5 + [c_i64, c_i64, c_vp, c_vp, c_vp, c_f64] + [c_vp] * 19),
+    "rn_mot_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rn_mot_reduce": (c_i32, [c_i64, c_i64] + [c_vp] * 16 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
 }
 
 class ConvDesc(ctypes.Structure):

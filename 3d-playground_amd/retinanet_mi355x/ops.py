@@ -658,6 +658,158 @@ def linear_sum_assignment(cost):
     return rows, row_match[rows].long()
 
 
+# ------------------------------------------------------------------------------------------------ tracking evaluation
+MOT_MAX = 512                      # RN_MOT_MAX: objects of one frame on either side
+MOT_MAX_IDS = 16384                # RN_MOT_MAX_IDS
+MOT_RESULT = 152                   # RN_MOT_RESULT
+MOT_OK, MOT_INVALID, MOT_INFEASIBLE, MOT_TOO_LARGE = 0, 1, 2, 3
+
+
+def _mot_typed(what, *specs):
+    for name, t, dtype in specs:
+        if t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError("%s: %s is a contiguous %s tensor, got %s" % (what, name, dtype, t.dtype))
+
+
+def mot_prepare(gt_im, gt_h0, gt_vel, pred_state, H, P):
+    """mot_evaluator.py:155-215 for all objects of a sequence: gt_im fp64 [G,8,2], gt_h0 / gt_vel fp32 [G], pred_state fp32
+    [M,7], H fp64 [3,3], P fp64 [3,4] -> (gt_state fp32 [G,7], gt_box fp32 [G,4], pred_box fp32 [M,4], pred_im fp64 [M,8,2])."""
+    lib = _hip.load()
+    _hip.need_gpu(gt_im, gt_h0, gt_vel, pred_state, H, P)
+    _mot_typed("mot_prepare", ("gt_im", gt_im, torch.float64), ("gt_h0", gt_h0, torch.float32), ("gt_vel", gt_vel, torch.float32),
+               ("pred_state", pred_state, torch.float32), ("H", H, torch.float64), ("P", P, torch.float64))
+    G, M, dev = gt_im.shape[0], pred_state.shape[0], gt_im.device
+    if gt_im.numel() != G * 16 or gt_h0.numel() != G or gt_vel.numel() != G or pred_state.numel() != M * 7 or H.numel() != 9 \
+            or P.numel() != 12:
+        raise RuntimeError("mot_prepare: gt_im [G,8,2], gt_h0 [G], gt_vel [G], pred_state [M,7], H [3,3], P [3,4]")
+    gt_state = torch.empty((G, 7), dtype=torch.float32, device=dev)
+    gt_box = torch.empty((G, 4), dtype=torch.float32, device=dev)
+    pred_box = torch.empty((M, 4), dtype=torch.float32, device=dev)
+    pred_im = torch.empty((M, 8, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_prepare(_hip.ptr(gt_im), _hip.ptr(gt_h0), _hip.ptr(gt_vel), G, _hip.ptr(pred_state), M, H.data_ptr(),
+                                      P.data_ptr(), gt_state.data_ptr(), gt_box.data_ptr(), pred_box.data_ptr(), pred_im.data_ptr(),
+                                      _hip.stream()), "rn_mot_prepare")
+    return gt_state, gt_box, pred_box, pred_im
+
+
+def mot_offsets(n_gt, n_pred, device):
+    """Per-frame object counts (host sequences) -> (gt_off, pr_off int32 [F+1], iou_off int64 [F+1], slot_off int32 [F+1]) on
+    the device and the host totals (max_n, max_cells, cells, S).  A frame above MOT_MAX raises here: nothing is launched."""
+    ng, npr = np.asarray(n_gt, np.int64).reshape(-1), np.asarray(n_pred, np.int64).reshape(-1)
+    if ng.shape != npr.shape or (ng < 0).any() or (npr < 0).any():
+        raise RuntimeError("mot_offsets: one non-negative count per frame on both sides")
+    max_n = int(max(ng.max(initial=0), npr.max(initial=0)))
+    if max_n > MOT_MAX:
+        raise RuntimeError("a frame holds %d objects; the assignment takes at most MOT_MAX = %d per side" % (max_n, MOT_MAX))
+    cells, slots = ng * npr, np.minimum(ng, npr)
+    if ng.sum() >= 2 ** 31 or npr.sum() >= 2 ** 31:
+        raise RuntimeError("mot_offsets: more than 2^31 objects")
+
+    def off(x, dtype):
+        return torch.from_numpy(np.concatenate(([0], np.cumsum(x))).astype(dtype)).to(device)
+    return ((off(ng, np.int32), off(npr, np.int32), off(cells, np.int64), off(slots, np.int32)),
+            (max_n, int(cells.max(initial=0)), int(cells.sum()), int(slots.sum())))
+
+
+def mot_iou(gt_box, pred_box, offsets, totals):
+    """Every frame's IoU matrix in self.iou's fp32 arithmetic (mot_evaluator.py:87-118, 219-222) -> flat fp64 [cells]."""
+    lib = _hip.load()
+    _hip.need_gpu(gt_box, pred_box, *offsets)
+    _mot_typed("mot_iou", ("gt_box", gt_box, torch.float32), ("pred_box", pred_box, torch.float32))
+    gt_off, pr_off, iou_off, _ = offsets
+    max_n, max_cells, cells, _ = totals
+    iou = torch.empty(cells, dtype=torch.float64, device=gt_box.device)
+    with torch.cuda.device(gt_box.device):
+        _hip.check(lib.rn_mot_iou(_hip.ptr(gt_box), _hip.ptr(pred_box), gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(),
+                                  gt_off.numel() - 1, max_cells, _hip.ptr(iou), _hip.stream()), "rn_mot_iou")
+    return iou
+
+
+def mot_assign(iou, offsets, totals, M):
+    """linear_sum_assignment(ious, maximize=True) of every frame (mot_evaluator.py:225) ->
+    (slot_row, slot_col int32 [S], pred_assigned uint8 [M], frame_status int32 [F])."""
+    lib = _hip.load()
+    _hip.need_gpu(iou, *offsets)
+    _mot_typed("mot_assign", ("iou", iou, torch.float64))
+    gt_off, pr_off, iou_off, slot_off = offsets
+    max_n, _, cells, S = totals
+    if iou.numel() != cells:
+        raise RuntimeError("mot_assign: iou holds %d cells, the offsets describe %d" % (iou.numel(), cells))
+    if max_n > MOT_MAX:
+        raise RuntimeError("a frame holds %d objects; the assignment takes at most MOT_MAX = %d per side" % (max_n, MOT_MAX))
+    dev, F = iou.device, gt_off.numel() - 1
+    slot_row = torch.empty(S, dtype=torch.int32, device=dev)
+    slot_col = torch.empty(S, dtype=torch.int32, device=dev)
+    pred_assigned = torch.empty(M, dtype=torch.uint8, device=dev)
+    frame_status = torch.zeros(F, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_assign(_hip.ptr(iou), gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(), slot_off.data_ptr(), F,
+                                     max_n, S, M, _hip.ptr(slot_row), _hip.ptr(slot_col), _hip.ptr(pred_assigned),
+                                     _hip.ptr(frame_status), _hip.stream()), "rn_mot_assign")
+    return slot_row, slot_col, pred_assigned, frame_status
+
+
+def mot_frame_metrics(iou, offsets, totals, assigned, match_iou, gt_state, pred_state, gt_im, pred_im, gt_cls, pred_cls, gt_id, pred_id):
+    """mot_evaluator.py:229-238, 283-290, 301-341 per frame.  assigned = what mot_assign returns.  ->
+    (slot_iou fp64 [S], slot_gid, slot_pid int32 [S] (-1 below match_iou), state_err fp32 [S,7], bot, top fp64 [S], cell uint8
+    [S], frame_edge, frame_match int32 [F])."""
+    lib = _hip.load()
+    slot_row, slot_col, pred_assigned, frame_status = assigned
+    gt_off, pr_off, iou_off, slot_off = offsets
+    _hip.need_gpu(iou, gt_state, pred_state, gt_im, pred_im, gt_cls, pred_cls, gt_id, pred_id, *assigned)
+    _mot_typed("mot_frame_metrics", ("iou", iou, torch.float64), ("gt_state", gt_state, torch.float32),
+               ("pred_state", pred_state, torch.float32), ("gt_im", gt_im, torch.float64), ("pred_im", pred_im, torch.float64),
+               ("gt_cls", gt_cls, torch.int32), ("pred_cls", pred_cls, torch.int32), ("gt_id", gt_id, torch.int32),
+               ("pred_id", pred_id, torch.int32))
+    G, M = gt_id.numel(), pred_id.numel()
+    if gt_state.numel() != G * 7 or pred_state.numel() != M * 7 or gt_im.numel() != G * 16 or pred_im.numel() != M * 16 \
+            or gt_cls.numel() != G or pred_cls.numel() != M or pred_assigned.numel() != M:
+        raise RuntimeError("mot_frame_metrics: per-object arrays disagree on G = %d / M = %d" % (G, M))
+    dev, F, S = iou.device, gt_off.numel() - 1, totals[3]
+    slot_iou = torch.empty(S, dtype=torch.float64, device=dev)
+    slot_gid = torch.empty(S, dtype=torch.int32, device=dev)
+    slot_pid = torch.empty(S, dtype=torch.int32, device=dev)
+    state_err = torch.empty((S, 7), dtype=torch.float32, device=dev)
+    bot = torch.empty(S, dtype=torch.float64, device=dev)
+    top = torch.empty(S, dtype=torch.float64, device=dev)
+    cell = torch.empty(S, dtype=torch.uint8, device=dev)
+    frame_edge = torch.zeros(F, dtype=torch.int32, device=dev)
+    frame_match = torch.zeros(F, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_frame_metrics(
+            _hip.ptr(iou), gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(), slot_off.data_ptr(), F, S, _hip.ptr(slot_row),
+            _hip.ptr(slot_col), _hip.ptr(frame_status), float(match_iou), _hip.ptr(gt_state), _hip.ptr(pred_state), _hip.ptr(gt_im),
+            _hip.ptr(pred_im), _hip.ptr(gt_cls), _hip.ptr(pred_cls), _hip.ptr(gt_id), _hip.ptr(pred_id), _hip.ptr(pred_assigned),
+            _hip.ptr(slot_iou), _hip.ptr(slot_gid), _hip.ptr(slot_pid), _hip.ptr(state_err), _hip.ptr(bot), _hip.ptr(top),
+            _hip.ptr(cell), _hip.ptr(frame_edge), _hip.ptr(frame_match), _hip.stream()), "rn_mot_frame_metrics")
+    return slot_iou, slot_gid, slot_pid, state_err, bot, top, cell, frame_edge, frame_match
+
+
+def mot_reduce(offsets, totals, assigned, per_slot, gt_id, pred_id, n_gid, n_pid):
+    """The sequence-order walk and the sums (mot_evaluator.py:135-152, 294-299, 348-397) -> result fp64 [MOT_RESULT] on the
+    device (layout: include/retinanet_mi355x.h).  gt_id / pred_id are dense indices below n_gid / n_pid; the kernel leaves an id
+    outside that range out of every count instead of indexing with it, so nothing here reads the device."""
+    lib = _hip.load()
+    gt_off, pr_off, iou_off, slot_off = offsets
+    slot_row, slot_col, pred_assigned, frame_status = assigned
+    slot_iou, slot_gid, slot_pid, state_err, bot, top, cell, frame_edge, frame_match = per_slot
+    _hip.need_gpu(gt_id, pred_id, *per_slot)
+    _mot_typed("mot_reduce", ("gt_id", gt_id, torch.int32), ("pred_id", pred_id, torch.int32))
+    if n_gid > MOT_MAX_IDS or n_pid > MOT_MAX_IDS:
+        raise RuntimeError("mot_reduce takes at most %d distinct ids per side, got %d and %d" % (MOT_MAX_IDS, n_gid, n_pid))
+    dev, F, S = gt_id.device, gt_off.numel() - 1, totals[3]
+    ws = torch.empty(max(16, lib.rn_mot_workspace_bytes(n_gid, n_pid)), dtype=torch.uint8, device=dev)
+    result = torch.empty(MOT_RESULT, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_reduce(F, S, gt_off.data_ptr(), pr_off.data_ptr(), slot_off.data_ptr(), _hip.ptr(frame_status),
+                                     _hip.ptr(frame_edge), _hip.ptr(frame_match), _hip.ptr(slot_row), _hip.ptr(slot_iou),
+                                     _hip.ptr(slot_gid), _hip.ptr(slot_pid), _hip.ptr(state_err), _hip.ptr(bot), _hip.ptr(top),
+                                     _hip.ptr(cell), _hip.ptr(gt_id), _hip.ptr(pred_id), n_gid, n_pid, ws.data_ptr(),
+                                     result.data_ptr(), _hip.stream()), "rn_mot_reduce")
+    return result
+
+
 # ------------------------------------------------------------------------------------------------ time stamp bias
 TS_MAX_CAMS = 1024                 # RN_TS_MAX_CAMS
 TS_OK, TS_OVERFLOW, TS_BAD_CAMERA = 0, 1, 2

@@ -27,11 +27,13 @@ Operator                                         reference code it stands for
   eval_select(scores, labels, boxes, table, ..)  _get_detections' selection (in place)  R/csv_eval.py:102-123
   eval_match(table, img_rows, ann_box, off, ..)  evaluate's greedy matching             R/csv_eval.py:189-213, 21-35
   eval_ap(table, state, tp, num_annotations)     per-class sort + _compute_ap           R/csv_eval.py:216-235, 38-62
+  mot_prepare / mot_iou / mot_assign /           MOT_Evaluator.evaluate, all frames    mot_evaluator.py:120-412
+  mot_frame_metrics / mot_reduce
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
 """
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -293,6 +295,82 @@ def _(table, state, tp, num_annotations):
     return (table.new_empty((num_annotations.shape[0],), dtype=torch.float64), table.new_empty((table.shape[0],), dtype=torch.int32))
 
 
+# ---- tracking evaluation (MOT metrics): the per-frame counts travel as host int lists, as ops.mot_offsets takes them
+def _mot_layout(n_gt, n_pred, device):
+    return ops.mot_offsets(n_gt, n_pred, device)
+
+
+@_lib.custom_op(NS + "::mot_prepare", mutates_args=(), device_types="cuda")
+def mot_prepare(gt_im: torch.Tensor, gt_h0: torch.Tensor, gt_vel: torch.Tensor, pred_state: torch.Tensor, H: torch.Tensor,
+                P: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.mot_prepare(gt_im, gt_h0, gt_vel, pred_state, H, P)
+
+
+@mot_prepare.register_fake
+def _(gt_im, gt_h0, gt_vel, pred_state, H, P):
+    G, M = gt_im.shape[0], pred_state.shape[0]
+    return (gt_im.new_empty((G, 7), dtype=torch.float32), gt_im.new_empty((G, 4), dtype=torch.float32),
+            gt_im.new_empty((M, 4), dtype=torch.float32), gt_im.new_empty((M, 8, 2), dtype=torch.float64))
+
+
+@_lib.custom_op(NS + "::mot_iou", mutates_args=(), device_types="cuda")
+def mot_iou(gt_box: torch.Tensor, pred_box: torch.Tensor, n_gt: List[int], n_pred: List[int]) -> torch.Tensor:
+    offsets, totals = _mot_layout(n_gt, n_pred, gt_box.device)
+    return ops.mot_iou(gt_box, pred_box, offsets, totals)
+
+
+@mot_iou.register_fake
+def _(gt_box, pred_box, n_gt, n_pred):
+    return gt_box.new_empty((sum(a * b for a, b in zip(n_gt, n_pred)),), dtype=torch.float64)
+
+
+@_lib.custom_op(NS + "::mot_assign", mutates_args=(), device_types="cuda")
+def mot_assign(iou: torch.Tensor, n_gt: List[int], n_pred: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    offsets, totals = _mot_layout(n_gt, n_pred, iou.device)
+    return ops.mot_assign(iou, offsets, totals, sum(n_pred))
+
+
+@mot_assign.register_fake
+def _(iou, n_gt, n_pred):
+    S = sum(min(a, b) for a, b in zip(n_gt, n_pred))
+    return (iou.new_empty((S,), dtype=torch.int32), iou.new_empty((S,), dtype=torch.int32),
+            iou.new_empty((sum(n_pred),), dtype=torch.uint8), iou.new_empty((len(n_gt),), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::mot_frame_metrics", mutates_args=(), device_types="cuda")
+def mot_frame_metrics(iou: torch.Tensor, n_gt: List[int], n_pred: List[int], slot_row: torch.Tensor, slot_col: torch.Tensor,
+                      pred_assigned: torch.Tensor, frame_status: torch.Tensor, match_iou: float, gt_state: torch.Tensor,
+                      pred_state: torch.Tensor, gt_im: torch.Tensor, pred_im: torch.Tensor, gt_cls: torch.Tensor,
+                      pred_cls: torch.Tensor, gt_id: torch.Tensor, pred_id: torch.Tensor) -> List[torch.Tensor]:
+    offsets, totals = _mot_layout(n_gt, n_pred, iou.device)
+    return list(ops.mot_frame_metrics(iou, offsets, totals, (slot_row, slot_col, pred_assigned, frame_status), match_iou, gt_state,
+                                      pred_state, gt_im, pred_im, gt_cls, pred_cls, gt_id, pred_id))
+
+
+@mot_frame_metrics.register_fake
+def _(iou, n_gt, n_pred, slot_row, slot_col, pred_assigned, frame_status, match_iou, gt_state, pred_state, gt_im, pred_im, gt_cls,
+      pred_cls, gt_id, pred_id):
+    S, F = slot_row.shape[0], len(n_gt)
+    e = iou.new_empty
+    return [e((S,), dtype=torch.float64), e((S,), dtype=torch.int32), e((S,), dtype=torch.int32), e((S, 7), dtype=torch.float32),
+            e((S,), dtype=torch.float64), e((S,), dtype=torch.float64), e((S,), dtype=torch.uint8), e((F,), dtype=torch.int32),
+            e((F,), dtype=torch.int32)]
+
+
+@_lib.custom_op(NS + "::mot_reduce", mutates_args=(), device_types="cuda")
+def mot_reduce(n_gt: List[int], n_pred: List[int], slot_row: torch.Tensor, slot_col: torch.Tensor, pred_assigned: torch.Tensor,
+               frame_status: torch.Tensor, per_slot: List[torch.Tensor], gt_id: torch.Tensor, pred_id: torch.Tensor, n_gid: int,
+               n_pid: int) -> torch.Tensor:
+    offsets, totals = _mot_layout(n_gt, n_pred, gt_id.device)
+    return ops.mot_reduce(offsets, totals, (slot_row, slot_col, pred_assigned, frame_status), tuple(per_slot), gt_id, pred_id,
+                          n_gid, n_pid)
+
+
+@mot_reduce.register_fake
+def _(n_gt, n_pred, slot_row, slot_col, pred_assigned, frame_status, per_slot, gt_id, pred_id, n_gid, n_pid):
+    return gt_id.new_empty((ops.MOT_RESULT,), dtype=torch.float64)
+
+
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
              "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "augment_frames", "augment_crops",
-             "eval_select", "eval_match", "eval_ap")
+             "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce")

@@ -870,6 +870,62 @@ int rn_opt_clip_adam_dev(const void *tensor_table, const void *chunk_table, int 
 int rn_opt_clip_adam_hp(const void *tensor_table, const void *chunk_table, int n_chunks, const float *hp, int *step_dev,
                         int write_clipped, void *workspace, float *total_norm, void *stream);
 
+/* ---------------------------------------------------------------- tracking evaluation (MOT metrics) --------
+ * MOT_Evaluator.evaluate (mot_evaluator.py:120-412) over all frames of a sequence at once.  The host packs the frames in
+ * increasing order into flat arrays: gt_off / pr_off int32 [F+1] (objects of frame f; 0 objects = the frame is missing on
+ * that side), iou_off int64 [F+1] (prefix sum of n_gt * n_pred), slot_off int32 [F+1] (prefix sum of min(n_gt, n_pred): one
+ * slot per assigned pair).  Ids and classes are dense int32 indices (class -1 = not in class_dict).  No synchronisation.
+ *   rn_mot_prepare        replaces :155-179 and :182-195 and the footprints of :201-215.  gt_im fp64 [G,8,2], gt_h0 fp32 [G]
+ *                         (guess_heights), gt_vel fp32 [G], pred_state fp32 [M,7], H fp64 [9], P fp64 [12] ->
+ *                         gt_state fp32 [G,7], gt_box / pred_box fp32 [G,4] / [M,4] (xmin ymin xmax ymax), pred_im fp64 [M,8,2]
+ *   rn_mot_iou            replaces the double loop over self.iou (:87-118, 219-222): fp32 arithmetic, fp64 matrix.
+ *                         max_cells = the largest n_gt * n_pred of a frame
+ *   rn_mot_assign         replaces linear_sum_assignment(ious, maximize=True) (:225) for every frame: slot_row / slot_col
+ *                         int32 [S] (ground-truth row ascending, -1 = no pair), pred_assigned uint8 [M], frame_status int32
+ *                         [F]: RN_MOT_OK, RN_MOT_INVALID (a NaN or +inf IoU), RN_MOT_INFEASIBLE, RN_MOT_TOO_LARGE.
+ *                         max_n = the largest n_gt or n_pred of a frame; above RN_MOT_MAX the call returns RN_EINVAL and
+ *                         launches nothing
+ *   rn_mot_frame_metrics  replaces :229-238, 283-290, 301-341 per frame: per slot the IoU, the matched ids (slot_gid /
+ *                         slot_pid, -1 = below match_iou), state_err fp32 [S,7], im_bot_err / im_top_err fp64 [S], the
+ *                         confusion cell uint8 [S] (10 * gt + pred); per frame the outside-the-frame count and the matches
+ *   rn_mot_reduce         replaces :135-152, 294-299 and :348-397: result fp64 [RN_MOT_RESULT] =
+ *                         [0..11] TP FP FN "FP edge-case" "FP @ 0.2" "FN @ 0.2" unique-gt unique-pred fragmentations
+ *                         ID-switches assigned-pairs status, [12] the first frame with a status,
+ *                         [16 + 3q ..] (count, sum, sum of squared deviations) of figure q = pre-threshold IoU, match IoU,
+ *                         state_err columns 0..6, bottom, top -- fp64 in a fixed order (slot k to partial k % 256, the
+ *                         partials in increasing order), [52..151] the confusion matrix [10,10].
+ *                         n_gid / n_pid = the number of distinct ids (<= RN_MOT_MAX_IDS); workspace:
+ *                         rn_mot_workspace_bytes(n_gid, n_pid) bytes. */
+#define RN_MOT_MAX 512          /* objects of one frame on either side: the solver's vectors (42 B / object) stay in LDS */
+#define RN_MOT_MAX_IDS 16384
+#define RN_MOT_RESULT 152
+#define RN_MOT_OK 0
+#define RN_MOT_INVALID 1
+#define RN_MOT_INFEASIBLE 2
+#define RN_MOT_TOO_LARGE 3
+int rn_mot_prepare(const double *gt_im, const float *gt_h0, const float *gt_vel, int64_t G, const float *pred_state,
+                   int64_t M, const double *H, const double *P, float *gt_state, float *gt_box, float *pred_box,
+                   double *pred_im, void *stream);
+int rn_mot_iou(const float *gt_box, const float *pred_box, const int32_t *gt_off, const int32_t *pr_off,
+               const int64_t *iou_off, int64_t F, int64_t max_cells, double *iou, void *stream);
+int rn_mot_assign(const double *iou, const int32_t *gt_off, const int32_t *pr_off, const int64_t *iou_off,
+                  const int32_t *slot_off, int64_t F, int64_t max_n, int64_t S, int64_t M, int32_t *slot_row,
+                  int32_t *slot_col, uint8_t *pred_assigned, int32_t *frame_status, void *stream);
+int rn_mot_frame_metrics(const double *iou, const int32_t *gt_off, const int32_t *pr_off, const int64_t *iou_off,
+                         const int32_t *slot_off, int64_t F, int64_t S, const int32_t *slot_row, const int32_t *slot_col,
+                         const int32_t *frame_status, double match_iou, const float *gt_state, const float *pred_state,
+                         const double *gt_im, const double *pred_im, const int32_t *gt_cls, const int32_t *pred_cls,
+                         const int32_t *gt_id, const int32_t *pred_id, const uint8_t *pred_assigned, double *slot_iou,
+                         int32_t *slot_gid, int32_t *slot_pid, float *slot_state_err, double *slot_bot, double *slot_top,
+                         uint8_t *slot_cls, int32_t *frame_edge, int32_t *frame_match, void *stream);
+int64_t rn_mot_workspace_bytes(int64_t n_gid, int64_t n_pid);
+int rn_mot_reduce(int64_t F, int64_t S, const int32_t *gt_off, const int32_t *pr_off, const int32_t *slot_off,
+                  const int32_t *frame_status, const int32_t *frame_edge, const int32_t *frame_match,
+                  const int32_t *slot_row, const double *slot_iou, const int32_t *slot_gid, const int32_t *slot_pid,
+                  const float *slot_state_err, const double *slot_bot, const double *slot_top, const uint8_t *slot_cls,
+                  const int32_t *gt_id, const int32_t *pred_id, int64_t n_gid, int64_t n_pid, void *workspace,
+                  double *result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

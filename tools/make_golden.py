@@ -1372,6 +1372,148 @@ def gen_augment_crop():
     out["names"] = np.array([c[0] for c in cc.GOLDEN])
     np.savez_compressed(os.path.join(OUT, "augment_crop.npz"), **out)
 
+# ----------------------------------------------------------------------------- tracking evaluation (MOT metrics)
+MOT_FRAMES = 100                    # the result files are cut to frames below this (959 frames, ~7 rows each, in full)
+# name -> (prediction file, match_iou, cutoff_frame).  The 100-frame cases pin the restatement and feed the staged
+# comparison; the trackers drift apart after the first frames (most pairs stop overlapping and scipy's tie rule decides),
+# so the end-to-end comparison, which needs frames that stay decided under a last-bit change of the IoU, runs on the
+# "_first" cases: the longest prefixes in which every frame is stable (tests/test_mot_eval_host.py asserts it).
+MOT_CASES = {"p20_iou0": ("pred20", 0, MOT_FRAMES), "p20_iou51": ("pred20", 0.51, MOT_FRAMES),
+             "p90_iou0": ("pred90", 0, MOT_FRAMES), "p90_iou51": ("pred90", 0.51, MOT_FRAMES),
+             "p20_iou0_first": ("pred20", 0, 9), "p20_iou51_first": ("pred20", 0.51, 9),
+             "p90_iou0_first": ("pred90", 0, 5), "p90_iou51_first": ("pred90", 0.51, 5)}
+
+
+def _fit_projective(src, dst):
+    """The [3, k+1] matrix M with dst ~ M [src; 1] (k = 2: a plane homography, k = 3: a camera matrix): normalised DLT on
+    the normal equations.  Only elementwise numpy sums and a symmetric 9x9 / 12x12 eigenproblem, and the result is
+    rounded to 15 digits, so that it regenerates bit for bit."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+
+    def norm(x):
+        T = np.eye(x.shape[1] + 1)
+        s = float(np.round(x.std(0).mean(), 3))
+        T[:-1, :-1] /= s
+        T[:-1, -1] = -np.round(x.mean(0), 3) / s
+        return T
+    Ts, Td = norm(src), norm(dst)
+    s = (Ts[None] * np.concatenate((src, np.ones((len(src), 1))), 1)[:, None, :]).sum(2)
+    d = (Td[None] * np.concatenate((dst, np.ones((len(dst), 1))), 1)[:, None, :]).sum(2)
+    z = np.zeros_like(s)
+    A = np.concatenate((np.concatenate((s, z, -d[:, 0:1] * s), 1), np.concatenate((z, s, -d[:, 1:2] * s), 1)), 0)
+    N = (A[:, :, None] * A[:, None, :]).sum(0)
+    w, v = np.linalg.eigh((N + N.T) / 2)
+    M = np.linalg.inv(Td) @ v[:, 0].reshape(3, -1) @ Ts
+    M = M / M[2, -1]
+    return np.array([[float("%.14e" % x) for x in row] for row in M])
+
+
+def _fit_camera(rows):
+    """H (image -> road plane) and P (space -> image) of the camera that wrote the result file, from the file's own state
+    and image-corner columns.  The matrices of the homography fixture are synthetic: through them the file's image
+    corners land nowhere near its states and nothing overlaps."""
+    from oracle import homography as ohg
+    st = np.array([[r[c] for c in (39, 40, 43, 42, 44, 35)] for r in rows]).astype(float).astype(np.float32)
+    im = np.array([r[11:27] for r in rows]).astype(float).reshape(-1, 8, 2)
+    sp = ohg.state_to_space(st).astype(np.float64)
+    P = _fit_projective(sp.reshape(-1, 3), im.reshape(-1, 2))
+    H = _fit_projective(im[:, 0:4].reshape(-1, 2), sp[:, 0:4, 0:2].reshape(-1, 2))
+    assert np.abs(ohg.state_to_im(st, P) - im).max() < 0.05                                    # px; the file keeps fp32 states
+    assert np.abs(ohg.im_to_space(im, H, np.zeros(len(im)))[:, 0:4, 0:2] - sp[:, 0:4, 0:2]).max() < 1e-3     # ft
+    return H, P
+
+
+def _cut_csv(fn, frames):
+    """The header line and the rows of the first frames of one of the reference's result files, as bytes."""
+    keep = []
+    with open(os.path.join(REF, fn), newline="") as f:
+        for k, line in enumerate(f):
+            if k == 0 or (line.strip() and int(line.split(",", 1)[0]) < frames):
+                keep.append(line)
+    return np.frombuffer("".join(keep).encode(), np.uint8)
+
+
+def gen_mot_eval():
+    """The reference's MOT_Evaluator.evaluate on its own result files (data): 3D_tracking_results.csv as the ground truth
+    against the _20 and _90 files, cut to their first frames, through a Homography holding the camera fitted to the
+    ground-truth file itself (_fit_camera).  scipy's solver is wrapped to record each frame's IoU matrix and assignment."""
+    import contextlib
+    import io
+    import tempfile
+    for k in [k for k in sys.modules if k == "homography"]:
+        del sys.modules[k]
+    sys.path.insert(0, REF)
+    try:
+        hgmod = importlib.import_module("homography")
+        ev_mod = ref_module_from_file("ref_mot_evaluator", "mot_evaluator.py")
+    finally:
+        sys.path.remove(REF)
+    assert os.path.realpath(hgmod.__file__).startswith(os.path.realpath(REF) + os.sep)
+    del sys.modules["homography"]
+    hg = hgmod.Homography()
+    out = {}
+    files = {"gt": "3D_tracking_results.csv", "pred20": "3D_tracking_results_20.csv", "pred90": "3D_tracking_results_90.csv"}
+    solve = ev_mod.linear_sum_assignment
+    with tempfile.TemporaryDirectory() as tmp:
+        for key, fn in files.items():
+            out[key + "_csv"] = _cut_csv(fn, MOT_FRAMES)
+            with open(os.path.join(tmp, key + ".csv"), "wb") as f:
+                f.write(out[key + "_csv"].tobytes())
+        gt_rows = [r for rows in hgmod.load_i24_csv(os.path.join(tmp, "gt.csv"))[1].values() for r in rows]
+        H, P = _fit_camera(gt_rows)
+        hg.correspondence = {gt_rows[0][36]: {"P": P, "H": H, "H_inv": np.linalg.inv(H)}}
+        hg.default_correspondence = gt_rows[0][36]
+        out["P"], out["H"] = P, H
+        for case, (pkey, thr, frames) in MOT_CASES.items():
+            rec = []
+
+            def recording(ious, maximize=False):
+                a, b = solve(ious, maximize=maximize)
+                rec.append((ious.copy(), a.copy(), b.copy()))
+                return a, b
+            ev_mod.linear_sum_assignment = recording
+            ev = ev_mod.MOT_Evaluator(os.path.join(tmp, "gt.csv"), os.path.join(tmp, pkey + ".csv"), hg,
+                                      params={"match_iou": thr, "cutoff_frame": frames})
+            text = io.StringIO()
+            raised = False
+            with contextlib.redirect_stdout(text):
+                try:
+                    ev.evaluate()
+                except ZeroDivisionError:                   # TP = 0 (:360): the bookkeeping in ev.m is complete by then
+                    raised = True
+            ev_mod.linear_sum_assignment = solve
+            out[case + "_raises_zero_division"] = np.array(raised)
+            both = [f for f in range(frames) if f in ev.gt and f in ev.pred]
+            assert len(both) == len(rec)
+            out[case + "_iou_frames"] = np.array([[f, r[0].shape[0], r[0].shape[1]] for f, r in zip(both, rec)], np.int64)
+            out[case + "_iou"] = np.concatenate([r[0].reshape(-1) for r in rec])
+            out[case + "_assign"] = np.array([[f, i, j] for f, r in zip(both, rec) for i, j in zip(r[1], r[2])], np.int64)
+            m = ev.m
+            out[case + "_pre_thresh_iou"] = np.array(m["pre_thresh_IOU"], np.float64)
+            out[case + "_match_iou"] = np.array(m["match_IOU"], np.float64)
+            out[case + "_counters"] = np.array([m[k] for k in ("TP", "FP", "FN", "FP edge-case", "FP @ 0.2", "FN @ 0.2")], np.int64)
+            out[case + "_state_err"] = torch.stack(m["state_err"]).numpy() if m["state_err"] else np.zeros((0, 7), np.float32)
+            out[case + "_bot_err"] = torch.stack(m["im_bot_err"]).numpy() if m["im_bot_err"] else np.zeros(0, np.float64)
+            out[case + "_top_err"] = torch.stack(m["im_top_err"]).numpy() if m["im_top_err"] else np.zeros(0, np.float64)
+            assert out[case + "_state_err"].dtype == np.float32 and out[case + "_bot_err"].dtype == np.float64
+            out[case + "_ids"] = np.array([[g, p] for g, v in m["ids"].items() for p in v], np.int64).reshape(-1, 2)
+            out[case + "_gt_ids"] = np.array(m["gt_ids"], np.int64)
+            out[case + "_pred_ids"] = np.array(m["pred_ids"], np.int64)
+            out[case + "_confusion"] = np.asarray(m["cls"], np.int64)
+            if raised:
+                continue
+            scalar = [k for k, v in ev.metrics.items() if not isinstance(v, tuple)]
+            pair = [k for k, v in ev.metrics.items() if isinstance(v, tuple)]
+            out[case + "_metric_names"] = np.array(scalar)
+            out[case + "_metric_values"] = np.array([float(ev.metrics[k]) for k in scalar], np.float64)
+            out[case + "_figure_names"] = np.array(pair)
+            out[case + "_figure_values"] = np.array([[float(ev.metrics[k][0]), float(ev.metrics[k][1])] for k in pair], np.float64)
+            out[case + "_figure_is_f32"] = np.array([isinstance(ev.metrics[k][0], torch.Tensor) and ev.metrics[k][0].dtype == torch.float32
+                                                    for k in pair])
+            table = text.getvalue()
+            out[case + "_table"] = np.frombuffer(table[table.index("\n\n"):].encode(), np.uint8)
+    np.savez_compressed(os.path.join(OUT, "mot_eval.npz"), **out)
+
 
 def main():
     if not os.path.isdir(REF):
@@ -1389,7 +1531,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1426,6 +1568,8 @@ def main():
         gen_augment()
     if "augment_crop" in which:
         gen_augment_crop()
+    if "mot_eval" in which:
+        gen_mot_eval()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
