@@ -85,6 +85,10 @@ SIGNATURES = {
     "rn_mot_frame_metrics": (c_i32, [c_vp] * 5 + [c_i64, c_i64, c_vp, c_vp, c_vp, c_f64] + [c_vp] * 19),
     "rn_mot_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rn_mot_reduce": (c_i32, [c_i64, c_i64] + [c_vp] * 16 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rn_vanishing_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rn_hg_reproj_error": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "rn_hg_scale_z": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rn_fit_homography": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
 }
 
 class ConvDesc(ctypes.Structure):

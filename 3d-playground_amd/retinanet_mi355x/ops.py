@@ -1248,3 +1248,101 @@ def crop_select(reg_boxes, cls, crop_bx, cam_idxs, pre_loc, H1, H2, P1, P2, cs=1
                                           H1.shape[0], n, A, C, float(cs), int(cd_max), float(W), st.data_ptr(), oc.data_ptr(),
                                           of.data_ptr(), _hip.stream()), "rn_crop_select")
     return st, oc, of
+
+
+# ------------------------------------------------------------------------------------------------ camera calibration
+VP_LEVELS = 16
+VP_FEW_LINES, VP_BAD_START, VP_LONG_AXIS, VP_BAD_OFFSETS = 1, 2, 4, 8
+SZ_MAX_ITERS = 64
+SZ_BAD_FIRST_STEP, SZ_NO_WINNER, SZ_TOO_MANY = 1, 2, 4
+FIT_FEW_POINTS, FIT_DEGENERATE, FIT_NOT_FINITE, FIT_BAD_OFFSETS = 1, 2, 4, 8
+
+
+def _csr(offsets, what):
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 2:
+        raise RuntimeError("%s: offsets are int64 [sets + 1], got %s %s" % (what, offsets.dtype, tuple(offsets.shape)))
+    return offsets.contiguous()
+
+
+def vanishing_points(lines, offsets):
+    """find_vanishing_point (homography.py:96-154) of every line set in one launch, see include/retinanet_mi355x.h.
+    lines fp64 [N,4], offsets int64 [S+1] (CSR row ranges; a range outside the N rows sets the VP_BAD_OFFSETS bit) ->
+    (out fp64 [S,3] = (px, py, best distance), trace fp64 [S,16,3], status int32 [S]); nothing is synchronised."""
+    lib = _hip.load()
+    _hip.need_gpu(lines, offsets)
+    if lines.dim() != 2 or lines.shape[1] != 4 or lines.dtype != torch.float64:
+        raise RuntimeError("vanishing_points: lines are fp64 [N,4] (x0, y0, x1, y1), got %s %s" % (lines.dtype, tuple(lines.shape)))
+    offsets = _csr(offsets, "vanishing_points")
+    lines = lines.contiguous()
+    S = offsets.shape[0] - 1
+    dev = lines.device
+    out = torch.empty((S, 3), dtype=torch.float64, device=dev)
+    trace = torch.zeros((S, VP_LEVELS, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_vanishing_points(lines.data_ptr(), lines.shape[0], offsets.data_ptr(), S, out.data_ptr(), trace.data_ptr(),
+                                           status.data_ptr(), _hip.stream()), "rn_vanishing_points")
+    return out, trace, status
+
+
+def _calib_inputs(boxes, heights, H, P, what):
+    if boxes.dim() != 3 or boxes.shape[1:] != (8, 2) or boxes.shape[0] == 0:
+        raise RuntimeError("%s: boxes are [d,8,2] image corners with d >= 1, got %s" % (what, tuple(boxes.shape)))
+    if heights.dim() != 1 or heights.shape[0] != boxes.shape[0]:
+        raise RuntimeError("%s: one height per box, got %s for %d boxes" % (what, tuple(heights.shape), boxes.shape[0]))
+    if tuple(H.shape) != (3, 3) or tuple(P.shape) != (3, 4) or H.dtype != torch.float64 or P.dtype != torch.float64:
+        raise RuntimeError("%s: H is fp64 [3,3] and P fp64 [3,4], got %s and %s" % (what, tuple(H.shape), tuple(P.shape)))
+    return boxes.double().contiguous(), _hip.f32c(heights), H.contiguous(), P.contiguous()
+
+
+def hg_reproj_error(boxes, heights, H, P_orig, C):
+    """test_transformation's arithmetic (homography.py:581-587) for every scale C [K] of P_orig's third column ->
+    fp64 [K,2] = (top, bottom) mean corner distance in pixels."""
+    lib = _hip.load()
+    _hip.need_gpu(boxes, heights, H, P_orig, C)
+    boxes, heights, H, P_orig = _calib_inputs(boxes, heights, H, P_orig, "hg_reproj_error")
+    if C.dim() != 1 or C.shape[0] == 0 or C.dtype != torch.float64:
+        raise RuntimeError("hg_reproj_error: C is fp64 [K] with K >= 1, got %s %s" % (C.dtype, tuple(C.shape)))
+    C = C.contiguous()
+    out = torch.empty((C.shape[0], 2), dtype=torch.float64, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        _hip.check(lib.rn_hg_reproj_error(boxes.data_ptr(), heights.data_ptr(), H.data_ptr(), P_orig.data_ptr(), C.data_ptr(),
+                                          boxes.shape[0], C.shape[0], out.data_ptr(), _hip.stream()), "rn_hg_reproj_error")
+    return out
+
+
+def hg_scale_z(boxes, heights, H, P_orig, granularity=1e-06, max_scale=10.0):
+    """The search of scale_Z (homography.py:607-666) in one launch -> (trace fp64 [SZ_MAX_ITERS,10,2] = (C, error), zero
+    beyond the iterations run (the search shrinks its step 4.5 x per iteration: 10 iterations at the defaults); out fp64 [3] = (last C evaluated, best C, best error of the last iteration);
+    info int32 [2] = (iterations, status bits))."""
+    lib = _hip.load()
+    _hip.need_gpu(boxes, heights, H, P_orig)
+    boxes, heights, H, P_orig = _calib_inputs(boxes, heights, H, P_orig, "hg_scale_z")
+    dev = boxes.device
+    trace = torch.zeros((SZ_MAX_ITERS, 10, 2), dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_hg_scale_z(boxes.data_ptr(), heights.data_ptr(), H.data_ptr(), P_orig.data_ptr(), boxes.shape[0],
+                                     float(granularity), float(max_scale), SZ_MAX_ITERS, trace.data_ptr(), out.data_ptr(),
+                                     info.data_ptr(), _hip.stream()), "rn_hg_scale_z")
+    return trace, out, info
+
+
+def fit_homography(src, dst, offsets, refine=True):
+    """Plane homographies dst ~ H [src; 1], one per CSR row range: src, dst fp64 [N,2], offsets int64 [B+1] ->
+    (H fp64 [B,3,3] with H[2,2] = 1, NaN where the status is not 0; status int32 [B]).  Stands in for
+    cv2.findHomography(src, dst) at its default method; parity with OpenCV is unpinned (include/retinanet_mi355x.h)."""
+    lib = _hip.load()
+    _hip.need_gpu(src, dst, offsets)
+    if src.dim() != 2 or src.shape[1] != 2 or src.shape != dst.shape or src.dtype != torch.float64 or dst.dtype != torch.float64:
+        raise RuntimeError("fit_homography: src and dst are fp64 [N,2], got %s and %s" % (tuple(src.shape), tuple(dst.shape)))
+    offsets = _csr(offsets, "fit_homography")
+    src, dst = src.contiguous(), dst.contiguous()
+    B = offsets.shape[0] - 1
+    H = torch.empty((B, 3, 3), dtype=torch.float64, device=src.device)
+    status = torch.empty(B, dtype=torch.int32, device=src.device)
+    with torch.cuda.device(src.device):
+        _hip.check(lib.rn_fit_homography(src.data_ptr(), dst.data_ptr(), src.shape[0], offsets.data_ptr(), B, int(bool(refine)), H.data_ptr(),
+                                         status.data_ptr(), _hip.stream()), "rn_fit_homography")
+    return H, status

@@ -29,6 +29,10 @@ Operator                                         reference code it stands for
   eval_ap(table, state, tp, num_annotations)     per-class sort + _compute_ap           R/csv_eval.py:216-235, 38-62
   mot_prepare / mot_iou / mot_assign /           MOT_Evaluator.evaluate, all frames    mot_evaluator.py:120-412
   mot_frame_metrics / mot_reduce
+  vanishing_points(lines, offsets)               find_vanishing_point, many sets       homography.py:96-154
+  hg_reproj_error(boxes, heights, H, P, C)       test_transformation's arithmetic      homography.py:581-587
+  hg_scale_z(boxes, heights, H, P, gran, max)    scale_Z's search                      homography.py:607-666
+  fit_homography(src, dst, offsets, refine)      cv2.findHomography (parity unpinned)  homography.py:354-355
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -371,6 +375,53 @@ def _(n_gt, n_pred, slot_row, slot_col, pred_assigned, frame_status, per_slot, g
     return gt_id.new_empty((ops.MOT_RESULT,), dtype=torch.float64)
 
 
+# ---- camera calibration
+@_lib.custom_op(NS + "::vanishing_points", mutates_args=(), device_types="cuda")
+def vanishing_points(lines: torch.Tensor, offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.vanishing_points(lines, offsets)
+
+
+@vanishing_points.register_fake
+def _(lines, offsets):
+    S = offsets.shape[0] - 1
+    return (lines.new_empty((S, 3), dtype=torch.float64), lines.new_empty((S, ops.VP_LEVELS, 3), dtype=torch.float64),
+            lines.new_empty((S,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::hg_reproj_error", mutates_args=(), device_types="cuda")
+def hg_reproj_error(boxes: torch.Tensor, heights: torch.Tensor, H: torch.Tensor, P_orig: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+    return ops.hg_reproj_error(boxes, heights, H, P_orig, C)
+
+
+@hg_reproj_error.register_fake
+def _(boxes, heights, H, P_orig, C):
+    return boxes.new_empty((C.shape[0], 2), dtype=torch.float64)
+
+
+@_lib.custom_op(NS + "::hg_scale_z", mutates_args=(), device_types="cuda")
+def hg_scale_z(boxes: torch.Tensor, heights: torch.Tensor, H: torch.Tensor, P_orig: torch.Tensor, granularity: float,
+               max_scale: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.hg_scale_z(boxes, heights, H, P_orig, granularity, max_scale)
+
+
+@hg_scale_z.register_fake
+def _(boxes, heights, H, P_orig, granularity, max_scale):
+    return (boxes.new_empty((ops.SZ_MAX_ITERS, 10, 2), dtype=torch.float64), boxes.new_empty((3,), dtype=torch.float64),
+            boxes.new_empty((2,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::fit_homography", mutates_args=(), device_types="cuda")
+def fit_homography(src: torch.Tensor, dst: torch.Tensor, offsets: torch.Tensor, refine: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.fit_homography(src, dst, offsets, refine)
+
+
+@fit_homography.register_fake
+def _(src, dst, offsets, refine):
+    B = offsets.shape[0] - 1
+    return src.new_empty((B, 3, 3), dtype=torch.float64), src.new_empty((B,), dtype=torch.int32)
+
+
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
              "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "augment_frames", "augment_crops",
-             "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce")
+             "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce",
+             "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography")

@@ -926,6 +926,64 @@ int rn_mot_reduce(int64_t F, int64_t S, const int32_t *gt_off, const int32_t *pr
                   const int32_t *gt_id, const int32_t *pred_id, int64_t n_gid, int64_t n_pid, void *workspace,
                   double *result, void *stream);
 
+/* ---- camera calibration (csrc/calibrate.hip): the set-up half of homography.py, fp64 in the reference's order --------
+ * rn_vanishing_points  replaces find_vanishing_point (homography.py:96-154) for `sets` line sets in one launch, one
+ *                      workgroup per set: lines fp64 [N,4] (x0, y0, x1, y1), offsets int64 [sets+1] (CSR rows into
+ *                      lines).  The start point is homography.py:113-122 as written (only lines 0 and 1 enter); 16
+ *                      levels g = 1e16 .. 10; each axis is np.arange(p - 15 g, p + 15 g, g) by numpy's own rule (length
+ *                      ceil((stop - start) / g), element i = start + i * ((start + g) - start)), up to RN_VP_MAX_AXIS
+ *                      points; the squared line distances are added over the set's lines in order; of a level's grid
+ *                      the smallest distance wins, the lowest scan index (x outer, y inner) among equals, and only if it
+ *                      is below the best carried over from the levels before; NaN never wins.
+ *                      out fp64 [sets,3] = (px, py, best); trace fp64 [sets,16,3] = (px, py, best) each level STARTED
+ *                      with (zero-filled by the caller: levels not reached stay as they are); status int32 [sets], bits:
+ *                      RN_VP_FEW_LINES (fewer than 2 lines: IndexError in the reference), RN_VP_BAD_START (start not
+ *                      finite: np.arange raises there), RN_VP_LONG_AXIS (an axis longer than RN_VP_MAX_AXIS was cut),
+ *                      RN_VP_BAD_OFFSETS (the set's row range is not inside the `rows` rows of lines: nothing was read).
+ * rn_hg_reproj_error   replaces test_transformation's arithmetic (homography.py:581-587) for K scales of P's third column
+ *                      in one launch: boxes fp64 [d,8,2], heights fp32 [d], H fp64 [3,3], P_orig fp64 [3,4], C fp64 [K];
+ *                      out fp64 [K,2] = (top, bottom) mean corner distance with P[:,2] = P_orig[:,2] * C.  image ->
+ *                      state is projected in fp64 and rounded to the fp32 state, state -> space is fp32, the projection
+ *                      back fp64.  The means: per box ((e0 + e1) + e2) + e3, box b into partial b % 256 in ascending b,
+ *                      the partials folded pairwise (t += t + s, s = 128 .. 1), divided by 4 d.
+ * rn_hg_scale_z        replaces the search of scale_Z (homography.py:607-666) in one launch: np.linspace's rule (step =
+ *                      (hi - lo) / 9, y[i] = i * step + lo, y[9] = hi), step_size = y[1] - y[0], while step_size >
+ *                      granularity: the 10 errors (top + bottom as above), the first smallest wins, new bounds best_C -+
+ *                      step_size.  trace fp64 [max_iters,10,2] = (C, error); out fp64 [3] = (the LAST C evaluated -- the
+ *                      reference leaves P scaled by it, not by the best --, best C, best error of the last iteration);
+ *                      info int32 [2] = (iterations, status bits: RN_SZ_BAD_FIRST_STEP the first step is not above the
+ *                      granularity, RN_SZ_NO_WINNER every error of an iteration was NaN, RN_SZ_TOO_MANY max_iters reached).
+ * rn_fit_homography    stands in for cv2.findHomography(src, dst) at its default method (homography.py:354-355; parity
+ *                      with OpenCV is NOT pinned): src, dst fp64 [N,2], offsets int64 [problems+1], one workgroup per
+ *                      problem.  Hartley-normalised DLT, the 9x9 normal matrix summed in point order, cyclic Jacobi with
+ *                      12 sweeps, the eigenvector of the smallest eigenvalue; for n > 4 and refine != 0 ten damped
+ *                      Gauss-Newton steps on the forward transfer error over the eight free entries (8x8 solve with
+ *                      partial pivoting; a step is kept only if the error falls); denormalised, H[2,2] = 1.
+ *                      H fp64 [problems,3,3] (NaN where status != 0); status int32 [problems]: RN_FIT_FEW_POINTS n < 4,
+ *                      RN_FIT_DEGENERATE collinear / coincident points, RN_FIT_NOT_FINITE, RN_FIT_BAD_OFFSETS (the row
+ *                      range is not inside the `rows` rows of src / dst). */
+#define RN_VP_MAX_AXIS 32
+#define RN_VP_FEW_LINES 1
+#define RN_VP_BAD_START 2
+#define RN_VP_LONG_AXIS 4
+#define RN_VP_BAD_OFFSETS 8
+#define RN_SZ_BAD_FIRST_STEP 1
+#define RN_SZ_NO_WINNER 2
+#define RN_SZ_TOO_MANY 4
+#define RN_FIT_FEW_POINTS 1
+#define RN_FIT_DEGENERATE 2
+#define RN_FIT_NOT_FINITE 4
+#define RN_FIT_BAD_OFFSETS 8
+int rn_vanishing_points(const double *lines, int64_t rows, const int64_t *offsets, int64_t sets, double *out, double *trace,
+                        int32_t *status, void *stream);
+int rn_hg_reproj_error(const double *boxes, const float *heights, const double *H, const double *P_orig, const double *C,
+                       int64_t d, int64_t K, double *out, void *stream);
+int rn_hg_scale_z(const double *boxes, const float *heights, const double *H, const double *P_orig, int64_t d,
+                  double granularity, double max_scale, int max_iters, double *trace, double *out, int32_t *info,
+                  void *stream);
+int rn_fit_homography(const double *src, const double *dst, int64_t rows, const int64_t *offsets, int64_t problems, int refine,
+                      double *H, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

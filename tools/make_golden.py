@@ -1515,6 +1515,83 @@ def gen_mot_eval():
     np.savez_compressed(os.path.join(OUT, "mot_eval.npz"), **out)
 
 
+def gen_calibration():
+    """The reference's own find_vanishing_point, test_transformation and scale_Z (homography.py:96-154, 554-666) on the
+    synthetic cases of tests/calib_cases.py, behind the empty cv2.  The module's ``np`` is wrapped to record every
+    np.arange / np.linspace call, and the instance's test_transformation to record P's third column and the error of
+    every evaluation.  Data only: inputs, outputs, the recorded calls."""
+    import contextlib
+    import io
+    import warnings
+    import calib_cases as cc
+    hgmod = ref_module_from_file("_reference_homography_calib", "homography.py")
+
+    class Recorder:
+        def __init__(self):
+            self.aranges, self.linspaces = [], []
+
+        def __getattr__(self, k):
+            return getattr(np, k)
+
+        def arange(self, a, b, step):
+            r = np.arange(a, b, step)
+            self.aranges.append((float(a), float(b), float(step), float(len(r)), float(r[0]) if len(r) else np.nan,
+                                 float(r[-1]) if len(r) else np.nan))
+            return r
+
+        def linspace(self, a, b, num=50):
+            r = np.linspace(a, b, num=num)
+            self.linspaces.append(r.copy())
+            return r
+    out = {}
+    for name in cc.VP_GOLDEN:
+        rec = Recorder()
+        hgmod.np = rec
+        lines = cc.vp_lines(name)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            vp = hgmod.find_vanishing_point([row for row in lines])
+        out["vp_%s_lines" % name] = lines
+        out["vp_%s_point" % name] = np.array([float(vp[0]), float(vp[1])])
+        out["vp_%s_arange" % name] = np.array(rec.aranges, np.float64).reshape(16, 2, 6)
+    names, _, _, (Ps, Hs), _ = gc.homography_inputs()
+    for cam, d in enumerate(cc.SZ_D):
+        rec = Recorder()
+        hgmod.np = rec
+        H, P_true = Hs[cam], Ps[cam]
+        st, heights, P0 = cc.sz_case(d, P_true, H)
+        hg = hgmod.Homography()
+        hg.correspondence = {"true": {"H": H, "P": P_true, "H_inv": np.linalg.inv(H)}, "cam": {"H": H, "P": P0.copy(), "H_inv": np.linalg.inv(H)}}
+        hg.default_correspondence = "cam"
+        boxes = hg.state_to_im(torch.from_numpy(st), name="true")
+        boxes = boxes + torch.from_numpy(synth.normal((d, 8, 2), 400 + d, std=0.7).astype(np.float64))
+        hts = torch.from_numpy(heights)
+        tag = "sz_d%d_" % d
+        out[tag + "boxes"], out[tag + "heights"], out[tag + "H"], out[tag + "P0"] = t2n(boxes), heights, H, P0
+        text = io.StringIO()
+        with contextlib.redirect_stdout(text):
+            err0 = hg.test_transformation(boxes, heights=hts)
+        out[tag + "tt_text"] = np.frombuffer(text.getvalue().encode(), np.uint8)
+        out[tag + "tt_error"] = np.array(float(err0))
+        evals = []
+        inner = hg.test_transformation
+
+        def recording(points, **kw):
+            e = inner(points, **kw)
+            evals.append(np.concatenate((hg.correspondence["cam"]["P"][:, 2], [float(e)])))
+            return e
+        hg.test_transformation = recording
+        text = io.StringIO()
+        with contextlib.redirect_stdout(text):
+            hg.scale_Z(boxes, hts)
+        out[tag + "sz_text"] = np.frombuffer(text.getvalue().encode(), np.uint8)
+        out[tag + "P_final"] = hg.correspondence["cam"]["P"]
+        out[tag + "grids"] = np.stack(rec.linspaces)                           # [iterations + 1, 10]: the last is never evaluated
+        out[tag + "evals"] = np.stack(evals)                                   # [iterations * 10, 4] = (P[:,2], error)
+    hgmod.np = np
+    np.savez_compressed(os.path.join(OUT, "calibration.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -1531,7 +1608,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1570,6 +1647,8 @@ def main():
         gen_augment_crop()
     if "mot_eval" in which:
         gen_mot_eval()
+    if "calibration" in which:
+        gen_calibration()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
