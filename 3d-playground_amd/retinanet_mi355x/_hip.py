@@ -74,6 +74,8 @@ SIGNATURES = {
     "rn_eval_ap_workspace_bytes": (c_i64, [c_i64]),
     "rn_eval_ap": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rn_frame_ingest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp]),
+    "rn_frame_ingest_half": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp, c_vp]),
+    "rn_parse_frame_timestamps": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_vp, c_i32] + [c_vp] * 9),
     "rn_augment_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "rn_augment_frames": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64] + [c_f32] * 6 + [c_vp, c_vp, c_vp]),
     "rn_augment_crops_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),

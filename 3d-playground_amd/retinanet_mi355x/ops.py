@@ -1086,6 +1086,125 @@ def frame_ingest(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ 4K frames
+TS_MAX_SETS, TS_MAX_CELLS, TS_MAX_KEYS, TS_ROW, TS_MAX_CELL_PIXELS = 4, 16, 64, 8, 4096     # RN_TS_* of the header
+TS_READ, TS_FAILED, TS_FELL_BACK = 0, 1, 2
+TS_GEOMETRY_KEYS = ("x0", "y0", "w", "h", "n", "h13", "h23", "w12")
+
+
+def _u8_frames(frames_u8, what):
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8.unsqueeze(0)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise RuntimeError("%s takes uint8 [B,H,W,3] frames, got %s %s" % (what, frames_u8.dtype, tuple(frames_u8.shape)))
+    return frames_u8
+
+
+def frame_ingest_half(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, nhwc4=False, keep_u8=False):
+    """The loader's 2x reduction + to_tensor + normalize in one pass (include/retinanet_mi355x.h, rn_frame_ingest_half;
+    util_track/mp_loader.py:237-243).  frames_u8: uint8 [B,2H,2W,3] (or [2H,2W,3]) -> float32 [B,3,H,W], or [B,H,W,4] with
+    nhwc4=True: ``frame_ingest`` of the reduced frame, bit for bit.  keep_u8=True -> (tensor, reduced uint8 [B,H,W,3])."""
+    lib = _hip.load()
+    _hip.need_gpu(frames_u8)
+    f = _u8_frames(frames_u8, "frame_ingest_half")
+    B, H2, W2, _ = f.shape
+    if B < 1 or H2 < 2 or W2 < 2 or H2 % 2 or W2 % 2:
+        raise RuntimeError("frame_ingest_half halves exactly: it takes even, non-empty frame sizes, got %s" % (tuple(f.shape),))
+    f = f.contiguous()
+    H, W = H2 // 2, W2 // 2
+    out = torch.empty((B, H, W, 4) if nhwc4 else (B, 3, H, W), dtype=torch.float32, device=f.device)
+    u8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=f.device) if keep_u8 else None
+    with torch.cuda.device(f.device):
+        _hip.check(lib.rn_frame_ingest_half(f.data_ptr(), B, H2, W2, int(bool(swap_rb)), *[float(m) for m in mean],
+                                            *[float(s) for s in std], int(bool(nhwc4)), out.data_ptr(), _hip.ptr(u8),
+                                            _hip.stream()), "rn_frame_ingest_half")
+    return (out, u8) if keep_u8 else out
+
+
+def pack_timestamp_sets(sets):
+    """Host side of ``parse_frame_timestamps``: sets = a sequence of up to 4 (geometry, checksums) pairs -- geometry a mapping
+    with x0, y0, w, h, n, h13, h23, w12 (the reference's h12 is read there and never used); checksums a mapping key -> six
+    counts (3x2, band major) in the order the reference's ``min`` walks it.  -> (int32 [G,9] geometry rows with K appended,
+    int32 [G,64,8] table rows: the six counts, then the key's digit).  ValueError for a key whose ``str()`` is not one decimal
+    digit (the fp64 value needs digits) and for sizes the kernel refuses."""
+    sets = list(sets)
+    if not 1 <= len(sets) <= TS_MAX_SETS:
+        raise ValueError("between 1 and %d (geometry, checksums) sets, got %d" % (TS_MAX_SETS, len(sets)))
+    geo = np.zeros((len(sets), 9), np.int32)
+    tab = np.zeros((len(sets), TS_MAX_KEYS, TS_ROW), np.int32)
+    for g, (geom, table) in enumerate(sets):
+        x0, y0, w, h, n, h13, h23, w12 = (int(geom[k]) for k in TS_GEOMETRY_KEYS)
+        K = len(table)
+        if not 1 <= n <= TS_MAX_CELLS or not 1 <= K <= TS_MAX_KEYS:
+            raise ValueError("set %d: n = %d cells (1..%d), %d table entries (1..%d)" % (g, n, TS_MAX_CELLS, K, TS_MAX_KEYS))
+        if x0 < 0 or y0 < 0 or w < 1 or h < 1 or w * h > TS_MAX_CELL_PIXELS or not 0 <= h13 <= h23 <= h or not 0 <= w12 <= w:
+            raise ValueError("set %d: geometry %r is refused (x0, y0 >= 0; 0 <= h13 <= h23 <= h; 0 <= w12 <= w; 1 <= w * h <= %d)"
+                             % (g, dict((k, int(geom[k])) for k in TS_GEOMETRY_KEYS), TS_MAX_CELL_PIXELS))
+        geo[g] = (x0, y0, w, h, n, h13, h23, w12, K)
+        for k, (key, cs) in enumerate(table.items()):
+            text = str(key)
+            if len(text) != 1 or text not in "0123456789":
+                raise ValueError("set %d: table key %r does not read as one decimal digit" % (g, key))
+            tab[g, k, :6] = np.asarray(cs, np.int64).reshape(6)
+            tab[g, k, 6] = int(text)
+    return geo, tab
+
+
+def parse_frame_timestamps(frames_u8, sets, prev=None, swap_rb=False, want_mask=False):
+    """timestamp_utilities.parse_frame_timestamp for B frames and up to 4 sets tried in order, on device
+    (include/retinanet_mi355x.h, rn_parse_frame_timestamps).  frames_u8: uint8 [B,H,W,3] on the device, any strides as long
+    as a pixel's three bytes are adjacent (a strip sliced from a frame is read in place); sets: (geometry, checksums) pairs,
+    or what ``pack_timestamp_sets`` made of them with the table already on the device (geometry int32 [G,9] numpy, table
+    int32 [G,64,8] device tensor); prev: optional fp64 [B] on the device.
+    -> (times fp64 [B], status i32 [B] (TS_READ / TS_FAILED / TS_FELL_BACK), set index i32 [B], digits i8 [B,16],
+        first failing cell of the first set i32 [B], the first set's mask uint8 [B,h,n*w] or None)."""
+    lib = _hip.load()
+    _hip.need_gpu(frames_u8, prev)
+    f = _u8_frames(frames_u8, "parse_frame_timestamps")
+    if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray) and torch.is_tensor(sets[1]):
+        geo, tab = sets
+        _hip.need_gpu(tab)
+    else:
+        geo, tab = pack_timestamp_sets(sets)
+        tab = torch.from_numpy(tab).to(f.device)
+    geo = np.ascontiguousarray(geo, np.int32)
+    if tab.dtype != torch.int32 or tuple(tab.shape) != (geo.shape[0], TS_MAX_KEYS, TS_ROW) or not tab.is_contiguous():
+        raise RuntimeError("parse_frame_timestamps: the table is int32 [G,%d,%d], contiguous" % (TS_MAX_KEYS, TS_ROW))
+    B, H, W, _ = f.shape
+    if B < 1 or H < 1 or W < 1:
+        raise RuntimeError("parse_frame_timestamps: empty frames %s" % (tuple(f.shape),))
+    if f.stride(3) != 1 or f.stride(2) != 3 or f.stride(1) < 3 * W or (B > 1 and f.stride(0) < (H - 1) * f.stride(1) + 3 * W):
+        f = f.contiguous()
+    if prev is not None:
+        if prev.dtype != torch.float64 or tuple(prev.shape) != (B,):
+            raise RuntimeError("parse_frame_timestamps: prev is float64 [B]")
+        prev = prev.contiguous()
+    dev = f.device
+    times = torch.empty(B, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    set_index = torch.empty(B, dtype=torch.int32, device=dev)
+    digits = torch.empty((B, TS_MAX_CELLS), dtype=torch.int8, device=dev)
+    fail_cell = torch.empty(B, dtype=torch.int32, device=dev)
+    mask = torch.empty((B, int(geo[0, 3]), int(geo[0, 4]) * int(geo[0, 2])), dtype=torch.uint8, device=dev) if want_mask else None
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_parse_frame_timestamps(f.data_ptr(), B, H, W, f.stride(0) if B > 1 else 0, f.stride(1), int(bool(swap_rb)),
+                                                 geo.ctypes.data, geo.shape[0], tab.data_ptr(), _hip.ptr(prev), times.data_ptr(),
+                                                 status.data_ptr(), set_index.data_ptr(), digits.data_ptr(), fail_cell.data_ptr(),
+                                                 _hip.ptr(mask), _hip.stream()), "rn_parse_frame_timestamps")
+    return times, status, set_index, digits, fail_cell, mask
+
+
+def load_frames_4k(frames_u8, reader, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, nhwc4=False, keep_u8=False):
+    """One tracker step's input from one upload (util_track/mp_loader.py:230-243 for every camera): the time stamps of the
+    4K frames through ``reader`` (a ``timestamp_utilities.TimestampReader``: tables and the previous stamps on the device)
+    and ``frame_ingest_half``, both on the current stream.  swap_rb concerns the detector's tensor only; the reader carries its
+    own channel order.  -> (frames, timestamps fp64 [B], status i32 [B]); frames is (tensor, reduced uint8) with keep_u8."""
+    _hip.need_gpu(frames_u8)
+    timestamps, status = reader(frames_u8)
+    frames = frame_ingest_half(frames_u8, swap_rb=swap_rb, mean=mean, std=std, nhwc4=nhwc4, keep_u8=keep_u8)
+    return frames, timestamps, status
+
+
 def augment_frames(frames_u8, params, noise=None, seed=0, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """The image chain of the reference's training loader on device (include/retinanet_mi355x.h, rn_augment_frames;
     corrected_3D_dataset.py:330-478).  frames_u8: uint8 [B,H,W,3]; params: (records, table_x, table_y) as

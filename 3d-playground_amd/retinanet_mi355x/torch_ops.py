@@ -22,6 +22,8 @@ Operator                                         reference code it stands for
   residual_moments(E, group, groups)             mean / covariance loops               fit_filter_3D.py:292-299, 377-384, 426-434
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
   frame_ingest(frames_u8, swap_rb, nhwc4)        to_tensor + normalize of the loaders  util_track/mp_loader.py:239-243
+  frame_ingest_half(frames_u8, swap_rb, nhwc4)   cv2.resize (exact halving) + the above   util_track/mp_loader.py:237-243
+  parse_frame_timestamps(frames_u8, geometry, ..) parse_frame_timestamp, sets tried in turn  timestamp_utilities.py:46-115
   augment_frames(frames_u8, records, tx, ty, ..) Detection_Dataset.__getitem__'s image chain  corrected_3D_dataset.py:330-478
   augment_crops(frames_u8, records, 4 tables, ..) ... with CROP > 0 (the crop detector's)     corrected_3D_dataset.py:501-594
   eval_select(scores, labels, boxes, table, ..)  _get_detections' selection (in place)  R/csv_eval.py:102-123
@@ -244,6 +246,38 @@ def _(frames_u8, swap_rb, nhwc4):
     return frames_u8.new_empty((B, H, W, 4) if nhwc4 else (B, 3, H, W), dtype=torch.float32)
 
 
+@_lib.custom_op(NS + "::frame_ingest_half", mutates_args=(), device_types="cuda")
+def frame_ingest_half(frames_u8: torch.Tensor, swap_rb: bool, nhwc4: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Always with the reduced uint8 frame (the reference's original_im)."""
+    return ops.frame_ingest_half(frames_u8, swap_rb=swap_rb, nhwc4=nhwc4, keep_u8=True)
+
+
+@frame_ingest_half.register_fake
+def _(frames_u8, swap_rb, nhwc4):
+    B, H2, W2, _ = frames_u8.shape
+    H, W = H2 // 2, W2 // 2
+    return (frames_u8.new_empty((B, H, W, 4) if nhwc4 else (B, 3, H, W), dtype=torch.float32), frames_u8.new_empty((B, H, W, 3)))
+
+
+@_lib.custom_op(NS + "::parse_frame_timestamps", mutates_args=(), device_types="cuda")
+def parse_frame_timestamps(frames_u8: torch.Tensor, geometry: List[int], tables: torch.Tensor, prev: Optional[torch.Tensor],
+                           swap_rb: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """geometry: the rows of ``ops.pack_timestamp_sets`` flattened (9 ints per set); tables: its table on the device.  Always
+    with the first set's mask."""
+    import numpy as np
+    geo = np.asarray(geometry, np.int32).reshape(-1, 9)
+    return ops.parse_frame_timestamps(frames_u8, (geo, tables), prev=prev, swap_rb=swap_rb, want_mask=True)
+
+
+@parse_frame_timestamps.register_fake
+def _(frames_u8, geometry, tables, prev, swap_rb):
+    B = frames_u8.shape[0]
+    w, h, n = geometry[2], geometry[3], geometry[4]
+    return (frames_u8.new_empty((B,), dtype=torch.float64), frames_u8.new_empty((B,), dtype=torch.int32),
+            frames_u8.new_empty((B,), dtype=torch.int32), frames_u8.new_empty((B, ops.TS_MAX_CELLS), dtype=torch.int8),
+            frames_u8.new_empty((B,), dtype=torch.int32), frames_u8.new_empty((B, h, n * w)))
+
+
 @_lib.custom_op(NS + "::augment_frames", mutates_args=(), device_types="cuda")
 def augment_frames(frames_u8: torch.Tensor, records: torch.Tensor, table_x: torch.Tensor, table_y: torch.Tensor,
                    noise: Optional[torch.Tensor], seed: int) -> torch.Tensor:
@@ -422,6 +456,6 @@ def _(src, dst, offsets, refine):
 
 
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "augment_frames", "augment_crops",
+             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "frame_ingest_half", "parse_frame_timestamps", "augment_frames", "augment_crops",
              "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce",
              "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography")

@@ -330,6 +330,60 @@ int rn_eval_ap(const void *table, int64_t table_rows, const int32_t *state, cons
 int rn_frame_ingest(const uint8_t *frames, int B, int H, int W, int swap_rb, float mean0, float mean1, float mean2,
                     float std0, float std1, float std2, int layout, float *out, void *stream);
 
+/* ---------------------------------------------------------------- 4K frames: reduction + ingest ------------
+ * The loader's cv2.resize(original_im, (1920, 1080)) of a 3840x2160 frame followed by to_tensor + normalize
+ * (util_track/mp_loader.py:237-243) in one pass.  frames uint8 [B,H2,W2,3]; H2 and W2 even (the exact halving, the
+ * loader's only case; anything else is RN_EINVAL).  Per channel the reduced byte is (a + b + c + d + 2) >> 2 of the 2x2
+ * block -- what OpenCV's resize yields for an exact halving of 8-bit data (parity with cv2 itself unpinned: DESIGN.md,
+ * "4K frames") -- then rn_frame_ingest's arithmetic unchanged: out equals rn_frame_ingest of the reduced bytes bit for
+ * bit, layout 0 NCHW [B,3,H2/2,W2/2], layout 1 NHWC4 [B,H2/2,W2/2,4].  out_u8 (may be NULL): the reduced frame
+ * uint8 [B,H2/2,W2/2,3], the reference's original_im. */
+int rn_frame_ingest_half(const uint8_t *frames, int B, int H2, int W2, int swap_rb, float mean0, float mean1,
+                         float mean2, float std0, float std1, float std2, int layout, float *out, uint8_t *out_u8,
+                         void *stream);
+
+/* ---------------------------------------------------------------- 4K frames: burnt-in time stamps ---------
+ * timestamp_utilities.parse_frame_timestamp (timestamp_utilities.py:46-115) for B frames and up to RN_TS_MAX_SETS
+ * (geometry, checksum table) sets tried in order (datareader.py:59-63), with the callers' fall-back.
+ * frames: uint8 [H,W,3] each, frame b at frames + b * frame_stride, row y at + y * row_stride (bytes): a strip cut from
+ *   a frame works as the frame.  Channel order B,G,R; swap_rb != 0 reads R,G,B.
+ * sets: HOST array of G geometries.  The strip is rows [y0, y0+h), columns [x0, x0+n*w); a pixel outside the frame is
+ *   dark.  White: gray > 127 with gray = (3735 B + 19235 G + 9798 R + 16384) >> 15.  Cell j = columns [j*w, (j+1)*w);
+ *   cell 10 (the decimal point) is never looked at.  Six counts per cell: the white pixels of the row bands [0,h13),
+ *   [h13,h23), [h23,h) crossed with the column halves [0,w12), [w12,w), in that order (band major).
+ * tables: DEVICE int32 [G, RN_TS_MAX_KEYS, RN_TS_ROW]; row k of set g = the six counts of the table's k-th entry, then
+ *   the decimal digit it stands for (0-9), then 0; rows at and beyond K are not read.  A cell reads as the FIRST row
+ *   equal in all six counts; a cell without one fails the set, and the first such cell in j order is the one reported.
+ * Per frame the first set that reads every cell is used.  Outputs, all on the device:
+ *   times [B] fp64: the digits as one integer D over 10^max(n-11,0), one fp64 division (both exact, so the correctly
+ *     rounded value of the decimal string); nobody reads the frame: prev[b] + 1/30.0 (one fp64 add) with prev fp64 [B],
+ *     or NaN when prev is NULL
+ *   status [B] i32: RN_TS_READ, RN_TS_FAILED (NaN) or RN_TS_FELL_BACK;  set_index [B] i32: the set used, or -1
+ *   digits [B,RN_TS_MAX_CELLS] i8: the table row per cell of the set used (of the FIRST set when none reads), -1 for the
+ *     point, beyond n, and a cell without an equal row
+ *   fail_cell [B] i32: the first failing cell of the FIRST set, -1 if it read the frame
+ *   mask (may be NULL) uint8 [B,h,n*w] of the FIRST set: its 0 / 255 threshold strip, the point's cell included.
+ * RN_EINVAL before any launch: a null pointer (prev and mask excepted), B, H, W <= 0, n outside [1,RN_TS_MAX_CELLS], K
+ * outside [1,RN_TS_MAX_KEYS], G outside [1,RN_TS_MAX_SETS], x0 or y0 negative, 0 <= h13 <= h23 <= h or 0 <= w12 <= w
+ * violated, w or h < 1, w*h > RN_TS_MAX_CELL_PIXELS, a coordinate above RN_TS_MAX_COORD, row_stride < 3 W, frames that
+ * overlap.  One launch (a workgroup per frame), no synchronisation. */
+#define RN_TS_MAX_SETS 4
+#define RN_TS_MAX_CELLS 16
+#define RN_TS_MAX_KEYS 64
+#define RN_TS_ROW 8
+#define RN_TS_MAX_CELL_PIXELS 4096
+#define RN_TS_MAX_COORD (1 << 24)
+#define RN_TS_READ 0
+#define RN_TS_FAILED 1
+#define RN_TS_FELL_BACK 2
+typedef struct rn_ts_geometry {
+    int32_t x0, y0, w, h, n, h13, h23, w12, K;
+} rn_ts_geometry;
+int rn_parse_frame_timestamps(const uint8_t *frames, int B, int H, int W, int64_t frame_stride, int64_t row_stride,
+                              int swap_rb, const rn_ts_geometry *sets, int G, const int32_t *tables, const double *prev,
+                              double *times, int32_t *status, int32_t *set_index, int8_t *digits, int32_t *fail_cell,
+                              uint8_t *mask, void *stream);
+
 /* ---------------------------------------------------------------- training-batch augmentation -------------
  * The image chain of the reference's training loader (corrected_3D_dataset.py: Detection_Dataset.__getitem__, :330-478,
  * CROP == 0) on device, byte for byte what torchvision's PIL backend computes: frames uint8 [B,H,W,3] -> fp32 NCHW

@@ -1592,6 +1592,27 @@ def gen_calibration():
     np.savez_compressed(os.path.join(OUT, "calibration.npz"), **out)
 
 
+def gen_frames4k():
+    """The reference's own parse_frame_timestamp (timestamp_utilities.py:46-115) on tests/frames4k_cases.golden_cases().  Its
+    two cv2 calls go to a stand-in that provides only cvtColor, threshold and the two constants, made of the restated gray
+    rule (cv2 is not installed: that rule alone stays unpinned); the slicing, the six areas, the table search, the point at
+    cell 10 and the literal are the reference's.  The empty cv2 stub is put back afterwards.  Data only: inputs, the
+    returned time (NaN for None) and the returned error pixels."""
+    import frames4k_cases as fc
+    stand_in = types.ModuleType("cv2")
+    stand_in.COLOR_BGR2GRAY, stand_in.THRESH_BINARY = 6, 0
+    stand_in.cvtColor = lambda img, code: fc.gray(img).astype(np.uint8)
+    stand_in.threshold = lambda g, thresh, maxval, kind: (float(thresh), np.where(g > thresh, maxval, 0).astype(np.uint8))
+    empty = sys.modules["cv2"]
+    sys.modules["cv2"] = stand_in
+    try:
+        tsu = ref_module_from_file("_reference_timestamp_utilities", "timestamp_utilities.py")
+        results = [tsu.parse_frame_timestamp(c["geom"], c["table"], frame_pixels=c["frame"]) for c in fc.golden_cases()]
+    finally:
+        sys.modules["cv2"] = empty
+    fc.save_golden(os.path.join(OUT, "frames4k.npz"), results)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
@@ -1608,7 +1629,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1649,6 +1670,8 @@ def main():
         gen_mot_eval()
     if "calibration" in which:
         gen_calibration()
+    if "frames4k" in which:
+        gen_frames4k()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
