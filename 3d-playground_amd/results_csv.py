@@ -87,16 +87,22 @@ def write_detections_csv(data_list, sequence, fps, out_dir="_outputs"):
 
 
 # ------------------------------------------------------------------------------------------------ tracking results file
-def results_rows(ids, timestamps, states, space, im, class_names, ts_bias, camera="p1c1", gen="3D Detector"):
+def results_rows(ids, timestamps, states, space, im, class_names, ts_bias, camera="p1c1", gen="3D Detector", box=None):
     """Rows of write_results_csv (:1395-1453) from arrays: states [n,7] float32 (x, y, l, w, h, direction, speed),
-    space [n,4,2] float32 (the first four road-plane corners), im [n,8,2] float64 (image corners)."""
+    space [n,4,2] float32 (the first four road-plane corners), im [n,8,2] float64 (image corners).  camera: one name for
+    every row or one per row; box [n,4] float64 (min x, min y, max x, max y of im) where the caller has it already --
+    Data_Reader.write_to_file (datareader.py:553-584) builds the same rows with both."""
     rows = []
     for i in range(len(ids)):
         st, b3 = states[i], im[i]
-        row = ["-", timestamps[i], ids[i], class_names[i],
-               b3[:, 0].min().item(), b3[:, 1].min().item(), b3[:, 0].max().item(), b3[:, 1].max().item(), 0, 0, gen]
+        if box is None:
+            b2 = [b3[:, 0].min().item(), b3[:, 1].min().item(), b3[:, 0].max().item(), b3[:, 1].max().item()]
+        else:
+            b2 = [v.item() for v in box[i]]
+        cam = camera if isinstance(camera, str) else camera[i]
+        row = ["-", timestamps[i], ids[i], class_names[i]] + b2 + [0, 0, gen]
         row += list(b3.reshape(-1)) + list(space[i].reshape(-1))
-        row += [st[5], camera, 0, st[6], st[0], st[1], np.pi / 2.0 if st[5] == -1 else 0, st[3], st[2], st[4], ts_bias[i]]
+        row += [st[5], cam, 0, st[6], st[0], st[1], np.pi / 2.0 if st[5] == -1 else 0, st[3], st[2], st[4], ts_bias[i]]
         rows.append(row)
     return rows
 

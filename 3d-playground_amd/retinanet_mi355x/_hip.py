@@ -91,6 +91,10 @@ SIGNATURES = {
     "rn_hg_reproj_error": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rn_hg_scale_z": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rn_fit_homography": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "rn_reinterp_mate": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rn_reinterp_offsets": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64] + [c_vp] * 5),
+    "rn_reinterp_rows": (c_i32, [c_vp] * 7 + [c_i64] * 4 + [c_vp] * 5),
+    "rn_track_rows": (c_i32, [c_vp] * 5 + [c_i64, c_i64] + [c_vp] * 7),
 }
 
 class ConvDesc(ctypes.Structure):

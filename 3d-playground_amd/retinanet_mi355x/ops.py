@@ -810,8 +810,140 @@ def mot_reduce(offsets, totals, assigned, per_slot, gt_id, pred_id, n_gid, n_pid
     return result
 
 
+# ------------------------------------------------------------------------------------------------ tracking CSV resampling
+REINTERP_TILE = 1024               # RN_REINTERP_TILE: ids of the next frame per LDS tile
+REINTERP_BAD_OFFSETS, REINTERP_BAD_PAIR, REINTERP_BAD_MATE, REINTERP_BAD_PREFIX, REINTERP_BAD_MAT_INDEX = 1, 2, 4, 8, 16
+_REINTERP_BITS = ((REINTERP_BAD_OFFSETS, "frame offsets out of order or outside the rows"),
+                  (REINTERP_BAD_PAIR, "an instant's frame pair outside the frames"),
+                  (REINTERP_BAD_MATE, "a mate outside the next frame"),
+                  (REINTERP_BAD_PREFIX, "a destination outside its prefix slot"),
+                  (REINTERP_BAD_MAT_INDEX, "a mat_index outside the matrices"))
+
+
+def reinterp_status(device, status=None):
+    """The status word the four entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    _hip.need_gpu(status)
+    _mot_typed("reinterp", ("status", status, torch.int32))
+    if status.numel() != 1:
+        raise RuntimeError("reinterp: status is one int32")
+    return status
+
+
+def reinterp_check(status):
+    """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
+    bits = int(status)
+    if bits:
+        raise RuntimeError("the resampling kernels refused their input: " + "; ".join(t for b, t in _REINTERP_BITS if bits & b)
+                           + " (status %d)" % bits)
+
+
+def _reinterp_frames(what, offsets, R):
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError("%s: offsets is int64 [F+1]" % what)
+    if R >= 2 ** 31 or offsets.numel() - 1 >= 2 ** 31:
+        raise RuntimeError("%s: more than 2^31 rows or frames" % what)
+    return offsets.numel() - 1
+
+
+def reinterp_mate(offsets, ids, status=None):
+    """datareader.py:416-417 for every row: offsets int64 [F+1], ids int64 [R] -> (mate int32 [R] = the row of the next frame
+    with the same id or -1, status)."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, ids)
+    _mot_typed("reinterp_mate", ("offsets", offsets, torch.int64), ("ids", ids, torch.int64))
+    if ids.dim() != 1:
+        raise RuntimeError("reinterp_mate: ids is int64 [R]")
+    R, F, dev = ids.numel(), _reinterp_frames("reinterp_mate", offsets, ids.numel()), ids.device
+    status = reinterp_status(dev, status)
+    mate = torch.empty(R, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_reinterp_mate(offsets.data_ptr(), _hip.ptr(ids), F, R, _hip.ptr(mate), status.data_ptr(), _hip.stream()),
+                   "rn_reinterp_mate")
+    return mate, status
+
+
+def reinterp_offsets(offsets, mate, inst_a, status=None):
+    """offsets int64 [F+1], mate int32 [R], inst_a int32 [T] -> (count int32 [T] = mated rows of frame inst_a[t], prefix int64
+    [T+1] = its exclusive prefix, status)."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, mate, inst_a)
+    _mot_typed("reinterp_offsets", ("offsets", offsets, torch.int64), ("mate", mate, torch.int32), ("inst_a", inst_a, torch.int32))
+    if mate.dim() != 1 or inst_a.dim() != 1:
+        raise RuntimeError("reinterp_offsets: mate is int32 [R], inst_a int32 [T]")
+    R, T, F, dev = mate.numel(), inst_a.numel(), _reinterp_frames("reinterp_offsets", offsets, mate.numel()), mate.device
+    if T >= 2 ** 31:
+        raise RuntimeError("reinterp_offsets: more than 2^31 instants")
+    status = reinterp_status(dev, status)
+    frame_count = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
+    count = torch.empty(T, dtype=torch.int32, device=dev)
+    prefix = torch.empty(T + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_reinterp_offsets(offsets.data_ptr(), _hip.ptr(mate), F, R, _hip.ptr(inst_a), T, frame_count.data_ptr(),
+                                           _hip.ptr(count), prefix.data_ptr(), status.data_ptr(), _hip.stream()),
+                   "rn_reinterp_offsets")
+    return count, prefix, status
+
+
+def reinterp_rows(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix, rows, status=None):
+    """datareader.py:418-430 for every instant: frame_ts fp64 [F], fields fp64 [R,6], inst_time fp64 [T], prefix as
+    reinterp_offsets returns it, rows = the size of the output (at least prefix[T]; the host's upper bound, so that nothing
+    is read back in between) -> (out_fields fp64 [rows,6], out_src int32 [rows], out_inst int32 [rows], status); only rows
+    below prefix[T] are written."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix)
+    _mot_typed("reinterp_rows", ("offsets", offsets, torch.int64), ("frame_ts", frame_ts, torch.float64),
+               ("fields", fields, torch.float64), ("mate", mate, torch.int32), ("inst_a", inst_a, torch.int32),
+               ("inst_time", inst_time, torch.float64), ("prefix", prefix, torch.int64))
+    R, T, dev = mate.numel(), inst_a.numel(), fields.device
+    F = _reinterp_frames("reinterp_rows", offsets, R)
+    rows = int(rows)
+    if fields.numel() != R * 6 or frame_ts.numel() != F or inst_time.numel() != T or prefix.numel() != T + 1 or rows < 0 \
+            or T >= 2 ** 31:
+        raise RuntimeError("reinterp_rows: frame_ts [F], fields [R,6], mate [R], inst_a / inst_time [T], prefix [T+1], rows >= 0")
+    status = reinterp_status(dev, status)
+    out_fields = torch.empty((rows, 6), dtype=torch.float64, device=dev)
+    out_src = torch.empty(rows, dtype=torch.int32, device=dev)
+    out_inst = torch.empty(rows, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_reinterp_rows(offsets.data_ptr(), _hip.ptr(frame_ts), _hip.ptr(fields), _hip.ptr(mate), _hip.ptr(inst_a),
+                                        _hip.ptr(inst_time), prefix.data_ptr(), F, R, T, rows, _hip.ptr(out_fields),
+                                        _hip.ptr(out_src), _hip.ptr(out_inst), status.data_ptr(), _hip.stream()),
+                   "rn_reinterp_rows")
+    return out_fields, out_src, out_inst, status
+
+
+def track_rows(fields, direction, P, P2=None, mat_index=None, status=None):
+    """datareader.py:530-550 for N rows: fields fp64 [N,6] (x, y, l, w, h, v), direction fp64 [N], P fp64 [n,3,4] (P2: the
+    Homography_Wrapper's second set), mat_index int32 [N] or None (matrix 0) -> (state fp32 [N,7], space fp32 [N,4,2], im fp64
+    [N,8,2], box fp64 [N,4], keep uint8 [N], status)."""
+    lib = _hip.load()
+    _hip.need_gpu(fields, direction, P, P2, mat_index)
+    _mot_typed("track_rows", ("fields", fields, torch.float64), ("direction", direction, torch.float64), ("P", P, torch.float64))
+    if P2 is not None:
+        _mot_typed("track_rows", ("P2", P2, torch.float64))
+    if mat_index is not None:
+        _mot_typed("track_rows", ("mat_index", mat_index, torch.int32))
+    N, dev = direction.numel(), fields.device
+    if P.dim() != 3 or tuple(P.shape[1:]) != (3, 4) or P.shape[0] < 1 or (P2 is not None and P2.shape != P.shape) \
+            or fields.numel() != N * 6 or direction.dim() != 1 or (mat_index is not None and tuple(mat_index.shape) != (N,)):
+        raise RuntimeError("track_rows: fields [N,6], direction [N], P (and P2) [n,3,4], mat_index [N]")
+    status = reinterp_status(dev, status)
+    state = torch.empty((N, 7), dtype=torch.float32, device=dev)
+    space = torch.empty((N, 4, 2), dtype=torch.float32, device=dev)
+    im = torch.empty((N, 8, 2), dtype=torch.float64, device=dev)
+    box = torch.empty((N, 4), dtype=torch.float64, device=dev)
+    keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_track_rows(_hip.ptr(fields), _hip.ptr(direction), _hip.ptr(mat_index), P.data_ptr(), _hip.ptr(P2),
+                                     P.shape[0], N, _hip.ptr(state), _hip.ptr(space), _hip.ptr(im), _hip.ptr(box), _hip.ptr(keep),
+                                     status.data_ptr(), _hip.stream()), "rn_track_rows")
+    return state, space, im, box, keep, status
+
+
 # ------------------------------------------------------------------------------------------------ time stamp bias
-TS_MAX_CAMS = 1024                 # RN_TS_MAX_CAMS
+TS_MAX_CAMS = 1024                # RN_TS_MAX_CAMS
 TS_OK, TS_OVERFLOW, TS_BAD_CAMERA = 0, 1, 2
 
 

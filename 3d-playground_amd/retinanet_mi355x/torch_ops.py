@@ -35,6 +35,9 @@ Operator                                         reference code it stands for
   hg_reproj_error(boxes, heights, H, P, C)       test_transformation's arithmetic      homography.py:581-587
   hg_scale_z(boxes, heights, H, P, gran, max)    scale_Z's search                      homography.py:607-666
   fit_homography(src, dst, offsets, refine)      cv2.findHomography (parity unpinned)  homography.py:354-355
+  reinterp_mate / reinterp_offsets /             Data_Reader.reinterpolate, all rows   datareader.py:411-434
+  reinterp_rows
+  track_rows(fields, direction, P, P2, index)    Data_Reader.write_to_file's row math  datareader.py:530-550
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -455,7 +458,55 @@ def _(src, dst, offsets, refine):
     return src.new_empty((B, 3, 3), dtype=torch.float64), src.new_empty((B,), dtype=torch.int32)
 
 
+# ---- tracking CSV resampling and rewrite: every op returns the status word last (ops.reinterp_check raises on it)
+@_lib.custom_op(NS + "::reinterp_mate", mutates_args=(), device_types="cuda")
+def reinterp_mate(offsets: torch.Tensor, ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.reinterp_mate(offsets, ids)
+
+
+@reinterp_mate.register_fake
+def _(offsets, ids):
+    return ids.new_empty((ids.shape[0],), dtype=torch.int32), ids.new_empty((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::reinterp_offsets", mutates_args=(), device_types="cuda")
+def reinterp_offsets(offsets: torch.Tensor, mate: torch.Tensor, inst_a: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.reinterp_offsets(offsets, mate, inst_a)
+
+
+@reinterp_offsets.register_fake
+def _(offsets, mate, inst_a):
+    T = inst_a.shape[0]
+    return (mate.new_empty((T,), dtype=torch.int32), mate.new_empty((T + 1,), dtype=torch.int64), mate.new_empty((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::reinterp_rows", mutates_args=(), device_types="cuda")
+def reinterp_rows(offsets: torch.Tensor, frame_ts: torch.Tensor, fields: torch.Tensor, mate: torch.Tensor, inst_a: torch.Tensor,
+                  inst_time: torch.Tensor, prefix: torch.Tensor, rows: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.reinterp_rows(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix, rows)
+
+
+@reinterp_rows.register_fake
+def _(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix, rows):
+    e = fields.new_empty
+    return e((rows, 6), dtype=torch.float64), e((rows,), dtype=torch.int32), e((rows,), dtype=torch.int32), e((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::track_rows", mutates_args=(), device_types="cuda")
+def track_rows(fields: torch.Tensor, direction: torch.Tensor, P: torch.Tensor, P2: Optional[torch.Tensor],
+               mat_index: Optional[torch.Tensor]) -> List[torch.Tensor]:
+    return list(ops.track_rows(fields, direction, P, P2, mat_index))
+
+
+@track_rows.register_fake
+def _(fields, direction, P, P2, mat_index):
+    N, e = direction.shape[0], fields.new_empty
+    return [e((N, 7), dtype=torch.float32), e((N, 4, 2), dtype=torch.float32), e((N, 8, 2), dtype=torch.float64),
+            e((N, 4), dtype=torch.float64), e((N,), dtype=torch.uint8), e((1,), dtype=torch.int32)]
+
+
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
              "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "frame_ingest_half", "parse_frame_timestamps", "augment_frames", "augment_crops",
              "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce",
-             "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography")
+             "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography", "reinterp_mate", "reinterp_offsets", "reinterp_rows",
+             "track_rows")

@@ -1038,6 +1038,42 @@ int rn_hg_scale_z(const double *boxes, const float *heights, const double *H, co
 int rn_fit_homography(const double *src, const double *dst, int64_t rows, const int64_t *offsets, int64_t problems, int refine,
                       double *H, int32_t *status, void *stream);
 
+/* ---- tracking CSV resampling and rewrite (csrc/datareader.hip): Data_Reader.reinterpolate / write_to_file --------
+ * The host packs the frames of Data_Reader.data in order: offsets int64 [F+1] (rows of frame f), ids int64 [R], fields fp64
+ * [R,6] (x, y, l, w, h, v), frame_ts fp64 [F]; and walks the output instants as the reference does (datareader.py:406-444):
+ * inst_a int32 [T] (the instant falls in frame pair (a, a + 1)), inst_time fp64 [T].  fp64 with one rounding per operation.
+ * All four share one status word (int32, zeroed by the caller, bits OR-ed in): a bad index is never used, its item is left out.
+ *   rn_reinterp_mate     replaces `if id in next_ts_data.keys()` (:416-417) for every row: mate int32 [R] = the row of the next
+ *                        frame with the same id, else -1.  One workgroup per frame pair; the next frame's ids go through LDS
+ *                        in tiles of RN_REINTERP_TILE, so a frame of any size works.  The first match wins.
+ *   rn_reinterp_offsets  count int32 [T] = mated rows of frame inst_a[t]; prefix int64 [T+1] = its exclusive prefix (prefix[T]
+ *                        = all output rows).  frame_count int32 [F] is workspace.
+ *   rn_reinterp_rows     replaces the loop body (:418-430): one workgroup per instant compacts the mated rows of frame a in the
+ *                        frame's own order into rows prefix[t] .. prefix[t+1] - 1 of out_fields fp64 [U,6] / out_src int32 [U]
+ *                        (the row of frame a) / out_inst int32 [U] (t).  r1 = (t - ts) / (next_ts - ts), r2 = 1 - r1, value =
+ *                        field * r1 + next_field * r2: the reference's weights as written (the NEXT frame's value at t == ts).
+ *   rn_track_rows        replaces write_to_file's per-row arithmetic (:530-550): state fp32 [N,7] = (x, y, l, w, h, direction,
+ *                        v) rounded from fp64; keep uint8 [N] = state[0] != 0 on the fp32 value; space fp32 [N,4,2] (the first
+ *                        four corners, x and y); im fp64 [N,8,2] through matrix mat_index[i] of P fp64 [n_mats,3,4] (nullptr:
+ *                        matrix 0; P2 != nullptr: Homography_Wrapper's switch on corner-0 y > 60, as rn_state_to_im); box fp64
+ *                        [N,4] = (min x, min y, max x, max y) of the eight image corners. */
+#define RN_REINTERP_TILE 1024
+#define RN_REINTERP_BAD_OFFSETS 1     /* frame offsets not monotone or outside the R rows */
+#define RN_REINTERP_BAD_PAIR 2        /* inst_a < 0 or inst_a + 1 >= F */
+#define RN_REINTERP_BAD_MATE 4        /* a non-negative mate outside the next frame */
+#define RN_REINTERP_BAD_PREFIX 8      /* a destination outside its prefix slot or outside the U output rows */
+#define RN_REINTERP_BAD_MAT_INDEX 16  /* mat_index outside the n_mats matrices */
+int rn_reinterp_mate(const int64_t *offsets, const int64_t *ids, int64_t F, int64_t R, int32_t *mate, int32_t *status,
+                     void *stream);
+int rn_reinterp_offsets(const int64_t *offsets, const int32_t *mate, int64_t F, int64_t R, const int32_t *inst_a, int64_t T,
+                        int32_t *frame_count, int32_t *count, int64_t *prefix, int32_t *status, void *stream);
+int rn_reinterp_rows(const int64_t *offsets, const double *frame_ts, const double *fields, const int32_t *mate,
+                     const int32_t *inst_a, const double *inst_time, const int64_t *prefix, int64_t F, int64_t R, int64_t T,
+                     int64_t U, double *out_fields, int32_t *out_src, int32_t *out_inst, int32_t *status, void *stream);
+int rn_track_rows(const double *fields, const double *direction, const int32_t *mat_index, const double *P, const double *P2,
+                  int64_t n_mats, int64_t N, float *state, float *space, double *im, double *box, uint8_t *keep,
+                  int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

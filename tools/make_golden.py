@@ -463,6 +463,14 @@ def gen_crop_refine():
     np.savez_compressed(os.path.join(OUT, "crop_refine.npz"), **out)
 
 
+def gen_datareader():
+    """tests/golden/datareader.npz: the reference's Data_Reader on the cases of tests/datareader_cases.py.  Its own script
+    (tools/make_golden_datareader.py), in a child process: it imports the reference's datareader and homography modules under
+    their own names, which this process must not see."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_datareader.py"), "--out", OUT])
+
+
 def ref_module_from_file(alias, relpath):
     """A reference module loaded from its file, under a private name: this repository ships same-named drop-ins
     (util_track/kf.py, homography.py) that come first on sys.path, and a golden must come from the REFERENCE's code."""
@@ -1629,7 +1637,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1672,6 +1680,8 @@ def main():
         gen_calibration()
     if "frames4k" in which:
         gen_frames4k()
+    if "datareader" in which:
+        gen_datareader()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
