@@ -167,17 +167,31 @@ class Torch_KF(object):
 
     def update(self, detections, obj_ids, measurement_idx=1):              # kf.py:335-403
         if measurement_idx == 1:
-            mu_R, H, R = self.mu_R, self.H, self.R
+            names = ("mu_R", "H", "R")
         elif measurement_idx in (2, 3):
-            mu_R, H, R = (getattr(self, "%s%d" % (k, measurement_idx)) for k in ("mu_R", "H", "R"))
+            names = tuple("%s%d" % (k, measurement_idx) for k in ("mu_R", "H", "R"))
         else:
             print("This measurement index does not exist in this filter")
             raise ValueError
+        # the kernel reads H [5,6], R [5,5] and mu_R [5] as float32 on the filter's device: anything else is refused here
+        # (the reference's bmm raises a shape error; the default constructor leaves R2 on the CPU and defines no H2)
+        dev = self.F.device                                   # the filter's device with its index resolved
+        for name, shape in zip(names, ((1, 5), (5, 6), (1, 5, 5))):
+            m = getattr(self, name, None)
+            if not isinstance(m, torch.Tensor) or tuple(m.shape) != shape or m.dtype != torch.float32 or m.device != dev:
+                raise RuntimeError("update: %s must be a float32 tensor of shape %s on %s, got %s"
+                                   % (name, shape, dev, "nothing" if not isinstance(m, torch.Tensor) else
+                                      "%s %s on %s" % (m.dtype, tuple(m.shape), m.device)))
+        mu_R, H, R = (getattr(self, name) for name in names)
         rows = [self.obj_idxs[oid] for oid in obj_ids]
         if len(set(rows)) != len(rows):
             raise RuntimeError("update: an object id appears twice (the reference lets the last write win; the kernel "
                                "updates rows in parallel)")
-        z = (torch.from_numpy(detections) if isinstance(detections, np.ndarray) else detections).to(self.device).double().contiguous()
+        z = torch.from_numpy(detections) if isinstance(detections, np.ndarray) else detections
+        if tuple(z.shape) != (len(rows), 5) and not (len(rows) == 0 and z.numel() == 0):
+            raise RuntimeError("update: detections are %s for %d objects, expected [%d, 5]"
+                               % (tuple(z.shape), len(rows), len(rows)))
+        z = z.to(self.device).double().contiguous()
         if len(rows) == 0:
             return
         r = torch.as_tensor(rows, dtype=torch.int32, device=self.device)
