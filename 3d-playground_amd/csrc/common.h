@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/retinanet_mi355x.h"
 
@@ -41,6 +42,12 @@
     } while (0)
 
 static inline int rn_blocks(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
+// An integer knob from the environment (A/B switches of the launchers).  Use as the initialiser of a function-local `static const int`:
+// the variable is then read once per process, at the first launch that asks, never per launch.
+static inline int rn_env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // Sum over the 64 lanes of a wave; every lane gets the total.
 __device__ __forceinline__ float wave_sum(float v) {

@@ -23,9 +23,7 @@
 // one operand.  fp32 atomics into the same packed fp32 [Cout][Kpad] gradient buffer the fp32 path uses.
 //
 // Roofline: MFMA by FLOPs (2.5 PF dense), in practice the staging bandwidth (see above) and, for the 1x1 layers, HBM.
-#include <stdlib.h>
-
-#include "common.h"
+#include "conv_launch.h"
 #include "conv_wgrad_geom.h"
 
 #ifndef RN_WG_KO
@@ -51,10 +49,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #define BF_OCC 4                 // waves per SIMD the register budget is cut for = workgroups per CU that fit next to the LDS
 #endif
 
-__device__ __forceinline__ int bf_xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 __device__ __forceinline__ int bf_swz(int row) { return (row >> 2) & 3; }     // 64-byte rows (conv_igemm_tile.h: lds_swz<16>)
 
 __device__ __forceinline__ void bf_load4(const __bf16 *p, float (&v)[4]) {
@@ -102,10 +96,7 @@ extern "C" int rn_bf16_to_f32(const void *src, float *dst, int64_t n, void *stre
 // ---------------------------------------------------------------------------------------------- implicit GEMM
 // One (64*WM) x (64*WN) output tile by WM x WN waves, each a 64 x 64 sub-tile = 2 x 2 accumulators of the 32x32x16 MFMA:
 //   <2,2>  128 x 128, 256 threads, four workgroups per CU  -- 64 FLOP per staged byte;
-//   <4,4>  256 x 256, 1024 threads, one workgroup per CU   -- 128 FLOP per staged byte: the per-wave work (8 MFMAs and
-//          8 ds_read_b128 per K-step) is the same, only HALF the bytes come through L2 -> LDS per FLOP, which is what
-//          bounds the small tile (~800 TFLOP/s = 12.5 TB/s of staging against 17-19 TB/s the LDS-DMA path delivers from L2).
-//          Used where the problem has enough 256-tiles to fill the chip (launcher).
+//   <4,1>  256 x 64 for at most 64 output channels; <2,2> with TM = 4: 256 x 128, two workgroups per CU (launcher: bf16_is_tall).
 // YF32: the output is written as fp32 (head outputs feeding the loss) instead of bf16; addend and mask are bf16.
 template <bool YF32, int WM, int WN, bool DENSE, int TM = 2>
 __device__ __forceinline__ void conv_igemm_bf16_tile(const rn_conv_desc &d, const __bf16 *__restrict__ x,
@@ -317,7 +308,7 @@ __device__ __forceinline__ void conv_igemm_bf16_tile(const rn_conv_desc &d, cons
     __bf16 *yb = reinterpret_cast<__bf16 *>(yv);
     float *yf = reinterpret_cast<float *>(yv);
     // DENSE (a template parameter: both paths in one kernel cost registers the K loop needs): result and addend in the problem's
-    // own pixel order, so the offset of row m is m * Cout and there is nothing to decompose (bf16_desc_is_dense)
+    // own pixel order, so the offset of row m is m * Cout and there is nothing to decompose (conv_launch.h: rn_conv_dense)
 #pragma unroll 1
     for (int pass = 0; pass < BM / RP; ++pass) {
         if (pass) __syncthreads();
@@ -422,7 +413,7 @@ __global__ __launch_bounds__(64 * WM * WN, TM == 4 ? 2 : BF_OCC) void conv_igemm
                                                                  const __bf16 *__restrict__ w, void *__restrict__ yv,
                                                                  const float *__restrict__ scale, const float *__restrict__ shift,
                                                                  const __bf16 *__restrict__ add, const __bf16 *__restrict__ mask) {
-    conv_igemm_bf16_tile<YF32, WM, WN, DENSE, TM>(d, x, w, yv, scale, shift, add, mask, bf_xcd_remap(blockIdx.x, gridDim.x));
+    conv_igemm_bf16_tile<YF32, WM, WN, DENSE, TM>(d, x, w, yv, scale, shift, add, mask, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Grouped launch (rn_conv_igemm_grouped's form): up to RN_MAX_GROUP problems sharing weights and epilogue scalars -- the five
@@ -431,10 +422,8 @@ template <bool YF32, int WM, int WN, bool DENSE, int TM = 2>
 __global__ __launch_bounds__(64 * WM * WN, TM == 4 ? 2 : BF_OCC) void conv_igemm_bf16_grouped_kernel(const rn_conv_group g, const __bf16 *__restrict__ w,
                                                                          const float *__restrict__ scale,
                                                                          const float *__restrict__ shift) {
-    const int tile = bf_xcd_remap(blockIdx.x, gridDim.x);
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
+    const int tile = xcd_remap(blockIdx.x, gridDim.x);
+    const int p = rn_group_index(g, tile);
     rn_conv_desc d = g.d[0];
     const float *x = g.x[0], *add = g.add[0], *mask = g.mask[0];
     float *y = g.y[0];
@@ -461,40 +450,23 @@ static inline bool bf16_p8_pick(const rn_conv_desc *d, int y_is_f32, int64_t til
     const int mode = rn_get_option(RN_OPT_BF16_P8);
     if (mode == 0 || !rn_bf16_p8_legal(d, y_is_f32)) return false;
     if (mode == 2) return true;
-    static const int min_k = [] { const char *e = getenv("RN_BF16_P8_MIN_K"); return e ? atoi(e) : 256; }();
-    static const int min_tiles = [] { const char *e = getenv("RN_BF16_P8_MIN_TILES"); return e ? atoi(e) : 200; }();
+    static const int min_k = rn_env_int("RN_BF16_P8_MIN_K", 256);
+    static const int min_tiles = rn_env_int("RN_BF16_P8_MIN_TILES", 200);
     if ((d->Cout & 255) != 0 || tiles_in_launch < min_tiles) return false;
     return d->kh * d->kw * d->Cin >= min_k || d->mask_mode == 0;
 }
 static inline bool bf16_group_is_p8(const rn_conv_group *g, int y_is_f32) {
     int64_t t = 0;
-    for (int i = 0; i < g->n; ++i) t += (((int64_t)g->d[i].N * g->d[i].Ho * g->d[i].Wo + 255) / 256) * ((g->d[i].Cout + 255) / 256);
+    for (int i = 0; i < g->n; ++i) t += rn_conv_tiles(&g->d[i], 256, 256);
     for (int i = 0; i < g->n; ++i)
         if (!bf16_p8_pick(&g->d[i], y_is_f32, t)) return false;
     return true;
 }
 
-static inline bool bf16_desc_is_dense(const rn_conv_desc *d) {
-    return d->os == 1 && d->oo_h == 0 && d->oo_w == 0 && d->Hy == d->Ho && d->Wy == d->Wo &&
-           d->y_batch_stride == (int64_t)d->Ho * d->Wo * d->Cout && d->add_mode != 2 &&
-           (d->add_mode == 0 || d->add_batch_stride == d->y_batch_stride);
-}
-
+// What the bf16 launchers accept (conv_launch.h has the rules every form shares): 2-byte elements, tiles of up to 256 rows.
 static inline int check_desc_bf16(const rn_conv_desc *d) {
-    if (d->N <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0) return RN_EINVAL;
-    if (d->Cin < 8 || (d->Cin & 7) || (d->Cout & 3) || d->w_format != 0) return RN_EINVAL;   // 16-byte chunks of 8 channels; 16-byte stores
-    if ((int64_t)d->Hi * d->Wi * d->Cin * 2 > 0x7fffffffLL) return RN_EINVAL;
-    const int64_t HoWo = (int64_t)d->Ho * d->Wo, span = 255 / HoWo + 2;    // images a 256-row tile can touch
-    if (d->x_batch_stride < 0 || ((span - 1) * d->x_batch_stride + (int64_t)d->Hi * d->Wi * d->Cin) * 2 > 0x7fffffffLL) return RN_EINVAL;
-    const int64_t Kpad = ((int64_t)d->kh * d->kw * d->Cin + 31) / 32 * 32;
-    if (d->Cout * Kpad * 2 > 0x7fffffffLL || (int64_t)d->N * HoWo > 0x7fffffffLL) return RN_EINVAL;
-    if (d->kh <= 0 || d->kw <= 0 || d->div_shift < 0 || d->div_shift > 2) return RN_EINVAL;
-    if (d->add_mode < 0 || d->add_mode > 2 || d->act < 0 || d->act > 2) return RN_EINVAL;
-    if (d->mask_mode < 0 || (d->mask_mode & ~(3 | RN_MASK_BITS)) || (d->mask_mode & 3) == 3 || d->mask_mode == RN_MASK_BITS) return RN_EINVAL;
-    if (((d->mask_mode & RN_MASK_BITS) || d->sign_out != nullptr) && ((d->Cout & 31) || (d->y_batch_stride & 31))) return RN_EINVAL;
-    if (d->os < 1 || d->oo_h < 0 || d->oo_w < 0) return RN_EINVAL;
-    if ((d->Ho - 1) * d->os + d->oo_h >= d->Hy || (d->Wo - 1) * d->os + d->oo_w >= d->Wy) return RN_EINVAL;
-    if (d->os != 1 && d->add_mode == 2) return RN_EINVAL;
+    if (rn_check_desc_core(d, 2, 256, 32) || rn_check_desc_mask(d)) return RN_EINVAL;
+    if ((d->Cout & 3) || d->w_format != 0) return RN_EINVAL;                            // 16-byte stores
     if (d->in_relu || d->add2_mode != 0 || d->w_batch_stride != 0) return RN_EINVAL;   // not in the bf16 form (yet)
     return RN_OK;
 }
@@ -512,104 +484,80 @@ static inline int check_ptrs_bf16(const rn_conv_desc *d, const void *x, const vo
 
 // (Rounds 2-4 also carried a 256 x 256 tile of sixteen waves, one 1024-thread workgroup per CU, behind RN_BF16_BIG_TILE: +25 % on long-K 3x3
 // layers alone, -5 % on the whole step (171.1 against 180.0 images/s), and superseded by the eight-wave phased kernel of conv_bf16_p8.hip
-// in round 4.  Its instances left the library in round 5; the 256 x 256 tile rows below are the phased kernel's.)
-static inline bool bf16_big_tile(int64_t, int, int, int) { return false; }
-static inline bool bf16_tile_is_big(const rn_conv_group *, int) { return false; }
-// 256 x 128 tile for a group: dense bf16 results, Cout a multiple of 128, a long K loop and enough tiles (see the single launcher)
-static inline bool bf16_group_is_tall(const rn_conv_group *g, int y_is_f32) {
-    static const int tall_env = [] { const char *e = getenv("RN_BF16_TALL_TILE"); return e ? atoi(e) : -1; }();
-    if (y_is_f32 || tall_env == 0 || bf16_tile_is_big(g, y_is_f32) || (g->d[0].Cout & 127) != 0) return false;
+// in round 4.  Its instances left the library in round 5; the 256 x 256 tiles below are the phased kernel's.)
+// 256 x 128 tile (4 waves of 128 x 64, two workgroups per CU): 85 FLOP per staged byte instead of 64, for the n problems of a launch (one,
+// or a group) when all results are dense bf16, Cout is a multiple of 128, the K loop is long and there are enough tiles.
+// RN_BF16_TALL_TILE=0 turns it off, =1 forces it where it is legal.
+static inline bool bf16_is_tall(const rn_conv_desc *d, int n, int y_is_f32) {
+    static const int tall_env = rn_env_int("RN_BF16_TALL_TILE", -1);
+    if (y_is_f32 || tall_env == 0 || (d[0].Cout & 127) != 0) return false;
     int64_t t = 0;
-    for (int i = 0; i < g->n; ++i) {
-        if (!bf16_desc_is_dense(&g->d[i])) return false;
-        t += (((int64_t)g->d[i].N * g->d[i].Ho * g->d[i].Wo + 255) / 256) * ((g->d[i].Cout + 127) / 128);
+    for (int i = 0; i < n; ++i) {
+        if (!rn_conv_dense(&d[i])) return false;
+        t += rn_conv_tiles(&d[i], 256, 128);
     }
-    return tall_env == 1 || (g->d[0].kh * g->d[0].kw * g->d[0].Cin >= 1024 && t >= 512);
+    return tall_env == 1 || (d[0].kh * d[0].kw * d[0].Cin >= 1024 && t >= 512);
 }
 // Tile shape rn_conv_igemm_bf16_grouped will use for this group: the caller builds tile_end with it
 // (tile_end[i] = running sum of ceil(N*Ho*Wo / rows) * ceil(Cout / cols)).  Returns rows * 1000 + cols.
 extern "C" int rn_conv_igemm_bf16_tile_rows(const rn_conv_group *g, int y_is_f32) {
     if (g->n < 1 || g->n > RN_MAX_GROUP) return 0;
     if (bf16_group_is_p8(g, y_is_f32)) return 256 * 1000 + 256;
-    if (bf16_tile_is_big(g, y_is_f32)) return 256 * 1000 + 256;
-    if (bf16_group_is_tall(g, y_is_f32)) return 256 * 1000 + 128;
+    if (bf16_is_tall(g->d, g->n, y_is_f32)) return 256 * 1000 + 128;
     return 128 * 1000 + 128;
 }
 
 // The tile a SINGLE launch (rn_conv_igemm_bf16) takes: rows * 1000 + cols, + 1 000 000 for the eight-wave phased kernel (profiling / tests).
 extern "C" int rn_conv_igemm_bf16_tile(const rn_conv_desc *d, int y_is_f32) {
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    if (bf16_p8_pick(d, y_is_f32, ((M + 255) / 256) * ((d->Cout + 255) / 256))) return 1000000 + 256 * 1000 + 256;
-    if (bf16_big_tile(((M + 255) / 256) * ((d->Cout + 255) / 256), d->Cout, d->kh * d->kw * d->Cin, y_is_f32)) return 256 * 1000 + 256;
-    return 128 * 1000 + 128;                                  // (or 256 x 128 for long dense launches: rn_conv_igemm_bf16)
+    if (bf16_p8_pick(d, y_is_f32, rn_conv_tiles(d, 256, 256))) return 1000000 + 256 * 1000 + 256;
+    return 128 * 1000 + 128;                                  // (or 256 x 128 / 256 x 64 for dense launches: rn_conv_igemm_bf16)
 }
 
 extern "C" int rn_conv_igemm_bf16_grouped(const rn_conv_group *g, const void *w_packed, int y_is_f32, const float *scale,
                                           const float *shift, void *stream) {
     if (g->n < 1 || g->n > RN_MAX_GROUP || ((uintptr_t)w_packed & 15)) return RN_EINVAL;
     const rn_conv_desc &d0 = g->d[0];
-    const bool p8 = bf16_group_is_p8(g, y_is_f32);
-    const bool big = p8 || bf16_tile_is_big(g, y_is_f32);    // the caller's tile_end must follow rn_conv_igemm_bf16_tile_rows()
-    const bool tall = !p8 && bf16_group_is_tall(g, y_is_f32);
-    const int TR = big ? 256 : 128, TRM = (big || tall) ? 256 : 128;
-    int prev = 0;
-    for (int i = 0; i < g->n; ++i) {
-        const rn_conv_desc &d = g->d[i];
-        int rc = check_desc_bf16(&d);
-        if (rc) return rc;
-        rc = check_ptrs_bf16(&d, g->x[i], g->y[i], g->add[i], g->mask[i], y_is_f32);
-        if (rc) return rc;
-        if (d.Cin != d0.Cin || d.Cout != d0.Cout || d.kh != d0.kh || d.kw != d0.kw || d.act != d0.act) return RN_EINVAL;
-        const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-        const int64_t tiles = ((M + TRM - 1) / TRM) * ((d.Cout + TR - 1) / TR);
-        if (g->tile_end[i] - prev != tiles) return RN_EINVAL;
-        prev = g->tile_end[i];
-    }
+    const bool p8 = bf16_group_is_p8(g, y_is_f32);           // the caller's tile_end must follow rn_conv_igemm_bf16_tile_rows()
+    const bool tall = !p8 && bf16_is_tall(g->d, g->n, y_is_f32);
+    int tiles = 0;
+    const int rg = rn_check_group(g, (p8 || tall) ? 256 : 128, p8 ? 256 : 128, [&](const rn_conv_desc &d, int i) {
+        if (check_desc_bf16(&d) || check_ptrs_bf16(&d, g->x[i], g->y[i], g->add[i], g->mask[i], y_is_f32)) return RN_EINVAL;
+        return d.act != d0.act ? RN_EINVAL : RN_OK;
+    }, &tiles);
+    if (rg) return rg;
+    if (p8) return rn_bf16_p8_launch_grouped(g, tiles, w_packed, scale, shift, (hipStream_t)stream);
     const __bf16 *wb = reinterpret_cast<const __bf16 *>(w_packed);
     bool dense = true;
-    for (int i = 0; i < g->n; ++i) dense = dense && bf16_desc_is_dense(&g->d[i]);
-    if (p8) return rn_bf16_p8_launch_grouped(g, prev, w_packed, scale, shift, (hipStream_t)stream);
-    {
-        const dim3 grid((unsigned)prev), block(256);
-        if (y_is_f32) hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<true, 2, 2, false>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
-        else if (tall) hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<false, 2, 2, true, 4>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
-        else if (dense) hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<false, 2, 2, true>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
-        else hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<false, 2, 2, false>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
-    }
+    for (int i = 0; i < g->n; ++i) dense = dense && rn_conv_dense(&g->d[i]);
+    const dim3 grid((unsigned)tiles), block(256);
+    if (y_is_f32) hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<true, 2, 2, false>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
+    else if (tall) hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<false, 2, 2, true, 4>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
+    else if (dense) hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<false, 2, 2, true>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
+    else hipLaunchKernelGGL((conv_igemm_bf16_grouped_kernel<false, 2, 2, false>), grid, block, 0, (hipStream_t)stream, *g, wb, scale, shift);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
 
 extern "C" int rn_conv_igemm_bf16(const rn_conv_desc *d, const void *x, const void *w_packed, void *y, int y_is_f32,
                                   const float *scale, const float *shift, const void *add, const void *mask, void *stream) {
-    const int rc = check_desc_bf16(d);
-    if (rc) return rc;
-    const int rp = check_ptrs_bf16(d, x, y, add, mask, y_is_f32);
-    if (rp || ((uintptr_t)w_packed & 15)) return RN_EINVAL;
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    if (bf16_p8_pick(d, y_is_f32, ((M + 255) / 256) * ((d->Cout + 255) / 256)))
+    if (check_desc_bf16(d) || check_ptrs_bf16(d, x, y, add, mask, y_is_f32) || ((uintptr_t)w_packed & 15)) return RN_EINVAL;
+    if (bf16_p8_pick(d, y_is_f32, rn_conv_tiles(d, 256, 256)))
         return rn_bf16_p8_launch(d, x, w_packed, y, scale, shift, add, mask, (hipStream_t)stream);
-    const bool big = bf16_big_tile(((M + 255) / 256) * ((d->Cout + 255) / 256), d->Cout, d->kh * d->kw * d->Cin, y_is_f32);
-    // 256 x 128 tile (4 waves of 128 x 64, two workgroups per CU): 85 FLOP per staged byte instead of 64, for dense bf16
-    // results with a long K loop and enough tiles (RN_BF16_TALL_TILE=0 turns it off, =1 forces it where it is legal)
-    static const int tall_env = [] { const char *e = getenv("RN_BF16_TALL_TILE"); return e ? atoi(e) : -1; }();
-    const int64_t tall_tiles = ((M + 255) / 256) * ((d->Cout + 127) / 128);
-    const bool tall_ok = !big && !y_is_f32 && bf16_desc_is_dense(d) && (d->Cout & 127) == 0;
-    const bool tall = tall_ok && (tall_env == 1 || (tall_env != 0 && d->kh * d->kw * d->Cin >= 1024 && tall_tiles >= 512));
+    const bool dense = rn_conv_dense(d);
+    const bool tall = bf16_is_tall(d, 1, y_is_f32);
     // 256 x 64 tile (4 x 1 waves of 64 x 64) for dense bf16 results with at most 64 output channels: the 128 x 128 tile computes half of
     // its columns for nothing there (3x3 64 -> 64, 1x1 256 -> 64 and their data gradients).  RN_BF16_NARROW_TILE=0 turns it off (A/B).
-    static const int narrow_env = [] { const char *e = getenv("RN_BF16_NARROW_TILE"); return e ? atoi(e) : 1; }();
-    const bool narrow = narrow_env != 0 && !big && !tall && !y_is_f32 && d->Cout <= 64 && bf16_desc_is_dense(d);
-    const int TR = big ? 256 : (narrow ? 64 : 128), TRM = (big || tall || narrow) ? 256 : 128;
-    const int64_t tiles = ((M + TRM - 1) / TRM) * ((d->Cout + TR - 1) / TR);
+    static const int narrow_env = rn_env_int("RN_BF16_NARROW_TILE", 1);
+    const bool narrow = narrow_env != 0 && !tall && !y_is_f32 && d->Cout <= 64 && dense;
+    const int64_t tiles = rn_conv_tiles(d, (tall || narrow) ? 256 : 128, narrow ? 64 : 128);
     if (tiles > 0x7fffffff) return RN_EINVAL;
-    const dim3 grid((unsigned)tiles), block(big ? 1024 : 256);
+    const dim3 grid((unsigned)tiles), block(256);
     const __bf16 *xb = reinterpret_cast<const __bf16 *>(x), *wb = reinterpret_cast<const __bf16 *>(w_packed);
     const __bf16 *ab = reinterpret_cast<const __bf16 *>(add), *mb = reinterpret_cast<const __bf16 *>(mask);
     if (tall) hipLaunchKernelGGL((conv_igemm_bf16_kernel<false, 2, 2, true, 4>), grid, block, 0, (hipStream_t)stream, *d, xb, wb, y, scale, shift, ab, mb);
     else if (narrow) hipLaunchKernelGGL((conv_igemm_bf16_kernel<false, 4, 1, true>), grid, block, 0, (hipStream_t)stream, *d, xb, wb, y, scale, shift, ab, mb);
     else if (y_is_f32) hipLaunchKernelGGL((conv_igemm_bf16_kernel<true, 2, 2, false>), grid, block, 0, (hipStream_t)stream, *d, xb, wb, y, scale, shift, ab, mb);
-    else if (bf16_desc_is_dense(d)) hipLaunchKernelGGL((conv_igemm_bf16_kernel<false, 2, 2, true>), grid, block, 0, (hipStream_t)stream, *d, xb, wb, y, scale, shift, ab, mb);
+    else if (dense) hipLaunchKernelGGL((conv_igemm_bf16_kernel<false, 2, 2, true>), grid, block, 0, (hipStream_t)stream, *d, xb, wb, y, scale, shift, ab, mb);
     else hipLaunchKernelGGL((conv_igemm_bf16_kernel<false, 2, 2, false>), grid, block, 0, (hipStream_t)stream, *d, xb, wb, y, scale, shift, ab, mb);
     RN_LAUNCH_CHECK();
     return RN_OK;
@@ -869,11 +817,17 @@ static int64_t wgrad_bf16_fill(WgradBf16Args &a, const void *dy, int ldy, const 
     }
     splits = (a.pixels + a.per_split - 1) / a.per_split;
     a.splits = (int)splits;
-    static const int xcd_env = [] { const char *e = getenv("RN_WGRAD_BF16_XCD"); return e ? atoi(e) : 1; }();
+    static const int xcd_env = rn_env_int("RN_WGRAD_BF16_XCD", 1);
     a.xcd_map = xcd_env != 0 && a.tiles >= 4 && splits >= 8;
     int64_t blocks = a.tiles * (a.xcd_map ? (splits + 7) / 8 * 8 : splits);
     if (pad8 && !a.xcd_map) blocks = (blocks + 7) / 8 * 8;      // grouped: every problem's range starts at a multiple of 8 (surplus ids: slice >= splits)
     return blocks;
+}
+
+// Workgroups a weight-gradient launch aims for (see rn_conv_wgrad_bf16); RN_WGRAD_BF16_WGS overrides.
+static int wgrad_bf16_target_wgs() {
+    static const int v = rn_env_int("RN_WGRAD_BF16_WGS", 0);
+    return v > 0 ? v : 768;
 }
 
 extern "C" int rn_conv_wgrad_bf16(const void *dy, int ldy, const void *x, float *dw, float *colsum, int N, int Hi, int Wi,
@@ -883,7 +837,7 @@ extern "C" int rn_conv_wgrad_bf16(const void *dy, int ldy, const void *x, float 
     if (((uintptr_t)dy & 15) || ((uintptr_t)x & 15)) return RN_EINVAL;
     // (A 256 x 256 eight-wave form of this reduction was built in round 4, correct and slower -- 0.51 against 0.40 ms on the head tower
     // layer, profiles/r04_wgrad_p8_knockouts.txt -- and now lives in tools/probes/quarantine_r05/.)
-    static const int target_wgs = [] { const char *e = getenv("RN_WGRAD_BF16_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 768; }();
+    const int target_wgs = wgrad_bf16_target_wgs();
     // K slices for ~768 workgroups = ONE resident round at three per CU.  Every slice ends in tile-sized fp32 atomics
     // (Cout x Kflat x slices of them per launch, ~1.3 TB/s chip-wide), and with the MFMAs eight times shorter than in the
     // fp32 kernel that tail weighs more: measured per training step (all weight gradients) 512: 11.6 ms, 768: 11.1,
@@ -902,7 +856,7 @@ extern "C" int rn_conv_wgrad_bf16(const void *dy, int ldy, const void *x, float 
 extern "C" int rn_conv_wgrad_bf16_grouped(int n, const void *const *dy, int ldy, const void *const *x, float *dw, float *colsum, int N,
                                           const int *Hi, const int *Wi, int Cin, int Cout, int kh, int kw, int stride, int pad, void *stream) {
     if (n < 1 || n > RN_MAX_GROUP || N <= 0 || Cout <= 0 || Cin < 8 || (Cin & 7) || (ldy & 7) || ldy < Cout) return RN_EINVAL;
-    static const int target_wgs = [] { const char *e = getenv("RN_WGRAD_BF16_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 768; }();
+    const int target_wgs = wgrad_bf16_target_wgs();
     int Ho[RN_MAX_GROUP], Wo[RN_MAX_GROUP];
     int64_t total_pixels = 0;
     for (int i = 0; i < n; ++i) {

@@ -20,7 +20,8 @@
 // Roofline: MFMA (2.5 PFLOP/s dense bf16).  Algorithmic bytes per tile: (256 + 256) rows x 128 B per K-tile from L2, 128 KB stored.
 #include <type_traits>
 
-#include "common.h"
+#include "conv_launch.h"
+#include "conv_p8_geom.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -38,7 +39,6 @@ __device__ __forceinline__ int p8_swz(int r) { return (r >> 1) & 7; }
 #ifndef P8_ABL
 #define P8_ABL 0                                 // knock-outs for profiles/ (bits): 1 no epilogue, 2 no validity test, 4 no staging after the prologue
 #endif
-struct P8Tap { int r, s, c; };                   // filter row, filter column, first channel of a K-tile (wave-uniform)
 
 // ---- epilogue: v = scale[c] * acc + shift[c]; [mask before the add]; v += add; [ReLU]; [mask after]; one rounding on the store
 // (conv_bf16.hip's arithmetic, in its order).  acc[rb][cb][e] is pixel row rb * 16 + lr, channel cb * 16 + 4 lg + e of the wave's
@@ -163,8 +163,7 @@ __device__ __forceinline__ void p8_tile(const rn_conv_desc &d, const __bf16 *__r
     const int Cin = d.Cin, K = d.kh * d.kw * Cin, nkt = K / P8_BK;
 
     // descriptors.  Pixels: the flat [M][Cin] tensor from `halo` rows in front of the tile (the farthest a tap reaches back).
-    const int ab = d.b < 0 ? -d.b : d.b;
-    const int halo = ((d.p < 0 ? -d.p : d.p) + (d.kh - 1) * ab) * d.Wi + (d.p_w < 0 ? -d.p_w : d.p_w) + (d.kw - 1) * ab;
+    const int halo = p8_halo<int>(d);
     const int base_row = m0 > halo ? m0 - halo : 0;
     const int64_t a_bytes = ((int64_t)M - base_row) * Cin * 2;
     const v4i32 rs_a = make_rsrc(x + (int64_t)base_row * Cin, (unsigned)(a_bytes > 0x7FFFFFFF ? 0x7FFFFFFF : a_bytes));
@@ -192,12 +191,6 @@ __device__ __forceinline__ void p8_tile(const rn_conv_desc &d, const __bf16 *__r
             }
         }
     }
-    auto uni = [](const v4i32 r) {
-        v4i32 o;
-        o.x = __builtin_amdgcn_readfirstlane(r.x); o.y = __builtin_amdgcn_readfirstlane(r.y);
-        o.z = __builtin_amdgcn_readfirstlane(r.z); o.w = __builtin_amdgcn_readfirstlane(r.w);
-        return o;
-    };
     // The pixel offsets of the four staging instructions AT THE CURRENT TAP (validity applied): recomputed when the staging cursor enters
     // a new tap (every Cin / 64 K-tiles), so that a K-tile's staging is four buffer loads with a scalar channel offset and no vector
     // arithmetic.  (Counters, profiles/r04_pmc_p8.txt: 2.1 VALU instructions per MFMA -- with the MFMA's own 8 issue cycles that fills
@@ -214,9 +207,9 @@ __device__ __forceinline__ void p8_tile(const rn_conv_desc &d, const __bf16 *__r
     auto dma = [&](const int i, const P8Tap &tp, const int kt, const int buf) {   // instruction i of this wave for K-tile kt (at tap tp: set_tap)
         const unsigned dst = lds0 + (unsigned)(buf * P8_BUFB + (wave_u + 8 * i) * 1024);
         if (i < 4) {
-            dma16(uni(rs_a), dst, va[i], (unsigned)__builtin_amdgcn_readfirstlane(tp.c * 2));
+            dma16(p8_uniform(rs_a), dst, va[i], (unsigned)__builtin_amdgcn_readfirstlane(tp.c * 2));
         } else {
-            dma16(uni(rs_b), dst, voff_b, (unsigned)__builtin_amdgcn_readfirstlane((kt * P8_BK + (i - 4) * 64 * K) * 2));
+            dma16(p8_uniform(rs_b), dst, voff_b, (unsigned)__builtin_amdgcn_readfirstlane((kt * P8_BK + (i - 4) * 64 * K) * 2));
         }
     };
     auto next_tap = [&](P8Tap &tp) {
@@ -385,31 +378,19 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_bf16_p8_grouped_kernel(cons
                                                                            const float *__restrict__ scale, const float *__restrict__ shift) {
     extern __shared__ __attribute__((aligned(16))) char p8_lds[];
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
-    p = __builtin_amdgcn_readfirstlane(p);
+    const int p = __builtin_amdgcn_readfirstlane(rn_group_index(g, tile));
     const int first = p > 0 ? g.tile_end[p - 1] : 0;
     p8_tile(g.d[p], reinterpret_cast<const __bf16 *>(g.x[p]), w, reinterpret_cast<__bf16 *>(g.y[p]), scale, shift,
             reinterpret_cast<const __bf16 *>(g.add[p]), reinterpret_cast<const __bf16 *>(g.mask[p]), tile - first, p8_lds);
 }
 
 // ---------------------------------------------------------------------------------------------- host side (used by conv_bf16.hip)
-// What the kernel can compute: a stride-1 convolution whose output plane is the input plane (so that pixel rows are one flat sequence
-// on both sides), batch-dense NHWC operands, Cin a multiple of the 64-channel K-tile, at most 4 x 4 taps, a dense bf16 result.
+// What the kernel can compute: conv_p8_geom.h's common rules, and of its own a stride-1 convolution whose output plane is the input
+// plane (so that pixel rows are one flat sequence on both sides), 16-byte bf16 stores, no mask together with sign bits.
 bool rn_bf16_p8_legal(const rn_conv_desc *d, int y_is_f32) {
-    if (y_is_f32 || d->a != 1 || d->div_shift != 0 || d->Hi != d->Ho || d->Wi != d->Wo) return false;
-    if (d->act == 2 || (d->mask_mode != 0 && d->sign_out != nullptr)) return false;      // epilogue forms the kernel has no instance of
-    if (d->Cin < 64 || (d->Cin & 63) || (d->Cout & 7) || d->kh > 4 || d->kw > 4) return false;
-    const int64_t plane = (int64_t)d->Hi * d->Wi;
-    if (d->x_batch_stride != plane * d->Cin || d->y_batch_stride != plane * d->Cout) return false;
-    if (d->os != 1 || d->oo_h != 0 || d->oo_w != 0 || d->Hy != d->Ho || d->Wy != d->Wo || d->add_mode == 2) return false;
-    if (d->add_mode == 1 && d->add_batch_stride != d->y_batch_stride) return false;
-    const int64_t K = (int64_t)d->kh * d->kw * d->Cin, M = (int64_t)d->N * plane;
-    const int64_t ab = d->b < 0 ? -d->b : d->b;
-    const int64_t halo = (llabs((long long)d->p) + (d->kh - 1) * ab) * d->Wi + llabs((long long)d->p_w) + (d->kw - 1) * ab;
-    if (M + 256 > 0x7fffffffLL || (256 + 2 * halo + 64) * d->Cin * 2 > 0x7fffffffLL || ((int64_t)d->Cout + 256) * K * 2 > 0x7fffffffLL) return false;
-    return true;
+    if (d->a != 1 || d->Hi != d->Ho || d->Wi != d->Wo || (d->Cout & 7)) return false;
+    if (d->mask_mode != 0 && d->sign_out != nullptr) return false;                       // an epilogue form the kernel has no instance of
+    return p8_common_legal(d, y_is_f32, 2);
 }
 // Whether the launchers take it: RN_OPT_BF16_P8 = 0 never, 2 wherever legal, 1 (default) where it has measured faster -- see the rule's
 // comment in conv_bf16.hip.
@@ -417,8 +398,7 @@ int rn_bf16_p8_launch(const rn_conv_desc *d, const void *x, const void *w, void 
                       const void *add, const void *mask, hipStream_t stream) {
     static const hipError_t attr = hipFuncSetAttribute((const void *)conv_igemm_bf16_p8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS);
     if (attr != hipSuccess) return (int)attr;
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    const int64_t tiles = ((M + 255) / 256) * ((d->Cout + 255) / 256);
+    const int64_t tiles = rn_conv_tiles(d, 256, 256);
     if (tiles > 0x7fffffff) return RN_EINVAL;
     hipLaunchKernelGGL(conv_igemm_bf16_p8_kernel, dim3((unsigned)tiles), dim3(512), P8_LDS, stream, *d, reinterpret_cast<const __bf16 *>(x),
                        reinterpret_cast<const __bf16 *>(w), reinterpret_cast<__bf16 *>(y), scale, shift, reinterpret_cast<const __bf16 *>(add),

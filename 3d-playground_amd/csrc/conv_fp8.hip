@@ -17,25 +17,16 @@
 // K-step a wave issues 8 reads against 4 MFMAs of 64 cycles: twice the FLOPs of the bf16 kernel on the same staged bytes.
 //
 // Roofline: MFMA by FLOPs (~5 PF dense fp8); in practice staging bandwidth, like the bf16 kernel.
-#include <stdlib.h>
-
-#include "common.h"
+#include "conv_fp8_common.h"
+#include "conv_launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #define F8_BK 64                 // K elements per step = 64 bytes per staged row
-#define F8_MAX 448.0f            // largest finite e4m3fn
 
 __device__ __forceinline__ int f8_swz(int row) { return (row >> 2) & 3; }
-
-// two floats -> two e4m3 in the low / high half of a dword (round to nearest even, saturating by the clamp in front)
-__device__ __forceinline__ float f8_clamp(float a) { return fminf(fmaxf(a, -F8_MAX), F8_MAX); }
-__device__ __forceinline__ int f8_pack4(float a, float b, float c, float d) {
-    const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(a), f8_clamp(b), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(c), f8_clamp(d), lo, true);
-}
 
 // ---------------------------------------------------------------------------------------------- quantisation
 // dst[i] = fp8(src[i] * inv_scale): activations entering the fp8 part of the network (per-tensor scale).
@@ -190,11 +181,6 @@ extern "C" int rn_fp8_quantize_rows(const float *w_packed, void *w_q, float *row
 }
 
 // ---------------------------------------------------------------------------------------------- implicit GEMM
-struct Fp8Args {
-    float add_scale;             // the addend's per-tensor scale (its values are fp8)
-    float out_inv_scale;         // 1 / the result's per-tensor scale (fp8 result), unused for an fp32 result
-};
-
 // 128 x 128 output tile by 2 x 2 waves, each a 64 x 64 sub-tile = 2 x 2 accumulators of the 32x32x64 MFMA.
 template <bool YF32>
 __device__ __forceinline__ void conv_igemm_fp8_tile(const rn_conv_desc &d, const unsigned char *__restrict__ x,
@@ -464,6 +450,8 @@ __global__ __launch_bounds__(256, 3) void conv_igemm_fp8_grouped_kernel(const rn
                                                                         const float *__restrict__ scale, const float *__restrict__ shift,
                                                                         const Fp8Args fa_) {
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
+    // (rn_group_index's chain, written out: behind the helper the compiler swaps two scalar register pairs that the e4m3 instance's
+    // epilogue addresses its stores and addend loads through -- the one site where the helper's effect reaches past the lookup)
     int p = 0;
 #pragma unroll
     for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
@@ -492,14 +480,14 @@ static inline bool fp8_p8_pick(const rn_conv_desc *d, int y_is_f32, int64_t tile
     const int mode = rn_get_option(RN_OPT_FP8_P8);
     if (mode == 0 || !rn_fp8_p8_legal(d, y_is_f32)) return false;
     if (mode == 2) return true;
-    static const int min_k = [] { const char *e = getenv("RN_FP8_P8_MIN_K"); return e ? atoi(e) : 0; }();
-    static const int min_tiles = [] { const char *e = getenv("RN_FP8_P8_MIN_TILES"); return e ? atoi(e) : 0; }();
+    static const int min_k = rn_env_int("RN_FP8_P8_MIN_K", 0);
+    static const int min_tiles = rn_env_int("RN_FP8_P8_MIN_TILES", 0);
     if (d->Cout <= 64 && d->kh * d->kw > 1) return false;      // a quarter of the 256-channel tile on a long reduction: 3x3 64 -> 64 measured 1.25 -> 1.54 ms
     return d->kh * d->kw * d->Cin >= min_k && tiles_in_launch >= min_tiles;
 }
 static inline bool fp8_group_is_p8(const rn_conv_group *g, int y_is_f32) {
     int64_t t = 0;
-    for (int i = 0; i < g->n; ++i) t += (((int64_t)g->d[i].N * g->d[i].Ho * g->d[i].Wo + 255) / 256) * ((g->d[i].Cout + 255) / 256);
+    for (int i = 0; i < g->n; ++i) t += rn_conv_tiles(&g->d[i], 256, 256);
     for (int i = 0; i < g->n; ++i)
         if (!rn_fp8_p8_group_ok(&g->d[i]) || !fp8_p8_pick(&g->d[i], y_is_f32, t)) return false;
     return true;
@@ -512,42 +500,27 @@ extern "C" int rn_conv_igemm_fp8_tile_rows(const rn_conv_group *g, int y_is_f32)
 
 // The tile a SINGLE launch (rn_conv_igemm_fp8) takes for this problem, rows * 1000 + cols (profiling / tests; the grouped form has fewer instances).
 extern "C" int rn_conv_igemm_fp8_tile(const rn_conv_desc *d, int y_is_f32) {
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    return fp8_p8_pick(d, y_is_f32, ((M + 255) / 256) * ((d->Cout + 255) / 256)) ? 256 * 1000 + 256 : 128 * 1000 + 128;
+    return fp8_p8_pick(d, y_is_f32, rn_conv_tiles(d, 256, 256)) ? 256 * 1000 + 256 : 128 * 1000 + 128;
 }
 
+// What the fp8 launchers accept (conv_launch.h has the rules every form shares): 1-byte elements, 128-row tiles, weight rows padded to 64.
 static int check_desc_fp8(const rn_conv_desc *d, int y_is_f32) {
-    if (d->N <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0) return RN_EINVAL;
-    if (d->Cin < 16 || (d->Cin & 15) || (d->Cout & (y_is_f32 ? 3 : 15)) || d->w_format != 0) return RN_EINVAL;
-    if ((int64_t)d->Hi * d->Wi * d->Cin > 0x7fffffffLL) return RN_EINVAL;
-    const int64_t HoWo = (int64_t)d->Ho * d->Wo, span = 127 / HoWo + 2;
-    if (d->x_batch_stride < 0 || (span - 1) * d->x_batch_stride + (int64_t)d->Hi * d->Wi * d->Cin > 0x7fffffffLL) return RN_EINVAL;
-    const int64_t Kpad = ((int64_t)d->kh * d->kw * d->Cin + 63) / 64 * 64;
-    if (d->Cout * Kpad > 0x7fffffffLL || (int64_t)d->N * HoWo > 0x7fffffffLL) return RN_EINVAL;
-    if (d->kh <= 0 || d->kw <= 0 || d->div_shift < 0 || d->div_shift > 2) return RN_EINVAL;
-    if (d->add_mode < 0 || d->add_mode > 2 || d->act < 0 || d->act > 2) return RN_EINVAL;
+    if (rn_check_desc_core(d, 1, 128, 64)) return RN_EINVAL;
+    if ((d->Cout & (y_is_f32 ? 3 : 15)) || d->w_format != 0) return RN_EINVAL;
     if (d->mask_mode != 0 || d->in_relu || d->add2_mode != 0 || d->w_batch_stride != 0) return RN_EINVAL;   // forward form only
-    if (d->os < 1 || d->oo_h < 0 || d->oo_w < 0) return RN_EINVAL;
-    if ((d->Ho - 1) * d->os + d->oo_h >= d->Hy || (d->Wo - 1) * d->os + d->oo_w >= d->Wy) return RN_EINVAL;
-    if (d->os != 1 && d->add_mode == 2) return RN_EINVAL;
     if (!y_is_f32 && ((d->y_batch_stride & 15) || (d->add_batch_stride & 3))) return RN_EINVAL;
     return RN_OK;
 }
 
 extern "C" int rn_conv_igemm_fp8(const rn_conv_desc *d, const void *x_q, const void *w_q, void *y, int y_is_f32, const float *scale,
                                  const float *shift, const void *add_q, float add_scale, float out_inv_scale, void *stream) {
-    const int rc = check_desc_fp8(d, y_is_f32);
-    if (rc) return rc;
-    if ((d->add_mode != 0) != (add_q != nullptr)) return RN_EINVAL;
+    if (check_desc_fp8(d, y_is_f32) || (d->add_mode != 0) != (add_q != nullptr)) return RN_EINVAL;
     if (((uintptr_t)x_q & 15) || ((uintptr_t)w_q & 15) || ((uintptr_t)y & 15) || ((uintptr_t)add_q & 3)) return RN_EINVAL;
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    if (!((uintptr_t)add_q & 15) && fp8_p8_pick(d, y_is_f32, ((M + 255) / 256) * ((d->Cout + 255) / 256)))
+    if (!((uintptr_t)add_q & 15) && fp8_p8_pick(d, y_is_f32, rn_conv_tiles(d, 256, 256)))
         return rn_fp8_p8_launch(d, x_q, w_q, y, scale, shift, add_q, add_scale, out_inv_scale, (hipStream_t)stream);
-    const int64_t tiles = ((M + 127) / 128) * ((d->Cout + 127) / 128);
+    const int64_t tiles = rn_conv_tiles(d, 128, 128);
     if (tiles > 0x7fffffff) return RN_EINVAL;
-    Fp8Args a;
-    a.add_scale = add_scale;
-    a.out_inv_scale = out_inv_scale;
+    const Fp8Args a = {add_scale, out_inv_scale};
     const dim3 grid((unsigned)tiles), block(256);
     const unsigned char *xb = reinterpret_cast<const unsigned char *>(x_q), *wb = reinterpret_cast<const unsigned char *>(w_q);
     const unsigned char *ab = reinterpret_cast<const unsigned char *>(add_q);
@@ -564,27 +537,18 @@ extern "C" int rn_conv_igemm_fp8_grouped(const rn_conv_group *g, const void *w_q
     if (g->n < 1 || g->n > RN_MAX_GROUP || ((uintptr_t)w_q & 15)) return RN_EINVAL;
     const rn_conv_desc &d0 = g->d[0];
     const bool p8 = fp8_group_is_p8(g, y_is_f32);               // the caller's tile_end must follow rn_conv_igemm_fp8_tile_rows()
-    const int TR = p8 ? 256 : 128;
-    int prev = 0;
-    for (int i = 0; i < g->n; ++i) {
-        const rn_conv_desc &d = g->d[i];
-        const int rc = check_desc_fp8(&d, y_is_f32);
-        if (rc) return rc;
-        if (d.Cin != d0.Cin || d.Cout != d0.Cout || d.kh != d0.kh || d.kw != d0.kw || d.act != d0.act) return RN_EINVAL;
-        if ((d.add_mode != 0) != (g->add[i] != nullptr)) return RN_EINVAL;
+    int tiles = 0;
+    const int rg = rn_check_group(g, p8 ? 256 : 128, p8 ? 256 : 128, [&](const rn_conv_desc &d, int i) {
+        if (check_desc_fp8(&d, y_is_f32) || d.act != d0.act || (d.add_mode != 0) != (g->add[i] != nullptr)) return RN_EINVAL;
         if (((uintptr_t)g->x[i] & 15) || ((uintptr_t)g->y[i] & 15) || ((uintptr_t)g->add[i] & (p8 ? 15 : 3))) return RN_EINVAL;
-        const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-        const int64_t tiles = ((M + TR - 1) / TR) * ((d.Cout + TR - 1) / TR);
-        if (g->tile_end[i] - prev != tiles) return RN_EINVAL;
-        prev = g->tile_end[i];
-    }
-    if (p8) return rn_fp8_p8_launch_grouped(g, prev, w_q, scale, shift, add_scale, out_inv_scale, (hipStream_t)stream);
-    Fp8Args a;
-    a.add_scale = add_scale;
-    a.out_inv_scale = out_inv_scale;
+        return RN_OK;
+    }, &tiles);
+    if (rg) return rg;
+    if (p8) return rn_fp8_p8_launch_grouped(g, tiles, w_q, scale, shift, add_scale, out_inv_scale, (hipStream_t)stream);
+    const Fp8Args a = {add_scale, out_inv_scale};
     const unsigned char *wb = reinterpret_cast<const unsigned char *>(w_q);
-    if (y_is_f32) hipLaunchKernelGGL((conv_igemm_fp8_grouped_kernel<true>), dim3((unsigned)prev), dim3(256), 0, (hipStream_t)stream, *g, wb, scale, shift, a);
-    else hipLaunchKernelGGL((conv_igemm_fp8_grouped_kernel<false>), dim3((unsigned)prev), dim3(256), 0, (hipStream_t)stream, *g, wb, scale, shift, a);
+    if (y_is_f32) hipLaunchKernelGGL((conv_igemm_fp8_grouped_kernel<true>), dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, *g, wb, scale, shift, a);
+    else hipLaunchKernelGGL((conv_igemm_fp8_grouped_kernel<false>), dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, *g, wb, scale, shift, a);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }

@@ -13,9 +13,9 @@
 // Epilogue: two exchange levels (v_permlane16_swap, then v_permlane32_swap) give a lane SIXTEEN consecutive channels of one pixel --
 // 16-byte e4m3 stores and addend loads, as in conv_fp8.hip.
 // Roofline: MFMA (~5 PFLOP/s dense fp8).
-#include <stdlib.h>
-
-#include "common.h"
+#include "conv_fp8_common.h"
+#include "conv_launch.h"
+#include "conv_p8_geom.h"
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -26,19 +26,11 @@ constexpr int Q8_BM = 256, Q8_BN = 256, Q8_BK = 128, Q8_ROWB = 128;
 constexpr int Q8_OPB = 256 * Q8_ROWB;            // bytes of one operand tile: 32 KB
 constexpr int Q8_BUFB = 2 * Q8_OPB;              // one K-tile: pixels' rows, then weights' rows
 constexpr int Q8_LDS = 2 * Q8_BUFB;              // 128 KB (dynamic)
-#define Q8_MAX 448.0f                            // largest finite e4m3fn
 __device__ __forceinline__ int q8_swz(int r) { return ((r >> 2) & 1) | (((r >> 1) & 1) << 2); }
-__device__ __forceinline__ float q8_clamp(float a) { return fminf(fmaxf(a, -Q8_MAX), Q8_MAX); }
-__device__ __forceinline__ int q8_pack4(float a, float b, float c, float d) {      // conv_fp8.hip: f8_pack4
-    const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(q8_clamp(a), q8_clamp(b), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(q8_clamp(c), q8_clamp(d), lo, true);
-}
 
 #ifndef Q8_ABL
 #define Q8_ABL 0                                 // knock-outs for profiles/ (bits): 1 no stores, 2 no addend loads, 4 no staging after a tile's first two K-tiles, 8 no MFMAs
 #endif
-struct Q8Tap { int r, s, c; };                   // filter row, filter column, first channel of a K-tile (wave-uniform)
-struct Q8Args { float add_scale, out_inv_scale; };   // conv_fp8.hip: Fp8Args
 
 // ---- epilogue: u = acc * scale[c] + shift[c]; u += add * add_scale; [ReLU]; y = e4m3(u * out_inv_scale) (conv_fp8.hip's arithmetic,
 // with out_inv_scale -- positive -- folded into the three factors: the ReLU commutes with it; results identical on exact operands).
@@ -58,7 +50,7 @@ __device__ __forceinline__ void q8_transpose4(unsigned (&p)[4]) {
 template <bool RELU, bool ADD>
 __device__ __forceinline__ void q8_epilogue(const f32x4 (&acc)[8][4], const rn_conv_desc &d, unsigned char *__restrict__ y,
                                             const float *__restrict__ scale, const float *__restrict__ shift,
-                                            const unsigned char *__restrict__ add, const Q8Args qa, const int mw, const int nw, const int M,
+                                            const unsigned char *__restrict__ add, const Fp8Args qa, const int mw, const int nw, const int M,
                                             const int lane) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const int lr = lane & 15, lg = lane >> 4;
@@ -108,9 +100,9 @@ __device__ __forceinline__ void q8_epilogue(const f32x4 (&acc)[8][4], const rn_c
                 u0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)aq[cb], false) * as2 + u0;
                 u1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)aq[cb], true) * as2 + u1;
             }
-            const float lo = RELU ? 0.f : -Q8_MAX;
-            const int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(u0.x, lo, Q8_MAX), __builtin_amdgcn_fmed3f(u0.y, lo, Q8_MAX), 0, false);
-            o[cb] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(u1.x, lo, Q8_MAX), __builtin_amdgcn_fmed3f(u1.y, lo, Q8_MAX), w0, true);
+            const float lo = RELU ? 0.f : -F8_MAX;
+            const int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(u0.x, lo, F8_MAX), __builtin_amdgcn_fmed3f(u0.y, lo, F8_MAX), 0, false);
+            o[cb] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(u1.x, lo, F8_MAX), __builtin_amdgcn_fmed3f(u1.y, lo, F8_MAX), w0, true);
         }
         q8_transpose4(o);                                        // -> dwords 0..3 of block lg
         const i32x4 ov = {(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
@@ -130,7 +122,7 @@ __device__ __forceinline__ void q8_epilogue(const f32x4 (&acc)[8][4], const rn_c
 template <bool HALF, bool PERSIST, bool ROWS>
 __device__ __forceinline__ void q8_tile(const rn_conv_desc &d, const unsigned char *__restrict__ x, const unsigned char *__restrict__ w,
                                         unsigned char *__restrict__ y, const float *__restrict__ scale, const float *__restrict__ shift,
-                                        const unsigned char *__restrict__ add, const Q8Args qa, int tile, const int tile_step,
+                                        const unsigned char *__restrict__ add, const Fp8Args qa, int tile, const int tile_step,
                                         const int tile_end, char *lds) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -141,8 +133,7 @@ __device__ __forceinline__ void q8_tile(const rn_conv_desc &d, const unsigned ch
     const int Cin = d.Cin, K = d.kh * d.kw * Cin, nkt = (K + Q8_BK - 1) / Q8_BK;
 
     // Pixels' descriptor: the flat [M][Cin] tensor from `halo` rows in front of the tile (the farthest a tap reaches back).
-    const int ab = d.b < 0 ? -d.b : d.b;
-    const int halo = ((d.p < 0 ? -d.p : d.p) + (d.kh - 1) * ab) * d.Wi + (d.p_w < 0 ? -d.p_w : d.p_w) + (d.kw - 1) * ab;
+    const int halo = p8_halo<int>(d);
     const v4i32 rs_b = make_rsrc(w, (unsigned)((int64_t)d.Cout * K));
     const unsigned lds0 = lds_addr(lds);
 
@@ -188,16 +179,10 @@ __device__ __forceinline__ void q8_tile(const rn_conv_desc &d, const unsigned ch
             }
         }
     };
-    auto uni = [](const v4i32 r) {
-        v4i32 o;
-        o.x = __builtin_amdgcn_readfirstlane(r.x); o.y = __builtin_amdgcn_readfirstlane(r.y);
-        o.z = __builtin_amdgcn_readfirstlane(r.z); o.w = __builtin_amdgcn_readfirstlane(r.w);
-        return o;
-    };
     // instruction i of this wave for K-tile kt (at tap tp).  live = false (past the last K-tile): every lane sends the out-of-range
     // offset -- zeros into a buffer nobody reads -- instead of a branch around the instruction: with branches in the K loop the compiler
     // sank the MFMAs of three phases below them (every operand live at once, nine accumulators spilled)
-    auto next_half = [&](Q8Tap &tp) {                            // selects, not branches (see dma)
+    auto next_half = [&](P8Tap &tp) {                            // selects, not branches (see dma)
         const int c2 = tp.c + 64;
         const bool wc_ = c2 == Cin;
         const int s2 = tp.s + (wc_ ? 1 : 0);
@@ -206,7 +191,7 @@ __device__ __forceinline__ void q8_tile(const rn_conv_desc &d, const unsigned ch
         tp.s = ws_ ? 0 : s2;
         tp.r += ws_ ? 1 : 0;
     };
-    auto dma = [&](const int i, const Q8Tap &tp, const Q8Tap &th, const int kt, const int buf, const bool live) {   // th: the tap of the second half
+    auto dma = [&](const int i, const P8Tap &tp, const P8Tap &th, const int kt, const int buf, const bool live) {   // th: the tap of the second half
         const unsigned dst = lds0 + (unsigned)(buf * Q8_BUFB + (wave_u + 8 * i) * 1024);
         const bool hi_live = live && kt * Q8_BK + 64 < K;        // HALF: the second half of the last K-tile may lie past K
         if (i < 4) {
@@ -217,16 +202,16 @@ __device__ __forceinline__ void q8_tile(const rn_conv_desc &d, const unsigned ch
                 const int sh_hi = __builtin_amdgcn_readfirstlane(((d.p + th.r * d.b) * d.Wi + d.p_w + th.s * d.b + (ROWS ? 0 : 64 * i)) * Cin + th.c);
                 const unsigned ok_hi = (pk >> (8 * i + (th.r & 3))) & (pk >> (8 * i + 4 + (th.s & 3))) & (hi_live ? 1u : 0u);
                 const unsigned okl = hi_lane ? ok_hi : ok;
-                dma16(uni(rs_a), dst, okl ? va + (unsigned)(hi_lane ? sh_hi : sh) : 0x80000000u, 0u);
+                dma16(p8_uniform(rs_a), dst, okl ? va + (unsigned)(hi_lane ? sh_hi : sh) : 0x80000000u, 0u);
             } else {
-                dma16(uni(rs_a), dst, ok ? va + (unsigned)sh : 0x80000000u, 0u);
+                dma16(p8_uniform(rs_a), dst, ok ? va + (unsigned)sh : 0x80000000u, 0u);
             }
         } else {
             const bool okb = HALF ? (hi_lane ? hi_live : live) : live;
-            dma16(uni(rs_b), dst, okb ? voff_b : 0x80000000u, (unsigned)__builtin_amdgcn_readfirstlane(live ? kt * Q8_BK + (i - 4) * 64 * K : 0));
+            dma16(p8_uniform(rs_b), dst, okb ? voff_b : 0x80000000u, (unsigned)__builtin_amdgcn_readfirstlane(live ? kt * Q8_BK + (i - 4) * 64 * K : 0));
         }
     };
-    auto next_tap = [&](Q8Tap &tp) {                            // a whole K-tile further
+    auto next_tap = [&](P8Tap &tp) {                            // a whole K-tile further
         next_half(tp);
         next_half(tp);
     };
@@ -275,9 +260,9 @@ __device__ __forceinline__ void q8_tile(const rn_conv_desc &d, const unsigned ch
     };                                                           // MFMAs of all of them is what the compiler prefers)
 
     // ---- a tile's prologue: K-tile 0 -> buffer 0, K-tile 1 -> buffer 1 (all 8 instructions each)
-    Q8Tap t2 = {0, 0, 0}, t2h = {0, 0, 0};
+    P8Tap t2 = {0, 0, 0}, t2h = {0, 0, 0};
     auto stage_first_two = [&]() {
-        t2 = Q8Tap{0, 0, 0};
+        t2 = P8Tap{0, 0, 0};
         t2h = t2;
         next_half(t2h);
 #pragma unroll
@@ -363,7 +348,7 @@ template <bool HALF, bool ROWS>
 __global__ __launch_bounds__(512, 2) void conv_igemm_fp8_p8_kernel(const rn_conv_desc d, const unsigned char *__restrict__ x,
                                                                   const unsigned char *__restrict__ w, unsigned char *__restrict__ y,
                                                                   const float *__restrict__ scale, const float *__restrict__ shift,
-                                                                  const unsigned char *__restrict__ add, const Q8Args qa) {
+                                                                  const unsigned char *__restrict__ add, const Fp8Args qa) {
     extern __shared__ __attribute__((aligned(16))) char q8_lds[];
     q8_tile<HALF, false, ROWS>(d, x, w, y, scale, shift, add, qa, xcd_remap(blockIdx.x, gridDim.x), 0, 0, q8_lds);
 }
@@ -374,7 +359,7 @@ template <bool HALF, bool ROWS>
 __global__ __launch_bounds__(512, 2) void conv_igemm_fp8_p8_persist_kernel(const rn_conv_desc d, const unsigned char *__restrict__ x,
                                                                           const unsigned char *__restrict__ w, unsigned char *__restrict__ y,
                                                                           const float *__restrict__ scale, const float *__restrict__ shift,
-                                                                          const unsigned char *__restrict__ add, const Q8Args qa, const int ntiles) {
+                                                                          const unsigned char *__restrict__ add, const Fp8Args qa, const int ntiles) {
     extern __shared__ __attribute__((aligned(16))) char q8_lds[];
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
     const int q = ntiles >> 3, r = ntiles & 7;
@@ -387,36 +372,24 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_fp8_p8_persist_kernel(const
 template <bool HALF>
 __global__ __launch_bounds__(512, 2) void conv_igemm_fp8_p8_grouped_kernel(const rn_conv_group g, const unsigned char *__restrict__ w,
                                                                           const float *__restrict__ scale, const float *__restrict__ shift,
-                                                                          const Q8Args qa) {
+                                                                          const Fp8Args qa) {
     extern __shared__ __attribute__((aligned(16))) char q8_lds[];
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
-    p = __builtin_amdgcn_readfirstlane(p);
+    const int p = __builtin_amdgcn_readfirstlane(rn_group_index(g, tile));
     const int first = p > 0 ? g.tile_end[p - 1] : 0;
     q8_tile<HALF, false, false>(g.d[p], reinterpret_cast<const unsigned char *>(g.x[p]), w, reinterpret_cast<unsigned char *>(g.y[p]), scale, shift,
                          reinterpret_cast<const unsigned char *>(g.add[p]), qa, tile - first, 0, 0, q8_lds);
 }
 
 // ---------------------------------------------------------------------------------------------- host side (used by conv_fp8.hip)
-// What the kernel can compute: a stride-1 convolution whose output plane is the input plane, batch-dense NHWC operands, Cin a multiple of
-// 64 (half a K-tile), at most 4 x 4 taps, a dense e4m3 result, no sigmoid, no upsampled addend.
+// What the kernel can compute: conv_p8_geom.h's common rules (Cin a multiple of 64: half a K-tile), and of its own stride 1 or 2 -- the
+// ROWS form takes a strided layer or an output plane that is not the input plane -- and 16-byte e4m3 stores.
 static inline bool q8_same_size(const rn_conv_desc *d) { return d->a == 1 && d->Hi == d->Ho && d->Wi == d->Wo; }
 bool rn_fp8_p8_group_ok(const rn_conv_desc *d) { return q8_same_size(d); }
 bool rn_fp8_p8_legal(const rn_conv_desc *d, int y_is_f32) {
-    if (y_is_f32 || d->a < 1 || d->a > 2 || d->div_shift != 0 || d->act == 2) return false;
-    if (d->Cin < 64 || (d->Cin & 63) || (d->Cout & 15) || d->kh > 4 || d->kw > 4) return false;
-    const int64_t plane = (int64_t)d->Hi * d->Wi, oplane = (int64_t)d->Ho * d->Wo;
-    if (d->x_batch_stride != plane * d->Cin || d->y_batch_stride != oplane * d->Cout) return false;
-    if (!q8_same_size(d) && ((int64_t)d->N * plane * d->Cin > 0x7fffffffLL || (d->b < 0))) return false;   // general geometry: offsets from the tile's first image
-    if (d->os != 1 || d->oo_h != 0 || d->oo_w != 0 || d->Hy != d->Ho || d->Wy != d->Wo || d->add_mode == 2) return false;
-    if (d->add_mode == 1 && d->add_batch_stride != d->y_batch_stride) return false;
-    const int64_t K = (int64_t)d->kh * d->kw * d->Cin, M = (int64_t)d->N * oplane;
-    const int64_t ab = d->b < 0 ? -d->b : d->b;
-    const int64_t halo = (llabs((long long)d->p) + (d->kh - 1) * ab) * d->Wi + llabs((long long)d->p_w) + (d->kw - 1) * ab;
-    if (M + 256 > 0x7fffffffLL || (256 + 2 * halo + 64) * d->Cin > 0x7fffffffLL || ((int64_t)d->Cout + 256) * K > 0x7fffffffLL) return false;
-    return true;
+    if (d->a < 1 || d->a > 2 || (d->Cout & 15)) return false;
+    if (!q8_same_size(d) && ((int64_t)d->N * d->Hi * d->Wi * d->Cin > 0x7fffffffLL || (d->b < 0))) return false;   // general geometry: offsets from the tile's first image
+    return p8_common_legal(d, y_is_f32, 1);
 }
 int rn_fp8_p8_launch(const rn_conv_desc *d, const void *x, const void *w, void *y, const float *scale, const float *shift, const void *add,
                      float add_scale, float out_inv_scale, hipStream_t stream) {
@@ -434,18 +407,14 @@ int rn_fp8_p8_launch(const rn_conv_desc *d, const void *x, const void *w, void *
     if (attr != hipSuccess) return (int)attr;
     // persistent form: one workgroup per CU (a multiple of 8) once every workgroup has at least two tiles; RN_P8_PERSIST=0: never (A/B)
     static const int n_wg = [] {
-        const char *e = getenv("RN_P8_PERSIST");
-        if (e && atoi(e) == 0) return 0;
+        if (rn_env_int("RN_P8_PERSIST", 1) == 0) return 0;
         int dev = 0, v = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 8) v = 256;
         return v / 8 * 8;
     }();
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    const int64_t tiles = ((M + 255) / 256) * ((d->Cout + 255) / 256);
+    const int64_t tiles = rn_conv_tiles(d, 256, 256);
     if (tiles > 0x7fffffff) return RN_EINVAL;
-    Q8Args qa;
-    qa.add_scale = add_scale;
-    qa.out_inv_scale = out_inv_scale;
+    const Fp8Args qa = {add_scale, out_inv_scale};
     const unsigned char *xb = reinterpret_cast<const unsigned char *>(x), *wb = reinterpret_cast<const unsigned char *>(w);
     const unsigned char *ab = reinterpret_cast<const unsigned char *>(add);
     unsigned char *yb = reinterpret_cast<unsigned char *>(y);
@@ -472,9 +441,7 @@ int rn_fp8_p8_launch_grouped(const rn_conv_group *g, int tiles, const void *w, c
         return e != hipSuccess ? e : hipFuncSetAttribute((const void *)conv_igemm_fp8_p8_grouped_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, Q8_LDS);
     }();
     if (attr != hipSuccess) return (int)attr;
-    Q8Args qa;
-    qa.add_scale = add_scale;
-    qa.out_inv_scale = out_inv_scale;
+    const Fp8Args qa = {add_scale, out_inv_scale};
     if (g->d[0].Cin & 127)
         hipLaunchKernelGGL(conv_igemm_fp8_p8_grouped_kernel<true>, dim3((unsigned)tiles), dim3(512), Q8_LDS, stream, *g,
                            reinterpret_cast<const unsigned char *>(w), scale, shift, qa);

@@ -43,16 +43,14 @@ __global__ __launch_bounds__(256, 4) void conv_igemm_kernel(const rn_conv_desc d
     conv_igemm_tile<WM, WN, GENERAL, BK, RELU, RAW>(d, x, w, y, scale, shift, add, mask, add2, xcd_remap(blockIdx.x, gridDim.x));
 }
 
-// Grouped launch: the workgroup looks up which problem its tile belongs to (wave-uniform compare chain, static
-// indices into the by-value table) and runs the same tile code with that problem's descriptor and pointers.
+// Grouped launch: the workgroup looks up which problem its tile belongs to (conv_launch.h) and runs the same tile code with
+// that problem's descriptor and pointers.
 template <int WM, int WN, int BK>
 __global__ __launch_bounds__(256, 4) void conv_igemm_grouped_kernel(const rn_conv_group g,
                                                             const float *__restrict__ w, const float *__restrict__ scale,
                                                             const float *__restrict__ shift) {
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
+    const int p = rn_group_index(g, tile);
     rn_conv_desc d = g.d[0];
     const float *x = g.x[0], *add = g.add[0], *mask = g.mask[0];
     float *y = g.y[0];
@@ -72,22 +70,16 @@ int rn_igemm_split_grouped_launch(bool narrow, unsigned tiles, const rn_conv_gro
 
 extern "C" int rn_conv_igemm_grouped(const rn_conv_group *g, const float *w_packed, const float *scale, const float *shift,
                                      void *stream) {
-    if (g->n < 1 || g->n > RN_MAX_GROUP) return RN_EINVAL;
     const rn_conv_desc &d0 = g->d[0];
     const bool narrow = d0.Cout <= 64;
     int prev = 0;
-    for (int i = 0; i < g->n; ++i) {
-        const rn_conv_desc &d = g->d[i];
-        const int rc = check_desc(&d);
-        if (rc) return rc;
-        if (d.Cin != d0.Cin || d.Cout != d0.Cout || d.kh != d0.kh || d.kw != d0.kw || d.add2_mode != 0) return RN_EINVAL;
+    const int rg = rn_check_group(g, narrow ? 256 : 128, narrow ? 64 : 128, [&](const rn_conv_desc &d, int i) {
+        if (check_desc(&d) || d.add2_mode != 0) return RN_EINVAL;
         if (d.in_relu) return RN_EINVAL;                       // the input ReLU has its own kernel: rn_conv_igemm only
         if ((d.add_mode != 0) != (g->add[i] != nullptr) || (d.mask_mode != 0) != (g->mask[i] != nullptr)) return RN_EINVAL;
-        const int64_t M = (int64_t)d.N * d.Ho * d.Wo;
-        const int64_t tiles = narrow ? (M + 255) / 256 : ((M + 127) / 128) * ((d.Cout + 127) / 128);
-        if (g->tile_end[i] - prev != tiles) return RN_EINVAL;
-        prev = g->tile_end[i];
-    }
+        return RN_OK;
+    }, &prev);
+    if (rg) return rg;
     const dim3 grid((unsigned)prev), block(256);
     hipStream_t s = (hipStream_t)stream;
     for (int i = 0; i < g->n; ++i)
@@ -110,14 +102,10 @@ extern "C" int rn_conv_igemm(const rn_conv_desc *d, const float *x, const float 
     if ((d->add_mode != 0) != (add != nullptr)) return RN_EINVAL;
     if ((d->mask_mode != 0) != (mask != nullptr)) return RN_EINVAL;
     if ((d->add2_mode != 0) != (add2 != nullptr)) return RN_EINVAL;
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
     hipStream_t s = (hipStream_t)stream;
-    const bool dense = d->os == 1 && d->oo_h == 0 && d->oo_w == 0 && d->Hy == d->Ho && d->Wy == d->Wo &&
-                       d->y_batch_stride == (int64_t)d->Ho * d->Wo * d->Cout && d->add_mode != 2 && d->add2_mode == 0 &&
-                       (d->add_mode == 0 || d->add_batch_stride == d->y_batch_stride);
-    // 256 x 64 tile for few output channels: no wasted N half.  (The input-ReLU form exists for the 128 x 128 tile only.)
-    const bool narrow = d->Cout <= 64 && !d->in_relu;
-    const int64_t tiles = narrow ? (M + 255) / 256 : ((M + 127) / 128) * ((d->Cout + 127) / 128);
+    const bool dense = rn_conv_dense(d) && d->add2_mode == 0;
+    const bool narrow = igemm_narrow(d);
+    const int64_t tiles = igemm_tiles(d, narrow);
     if (tiles > 0x7fffffff) return RN_EINVAL;
     const dim3 grid((unsigned)tiles), block(256);
 #define RN_LAUNCH_IGEMM(WM, WN, G, K) \

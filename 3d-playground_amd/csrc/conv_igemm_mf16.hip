@@ -455,9 +455,7 @@ __global__ __launch_bounds__(256, TERMS == 2 ? RN_MF16H_OCC : 3) void conv_igemm
                                                                       const float *__restrict__ scale,
                                                                       const float *__restrict__ shift) {
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
+    const int p = rn_group_index(g, tile);
     rn_conv_desc d = g.d[0];
     const float *x = g.x[0], *add = g.add[0], *mask = g.mask[0];
     float *y = g.y[0];
@@ -480,10 +478,7 @@ static bool mf16_ok(const rn_conv_desc *d) {
     if (d->w_format == 3) return d->x_amax != nullptr && d->w_unscale != nullptr;
     return d->w_format == 1;
 }
-static int64_t mf16_tiles(const rn_conv_desc *d) {
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    return ((M + 127) / 128) * ((d->Cout + 127) / 128);
-}
+static int64_t mf16_tiles(const rn_conv_desc *d) { return rn_conv_tiles(d, 128, 128); }
 
 // include/retinanet_mi355x.h: does this problem run on an fp16-split kernel in RN_FP32_SPLIT3 mode?  Since the 128 x 128 / 256 x 64 tiles
 // of conv_igemm_tile.h have the two-term form too (round 5, second half): every problem the split kernels take -- a reduction of at
@@ -497,22 +492,21 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
                           const float *shift, const float *add, const float *mask, const float *add2, hipStream_t s, int *rc) {
     if (!mf16_ok(d) || (variant != 0 && variant != 4 && variant != 5)) return false;
     const int64_t tiles = mf16_tiles(d);
-    const int64_t M_rows = (int64_t)d->N * d->Ho * d->Wo;
     if (tiles < mf16_min_tiles() || tiles > 0x7fffffff) return false;
     const dim3 grid((unsigned)tiles), block(256);
 #define RN_MF16_LAUNCH(G, R, T, S) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, T, S>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
     if (d->w_format == 3) {
         // staged activations (row-coalesced direct-to-LDS loads) where the K loop is long enough to pay for the longer prologue: measured
         // -4 % on the Winograd GEMMs (K = 256) and K >= 1024, +8 % on K = 64 / 128 (profiles/r05_mf16_bounds.txt, 4)
-        static const int stg_min_k = [] { const char *e = getenv("RN_MF16_STG_MIN_K"); return e ? atoi(e) : 256; }();
+        static const int stg_min_k = rn_env_int("RN_MF16_STG_MIN_K", 256);
         const bool stg = RN_MF16_STG != 0 && d->kh * d->kw * d->Cin >= stg_min_k;
         // eight waves on a 256 x 128 tile (staged form only; 70 KB of LDS, two workgroups per CU = sixteen waves instead of twelve): the
         // weights' planes are fetched once per 256 rows instead of per 128 -- 0.75 x the bytes through the CU's memory pipe per product.
         // Measured (tools/bench_conv.py, profiles/r05_mf16_bounds.txt, 7): 1x1 1024->256 0.136 -> 0.122 ms, its data gradient 0.129 -> 0.115,
         // 3x3 256->256 -4 %; the per-position launches of the Winograd stage (big -3 %, small +5 %; in the step 29.13 with them on it against
         // 29.0 ms without) keep four waves.  RN_MF16_WV8_MIN: fewest 256-row tiles a launch needs (default 1; 0: never).
-        static const int wv8_min = [] { const char *e = getenv("RN_MF16_WV8_MIN"); return e ? atoi(e) : 1; }();
-        const int64_t tiles8 = ((M_rows + 255) / 256) * ((d->Cout + 127) / 128);
+        static const int wv8_min = rn_env_int("RN_MF16_WV8_MIN", 1);
+        const int64_t tiles8 = rn_conv_tiles(d, 256, 128);
         if (stg && wv8_min > 0 && d->w_batch_stride == 0 && tiles8 >= wv8_min && tiles8 <= 0x7fffffff) {
             const dim3 grid8((unsigned)tiles8), block8(512);
 #define RN_MF16_LAUNCH8(G, R) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, 2, true, 8>), grid8, block8, 0, s, *d, x, w, y, scale, shift, add, mask, add2)

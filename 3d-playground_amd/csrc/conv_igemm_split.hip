@@ -30,9 +30,7 @@ __global__ __launch_bounds__(256, BK == 32 ? 2 : 3) void conv_igemm_split_groupe
                                                                           const float *__restrict__ scale,
                                                                           const float *__restrict__ shift) {
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) p += (i + 1 < g.n && tile >= g.tile_end[i]) ? 1 : 0;
+    const int p = rn_group_index(g, tile);
     rn_conv_desc d = g.d[0];
     const float *x = g.x[0], *add = g.add[0], *mask = g.mask[0];
     float *y = g.y[0];
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(256, BK == 32 ? 2 : 3) void conv_igemm_split_groupe
 // SPLIT 3 (conv_igemm_tile.h: the activation operand split once per workgroup into bf16 planes in LDS) for the 128 x 128 tile
 // when the weights come pre-split and a K-step lies inside one filter tap; RN_SPLIT_A_ONCE=0 keeps the SPLIT 2 kernels (A/B).
 static bool split_a_once(const rn_conv_desc *d) {
-    static const int on = [] { const char *e = getenv("RN_SPLIT_A_ONCE"); return e ? atoi(e) : 1; }();
+    static const int on = rn_env_int("RN_SPLIT_A_ONCE", 1);
     return on && d->w_format == 1 && (d->Cin % 16) == 0 && d->div_shift == 0 && d->kh * d->kw <= 24;
 }
 
@@ -56,7 +54,7 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
 bool rn_igemm_mf16_grouped_launch(const rn_conv_group *g, const float *w, const float *scale, const float *shift, hipStream_t s, int *rc);
 
 static int dbg_dyn_lds(const void *fn) {                  // occupancy experiment: RN_DBG_DYN_LDS bytes of unused dynamic LDS per workgroup
-    static const int v = getenv("RN_DBG_DYN_LDS") ? atoi(getenv("RN_DBG_DYN_LDS")) : 0;
+    static const int v = rn_env_int("RN_DBG_DYN_LDS", 0);
     if (v > 16384) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, v);
     return v;
 }

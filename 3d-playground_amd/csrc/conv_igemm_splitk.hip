@@ -60,9 +60,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const rn_conv_d
 // Slices worth using for this problem (1 = do not split) -- few output tiles and a long K loop.
 static int splitk_slices(const rn_conv_desc *d) {
     if (!rn_get_option(RN_OPT_SPLITK)) return 1;
-    const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
-    const bool narrow = d->Cout <= 64 && !d->in_relu;      // the input-ReLU form exists for the 128 x 128 tile only
-    const int64_t tiles = narrow ? (M + 255) / 256 : ((M + 127) / 128) * ((d->Cout + 127) / 128);
+    const int64_t tiles = igemm_tiles(d, igemm_narrow(d));
     const int K = d->kh * d->kw * d->Cin;
     const int bk = 16;
     const int nks = ((K + 31) / 32 * 32) / bk;
@@ -92,8 +90,8 @@ extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const
     if (slices <= 1 || !workspace) return RN_EINVAL;         // ask rn_conv_splitk_workspace_bytes first
     const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
     hipStream_t s = (hipStream_t)stream;
-    const bool narrow = d->Cout <= 64 && !d->in_relu;
-    const int64_t tiles = narrow ? (M + 255) / 256 : ((M + 127) / 128) * ((d->Cout + 127) / 128);
+    const bool narrow = igemm_narrow(d);
+    const int64_t tiles = igemm_tiles(d, narrow);
     const int K = d->kh * d->kw * d->Cin;
     const int bk = 16;
     const int nks = ((K + 31) / 32 * 32) / bk;
@@ -105,9 +103,7 @@ extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const
     else if (narrow) hipLaunchKernelGGL((conv_igemm_splitk_kernel<4, 1, 16>), grid, block, 0, s, *d, x, w_packed, ws, per, nks);
     else hipLaunchKernelGGL((conv_igemm_splitk_kernel<2, 2, 16>), grid, block, 0, s, *d, x, w_packed, ws, per, nks);
     RN_LAUNCH_CHECK();
-    const bool dense = d->os == 1 && d->oo_h == 0 && d->oo_w == 0 && d->Hy == d->Ho && d->Wy == d->Wo &&
-                       d->y_batch_stride == (int64_t)d->Ho * d->Wo * d->Cout && d->add_mode != 2 && d->add2_mode == 0 &&
-                       (d->add_mode == 0 || d->add_batch_stride == d->y_batch_stride);
+    const bool dense = rn_conv_dense(d) && d->add2_mode == 0;
     const int64_t chunks = M * ((d->Cout + 3) / 4);
     const dim3 fgrid((unsigned)((chunks + 255) / 256));
     if (dense) hipLaunchKernelGGL((conv_splitk_finish_kernel<false>), fgrid, block, 0, s, *d, (const float *)ws, used, y, scale, shift, add, mask, add2);

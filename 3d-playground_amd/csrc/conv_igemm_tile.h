@@ -2,14 +2,10 @@
 // check.  See conv_igemm.hip for the design notes.  (Two translation units: the split-K kernels are kept apart from the other
 // twelve instantiations of the force-inlined tile to bound compile time and memory.)
 #pragma once
-#include <stdlib.h>
-
-#include "common.h"
+#include "conv_launch.h"
 #include "mfma_split.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-
 
 // Epilogue of one 16-byte chunk (4 output channels of one output pixel m): v = scale*t + shift; [mask before add];
 // v += add (+ add2); act; [mask after]; store through the output map.  Three stages, expanded in place by the tile
@@ -785,30 +781,16 @@ __device__ __forceinline__ void conv_igemm_tile(const rn_conv_desc &d, const flo
     if (partial == nullptr && !rn_span) rn_amax_note(d.y_amax, m0 / HoWo, rn_am);
 }
 
-
-
-
+// What the fp32 launchers accept (conv_launch.h has the rules every form shares): 4-byte elements, tiles of up to 256 rows.
 static inline int check_desc(const rn_conv_desc *d) {
-    if (d->N <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0) return RN_EINVAL;
-    if (d->Cin < 4 || (d->Cin & 3)) return RN_EINVAL;                     // 16-byte chunks must not straddle taps
-    if ((int64_t)d->Hi * d->Wi * d->Cin > 0x7fffffffLL) return RN_EINVAL; // in-image offsets are 32-bit
-    {   // buffer addressing: the images one 256-row tile can touch, and the packed weights, within 2 GiB each
-        const int64_t HoWo = (int64_t)d->Ho * d->Wo, span = 255 / HoWo + 2;
-        if (d->x_batch_stride < 0 || (span - 1) * d->x_batch_stride * 4 + (int64_t)d->Hi * d->Wi * d->Cin * 4 > 0x7fffffffLL) return RN_EINVAL;
-        const int64_t Kpad = ((int64_t)d->kh * d->kw * d->Cin + 31) / 32 * 32;
-        if (d->Cout * Kpad * 4 > 0x7fffffffLL || (int64_t)d->N * HoWo > 0x7fffffffLL) return RN_EINVAL;
-    }
-    if (d->kh <= 0 || d->kw <= 0 || d->div_shift < 0 || d->div_shift > 2) return RN_EINVAL;
-    if (d->add_mode < 0 || d->add_mode > 2 || d->act < 0 || d->act > 2) return RN_EINVAL;
-    if (d->mask_mode < 0 || (d->mask_mode & ~(3 | RN_MASK_BITS)) || (d->mask_mode & 3) == 3 || d->mask_mode == RN_MASK_BITS) return RN_EINVAL;
-    // sign bits (read: mask_mode | RN_MASK_BITS; written: sign_out) live at element offset >> 5: whole words per pixel and per image
-    if (((d->mask_mode & RN_MASK_BITS) || d->sign_out != nullptr) && ((d->Cout & 31) || (d->y_batch_stride & 31))) return RN_EINVAL;
-    if (d->os < 1 || d->oo_h < 0 || d->oo_w < 0 || (d->add2_mode != 0 && d->add2_mode != 3)) return RN_EINVAL;
-    if ((d->Ho - 1) * d->os + d->oo_h >= d->Hy || (d->Wo - 1) * d->os + d->oo_w >= d->Wy) return RN_EINVAL;
-    if (d->os != 1 && d->add_mode == 2) return RN_EINVAL;
+    if (rn_check_desc_core(d, 4, 256, 32) || rn_check_desc_mask(d)) return RN_EINVAL;
+    if (d->add2_mode != 0 && d->add2_mode != 3) return RN_EINVAL;
     if (d->w_format < 0 || d->w_format > 3) return RN_EINVAL;
     if (d->w_format == 3 && (d->x_amax == nullptr || d->w_unscale == nullptr)) return RN_EINVAL;
     if (d->w_batch_stride < 0 || (d->w_batch_stride != 0 && ((int64_t)d->Ho * d->Wo) % 256 != 0)) return RN_EINVAL;
     return RN_OK;
 }
-
+// The tile of the fp32 launchers: 256 x 64 for few output channels (no wasted N half), else 128 x 128.  (The input-ReLU form exists for
+// the 128 x 128 tile only.)
+static inline bool igemm_narrow(const rn_conv_desc *d) { return d->Cout <= 64 && !d->in_relu; }
+static inline int64_t igemm_tiles(const rn_conv_desc *d, bool narrow) { return narrow ? rn_conv_tiles(d, 256, 64) : rn_conv_tiles(d, 128, 128); }

@@ -329,6 +329,26 @@ def test_head_output_into_concat_buffer(cv, dev):
     close(pad2, want2)
 
 
+GROUP_EDGE_PLANES = [(16, 16), (16, 24), (8, 8), (24, 24), (4, 4)]
+
+
+def test_grouped_launch_at_the_edges_of_the_tile_table(cv, dev):
+    """RN_MAX_GROUP = 5 problems in one launch, 1, 2, 1, 3 and 1 tiles of 256 rows (Cout = 64: the 256 x 64 tile): a problem boundary
+    after every entry of tile_end, single-tile problems first, in the middle and last, the last one a partial tile of 16 rows -- every
+    level against the single launch of the same problem."""
+    cin = cout = 64
+    w, b = rnd((cout, cin, 3, 3), 50, 0.05), rnd((cout,), 51)
+    wp = cv.pack_weights(w.to(dev), 0)
+    xs = [nhwc(rnd((1, cin, h, w_), 52 + i)).to(dev) for i, (h, w_) in enumerate(GROUP_EDGE_PLANES)]
+    probs = [dict(x=x, y=torch.zeros((1, x.shape[1], x.shape[2], cout), device=dev), geom=(x.shape[1], x.shape[2], cout, 3, 3, 1, 1, -1, 0))
+             for x in xs]
+    cv.conv_igemm_grouped(probs, wp, shift=b.to(dev), act=cv.ACT_RELU)
+    for x, pr in zip(xs, probs):
+        single = cv.fprop(x, wp, cout, 3, 1, 1, shift=b.to(dev), act=cv.ACT_RELU)
+        assert float(single.abs().max()) > 0
+        close(pr["y"], single)
+
+
 def test_maxpool_forward_backward_with_ties(cv, dev):
     N, C, H, W = 2, 8, 13, 15
     x = F.relu(rnd((N, C, H, W), 40))                    # many exact zeros: ties inside windows

@@ -201,6 +201,43 @@ def test_bf16_dominant_layer_1080p(cv, dev):
     close_f32(dw.view(C, 3, 3, C).permute(0, 3, 1, 2), wr.grad, tol=1e-4)
 
 
+def _group_tile(cv, problems):
+    """rows * 1000 + cols of the tile rn_conv_igemm_bf16_grouped takes for these problems."""
+    import ctypes
+    from retinanet_mi355x import _hip
+    g = _hip.ConvGroup()
+    g.n = len(problems)
+    for i, pr in enumerate(problems):
+        g.d[i] = cv._make_desc(pr["x"], pr["geom"], cv.ACT_RELU, 0, (0, 0), 0, False, None, None, None, None)
+    return _hip.load().rn_conv_igemm_bf16_tile_rows(ctypes.byref(g), 0)
+
+
+@pytest.mark.parametrize("form", ["128x128", "256x128"])
+def test_grouped_launch_at_the_edges_of_the_tile_table(cv, dev, form):
+    """RN_MAX_GROUP = 5 problems in one launch of conv_bf16.hip's own grouped kernels (the phased kernel off): single-tile problems in
+    the middle and last, the last one a partial tile of 16 rows -- every level against the single launch of the same problem.
+    128 x 128: 64 -> 64 on planes of 2, 3, 1, 5 and 1 row tiles.  256 x 128 wants Cout % 128 == 0, a reduction of at least 1024 and 512
+    tiles in the launch: 128 -> 128 with a first plane of 507 row tiles, then 2, 1, 3 and 1."""
+    cin, cout, first = (64, 64, (16, 16)) if form == "128x128" else (128, 128, (360, 360))
+    old = cv.get_option(cv.OPT_BF16_P8)
+    cv.set_option(cv.OPT_BF16_P8, 0)
+    try:
+        w, b = rnd((cout, cin, 3, 3), 50, (2.0 / (9 * cin)) ** 0.5), rnd((cout,), 51, 0.1).to(dev)
+        wp = cv.pack_weights_bf16(w.to(dev), 0)
+        gen = torch.Generator(device="cpu").manual_seed(52)            # (the first plane of the 256 x 128 form is 16.6 M values)
+        xs = [cv.to_bf16(torch.randn((1, h, w_, cin), generator=gen).to(dev)) for h, w_ in [first, (16, 24), (8, 8), (24, 24), (4, 4)]]
+        probs = [dict(x=x, y=torch.zeros((1, x.shape[1], x.shape[2], cout), dtype=torch.bfloat16, device=dev),
+                      geom=(x.shape[1], x.shape[2], cout, 3, 3, 1, 1, -1, 0)) for x in xs]
+        assert _group_tile(cv, probs) == (128128 if form == "128x128" else 256128)
+        cv.conv_igemm_bf16_grouped(probs, wp, shift=b, act=cv.ACT_RELU)
+        for x, pr in zip(xs, probs):
+            single = cv.fprop_bf16(x, wp, cout, 3, 1, 1, shift=b, act=cv.ACT_RELU)
+            assert float(single.float().abs().max()) > 0
+            close_bf16(pr["y"].float(), single.float())
+    finally:
+        cv.set_option(cv.OPT_BF16_P8, old)
+
+
 def test_grouped_weight_gradient_over_pyramid_levels(cv, dev):
     """rn_conv_wgrad_bf16_grouped: the levels of a head layer share one weight tensor, so its gradient is the SUM over the levels
     (D/model.py:110-205) -- one launch against torch's autograd over all levels and against the per-level launches."""

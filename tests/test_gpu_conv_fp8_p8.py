@@ -145,6 +145,46 @@ def test_grouped_pyramid_launch_and_the_default_rule(cv, dev):
     cv.set_option(cv.OPT_FP8_P8, 2)
 
 
+def test_grouped_128_tile_at_the_edges_of_the_tile_table(cv, dev):
+    """conv_fp8.hip's own grouped kernel (RN_OPT_FP8_P8 = 0: 128 x 128 tiles) with RN_MAX_GROUP = 5 problems of 2, 3, 1, 5 and 1 tiles:
+    single-tile problems in the middle and last, the last one a partial tile of 16 rows.  Exact operands (e4m3 values, exact sums), so
+    every level must equal the single launch of the same problem byte for byte."""
+    cin = cout = 64
+    w = (torch.round(rnd((cout, cin, 3, 3), 21, 2.0)) / 2).clamp(-2, 2)
+    wq = cv.fp8_quantize(cv.pack_weights(w.to(dev), 0, presplit=False), 1.0)
+    scale = torch.full((cout,), 2.0 ** -5, device=dev)
+    b = torch.round(rnd((cout,), 22, 2.0)).to(dev)
+    planes = [(16, 16), (16, 24), (8, 8), (24, 24), (4, 4)]
+    xs = [cv.fp8_quantize(nhwc(torch.round(rnd((1, cin, h, ww), 23 + i, 2.0)).clamp(-4, 4)).to(dev), 1.0) for i, (h, ww) in enumerate(planes)]
+    cv.set_option(cv.OPT_FP8_P8, 0)
+    try:
+        ys = [torch.zeros((1, h, ww, cout), dtype=torch.uint8, device=dev) for (h, ww) in planes]
+        problems = [dict(x=x, y=y, geom=(x.shape[1], x.shape[2], cout, 3, 3, 1, 1, -1, 0)) for x, y in zip(xs, ys)]
+        g = _hip_group(cv, problems)
+        assert _hip_lib().rn_conv_igemm_fp8_tile_rows(ctypes.byref(g), 0) == 128128
+        cv.conv_igemm_fp8_grouped(problems, wq, scale, shift=b, act=cv.ACT_RELU, out_scale=1.0)
+        for x, y in zip(xs, ys):
+            single = torch.zeros_like(y)
+            cv.conv_igemm_fp8(x, wq, single, (x.shape[1], x.shape[2], cout, 3, 3, 1, 1, -1, 0), scale, shift=b, act=cv.ACT_RELU, out_scale=1.0)
+            assert int(single.max()) > 0 and torch.equal(y, single)
+    finally:
+        cv.set_option(cv.OPT_FP8_P8, 2)
+
+
+def _hip_lib():
+    from retinanet_mi355x import _hip
+    return _hip.load()
+
+
+def _hip_group(cv, problems):
+    from retinanet_mi355x import _hip
+    g = _hip.ConvGroup()
+    g.n = len(problems)
+    for i, pr in enumerate(problems):
+        g.d[i] = cv._make_desc(pr["x"], pr["geom"], cv.ACT_RELU, 0, (0, 0), 0, False, None, None, None, None)
+    return g
+
+
 @pytest.mark.parametrize("case", [(64, 256, 1, 0, 2, 270, 261), (128, 320, 3, 1, 1, 259, 257), (256, 256, 3, 1, 3, 150, 301)])
 def test_persistent_form_identical_on_exact_operands(cv, dev, case):
     """Launches with at least two tiles per CU run as persistent workgroups that stage the next tile's first K-tiles before the current

@@ -129,6 +129,27 @@ def test_strided_head_slice_output_and_grouped_levels(cv, dev):
         off += h * w_ * cout
 
 
+def test_grouped_launch_at_the_edges_of_the_tile_table(cv, dev):
+    """RN_MAX_GROUP = 5 problems in one launch of this kernel's grouped form (Cout = 128, so that it takes the group), 2, 3, 1, 5 and 1
+    tiles of 128 rows: single-tile problems in the middle and last, the last one a partial tile of 16 rows -- every level against the
+    single launch of the same problem."""
+    cin, cout = 64, 128
+    w, b = rnd((cout, cin, 3, 3), 50, 0.05), rnd((cout,), 51)
+    wp = cv.pack_weights(w.to(dev), 0)
+    xs = [nhwc(rnd((1, cin, h, w_), 52 + i)).to(dev) for i, (h, w_) in enumerate([(16, 16), (16, 24), (8, 8), (24, 24), (4, 4)])]
+    probs = [dict(x=x, y=torch.zeros((1, x.shape[1], x.shape[2], cout), device=dev), geom=(x.shape[1], x.shape[2], cout, 3, 3, 1, 1, -1, 0))
+             for x in xs]
+    # what decides that the 16x16x32 grouped kernel takes the group (conv_igemm_mf16.hip: mf16_ok, mf16_min_tiles; the C ABI has no query
+    # for it): the option on, 12 tiles against its minimum, Cin % 32 == 0, 64 < Cout, Cout % 4 == 0, and the weights' pre-split form
+    assert cv.get_option(cv.OPT_MF16) == 1 and cv.get_option(cv.OPT_MF16_MIN) <= 12 and cin % 32 == 0 and cout > 64 and cout % 4 == 0
+    assert getattr(wp, "_rn_split16" if cv._half else "_rn_split", None) is not None
+    cv.conv_igemm_grouped(probs, wp, shift=b.to(dev), act=cv.ACT_RELU)
+    for x, pr in zip(xs, probs):
+        single = cv.fprop(x, wp, cout, 3, 1, 1, shift=b.to(dev), act=cv.ACT_RELU)
+        assert float(single.abs().max()) > 0
+        close(pr["y"], single)
+
+
 def test_winograd_group_takes_the_plain_gemm(cv, dev):
     """The Winograd path's batched GEMM (36 positions, per-position weights, T padded to 256) through this kernel's plain-GEMM
     form, against the direct convolution in fp64 (Winograd F(4x4,3x3): 1e-4 of the max)."""
