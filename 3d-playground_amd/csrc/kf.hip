@@ -10,45 +10,18 @@
 #include <math.h>
 
 #include "common.h"
-
-#define KS 6   // state size
-#define KM 5   // measurement size
-
-__device__ __forceinline__ float kf_f05(float D, double dt, int dt_is_tensor) {
-    return dt_is_tensor ? (float)((double)D * dt) : D * (float)dt;              // kf.py:278 / 310
-}
+#include "kf_dev.h"
 
 __global__ __launch_bounds__(128) void kf_view_kernel(const float *__restrict__ X, const float *__restrict__ D,
                                                       const float *__restrict__ F, const double *__restrict__ dt,
                                                       int dt_is_tensor, int with_direction, float *__restrict__ out, int n) {
     const int i = blockIdx.x * 128 + threadIdx.x;
     if (i >= n) return;
-    float x[KS], xp[KS];
+    float x[KS];
 #pragma unroll
     for (int a = 0; a < KS; ++a) x[a] = X[i * KS + a];
-    if (dt != nullptr) {
-        const float f05 = kf_f05(D[i], dt_is_tensor ? dt[i] : dt[0], dt_is_tensor);
-#pragma unroll
-        for (int a = 0; a < KS; ++a) {
-            float s = 0.f;
-#pragma unroll
-            for (int b = 0; b < KS; ++b) s += ((a == 0 && b == 5) ? f05 : F[a * KS + b]) * x[b];
-            xp[a] = s;
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < KS; ++a) xp[a] = x[a];
-    }
-    if (with_direction) {                                                       // cat(states[:, :-1], D, states[:, -1:]), kf.py:287
-        float *o = out + (int64_t)i * (KS + 1);
-#pragma unroll
-        for (int a = 0; a < KS - 1; ++a) o[a] = xp[a];
-        o[KS - 1] = D[i];
-        o[KS] = xp[KS - 1];
-    } else {
-#pragma unroll
-        for (int a = 0; a < KS; ++a) out[(int64_t)i * KS + a] = xp[a];
-    }
+    const double dti = dt == nullptr ? 0.0 : (dt_is_tensor ? dt[i] : dt[0]);
+    kf_view_row(x, D[i], F, dt != nullptr, dti, dt_is_tensor, with_direction, out + (int64_t)i * (with_direction ? KS + 1 : KS));
 }
 
 __global__ __launch_bounds__(128) void kf_predict_kernel(float *__restrict__ X, float *__restrict__ P, const float *__restrict__ D,

@@ -67,6 +67,7 @@ SIGNATURES = {
     "rn_ts_bias_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rn_estimate_ts_bias": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f64, c_f64, c_f32,
                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rn_track_crop_prior": (c_i32, [c_vp] * 7 + [c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "rn_fit_nearest": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rn_residual_moments": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rn_eval_select": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_i32, c_i32, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),

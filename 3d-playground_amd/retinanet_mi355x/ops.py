@@ -993,6 +993,44 @@ def estimate_ts_bias(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, 
     return (info, pairs, te) if details else info
 
 
+# ------------------------------------------------------------------------------------------------ crop frame front end
+def track_crop_prior(X, D, T, F, centers, stamps, bias, pre_loc=None):
+    """The start of a crop frame of MC_Crop_Tracker.track (MC3D_crop_tracker.py:1150-1171) on the device, see
+    include/retinanet_mi355x.h.  X [n,6] fp32, D [n] fp32, T [n] fp64, F [6,6] fp32: the tensors of a ``Torch_KF``;
+    centers [c,2] fp32; stamps / bias [c] fp64 (``timestamps`` and ``ts_bias``).  -> (pre_loc [n,7] fp32 = the filter's
+    ``view(with_direction=True, dt=1/30.0)``, cam [n] int32 = the nearest camera centre, dt [n] fp64 = the per-object dt
+    that rolls each track to its camera's corrected time stamp).  ``pre_loc``: an optional contiguous float32 [n,7] tensor to
+    write the view into.  Device tensors, no synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(X, D, T, F, centers, stamps, bias, pre_loc)
+    n = X.shape[0]
+    for name, t, dtype, shape in (("X", X, torch.float32, (n, 6)), ("D", D, torch.float32, (n,)), ("T", T, torch.float64, (n,)),
+                                  ("F", F, torch.float32, (6, 6))):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise RuntimeError("track_crop_prior: %s has to be %s of shape %s, got %s %s" % (name, dtype, shape, t.dtype, tuple(t.shape)))
+    c = centers.shape[0]
+    if centers.dtype != torch.float32 or centers.dim() != 2 or centers.shape[1] != 2 or c < 1:
+        raise RuntimeError("track_crop_prior: centers are float32 [c >= 1, 2], got %s %s" % (centers.dtype, tuple(centers.shape)))
+    for name, t in (("stamps", stamps), ("bias", bias)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (c,):
+            raise RuntimeError("track_crop_prior: %s has to be float64 of shape (%d,), got %s %s" % (name, c, t.dtype, tuple(t.shape)))
+    dev = X.device
+    if pre_loc is None:
+        pre_loc = torch.empty((n, 7), dtype=torch.float32, device=dev)
+    elif pre_loc.dtype != torch.float32 or tuple(pre_loc.shape) != (n, 7) or not pre_loc.is_contiguous():
+        raise RuntimeError("track_crop_prior: pre_loc has to be a contiguous float32 [%d, 7]" % n)
+    cam = torch.empty((n,), dtype=torch.int32, device=dev)
+    dt = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n:
+        X, D, T, F = X.contiguous(), D.contiguous(), T.contiguous(), F.contiguous()
+        centers, stamps, bias = centers.contiguous(), stamps.contiguous(), bias.contiguous()
+        with torch.cuda.device(dev):
+            _hip.check(lib.rn_track_crop_prior(X.data_ptr(), D.data_ptr(), T.data_ptr(), F.data_ptr(), centers.data_ptr(),
+                                               stamps.data_ptr(), bias.data_ptr(), c, pre_loc.data_ptr(), cam.data_ptr(),
+                                               dt.data_ptr(), n, _hip.stream()), "rn_track_crop_prior")
+    return pre_loc, cam, dt
+
+
 # ------------------------------------------------------------------------------------------------ fitting the filter
 FIT_MAX = 1 << 24                  # RN_FIT_MAX
 MOMENTS_MAX_K, MOMENTS_MAX_G = 8, 16

@@ -18,6 +18,7 @@ Operator                                         reference code it stands for
   nms(boxes, scores, thr)                        torchvision.ops.nms as the path uses it   D/model.py:383
   linear_sum_assignment(cost)                    scipy.optimize.linear_sum_assignment  MC3D_crop_tracker.py:706
   estimate_ts_bias(boxes, cams, objs, ts, bias..) MC_Crop_Tracker.estimate_ts_bias      MC3D_crop_tracker.py:237-315
+  track_crop_prior(X, D, T, F, centers, ts, bias) crop frame: view, nearest camera, dt  MC3D_crop_tracker.py:1150-1171
   fit_nearest(gt, det, offsets)                  nearest-box search of the R fit       fit_filter_3D.py:356-375
   residual_moments(E, group, groups)             mean / covariance loops               fit_filter_3D.py:292-299, 377-384, 426-434
   state_to_space / state_to_im / im_to_state     Homography transforms                 homography.py:305-320, 479-500
@@ -175,6 +176,18 @@ def estimate_ts_bias(boxes: torch.Tensor, camera_idxs: torch.Tensor, objs: torch
 @estimate_ts_bias.register_fake
 def _(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, mu_v, max_pairs):
     return boxes.new_empty((2,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::track_crop_prior", mutates_args=(), device_types="cuda")
+def track_crop_prior(X: torch.Tensor, D: torch.Tensor, T: torch.Tensor, F: torch.Tensor, centers: torch.Tensor,
+                     stamps: torch.Tensor, bias: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.track_crop_prior(X, D, T, F, centers, stamps, bias)
+
+
+@track_crop_prior.register_fake
+def _(X, D, T, F, centers, stamps, bias):
+    n = X.shape[0]
+    return X.new_empty((n, 7)), X.new_empty((n,), dtype=torch.int32), X.new_empty((n,), dtype=torch.float64)
 
 
 # ---- fitting the filter
@@ -506,7 +519,7 @@ def _(fields, direction, P, P2, mat_index):
 
 
 OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "decode_dir", "decode_2d", "clip_boxes_", "nms",
-             "linear_sum_assignment", "estimate_ts_bias", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "frame_ingest_half", "parse_frame_timestamps", "augment_frames", "augment_crops",
+             "linear_sum_assignment", "estimate_ts_bias", "track_crop_prior", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "frame_ingest_half", "parse_frame_timestamps", "augment_frames", "augment_crops",
              "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce",
              "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography", "reinterp_mate", "reinterp_offsets", "reinterp_rows",
              "track_rows")

@@ -142,12 +142,19 @@ class Torch_KF(object):
             return dt.to(self.device).double().contiguous(), 1
         return torch.tensor([float(dt)], dtype=torch.float64, device=self.device), 0
 
-    def view(self, dt=None, with_direction=False):                         # kf.py:264-289
+    def view(self, dt=None, with_direction=False, out=None):              # kf.py:264-289
+        """``out``: a contiguous float32 [n, 6 or 7] tensor on the filter's device to write the states into (the tracker's
+        track log hands in a slice of its buffer); by default a new one, as the reference returns."""
         if self.X is None or len(self.X) == 0:
             return [], []
         n = len(self.X)
         self.X, self.D = self.X.contiguous(), self.D.float().contiguous()
-        out = torch.empty((n, 7 if with_direction else 6), dtype=torch.float32, device=self.device)
+        cols = 7 if with_direction else 6
+        if out is None:
+            out = torch.empty((n, cols), dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or tuple(out.shape) != (n, cols) or not out.is_contiguous()
+              or out.device != self.F.device):
+            raise RuntimeError("view: out has to be a contiguous float32 [%d, %d] tensor on %s" % (n, cols, self.F.device))
         dtt, flag = (None, 0) if dt is None else self._dt(dt)
         with torch.cuda.device(self.device):
             _hip.check(_hip.load().rn_kf_view(_p(self.X), _p(self.D), _p(self.F), _hip.ptr(dtt), flag, int(bool(with_direction)),

@@ -244,6 +244,20 @@ int rn_estimate_ts_bias(const float *boxes, int64_t box_stride, const int64_t *c
                         void *workspace, int64_t max_pairs, int32_t *pairs_out, float *te_out, int32_t *info,
                         void *stream);
 
+/* ---------------------------------------------------------------- tracker: crop frame front end ----------
+ * The start of a crop frame in MC_Crop_Tracker.track (MC3D_crop_tracker.py:1150-1171), one lane per track, without
+ * leaving the device.  X [n,6], D [n] fp32, T [n] fp64, F [6,6] fp32: the filter's tensors (see rn_kf_view).  centers
+ * [n_cam,2] fp32 camera centres of view in state space; stamps / bias [n_cam] fp64 = timestamps and ts_bias.
+ *   pre_loc [n,7] fp32: exactly what rn_kf_view writes for the scalar dt = 1/30.0 with direction (:1150).
+ *   cam [n] i32: per track dist_k = |(cx_k - x)(cx_k - x) + (cy_k - y)(cy_k - y)| of that view in fp32, one rounding per
+ *     operation (:1156-1162); the first k attaining the minimum, a NaN distance counting as smaller than any number,
+ *     so the first NaN wins -- torch.argmin's rule on the CPU (:1163).
+ *   dt [n] fp64 = (stamps[cam] + bias[cam]) - T (:1169-1171), the per-object dt of the predict that follows.
+ * n == 0: success, nothing launched.  n_cam < 1: hipErrorInvalidValue.  No synchronisation. */
+int rn_track_crop_prior(const float *X, const float *D, const double *T, const float *F, const float *centers,
+                        const double *stamps, const double *bias, int n_cam, float *pre_loc, int32_t *cam, double *dt,
+                        int n, void *stream);
+
 /* ---------------------------------------------------------------- fitting the filter ----------------------
  * The two pieces of fit_filter_3D.py that the transforms and the filter kernels above do not cover.
  * rn_fit_nearest (fit_filter_3D.py:356-375): B frames, each with one ground-truth state gt [B,6] fp32 and the

@@ -471,6 +471,15 @@ def gen_datareader():
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_datareader.py"), "--out", OUT])
 
 
+def gen_tracker_run():
+    """tests/golden/tracker_run.npz: the reference's own MC_Crop_Tracker.track() and write_results_csv() on the scene of
+    tests/tracker_cases.py.  Its own script (tools/make_golden_tracker.py), in a child process: it patches module globals of
+    the reference's tracker (nms, roi_align) and torch.cuda for the duration of the run."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_tracker.py"), "--out", OUT],
+                          stdout=subprocess.DEVNULL)
+
+
 def ref_module_from_file(alias, relpath):
     """A reference module loaded from its file, under a private name: this repository ships same-named drop-ins
     (util_track/kf.py, homography.py) that come first on sys.path, and a golden must come from the REFERENCE's code."""
@@ -1637,7 +1646,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "tracker_run"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1682,6 +1691,8 @@ def main():
         gen_frames4k()
     if "datareader" in which:
         gen_datareader()
+    if "tracker_run" in which:
+        gen_tracker_run()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
