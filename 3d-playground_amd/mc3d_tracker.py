@@ -31,6 +31,14 @@ Differences from the reference:
     ``PLOT=False``, as the reference's own ``__main__`` does: these paths are cv2 drawing and image writers); a missing
     ``params["cam_centers"]`` raises ValueError; a camera without an entry in the homography raises KeyError.
   * A crop frame reached with ``cd=None`` raises RuntimeError naming ``cd``.
+  * Output frames.  ``PLOT`` / ``OUT`` stay refused (a cv2 window and cv2 writers); the picture of ``plot()`` (:733-917) is
+    asked for through ``params["render"]``, a dict with ``out`` (a directory for PNG frames in the reference's layout, or
+    None), ``label_len`` (5), ``single_box`` (True), ``fancy_crop`` (True) and ``every`` (1: render every n-th frame).  The
+    frame is rendered on the device (``mc3d_render.Renderer``) after the store block, under ``time_metrics["plot"]``, with
+    the detections of the frame's own branch: the parsed ones on a detection frame, the refined boxes and crop windows on a
+    crop frame (priors, with ``single_box=False``, on crop frames only).  ``rendered`` holds the last canvas on the device
+    (uint8 RGB, all cameras tiled), ``original_ims[i]`` camera i's window of it.  One device -> host copy per rendered frame
+    (the label numbers), a second one only when frames are written.  Without the key nothing of this runs.
   * ``all_confs`` / ``all_cameras`` receive Python numbers, as ``mc3d_track`` already does (the reference appends the whole
     ``confs`` tensor at :1250; both lists are write-only).
   * ``all_tracks`` is materialised lazily from the device track log: one device -> host copy of the whole log the first
@@ -180,6 +188,15 @@ class MC_Crop_Tracker(mc3d_post.DetectionParser, mc3d_track.TrackManager):
         self.centers = torch.tensor([camera_centers[key] for key in self.cameras])            # :132
         self.n_frames = len(self.loaders[0]) if self.loaders else 0
         self.ts = params["ts"] if "ts" in params else None
+        self.render_params = None
+        if "render" in params and params["render"] is not None:
+            known = dict(out=None, label_len=5, single_box=True, fancy_crop=True, every=1)
+            extra = set(params["render"]) - set(known)
+            if extra:
+                raise ValueError('params["render"] takes %s; got %s' % (sorted(known), sorted(extra)))
+            self.render_params = dict(known, **params["render"])
+            if int(self.render_params["every"]) < 1:
+                raise ValueError('params["render"]["every"] is a positive frame count')
         # the device (:95-98); everything above runs without one
         device_id = params["GPU"] if "GPU" in params else torch.cuda.current_device()
         self.device = torch.device("cuda:{}".format(device_id))
@@ -197,6 +214,10 @@ class MC_Crop_Tracker(mc3d_post.DetectionParser, mc3d_track.TrackManager):
         self._centers_dev = self.centers.to(self.device).float().reshape(-1, 2).contiguous()   # what int64 - float32 promotes to
         self.output_file = "_outputs/3D_tracking_results.csv"
         self.writers = []
+        self.renderer, self.rendered, self._render_inputs = None, None, None
+        if self.render_params is not None and self.render_params["out"] is not None:
+            import mc3d_render
+            self.writers.append(mc3d_render.PngWriter(self.render_params["out"], self.cameras))
         # data storage (:157-165)
         self.next_obj_id = 0
         self.fsld = {}
@@ -261,6 +282,7 @@ class MC_Crop_Tracker(mc3d_post.DetectionParser, mc3d_track.TrackManager):
     def _crop_frame(self):
         tm = self.time_metrics
         flt = self.filter
+        self._render_inputs = None
         if self.crop_detector is None:
             raise RuntimeError("frame %d is a crop frame (d = %s, s = %s) and needs the crop detector: pass cd=... to "
                                "MC_Crop_Tracker" % (self.frame_num, self.d, self.s))
@@ -295,6 +317,23 @@ class MC_Crop_Tracker(mc3d_post.DetectionParser, mc3d_track.TrackManager):
             self.all_cameras[oid].append(int(cams_h[i]))
         tm["update"] += time.time() - start
         self.crop_cameras = cams_h                                 # the last crop frame's picks, row order of pre_ids
+        if self.render_params is not None:
+            self._render_inputs = (detections, cam_idxs, pre_loc, crop_boxes)
+
+    def _render_frame(self):
+        """plot() (:733-917, called at :1288 with label_len = 5) on the device; see mc3d_render."""
+        import mc3d_render
+        rp = self.render_params
+        if self.renderer is None:
+            self.renderer = mc3d_render.Renderer(len(self.cameras), self.frames.shape[2], self.frames.shape[3], self.device)
+        detections, cams, pre_loc, crop_boxes = self._render_inputs if self._render_inputs is not None else (None,) * 4
+        self.rendered = self.renderer.render_tracker(self, detections, cams, pre_loc=pre_loc, crop_boxes=crop_boxes, crop_cams=cams,
+                                                     label_len=rp["label_len"], single_box=rp["single_box"],
+                                                     fancy_crop=rp["fancy_crop"])
+        self.original_ims = self.renderer.views()
+        if self.writers:
+            host = self.rendered.cpu().numpy()                       # the second copy: only when frames are written
+            self.writers[0](host, self.renderer.views(host))
 
     def track(self):
         tm = self.time_metrics
@@ -315,8 +354,12 @@ class MC_Crop_Tracker(mc3d_post.DetectionParser, mc3d_track.TrackManager):
                 start = time.time()
                 self.associate(detections, labels, scores, camera_idxs)            # :1100-1137
                 tm["update"] += time.time() - start
+                if self.render_params is not None:
+                    self._render_inputs = (detections, camera_idxs, None, None)
             elif self.frame_num % self.s == 0:
                 self._crop_frame()
+            else:
+                self._render_inputs = None
             # remove overlapping objects and anomalies (:1259-1261)
             start = time.time()
             self.prune()
@@ -333,6 +376,11 @@ class MC_Crop_Tracker(mc3d_post.DetectionParser, mc3d_track.TrackManager):
                 for _ in range(n):
                     self.all_ts_bias.append(self.ts_bias.copy())
             tm["store"] += time.time() - start
+            # the output frame (:1285-1289)
+            start = time.time()
+            if self.render_params is not None and self.frame_num % int(self.render_params["every"]) == 0:
+                self._render_frame()
+            tm["plot"] += time.time() - start
             # load next frame
             start = time.time()
             next(self)

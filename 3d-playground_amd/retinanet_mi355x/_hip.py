@@ -96,6 +96,10 @@ SIGNATURES = {
     "rn_reinterp_offsets": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64] + [c_vp] * 5),
     "rn_reinterp_rows": (c_i32, [c_vp] * 7 + [c_i64] * 4 + [c_vp] * 5),
     "rn_track_rows": (c_i32, [c_vp] * 5 + [c_i64, c_i64] + [c_vp] * 7),
+    "rn_render_edges": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "rn_render_rects": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "rn_render_text": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "rn_render_compose": (c_i32, [c_vp] + [c_f32] * 6 + [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
 }
 
 class ConvDesc(ctypes.Structure):

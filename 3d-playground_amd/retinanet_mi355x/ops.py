@@ -1635,3 +1635,119 @@ def fit_homography(src, dst, offsets, refine=True):
         _hip.check(lib.rn_fit_homography(src.data_ptr(), dst.data_ptr(), src.shape[0], offsets.data_ptr(), B, int(bool(refine)), H.data_ptr(),
                                          status.data_ptr(), _hip.stream()), "rn_fit_homography")
     return H, status
+
+
+# ------------------------------------------------------------------------------------------------ output frames
+RENDER_MAX_DIM = 16384             # RN_RENDER_MAX_DIM
+RENDER_BITS = dict(prior=0, crop_edge=1, track=2, det=3, in_crop=4, label=5, label_text=6, banner_edge=7, banner_text=8)
+RENDER_RECT_COLS = ("x0", "y0", "x1", "y1", "cam", "mode", "anchor", "bit")
+RENDER_RUN_COLS = ("x", "y", "cam", "anchor", "scale", "dilate", "bit", "start", "length")
+
+
+def render_mask(n_cam, H, W, device):
+    """A cleared mask plane uint16 [n_cam,H,W] whose buffer reaches to a multiple of 4 bytes, as the painters' two-pixel
+    atomics need it (include/retinanet_mi355x.h)."""
+    n = int(n_cam) * int(H) * int(W)
+    return torch.zeros(n + (n & 1), dtype=torch.uint16, device=device)[:n].view(int(n_cam), int(H), int(W))
+
+
+def _render_plane(what, mask):
+    if mask.dtype != torch.uint16 or mask.dim() != 3 or not mask.is_contiguous() or min(mask.shape) < 1 \
+            or max(mask.shape[1:]) > RENDER_MAX_DIM:
+        raise RuntimeError("%s: mask is a contiguous uint16 [n_cam,H,W] plane (H, W <= %d), got %s %s"
+                           % (what, RENDER_MAX_DIM, mask.dtype, tuple(mask.shape)))
+    room = mask.untyped_storage().nbytes() - 2 * mask.storage_offset()
+    if mask.data_ptr() % 4 or room < (2 * mask.numel() + 3) // 4 * 4:
+        raise RuntimeError("%s: the mask's buffer must be 4-byte aligned and reach to a multiple of 4 bytes: allocate it with "
+                           "ops.render_mask" % what)
+    return tuple(int(s) for s in mask.shape)
+
+
+def _render_boxes(what, name, boxes, dev):
+    if boxes is None:
+        return 0
+    _hip.need_gpu(boxes)
+    if boxes.dtype != torch.float64 or boxes.dim() != 3 or tuple(boxes.shape[1:]) != (8, 2) or not boxes.is_contiguous() \
+            or boxes.device != dev:
+        raise RuntimeError("%s: %s is a contiguous fp64 [n,8,2] tensor on the mask's device, got %s %s"
+                           % (what, name, boxes.dtype, tuple(boxes.shape)))
+    return boxes.shape[0]
+
+
+def render_edges(corners, cam, thickness, bit, mask):
+    """ORs bit number `bit` into mask along the 14 edges of every box: corners fp64 [n,8,2], cam int32 [n] (rn_render_edges)."""
+    lib = _hip.load()
+    _hip.need_gpu(corners, cam, mask)
+    n_cam, H, W = _render_plane("render_edges", mask)
+    n = _render_boxes("render_edges", "corners", corners, mask.device)
+    _mot_typed("render_edges", ("cam", cam, torch.int32))
+    if tuple(cam.shape) != (n,) or cam.device != mask.device:
+        raise RuntimeError("render_edges: cam is int32 [n] on the mask's device")
+    if not (1 <= int(thickness) <= 255 and 0 <= int(bit) <= 15):
+        raise RuntimeError("render_edges: 1 <= thickness <= 255 and 0 <= bit <= 15")
+    with torch.cuda.device(mask.device):
+        _hip.check(lib.rn_render_edges(_hip.ptr(corners), _hip.ptr(cam), n, int(thickness), int(bit), mask.data_ptr(), n_cam, H, W,
+                                       _hip.stream()), "rn_render_edges")
+    return mask
+
+
+def _render_records(what, name, rec, cols, dev):
+    _hip.need_gpu(rec)
+    if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] != cols or not rec.is_contiguous() or rec.device != dev:
+        raise RuntimeError("%s: %s is a contiguous int32 [n,%d] tensor on the mask's device, got %s %s"
+                           % (what, name, cols, rec.dtype, tuple(rec.shape)))
+    return rec.shape[0]
+
+
+def render_rects(rects, mask, anchors=None):
+    """rects int32 [n,8] (RENDER_RECT_COLS): half-open rectangles, filled (mode 0) or outlined (1), absolute or offset from
+    (int(min x), int(max y)) of box `anchor` of anchors fp64 [m,8,2] (rn_render_rects)."""
+    lib = _hip.load()
+    _hip.need_gpu(mask)
+    n_cam, H, W = _render_plane("render_rects", mask)
+    n = _render_records("render_rects", "rects", rects, len(RENDER_RECT_COLS), mask.device)
+    m = _render_boxes("render_rects", "anchors", anchors, mask.device)
+    with torch.cuda.device(mask.device):
+        _hip.check(lib.rn_render_rects(_hip.ptr(rects), n, _hip.ptr(anchors) if m else None, m, mask.data_ptr(), n_cam, H, W,
+                                       _hip.stream()), "rn_render_rects")
+    return mask
+
+
+def render_text(runs, text, font, mask, anchors=None):
+    """runs int32 [n,9] (RENDER_RUN_COLS) over the bytes of text uint8 [T]; font uint8 [95,8] (rn_render_text)."""
+    lib = _hip.load()
+    _hip.need_gpu(text, font, mask)
+    n_cam, H, W = _render_plane("render_text", mask)
+    n = _render_records("render_text", "runs", runs, len(RENDER_RUN_COLS), mask.device)
+    m = _render_boxes("render_text", "anchors", anchors, mask.device)
+    _mot_typed("render_text", ("text", text, torch.uint8), ("font", font, torch.uint8))
+    if text.dim() != 1 or tuple(font.shape) != (95, 8) or text.device != mask.device or font.device != mask.device:
+        raise RuntimeError("render_text: text is uint8 [T] and font uint8 [95,8], both on the mask's device")
+    with torch.cuda.device(mask.device):
+        _hip.check(lib.rn_render_text(_hip.ptr(runs), n, _hip.ptr(text), text.numel(), font.data_ptr(), _hip.ptr(anchors) if m else None,
+                                      m, mask.data_ptr(), n_cam, H, W, _hip.stream()), "rn_render_text")
+    return mask
+
+
+def render_compose(frames, mask, crops_present, cols, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """frames fp32 [n_cam,3,H,W] (normalised RGB) + mask uint16 [n_cam,H,W] -> the uint8 mosaic [R*H, cols*W, 3], camera i in
+    tile (i // cols, i % cols), unused tiles zero (rn_render_compose)."""
+    lib = _hip.load()
+    _hip.need_gpu(frames, mask, out)
+    n_cam, H, W = _render_plane("render_compose", mask)
+    if frames.dtype != torch.float32 or tuple(frames.shape) != (n_cam, 3, H, W) or not frames.is_contiguous() \
+            or frames.device != mask.device:
+        raise RuntimeError("render_compose: frames is a contiguous fp32 [%d,3,%d,%d] tensor on the mask's device, got %s %s"
+                           % (n_cam, H, W, frames.dtype, tuple(frames.shape)))
+    cols = int(cols)
+    if not 1 <= cols <= n_cam:
+        raise RuntimeError("render_compose: 1 <= cols <= n_cam")
+    rows = -(-n_cam // cols)
+    if out is None:
+        out = torch.empty((rows * H, cols * W, 3), dtype=torch.uint8, device=mask.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (rows * H, cols * W, 3) or not out.is_contiguous() or out.device != mask.device:
+        raise RuntimeError("render_compose: out is a contiguous uint8 [%d,%d,3] tensor on the mask's device" % (rows * H, cols * W))
+    with torch.cuda.device(mask.device):
+        _hip.check(lib.rn_render_compose(frames.data_ptr(), *[float(m) for m in mean], *[float(s) for s in std], mask.data_ptr(),
+                                         int(bool(crops_present)), out.data_ptr(), n_cam, H, W, cols, _hip.stream()), "rn_render_compose")
+    return out

@@ -39,6 +39,8 @@ Operator                                         reference code it stands for
   reinterp_mate / reinterp_offsets /             Data_Reader.reinterpolate, all rows   datareader.py:411-434
   reinterp_rows
   track_rows(fields, direction, P, P2, index)    Data_Reader.write_to_file's row math  datareader.py:530-550
+  render_edges / render_rects / render_text /    MC_Crop_Tracker.plot, plot_boxes      MC3D_crop_tracker.py:733-917
+  render_compose                                 (own drawing rules, no cv2)           homography.py:670-714
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -522,4 +524,31 @@ OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "dec
              "linear_sum_assignment", "estimate_ts_bias", "track_crop_prior", "fit_nearest", "residual_moments", "state_to_space", "state_to_im", "im_to_state", "frame_ingest", "frame_ingest_half", "parse_frame_timestamps", "augment_frames", "augment_crops",
              "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce",
              "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography", "reinterp_mate", "reinterp_offsets", "reinterp_rows",
-             "track_rows")
+             "track_rows", "render_edges", "render_rects", "render_text", "render_compose")
+
+
+# ---- output frames: the painters OR into the mask plane in place
+@_lib.custom_op(NS + "::render_edges", mutates_args=("mask",), device_types="cuda")
+def render_edges(corners: torch.Tensor, cam: torch.Tensor, thickness: int, bit: int, mask: torch.Tensor) -> None:
+    ops.render_edges(corners, cam, thickness, bit, mask)
+
+
+@_lib.custom_op(NS + "::render_rects", mutates_args=("mask",), device_types="cuda")
+def render_rects(rects: torch.Tensor, mask: torch.Tensor, anchors: Optional[torch.Tensor]) -> None:
+    ops.render_rects(rects, mask, anchors)
+
+
+@_lib.custom_op(NS + "::render_text", mutates_args=("mask",), device_types="cuda")
+def render_text(runs: torch.Tensor, text: torch.Tensor, font: torch.Tensor, mask: torch.Tensor, anchors: Optional[torch.Tensor]) -> None:
+    ops.render_text(runs, text, font, mask, anchors)
+
+
+@_lib.custom_op(NS + "::render_compose", mutates_args=(), device_types="cuda")
+def render_compose(frames: torch.Tensor, mask: torch.Tensor, crops_present: bool, cols: int) -> torch.Tensor:
+    return ops.render_compose(frames, mask, crops_present, cols)
+
+
+@render_compose.register_fake
+def _(frames, mask, crops_present, cols):
+    n_cam, H, W = mask.shape
+    return frames.new_empty((-(-n_cam // cols) * H, cols * W, 3), dtype=torch.uint8)

@@ -1088,6 +1088,56 @@ int rn_track_rows(const double *fields, const double *direction, const int32_t *
                   int64_t n_mats, int64_t N, float *state, float *space, double *im, double *box, uint8_t *keep,
                   int32_t *status, void *stream);
 
+/* ---- output frames (csrc/render.hip): MC_Crop_Tracker.plot (MC3D_crop_tracker.py:733-917), Homography.plot_boxes
+ * (homography.py:670-714) without cv2.  The drawing rules are this library's own, in exact integer arithmetic (DESIGN.md:
+ * "Rendering"); layer order, colours, blend weights and geometry are the reference's.
+ * Painting goes into a mask plane uint16 [n_cam,H,W], one bit per layer (RN_RENDER_*), with 32-bit atomicOr on the word that
+ * holds two pixels: a pixel's mask, and so the picture, does not depend on the order the primitives arrive in.  The plane's
+ * base is 4-byte aligned and its buffer reaches to a multiple of 4 bytes (one spare pixel when n_cam*H*W is odd); the caller
+ * clears it.  H, W <= RN_RENDER_MAX_DIM; coordinates are int32; a camera index outside [0, n_cam) paints nothing.  `bit` is a
+ * layer's bit NUMBER, 0..15 (the RN_RENDER_* values below are the masks 1 << bit the compose pass tests).
+ *   rn_render_edges    the 14 edges (RN_RENDER_EDGES pairs, the reference's DRAW table) of n boxes, corners fp64 [n,8,2] image
+ *                      points, cam int32 [n].  Endpoints truncate toward zero; an edge with a non-finite endpoint or one
+ *                      outside [-8192, 8191] is skipped whole.  Pixel (x, y) is covered when 4 d^2 <= thickness^2, d the
+ *                      distance to the segment, in int64 without division: 4 cross^2 <= t^2 len^2 where the projection
+ *                      falls inside, the endpoint distance otherwise (a zero-length edge is a disc).  One workgroup per
+ *                      edge, over a per-row interval around the segment clipped to the frame.  1 <= thickness <= 255.
+ *   rn_render_rects    rects int32 [n,8] = (x0, y0, x1, y1, cam, mode, anchor, bit): the half-open rectangle [x0,x1) x [y0,y1),
+ *                      mode 0 filled, 1 its first/last row and column.  anchor >= 0: x and y are offsets from (int(min x),
+ *                      int(max y)) of the eight corners of box `anchor` of anchors fp64 [n_anchor,8,2]; a box with a
+ *                      non-finite corner, or one outside [-8192, 8191], anchors nothing.  Empty and off-frame: no-ops.
+ *   rn_render_text     runs int32 [n,9] = (x, y, cam, anchor, scale, dilate, bit, start, length): bytes text[start .. start +
+ *                      length) on the baseline origin (x, y) (anchored as above).  font uint8 [95,8]: ASCII 32..126, 8 rows
+ *                      top to bottom of 6 bits, bit 5 the left column; other bytes draw as '?'.  Character i fills columns
+ *                      [x + 6 s i, x + 6 s (i + 1)) and rows [y - 8 s, y); dilate 1 adds every pixel with a covered
+ *                      8-neighbour.  1 <= scale <= 64, dilate 0 or 1, start + length <= n_text; clipped at the frame.
+ *   rn_render_compose  frames fp32 [n_cam,3,H,W] (normalised RGB) + mask -> out uint8 [R*H, C*W, 3], camera i in tile (i / C,
+ *                      i % C), R = ceil(n_cam / C), unused tiles 0.  Per channel, one fp32 rounding per operation:
+ *                        u = clamp(floor((x*std + mean)*255 + 0.5), 0, 255); v = u / 255
+ *                        PRIOR bit -> (255,255,0); CROP_EDGE -> 255; TRACK -> (0,200,25); DET -> (255,0,0)   (unsaturated)
+ *                        crops_present and IN_CROP clear: v = 0.3f*v
+ *                        LABEL or LABEL_TEXT: a = TEXT ? 0 : v; b = TEXT ? 0 : (LABEL ? 1 : v); v = 0.7f*a + 0.3f*b
+ *                        BANNER_EDGE -> 1; BANNER_TEXT -> 0;   out = (uint8)(clamp(v, 0, 1)*255 + 0.5)
+ *                      An empty mask gives the uint8 frame back exactly. */
+#define RN_RENDER_PRIOR 1
+#define RN_RENDER_CROP_EDGE 2
+#define RN_RENDER_TRACK 4
+#define RN_RENDER_DET 8
+#define RN_RENDER_IN_CROP 16
+#define RN_RENDER_LABEL 32
+#define RN_RENDER_LABEL_TEXT 64
+#define RN_RENDER_BANNER_EDGE 128
+#define RN_RENDER_BANNER_TEXT 256
+#define RN_RENDER_MAX_DIM 16384
+int rn_render_edges(const double *corners, const int32_t *cam, int64_t n, int thickness, int bit, uint16_t *mask, int n_cam,
+                    int H, int W, void *stream);
+int rn_render_rects(const int32_t *rects, int64_t n, const double *anchors, int64_t n_anchor, uint16_t *mask, int n_cam, int H,
+                    int W, void *stream);
+int rn_render_text(const int32_t *runs, int64_t n, const uint8_t *text, int64_t n_text, const uint8_t *font,
+                   const double *anchors, int64_t n_anchor, uint16_t *mask, int n_cam, int H, int W, void *stream);
+int rn_render_compose(const float *frames, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                      const uint16_t *mask, int crops_present, uint8_t *out, int n_cam, int H, int W, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
