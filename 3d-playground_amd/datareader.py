@@ -16,10 +16,23 @@ path.
 
 Differences a caller can see: ``reinterpolate`` writes to ``save`` (the reference ignores the argument and
 always writes its default name, :450-451; the default value is that name, so a call without arguments behaves the same);
-``frequency <= 0`` raises ValueError (the reference loops forever); ``Camera_Wrapper``, ``plot_labels``, ``plot_in`` and
-``test_integrity`` raise NotImplementedError (cv2 video I/O); the per-instant progress print of ``write_to_file`` is gone.
+``frequency <= 0`` raises ValueError (the reference loops forever); the per-instant progress print of ``write_to_file`` is
+gone.
+
+The video half (:24-89, 253-399, 586-653) runs on frames a loader hands over, without cv2: ``Camera_Wrapper(source, ds,
+reader)`` wraps an iterator of uint8 [h,w,3] frames that carries a ``.sequence`` string, reads the burnt-in time stamp through
+a ``timestamp_utilities.TimestampReader`` and keeps the fp64 running frame on the device; ``test_integrity`` counts doubled
+and skipped frames from an exact integer window sum (``ops.frame_absdiff``); ``plot_in(..., render={...})`` replays the file
+over the cameras: the loop over time stamps (:308-399) stays on the host, a handful of floats per frame, and every frame is
+shifted, projected, painted and tiled by ``mc3d_render.Replayer`` (csrc/replay.hip).  What still raises NotImplementedError,
+because it is cv2 itself: a ``str`` source (video decoding), ``plot_in`` without ``render=`` (window display) or with
+``savefile`` (the MPEG writer), and ``plot_labels`` (it takes and returns a host cv2 image; its label block is painted by the
+replay).  Further differences: a first frame that no set reads takes 0 + 1/30.0 (the reader's previous stamps start at zero;
+the reference raises TypeError on ``None + 1/30.0``); ``test_integrity`` takes ``n`` and ``save_dir`` (the reference: 1000 and
+a hard-coded desktop path) and returns its counts; the drawing rules are mc3d_render's (its "Differences").
 """
 import csv
+import os
 import re
 
 import numpy as np
@@ -33,16 +46,181 @@ DEFAULT_SAVE = "reinterpolated_3D_tracking_outputs.csv"        # :401, :451
 _NO_VIDEO = "{} reads or draws video frames through cv2 (datareader.py:{}); video I/O is outside this package"
 
 
+def _cuda(device=None):
+    dev = torch.device("cuda:0" if device is None else device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("the replay runs on an MI355X only: no usable device %s (no CPU fallback)" % (dev,))
+    return dev
+
+
 class Camera_Wrapper():
-    def __init__(self, sequence, ds=2):
-        raise NotImplementedError(_NO_VIDEO.format("Camera_Wrapper", "24-89"))
+    """datareader.py:24-89 around a loader instead of cv2.VideoCapture: ``source`` is an iterator of uint8 [h,w,3] frames
+    (device tensors, or host tensors / arrays uploaded here) with a ``.sequence`` string naming the camera (p?c?, digits);
+    ``reader`` a ``TimestampReader(sets, 1)`` whose sets are tried in order (the reference tries two geometries).
+    ``frame`` uint8 [H,W,3] on the device (ds == 2: the exact 2x reduction of ``ops.frame_ingest_half``), ``ts``, ``name``,
+    ``all_ts``, ``running_frame`` fp64 [H,W,3] on the device, ``ds`` as the reference's.  One ``__next__``: at most one upload,
+    the launches, one small copy back of (ts, status)."""
+
+    def __init__(self, source, ds=2, reader=None, device=None):
+        if isinstance(source, str):
+            raise NotImplementedError(_NO_VIDEO.format("Camera_Wrapper", "24-89"))
+        if reader is None:
+            raise ValueError("Camera_Wrapper needs reader=timestamp_utilities.TimestampReader(sets, 1): the reference's "
+                             "checksum tables are pickles at hard-coded paths and are not shipped")
+        self.source, self.ds, self.reader = source, ds, reader
+        self.device = _cuda(getattr(reader, "device", None) if device is None else device)
+        self.frame = None
+        self.ts = None
+        self.status = None
+        self.name = re.search(r"p\dc\d", source.sequence).group(0)
+        self.all_ts = []
+        self.running_frame = None
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        raw = next(self.source)                                 # StopIteration: the source has ended
+        raw = raw if torch.is_tensor(raw) else torch.from_numpy(np.ascontiguousarray(raw))
+        if raw.dim() != 3 or raw.shape[2] != 3 or raw.dtype != torch.uint8:
+            raise ValueError("a frame is uint8 [h,w,3], got %s %s" % (raw.dtype, tuple(raw.shape)))
+        raw = (raw if raw.is_cuda else raw.to(self.device)).contiguous()
+        times, status = self.reader(raw.unsqueeze(0))           # every set in turn, else prev + 1/30.0 (:60-66)
+        if self.ds == 2:
+            raw = ops.frame_ingest_half(raw, keep_u8=True)[1][0]
+        self.frame = raw
+        first = self.running_frame is None
+        if first:
+            self.running_frame = torch.empty(raw.shape, dtype=torch.float64, device=raw.device)
+        ops.running_frame(self.running_frame, raw, first)
+        ts, st = torch.cat((times, status.to(torch.float64))).tolist()        # the one copy back
+        self.ts, self.status = ts, int(st)
+        if self.status == ops.TS_FELL_BACK:
+            print("No timestamp parsed: {}".format(self.name))
+        self.all_ts.append(self.ts)
+
+    def release(self):
+        for name in ("release", "close"):
+            if hasattr(self.source, name):
+                getattr(self.source, name)()
+                return
+
+    def __len__(self):
+        return int(len(self.source))
+
+    def skip(self, count):
+        for i in range(count):
+            next(self.source)                                   # cap.grab(): taken and not looked at
+        next(self)
 
 
-def test_integrity(sequence):
-    raise NotImplementedError(_NO_VIDEO.format("test_integrity", "586-632"))
+def absdiff_mean(total, H, W):
+    """np.mean(|frame - prev|[100:500, 100:500, :]) from the window's exact integer sum; None for an empty window.  Every term
+    of numpy's sum is an integer below 2^53, so one division of two exact operands is its value bit for bit."""
+    count = ops.absdiff_window(H, W)
+    return None if count == 0 else int(total) / count
+
+
+def test_integrity(source, n=1000, save_dir=None, reader=None):
+    """datareader.py:586-653: counts doubled time stamps, doubled frames, both, and skipped stamps over up to ``n`` frames of
+    ``source`` (a loader, wrapped with ds = 1 and ``reader``, or a Camera_Wrapper).  -> dict of the five counts."""
+    if isinstance(source, str):
+        raise NotImplementedError(_NO_VIDEO.format("test_integrity", "586-632"))
+    cam = source if isinstance(source, Camera_Wrapper) else Camera_Wrapper(source, ds=1, reader=reader)
+    save = None
+    if save_dir is not None:
+        from PIL import Image
+        os.makedirs(save_dir, exist_ok=True)
+
+        def save(frame, i):
+            Image.fromarray(frame.cpu().numpy()).save(os.path.join(save_dir, "{}_{}.png".format(cam.name, i)))
+    counts = dict(doubled_ts=0, doubled_frame=0, doubled_both=0, skipped_ts=0, correct=0)
+    try:
+        next(cam)
+        prev_ts, prev_frame = cam.ts, cam.frame.clone()
+        for i in range(1, n):
+            next(cam)
+            ts, frame = cam.ts, cam.frame
+            DTS = ts - prev_ts == 0
+            mean = absdiff_mean(ops.frame_absdiff(frame, prev_frame).item(), frame.shape[0], frame.shape[1])
+            DF = mean is not None and mean < 0.2
+            STS = False
+            if DTS and DF:
+                counts["doubled_both"] += 1
+            elif DTS:
+                counts["doubled_ts"] += 1
+            elif DF:
+                counts["doubled_frame"] += 1
+            elif (ts - prev_ts) > 0.05:
+                counts["skipped_ts"] += 1
+                STS = True
+            else:
+                counts["correct"] += 1
+            if DTS or DF or STS:
+                if save is not None:
+                    save(frame, i)
+                    save(prev_frame, i - 1)
+                for k in (1, 2):                                # two more frames are consumed (:637-640)
+                    next(cam)
+                    if save is not None:
+                        save(cam.frame, i + k)
+            prev_frame = cam.frame.clone()
+            prev_ts = cam.ts
+    except StopIteration:
+        pass                                                    # the source ended early
+    print("Camera {} results for {} frames:".format(cam.name, n))
+    print("Doubled timestamps occured {} times".format(counts["doubled_ts"]))
+    print("Doubled both occured {} times".format(counts["doubled_both"]))
+    print("Doubled frames occured {} times".format(counts["doubled_frame"]))
+    print("Skipped timestamps occurred {} times".format(counts["skipped_ts"]))
+    return counts
 
 
 test_integrity.__test__ = False                                # a reference function name, not a test
+
+
+def replay_walk(reader, cameras, max_frames=None):
+    """The loop of plot_in (:308-399) without its drawing: a generator of (label instant index, ts_data, ts, [camera ts], [dt
+    per camera]) per output frame.  ``reader``: the Data_Reader (its ``__next__``); ``cameras``: objects with ``ts``, ``name``
+    and ``__next__``, already holding their first frame.  Ends when the labels run out, when a camera raises StopIteration or
+    after ``max_frames`` frames.  Serial, Python floats, as the reference writes it."""
+    ts_data, ts, next_ts, _ = next(reader)
+    done = 0
+    try:
+        while max_frames is None or done < max_frames:
+            max_time = max([cam.ts for cam in cameras])
+            for cam in cameras:
+                while cam.ts + 1 / 60.0 < max_time:
+                    next(cam)
+            if next_ts is None:
+                break
+            while max_time > next_ts:
+                ts_data, ts, next_ts, _ = next(reader)
+                if next_ts is None:
+                    break
+            stamps, dts = [], []
+            for camera in cameras:
+                try:
+                    bias = ts_data[list(ts_data.keys())[0]]["ts_bias"][camera.name]
+                except KeyError:
+                    bias = 0
+                stamps.append(camera.ts)
+                dts.append(camera.ts + bias - ts)
+            yield reader.d_idx - 1, ts_data, ts, stamps, dts
+            done += 1
+            next(cameras[0])
+    except StopIteration:
+        return
+
+
+def pack_states(data):
+    """Every datum of ``data`` as the fp32 row plot_in stacks (:338): (x, y, l, w, h, direction, v) -> (offsets int64 [F+1],
+    state7 fp32 [R,7]), frames and rows in their dict order."""
+    offsets, rows = [0], []
+    for frame in data:
+        rows += [[obj["x"], obj["y"], obj["l"], obj["w"], obj["h"], obj["direction"], obj["v"]] for obj in frame.values()]
+        offsets.append(len(rows))
+    return np.asarray(offsets, np.int64), np.asarray(rows, np.float64).reshape(-1, 7).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ host <-> device blocks
@@ -209,10 +387,53 @@ class Data_Reader():
             print(self.d_idx, self.data[self.d_idx])
 
     def plot_labels(self, im, boxes, state_boxes, classes, ids, speeds, directions, times):
+        """Refused: it takes and returns a host cv2 image.  Its label block (:262-290) is painted by the replay
+        (``plot_in(..., render=...)``, mc3d_render.Replayer)."""
         raise NotImplementedError(_NO_VIDEO.format("plot_labels", "253-290"))
 
-    def plot_in(self, camera_sequences, framerate=30, savefile=None):
-        raise NotImplementedError(_NO_VIDEO.format("plot_in", "293-399"))
+    def plot_in(self, sequences, framerate=10, savefile=None, render=None):
+        """datareader.py:293-399 with the tracker's switch (PLOT=True -> params["render"]): ``render = {"out": directory or
+        None, "size": (width, height) or None, "max_frames": int or None}`` replays the file over ``sequences`` -- a list of
+        Camera_Wrappers, or of loaders wrapped here with ``TimestampReader(render["sets"], 1)``; ``render["swap_rb"]`` says
+        the frames are B,G,R.  -> the number of frames rendered.  ``replayed``: the last canvas, uint8 RGB on the device;
+        ``replay_log``: per output frame (label instant index, [camera ts], [dt per camera]).  Frames go to
+        ``<out>/combined/00000.png ...``: one device -> host copy per written frame, none when ``out`` is None.  Without
+        ``render`` (window display) and with ``savefile`` (the MPEG writer) it raises: both are cv2."""
+        if render is None or savefile is not None:
+            raise NotImplementedError(_NO_VIDEO.format("plot_in", "293-399"))
+        import mc3d_render
+        import timestamp_utilities as tsu
+        dev = _cuda(self._device())
+        cameras = []
+        for sequence in sequences:
+            cap = sequence if isinstance(sequence, Camera_Wrapper) else \
+                Camera_Wrapper(sequence, reader=tsu.TimestampReader(render["sets"], 1, device=dev), device=dev)
+            if cap.ts is None:
+                next(cap)
+            cameras.append(cap)
+        self.replayed, self.replay_log = None, []
+        if not cameras:
+            return 0
+        names = [cam.name for cam in cameras]
+        P1, P2, idx = _matrices(self.hg, names, dev)
+        P1 = P1.index_select(0, idx.long()).contiguous()
+        P2 = None if P2 is None else P2.index_select(0, idx.long()).contiguous()
+        offsets, state7 = pack_states(self.data)
+        d_state7, = _upload(dev, [state7])                       # the whole file's rows, once
+        H, W = cameras[0].frame.shape[:2]
+        replayer = mc3d_render.Replayer(len(cameras), H, W, dev)
+        writer = None if render.get("out") is None else mc3d_render.PngWriter(render["out"], [])
+        for inst, ts_data, ts, stamps, dts in replay_walk(self, cameras, render.get("max_frames")):
+            view = state7[offsets[inst]:offsets[inst + 1]]      # l, w, h of a view are the row's own
+            lines = [[mc3d_render.replay_label_lines(view[i], obj["class"], obj["id"], ts + dt) for i, obj in enumerate(ts_data.values())]
+                     for dt in dts]
+            self.replayed = replayer.replay([cam.frame for cam in cameras], d_state7, int(offsets[inst]), len(view), dts, P1, P2,
+                                            lines, render.get("size"), render.get("swap_rb", False))
+            self.replay_log.append((inst, stamps, dts))
+            if writer is not None:
+                writer(self.replayed.cpu().numpy(), [])
+        self.replayer = replayer
+        return len(self.replay_log)
 
     def _walk(self, frequency):
         """datareader.py:406-444 without the per-object body: -> (a, output_time) per output instant, a = the index in

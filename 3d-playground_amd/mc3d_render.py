@@ -18,6 +18,11 @@ Differences from the reference:
     wrapper's own switch (``y > 60`` -> second homography).
   * The mosaic puts camera i at ``(i // cols, i % cols)``; see ``mosaic_layout``.
   * uint8 RGB output (the reference: float64 BGR, scaled by 255 in its writer).
+  * ``Replayer`` (Data_Reader.plot_in, datareader.py:253-399) shares the line and font rules above.  Its label goes over the
+    whole rectangle as 0.7 v + 0.3 * 255 and text wins everywhere; the reference draws every label's text into both of its
+    copies but lets a LATER label's rectangle grey an earlier label's text in one of them (:281-288).  Its canvas keeps the
+    reference's column-major tiles (``replay_layout``), resampled to the output size by this project's own integer bilinear
+    rule (include/retinanet_mi355x.h, rn_replay_compose), not cv2.resize.
 """
 import math
 import os
@@ -171,11 +176,12 @@ def banner_text(bias, mu_v):
     return "Estimated time bias: {:.4f}s ({:.1f}ft)".format(bias, float(bias * mu_v))           # :888
 
 
-def label_records(labels):
+def label_records(labels, bits=BITS):
     """labels: [(box index, camera, [lines])] -> (rect records int32 [n,8], text runs int32 [m,9], bytes) of the label blocks
     (:864-882 with the 6x8 cell in place of getTextSize): the rectangle from c1 = (int(min x), int(max y)) of the box to c1 +
     (6 L + 10, n_lines * 12) inclusive, L the longest line; line k (from 1) on the baseline c1.y + 12 k.  Labels with the same
-    lines (a track in every camera) share their bytes; the records are laid out with numpy, one pass over the labels."""
+    lines (a track in every camera) share their bytes; the records are laid out with numpy, one pass over the labels.
+    ``bits``: the table naming the ``label`` and ``label_text`` bit numbers (the replay's plane has its own)."""
     text, keys, shapes, spans = bytearray(), {}, [], []               # per distinct label: (longest, n_lines), [(start, length)]
     box, cam, key = (np.empty(len(labels), np.int32) for _ in range(3))
     for j, (b, c, lines) in enumerate(labels):
@@ -197,13 +203,13 @@ def label_records(labels):
     keep = n_lines > 0
     zero = np.zeros(int(keep.sum()), np.int32)
     rects = np.stack((zero, zero, CELL_W * longest[keep] + 11, LINE_H * n_lines[keep] + 1, cam[keep], zero, box[keep],
-                      zero + BITS["label"]), axis=1)
+                      zero + bits["label"]), axis=1)
     runs = []
     for k in range(int(n_lines.max())):                               # line k of every label that has one
         has = n_lines > k
         span = np.asarray([sp[k] if len(sp) > k else (0, 0) for sp in spans], np.int32).reshape(-1, 2)[key[has]]
         zero = np.zeros(int(has.sum()), np.int32)
-        runs.append(np.stack((zero, zero + LINE_H * (k + 1), cam[has], box[has], zero + 1, zero, zero + BITS["label_text"],
+        runs.append(np.stack((zero, zero + LINE_H * (k + 1), cam[has], box[has], zero + 1, zero, zero + bits["label_text"],
                               span[:, 0], span[:, 1]), axis=1))
     return rects.astype(np.int32), np.concatenate(runs).astype(np.int32) if runs else np.zeros((0, 9), np.int32), text
 
@@ -338,6 +344,86 @@ class Renderer:
         mu_v = float(flt.mu_v)
         banners = [banner_text(float(trk.ts_bias[c]), mu_v) for c in range(nc)] if getattr(trk, "est_ts", True) else None
         return self.render(trk.frames, tracks, dets, priors, crops, labels, banners, fancy_crop)
+
+
+REPLAY_BITS = _ops.REPLAY_BITS
+REPLAY_THICKNESS = 2                # plot_in's thickness argument (datareader.py:351)
+replay_layout = _ops.replay_layout
+
+
+def replay_label_lines(view7, class_name, obj_id, time):
+    """plot_labels' five lines (datareader.py:262-268) of one object: view7 = the fp32 view (x, y, l, w, h, direction, v), its
+    numbers formatted as the fp32 tensor elements the reference formats; ``time`` = ts + dt through ``str``."""
+    s = np.asarray(view7, dtype=np.float32)
+    return ["{} {}:".format(class_name, obj_id), "L: {:.1f}ft".format(float(s[2])), "W: {:.1f}ft".format(float(s[3])),
+            "H: {:.1f}ft".format(float(s[4])), "{}".format(time)]
+
+
+class Replayer:
+    """One output frame of ``Data_Reader.plot_in``: ``replay`` shifts and projects the objects of a label instant into every
+    camera (``ops.replay_boxes``), paints boxes and label blocks into its mask plane and composes the uint8 mosaic at the
+    output size (``ops.replay_compose``).  One host -> device copy per frame: the cameras' dt with the label records.
+    ``rendered``: the last canvas; ``last``: views, corners, side and camera of the last frame (device tensors)."""
+
+    def __init__(self, n_cam, H, W, device):
+        self.n_cam, self.H, self.W, self.device = int(n_cam), int(H), int(W), torch.device(device)
+        self.rows, self.cols = replay_layout(self.n_cam)
+        self.mask = _ops.render_mask(self.n_cam, self.H, self.W, self.device)
+        self.font = torch.from_numpy(FONT).to(self.device)
+        self.frames = torch.empty((self.n_cam, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        self.rendered, self.last = None, None
+
+    def records(self, lines_per_object):
+        """Label records of one frame, on the host: lines_per_object[c][i] = the lines of object i in camera c ->
+        (rects int32 [m,8], runs int32 [k,9], text bytes), anchored at box c * n + i."""
+        labels = []
+        for c, per_cam in enumerate(lines_per_object):
+            n = len(per_cam)
+            labels += [(c * n + i, c, lines) for i, lines in enumerate(per_cam)]
+        return label_records(labels, REPLAY_BITS)
+
+    def _upload(self, dts, rects, runs, text):
+        """dt, rect records, text runs and bytes in ONE host -> device copy; views of the device buffer."""
+        d = np.ascontiguousarray(dts, np.float64).reshape(-1)
+        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 8)
+        t = np.ascontiguousarray(runs, np.int32).reshape(-1, 9)
+        buf = np.concatenate((d.view(np.uint8), r.view(np.uint8).reshape(-1), t.view(np.uint8).reshape(-1), np.frombuffer(bytes(text), np.uint8)))
+        dev = torch.from_numpy(buf).to(self.device)
+        a = d.size * 8
+        b = a + r.size * 4
+        c = b + t.size * 4
+        return dev[:a].view(torch.float64), dev[a:b].view(torch.int32).view(-1, 8), dev[b:c].view(torch.int32).view(-1, 9), dev[c:]
+
+    def paint(self, corners, side, cam, d_rects, d_runs, d_text):
+        """Clears the mask plane and paints boxes (primary where side == 0, else secondary) and label blocks into it."""
+        mask = self.mask
+        mask.zero_()
+        if len(cam):
+            off = torch.full_like(cam, -1)                                      # a camera outside [0, n_cam) paints nothing
+            _ops.render_edges(corners, torch.where(side == 0, cam, off), REPLAY_THICKNESS, REPLAY_BITS["primary"], mask)
+            _ops.render_edges(corners, torch.where(side == 0, off, cam), REPLAY_THICKNESS, REPLAY_BITS["secondary"], mask)
+            if len(d_rects):
+                _ops.render_rects(d_rects, mask, corners)
+            if len(d_runs):
+                _ops.render_text(d_runs, d_text, self.font, mask, corners)
+        return mask
+
+    def replay(self, frames, state7, offset, count, dts, P1, P2, lines_per_object, size=None, swap_rb=False):
+        """frames: n_cam uint8 [H,W,3] device tensors (or one [n_cam,H,W,3]); state7 fp32 [R,7] on the device, rows [offset,
+        offset + count) the instant's objects; dts: n_cam host floats; lines_per_object as ``records``.  -> the canvas."""
+        if torch.is_tensor(frames):
+            stacked = frames
+        else:
+            for c, f in enumerate(frames):
+                self.frames[c].copy_(f)
+            stacked = self.frames
+        rects, runs, text = self.records(lines_per_object)
+        d_dt, d_rects, d_runs, d_text = self._upload(dts, rects, runs, text)
+        views, corners, side, cam = _ops.replay_boxes(state7, d_dt, P1, P2, offset, count)
+        self.paint(corners, side, cam, d_rects, d_runs, d_text)
+        self.last = dict(views=views, corners=corners, side=side, cam=cam)
+        self.rendered = _ops.replay_compose(stacked, self.mask, size, swap_rb)
+        return self.rendered
 
 
 class PngWriter:

@@ -100,6 +100,10 @@ SIGNATURES = {
     "rn_render_rects": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "rn_render_text": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "rn_render_compose": (c_i32, [c_vp] + [c_f32] * 6 + [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "rn_replay_boxes": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rn_replay_compose": (c_i32, [c_vp, c_i32, c_vp, c_vp] + [c_i32] * 6 + [c_vp]),
+    "rn_frame_absdiff": (c_i32, [c_vp, c_vp] + [c_i32] * 6 + [c_vp, c_vp, c_vp]),
+    "rn_running_frame": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
 }
 
 class ConvDesc(ctypes.Structure):

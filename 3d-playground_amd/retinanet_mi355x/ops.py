@@ -1751,3 +1751,123 @@ def render_compose(frames, mask, crops_present, cols, mean=IMAGENET_MEAN, std=IM
         _hip.check(lib.rn_render_compose(frames.data_ptr(), *[float(m) for m in mean], *[float(s) for s in std], mask.data_ptr(),
                                          int(bool(crops_present)), out.data_ptr(), n_cam, H, W, cols, _hip.stream()), "rn_render_compose")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ tracking CSV replay
+REPLAY_BITS = dict(primary=0, secondary=1, label=2, label_text=3)         # RN_REPLAY_* of the header, as bit numbers
+REPLAY_MAX_CANVAS = 1 << 20        # RN_REPLAY_MAX_CANVAS
+REPLAY_ABSDIFF_BLOCKS = 1024       # RN_REPLAY_ABSDIFF_BLOCKS
+
+
+def replay_layout(n_cam):
+    """(rows, cols) of the replay's canvas: rows = round(sqrt(n)), cols = ceil(n / rows); camera i in tile (i % rows, i //
+    rows), column-major as datareader.py:364-374 index it."""
+    rows = int(np.round(np.sqrt(int(n_cam))))
+    return rows, -(-int(n_cam) // rows)
+
+
+def replay_boxes(state7, dt, P1, P2=None, offset=0, count=None):
+    """Rows [offset, offset + count) of state7 fp32 [R,7] = (x, y, l, w, h, direction, v), the objects of one label instant,
+    in every camera: dt fp64 [C], P1 / P2 fp64 [C,3,4] -> (views fp32 [C*n,7], image corners fp64 [C*n,8,2], side int32 [C*n],
+    camera int32 [C*n]); row c*n + i is object i in camera c (rn_replay_boxes)."""
+    lib = _hip.load()
+    _hip.need_gpu(state7, dt, P1, P2)
+    _mot_typed("replay_boxes", ("state7", state7, torch.float32), ("dt", dt, torch.float64), ("P1", P1, torch.float64))
+    if state7.dim() != 2 or state7.shape[1] != 7 or dt.dim() != 1 or dt.shape[0] < 1:
+        raise RuntimeError("replay_boxes: state7 is fp32 [R,7] and dt fp64 [C], C >= 1, got %s and %s" % (tuple(state7.shape), tuple(dt.shape)))
+    C, dev = dt.shape[0], state7.device
+    for name, P in (("P1", P1), ("P2", P2)):
+        if P is not None and (P.dtype != torch.float64 or tuple(P.shape) != (C, 3, 4) or not P.is_contiguous() or P.device != dev):
+            raise RuntimeError("replay_boxes: %s is a contiguous fp64 [%d,3,4] tensor on state7's device, got %s %s"
+                               % (name, C, P.dtype, tuple(P.shape)))
+    if dt.device != dev:
+        raise RuntimeError("replay_boxes: dt is on state7's device")
+    offset = int(offset)
+    n = state7.shape[0] - offset if count is None else int(count)
+    if offset < 0 or n < 0 or offset + n > state7.shape[0]:
+        raise RuntimeError("replay_boxes: rows [%d, %d) are outside the %d rows of state7" % (offset, offset + n, state7.shape[0]))
+    if C > 65535 or C * n > 0x7FFFFFFF:
+        raise RuntimeError("replay_boxes: too many cameras or rows")
+    views = torch.empty((C * n, 7), dtype=torch.float32, device=dev)
+    im = torch.empty((C * n, 8, 2), dtype=torch.float64, device=dev)
+    side = torch.empty(C * n, dtype=torch.int32, device=dev)
+    cam = torch.empty(C * n, dtype=torch.int32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            _hip.check(lib.rn_replay_boxes(state7.data_ptr() + 28 * offset, n, dt.data_ptr(), P1.data_ptr(), _hip.ptr(P2), C,
+                                           views.data_ptr(), im.data_ptr(), side.data_ptr(), cam.data_ptr(), _hip.stream()),
+                       "rn_replay_boxes")
+    return views, im, side, cam
+
+
+def replay_compose(frames_u8, mask, size=None, swap_rb=False, out=None):
+    """frames uint8 [n_cam,H,W,3] + mask uint16 [n_cam,H,W] (bits REPLAY_BITS) -> the uint8 RGB mosaic [OH,OW,3], tiles as
+    ``replay_layout``; size = (OW, OH) or None for the canvas itself (rn_replay_compose)."""
+    lib = _hip.load()
+    _hip.need_gpu(frames_u8, mask, out)
+    n_cam, H, W = _render_plane("replay_compose", mask)
+    if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != (n_cam, H, W, 3) or not frames_u8.is_contiguous() \
+            or frames_u8.device != mask.device:
+        raise RuntimeError("replay_compose: frames is a contiguous uint8 [%d,%d,%d,3] tensor on the mask's device, got %s %s"
+                           % (n_cam, H, W, frames_u8.dtype, tuple(frames_u8.shape)))
+    rows, cols = replay_layout(n_cam)
+    if n_cam > 65535 or cols * W > REPLAY_MAX_CANVAS or rows * H > REPLAY_MAX_CANVAS:
+        raise RuntimeError("replay_compose: the canvas %d x %d is larger than %d" % (cols * W, rows * H, REPLAY_MAX_CANVAS))
+    OW, OH = (cols * W, rows * H) if size is None else (int(size[0]), int(size[1]))
+    if not (1 <= OW <= RENDER_MAX_DIM and 1 <= OH <= RENDER_MAX_DIM):
+        raise RuntimeError("replay_compose: the output size is (width, height), each in [1, %d], got %s" % (RENDER_MAX_DIM, (OW, OH)))
+    if out is None:
+        out = torch.empty((OH, OW, 3), dtype=torch.uint8, device=mask.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (OH, OW, 3) or not out.is_contiguous() or out.device != mask.device:
+        raise RuntimeError("replay_compose: out is a contiguous uint8 [%d,%d,3] tensor on the mask's device" % (OH, OW))
+    with torch.cuda.device(mask.device):
+        _hip.check(lib.rn_replay_compose(frames_u8.data_ptr(), int(bool(swap_rb)), mask.data_ptr(), out.data_ptr(), n_cam, H, W, rows,
+                                         OW, OH, _hip.stream()), "rn_replay_compose")
+    return out
+
+
+def _u8_frame(what, name, f):
+    if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or not f.is_contiguous() or min(f.shape) < 1 \
+            or max(f.shape[:2]) > RENDER_MAX_DIM:
+        raise RuntimeError("%s: %s is a contiguous uint8 [H,W,3] frame (H, W <= %d), got %s %s"
+                           % (what, name, RENDER_MAX_DIM, f.dtype, tuple(f.shape)))
+
+
+def frame_absdiff(a, b, y0=100, y1=500, x0=100, x1=500):
+    """sum |a - b| over a[y0:y1, x0:x1, :] of two uint8 [H,W,3] frames, the window clipped to the frame -> int64 [1] on the
+    device, an exact integer (rn_frame_absdiff; datareader.py:617 divides it by the window's size)."""
+    lib = _hip.load()
+    _hip.need_gpu(a, b)
+    _u8_frame("frame_absdiff", "a", a)
+    _u8_frame("frame_absdiff", "b", b)
+    if a.shape != b.shape or a.device != b.device:
+        raise RuntimeError("frame_absdiff: two frames of one size on one device, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    y0, y1, x0, x1 = (int(v) for v in (y0, y1, x0, x1))
+    if min(y0, y1, x0, x1) < 0 or max(y0, y1, x0, x1) > 0x7FFFFFFF:
+        raise RuntimeError("frame_absdiff: window bounds are non-negative int32")
+    partial = torch.empty(REPLAY_ABSDIFF_BLOCKS, dtype=torch.int64, device=a.device)
+    out = torch.empty(1, dtype=torch.int64, device=a.device)
+    with torch.cuda.device(a.device):
+        _hip.check(lib.rn_frame_absdiff(a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], y0, y1, x0, x1, partial.data_ptr(),
+                                        out.data_ptr(), _hip.stream()), "rn_frame_absdiff")
+    return out
+
+
+def absdiff_window(H, W, y0=100, y1=500, x0=100, x1=500):
+    """The number of bytes ``frame_absdiff`` sums for a frame of H x W: the clipped window's rows x columns x 3."""
+    return max(min(int(y1), int(H)) - max(int(y0), 0), 0) * max(min(int(x1), int(W)) - max(int(x0), 0), 0) * 3
+
+
+def running_frame(running, frame, first=False):
+    """running fp64 [H,W,3] <- frame's values (first) or 0.95 * running + 0.05 * frame, one rounding per operation, in place
+    (rn_running_frame; datareader.py:74-77).  -> running."""
+    lib = _hip.load()
+    _hip.need_gpu(running, frame)
+    _u8_frame("running_frame", "frame", frame)
+    if running.dtype != torch.float64 or running.shape != frame.shape or not running.is_contiguous() or running.device != frame.device:
+        raise RuntimeError("running_frame: running is a contiguous fp64 %s tensor on the frame's device, got %s %s"
+                           % (tuple(frame.shape), running.dtype, tuple(running.shape)))
+    with torch.cuda.device(frame.device):
+        _hip.check(lib.rn_running_frame(running.data_ptr(), frame.data_ptr(), frame.numel(), int(bool(first)), _hip.stream()),
+                   "rn_running_frame")
+    return running

@@ -41,6 +41,8 @@ Operator                                         reference code it stands for
   track_rows(fields, direction, P, P2, index)    Data_Reader.write_to_file's row math  datareader.py:530-550
   render_edges / render_rects / render_text /    MC_Crop_Tracker.plot, plot_boxes      MC3D_crop_tracker.py:733-917
   render_compose                                 (own drawing rules, no cv2)           homography.py:670-714
+  replay_boxes / replay_compose /                Data_Reader.plot_in, Camera_Wrapper,  datareader.py:24-89, 253-399
+  frame_absdiff / running_frame                  test_integrity                        datareader.py:586-653
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -552,3 +554,44 @@ def render_compose(frames: torch.Tensor, mask: torch.Tensor, crops_present: bool
 def _(frames, mask, crops_present, cols):
     n_cam, H, W = mask.shape
     return frames.new_empty((-(-n_cam // cols) * H, cols * W, 3), dtype=torch.uint8)
+
+
+# ---- tracking CSV replay (csrc/replay.hip)
+OPERATORS += ("replay_boxes", "replay_compose", "frame_absdiff", "running_frame")
+
+
+@_lib.custom_op(NS + "::replay_boxes", mutates_args=(), device_types="cuda")
+def replay_boxes(state7: torch.Tensor, dt: torch.Tensor, P1: torch.Tensor, P2: Optional[torch.Tensor], offset: int,
+                 count: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.replay_boxes(state7, dt, P1, P2, offset, count)
+
+
+@replay_boxes.register_fake
+def _(state7, dt, P1, P2, offset, count):
+    m, e = dt.shape[0] * count, state7.new_empty
+    return e((m, 7), dtype=torch.float32), e((m, 8, 2), dtype=torch.float64), e((m,), dtype=torch.int32), e((m,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::replay_compose", mutates_args=(), device_types="cuda")
+def replay_compose(frames: torch.Tensor, mask: torch.Tensor, width: int, height: int, swap_rb: bool) -> torch.Tensor:
+    return ops.replay_compose(frames, mask, (width, height), swap_rb)
+
+
+@replay_compose.register_fake
+def _(frames, mask, width, height, swap_rb):
+    return frames.new_empty((height, width, 3), dtype=torch.uint8)
+
+
+@_lib.custom_op(NS + "::frame_absdiff", mutates_args=(), device_types="cuda")
+def frame_absdiff(a: torch.Tensor, b: torch.Tensor, y0: int, y1: int, x0: int, x1: int) -> torch.Tensor:
+    return ops.frame_absdiff(a, b, y0, y1, x0, x1)
+
+
+@frame_absdiff.register_fake
+def _(a, b, y0, y1, x0, x1):
+    return a.new_empty((1,), dtype=torch.int64)
+
+
+@_lib.custom_op(NS + "::running_frame", mutates_args=("running",), device_types="cuda")
+def running_frame(running: torch.Tensor, frame: torch.Tensor, first: bool) -> None:
+    ops.running_frame(running, frame, first)

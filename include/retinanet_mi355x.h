@@ -1138,6 +1138,42 @@ int rn_render_text(const int32_t *runs, int64_t n, const uint8_t *text, int64_t 
 int rn_render_compose(const float *frames, float mean0, float mean1, float mean2, float std0, float std1, float std2,
                       const uint16_t *mask, int crops_present, uint8_t *out, int n_cam, int H, int W, int C, void *stream);
 
+/* ---- tracking CSV replay (csrc/replay.hip): Data_Reader.plot_in, Camera_Wrapper and test_integrity (datareader.py:24-89,
+ * 253-399, 586-653) without cv2.  Boxes, rectangles and text are painted by rn_render_edges / _rects / _text into a mask plane
+ * whose bits mean RN_REPLAY_* here (a bit is a number to the painters).
+ *   rn_replay_boxes    state7 fp32 [n,7] = (x, y, l, w, h, direction, v), the objects of one label instant; dt fp64 [n_cam];
+ *                      P1 / P2 fp64 [n_cam,3,4] (P2 may be nullptr).  Row c*n + i of the outputs is object i seen by camera c:
+ *                      views fp32 [n_cam*n,7] with x' = fl32(fl32(fl32(v * fl32(dt[c])) * direction) + x) (:345: torch's fp32
+ *                      arithmetic, the Python scalar rounded to fp32 first); im fp64 [n_cam*n,8,2] = rn_state_to_im of the
+ *                      view through camera c's matrices (P2 where corner 0's y > 60); side int32 = 1 where the view's y > 60
+ *                      (plot_state_boxes' split, homography.py:874); cam int32 = c.
+ *   rn_replay_compose  frames uint8 [n_cam,H,W,3] (swap_rb: B,G,R bytes) + mask uint16 [n_cam,H,W] -> out uint8 [OH,OW,3] RGB.
+ *                      Per channel v of a pixel, lowest layer first, integers throughout:
+ *                        PRIMARY -> (0,0,255); SECONDARY -> (0,255,0); LABEL -> (7 v + 3*255 + 5) / 10; LABEL_TEXT -> 0
+ *                      other mask bits are ignored.  The canvas is R x C tiles of H x W, C = ceil(n_cam / R), camera i in tile
+ *                      (row i % R, column i / R) (:371-374), unused tiles 0; CW = C W, CH = R H <= RN_REPLAY_MAX_CANVAS.
+ *                      Output pixel (X, Y), per axis (x shown): num = clamp((2X + 1) CW - OW, 0, 2 OW (CW - 1)); x0 = num /
+ *                      (2 OW); w1 = num - 2 OW x0; w0 = 2 OW - w1; x1 = min(x0 + 1, CW - 1);
+ *                        out = (sum over the four taps of wx wy p + 2 OW OH) / (4 OW OH)            (int64; p composed pixels)
+ *                      OW == CW and OH == CH is the identity.  The canvas is never written at another output size.
+ *   rn_frame_absdiff   out int64 [1] = sum |a - b| over rows [y0,y1) x columns [x0,x1) x 3 channels of two uint8 [H,W,3]
+ *                      frames, the window clipped to the frame (empty: 0).  partial: RN_REPLAY_ABSDIFF_BLOCKS int64 of
+ *                      workspace.  Integer adds in two stages: the same result every run.
+ *   rn_running_frame   running fp64 [n] <- first ? frame : fl(fl(0.95 running) + fl(0.05 frame)), frame uint8 [n] (:74-77). */
+#define RN_REPLAY_PRIMARY 1
+#define RN_REPLAY_SECONDARY 2
+#define RN_REPLAY_LABEL 4
+#define RN_REPLAY_LABEL_TEXT 8
+#define RN_REPLAY_MAX_CANVAS 1048576
+#define RN_REPLAY_ABSDIFF_BLOCKS 1024
+int rn_replay_boxes(const float *state7, int64_t n, const double *dt, const double *P1, const double *P2, int n_cam, float *views,
+                    double *im, int32_t *side, int32_t *cam, void *stream);
+int rn_replay_compose(const uint8_t *frames, int swap_rb, const uint16_t *mask, uint8_t *out, int n_cam, int H, int W, int R,
+                      int OW, int OH, void *stream);
+int rn_frame_absdiff(const uint8_t *a, const uint8_t *b, int H, int W, int y0, int y1, int x0, int x1, int64_t *partial,
+                     int64_t *out, void *stream);
+int rn_running_frame(double *running, const uint8_t *frame, int64_t n, int first, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

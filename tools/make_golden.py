@@ -471,6 +471,14 @@ def gen_datareader():
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_datareader.py"), "--out", OUT])
 
 
+def gen_replay():
+    """tests/golden/replay.npz: the reference's own Data_Reader.plot_in over scripted cameras behind a recording cv2 stand-in.
+    Its own script (tools/make_golden_replay.py), in a child process, for the reason gen_datareader gives."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_replay.py"), "--out", OUT],
+                          stdout=subprocess.DEVNULL)
+
+
 def gen_tracker_run():
     """tests/golden/tracker_run.npz: the reference's own MC_Crop_Tracker.track() and write_results_csv() on the scene of
     tests/tracker_cases.py.  Its own script (tools/make_golden_tracker.py), in a child process: it patches module globals of
@@ -1646,7 +1654,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "tracker_run"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1691,6 +1699,8 @@ def main():
         gen_frames4k()
     if "datareader" in which:
         gen_datareader()
+    if "replay" in which:
+        gen_replay()
     if "tracker_run" in which:
         gen_tracker_run()
     for fn in sorted(os.listdir(OUT)):
