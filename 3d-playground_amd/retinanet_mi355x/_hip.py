@@ -104,6 +104,10 @@ SIGNATURES = {
     "rn_replay_compose": (c_i32, [c_vp, c_i32, c_vp, c_vp] + [c_i32] * 6 + [c_vp]),
     "rn_frame_absdiff": (c_i32, [c_vp, c_vp] + [c_i32] * 6 + [c_vp, c_vp, c_vp]),
     "rn_running_frame": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "rn_label_pair_samples": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rn_label_outliers": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rn_label_interpolate_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rn_label_interpolate": (c_i32, [c_vp] * 4 + [c_i64] * 3 + [c_i32, c_i64] + [c_vp] * 7),
 }
 
 class ConvDesc(ctypes.Structure):

@@ -1871,3 +1871,118 @@ def running_frame(running, frame, first=False):
         _hip.check(lib.rn_running_frame(running.data_ptr(), frame.data_ptr(), frame.numel(), int(bool(first)), _hip.stream()),
                    "rn_running_frame")
     return running
+
+
+# ------------------------------------------------------------------------------------------------ multi-camera label audit
+LABEL_POINTS = 5                   # RN_LABEL_POINTS
+LABEL_MAX_CAMS = 1024              # RN_LABEL_MAX_CAMS
+LABEL_GUARD, LABEL_FOUND_CUR, LABEL_FOUND_PREV = 1, 2, 4
+LABEL_BAD_OFFSETS, LABEL_BAD_FRAME, LABEL_BAD_PREFIX = 1, 2, 4
+_LABEL_BITS = ((LABEL_BAD_OFFSETS, "tracklet offsets out of order or outside the rows"),
+               (LABEL_BAD_FRAME, "a frame index outside the frames or not ascending along its tracklet"),
+               (LABEL_BAD_PREFIX, "more missing frames than output rows"))
+
+
+def label_status(device, status=None):
+    """The status word the three entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    _hip.need_gpu(status)
+    _mot_typed("label", ("status", status, torch.int32))
+    if status.numel() != 1:
+        raise RuntimeError("label: status is one int32")
+    return status
+
+
+def label_check(status):
+    """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
+    bits = int(status)
+    if bits:
+        raise RuntimeError("the label kernels refused their input: " + "; ".join(t for b, t in _LABEL_BITS if bits & b)
+                           + " (status %d)" % bits)
+
+
+def label_pair_index(cam, prev):
+    """The pair index of (cam, prev < cam) in ``label_pair_samples``' output."""
+    return cam * (cam - 1) // 2 + prev
+
+
+def _label_table(what, offsets, cols, frame=None):
+    _mot_typed(what, ("offsets", offsets, torch.int64), ("cols", cols, torch.float64))
+    if offsets.dim() != 1 or offsets.numel() < 1 or cols.dim() != 2 or cols.shape[1] != 3:
+        raise RuntimeError("%s: offsets is int64 [T+1], cols fp64 [R,3]" % what)
+    T, R = offsets.numel() - 1, cols.shape[0]
+    if frame is not None:
+        _mot_typed(what, ("frame", frame, torch.int32))
+        if tuple(frame.shape) != (R,):
+            raise RuntimeError("%s: frame is int32 [R]" % what)
+    if T >= 2 ** 31 or R >= 2 ** 31:
+        raise RuntimeError("%s: more than 2^31 tracklets or rows" % what)
+    return T, R
+
+
+def label_pair_samples(offsets, cols, n_cam, key_col, val0, val1=-1, status=None):
+    """seems_to_be_working.py:1889-1916 for every (camera pair, object): offsets int64 [n_ids * n_cam + 1] (tracklet = object *
+    n_cam + camera), cols fp64 [R,3] (x, y, timestamp); key_col / val0 / val1 pick the columns (val1 -1: none) -> (flags uint8
+    [P, n_ids, 5], values fp64 [P, n_ids, 5, 4] = (cam's val0, prev's val0, cam's val1, prev's val1), status); pair
+    ``label_pair_index(cam, prev)``, P = n_cam (n_cam - 1) / 2."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, cols)
+    T, R = _label_table("label_pair_samples", offsets, cols)
+    n_cam, key_col, val0, val1 = int(n_cam), int(key_col), int(val0), int(val1)
+    if not 1 <= n_cam <= LABEL_MAX_CAMS or T % n_cam or key_col not in (0, 1, 2) or val0 not in (0, 1, 2) or val1 not in (-1, 0, 1, 2):
+        raise RuntimeError("label_pair_samples: 1 <= n_cam <= %d divides the tracklet count, columns are 0..2 (val1 may be -1)"
+                           % LABEL_MAX_CAMS)
+    n_ids, P, dev = T // n_cam, n_cam * (n_cam - 1) // 2, cols.device
+    status = label_status(dev, status)
+    flags = torch.empty((P, n_ids, LABEL_POINTS), dtype=torch.uint8, device=dev)
+    values = torch.empty((P, n_ids, LABEL_POINTS, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_pair_samples(offsets.data_ptr(), _hip.ptr(cols), R, n_cam, n_ids, key_col, val0, val1,
+                                             _hip.ptr(flags), _hip.ptr(values), status.data_ptr(), _hip.stream()),
+                   "rn_label_pair_samples")
+    return flags, values, status
+
+
+def label_outliers(offsets, cols, frame, n_frames, n_visit, status=None):
+    """seems_to_be_working.py:2195-2231 along every tracklet: frame int32 [R] (ascending inside a tracklet), n_frames =
+    len(data), n_visit = the frames the walk reaches before its break -> (delete uint8 [R], status)."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, cols, frame)
+    T, R = _label_table("label_outliers", offsets, cols, frame)
+    F, n_visit, dev = int(n_frames), int(n_visit), cols.device
+    if not 0 <= F < 2 ** 31 or n_visit < 0:
+        raise RuntimeError("label_outliers: 0 <= n_frames < 2^31, n_visit >= 0")
+    status = label_status(dev, status)
+    delete = torch.empty(R, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_outliers(offsets.data_ptr(), _hip.ptr(cols), _hip.ptr(frame), T, R, F, n_visit, _hip.ptr(delete),
+                                         status.data_ptr(), _hip.stream()), "rn_label_outliers")
+    return delete, status
+
+
+def label_interpolate(offsets, cols, frame, all_ts, rows, status=None):
+    """seems_to_be_working.py:800-828 for every missing frame between two present frames of every tracklet: all_ts fp64 [F,
+    n_cam]; rows = the size of the output (the host knows it from the frame column) -> (out fp64 [rows,3] = (x, y, timestamp),
+    out_src int32 [rows] = the row before the gap, out_frame int32 [rows], total int64 [1], status), in tracklet order, frames
+    ascending."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, cols, frame, all_ts)
+    T, R = _label_table("label_interpolate", offsets, cols, frame)
+    _mot_typed("label_interpolate", ("all_ts", all_ts, torch.float64))
+    rows, dev = int(rows), cols.device
+    if all_ts.dim() != 2 or not 1 <= all_ts.shape[1] <= LABEL_MAX_CAMS or T % all_ts.shape[1] or all_ts.shape[0] >= 2 ** 31 \
+            or rows < 0:
+        raise RuntimeError("label_interpolate: all_ts is fp64 [F, n_cam], n_cam divides the tracklet count, rows >= 0")
+    F, n_cam = all_ts.shape
+    status = label_status(dev, status)
+    ws = torch.empty(max(16, lib.rn_label_interpolate_workspace_bytes(T, R)), dtype=torch.uint8, device=dev)
+    out = torch.empty((rows, 3), dtype=torch.float64, device=dev)
+    out_src = torch.empty(rows, dtype=torch.int32, device=dev)
+    out_frame = torch.empty(rows, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_interpolate(offsets.data_ptr(), _hip.ptr(cols), _hip.ptr(frame), _hip.ptr(all_ts), T, R, F, n_cam,
+                                            rows, ws.data_ptr(), _hip.ptr(out), _hip.ptr(out_src), _hip.ptr(out_frame),
+                                            total.data_ptr(), status.data_ptr(), _hip.stream()), "rn_label_interpolate")
+    return out, out_src, out_frame, total, status

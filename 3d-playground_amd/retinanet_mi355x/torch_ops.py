@@ -43,6 +43,10 @@ Operator                                         reference code it stands for
   render_compose                                 (own drawing rules, no cv2)           homography.py:670-714
   replay_boxes / replay_compose /                Data_Reader.plot_in, Camera_Wrapper,  datareader.py:24-89, 253-399
   frame_absdiff / running_frame                  test_integrity                        datareader.py:586-653
+  label_pair_samples(offsets, cols, n_cam, ..)   Annotator.estimate_ts_bias, est_y_error,   seems_to_be_working.py:1845-2036,
+                                                 estimate_projection_error (the samples)    2249-2357
+  label_outliers(offsets, cols, frame, F, visit) Annotator.remove_outliers             seems_to_be_working.py:2192-2233
+  label_interpolate(offsets, cols, frame, ts, n) Annotator.interpolate, every object   seems_to_be_working.py:780-836
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -595,3 +599,44 @@ def _(a, b, y0, y1, x0, x1):
 @_lib.custom_op(NS + "::running_frame", mutates_args=("running",), device_types="cuda")
 def running_frame(running: torch.Tensor, frame: torch.Tensor, first: bool) -> None:
     ops.running_frame(running, frame, first)
+
+
+# ---- multi-camera label audit (csrc/label_audit.hip): every op returns the status word last (ops.label_check raises on it)
+OPERATORS += ("label_pair_samples", "label_outliers", "label_interpolate")
+
+
+@_lib.custom_op(NS + "::label_pair_samples", mutates_args=(), device_types="cuda")
+def label_pair_samples(offsets: torch.Tensor, cols: torch.Tensor, n_cam: int, key_col: int, val0: int,
+                       val1: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_pair_samples(offsets, cols, n_cam, key_col, val0, val1)
+
+
+@label_pair_samples.register_fake
+def _(offsets, cols, n_cam, key_col, val0, val1):
+    P, n, e = n_cam * (n_cam - 1) // 2, (offsets.shape[0] - 1) // n_cam, cols.new_empty
+    return (e((P, n, ops.LABEL_POINTS), dtype=torch.uint8), e((P, n, ops.LABEL_POINTS, 4), dtype=torch.float64),
+            e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::label_outliers", mutates_args=(), device_types="cuda")
+def label_outliers(offsets: torch.Tensor, cols: torch.Tensor, frame: torch.Tensor, n_frames: int,
+                   n_visit: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.label_outliers(offsets, cols, frame, n_frames, n_visit)
+
+
+@label_outliers.register_fake
+def _(offsets, cols, frame, n_frames, n_visit):
+    return cols.new_empty((cols.shape[0],), dtype=torch.uint8), cols.new_empty((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::label_interpolate", mutates_args=(), device_types="cuda")
+def label_interpolate(offsets: torch.Tensor, cols: torch.Tensor, frame: torch.Tensor, all_ts: torch.Tensor,
+                      rows: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_interpolate(offsets, cols, frame, all_ts, rows)
+
+
+@label_interpolate.register_fake
+def _(offsets, cols, frame, all_ts, rows):
+    e = cols.new_empty
+    return (e((rows, 3), dtype=torch.float64), e((rows,), dtype=torch.int32), e((rows,), dtype=torch.int32),
+            e((1,), dtype=torch.int64), e((1,), dtype=torch.int32))

@@ -1174,6 +1174,46 @@ int rn_frame_absdiff(const uint8_t *a, const uint8_t *b, int H, int W, int y0, i
                      int64_t *out, void *stream);
 int rn_running_frame(double *running, const uint8_t *frame, int64_t n, int first, void *stream);
 
+/* ---- multi-camera label audit (csrc/label_audit.hip): the batch passes of the annotator, seems_to_be_working.py ----------
+ * Annotator.estimate_ts_bias (:1845-1947), est_y_error (:1950-2036), estimate_projection_error (:2249-2357), remove_outliers
+ * (:2192-2233), interpolate (:780-836).  The host packs the labels once into a CSR table of tracklets: tracklet t = object *
+ * n_cam + camera, offsets int64 [T+1], rows in ascending frame, cols fp64 [R,3] = (x, y, timestamp), frame int32 [R].  fp64 with
+ * one rounding per operation.  All three share one status word (int32, zeroed by the caller, bits OR-ed in): a bad index is
+ * never used, its item is left out.
+ *   rn_label_pair_samples  one wave per (camera pair, object), pair = cam * (cam - 1) / 2 + prev for prev < cam, entry = pair *
+ *                          n_ids + object.  Key column key_col, value columns val0 and val1 (-1: none).  Both tracklets longer
+ *                          than one row and max(prev's key) > min(cam's key) (:1889), else the entry's flags are 0.  lo = max of the
+ *                          minima, hi = min of the maxima, points lo + ((hi - lo) / 4) * i, i < RN_LABEL_POINTS (:1892-1901); for
+ *                          each point and tracklet the LAST i with (K[i] - pt) * (K[i-1] - pt) <= 0 (:1907-1910), ratio = (pt -
+ *                          K[i-1]) / (K[i] - K[i-1] + 1e-08), value = V[i-1] + (V[i] - V[i-1]) * ratio.  flags uint8 [entries,
+ *                          RN_LABEL_POINTS] (RN_LABEL_GUARD | RN_LABEL_FOUND_CUR | RN_LABEL_FOUND_PREV), values fp64 [entries,
+ *                          RN_LABEL_POINTS, 4] = (cam's val0, prev's val0, cam's val1, prev's val1), 0.0 where nothing was found.
+ *   rn_label_outliers      one lane per tracklet, serial over its rows (:2195-2231): a row of frame f < n_visit is deleted when
+ *                          its key exists in frame f - 1 (frame 0: in the LAST frame, F - 1) and was not itself deleted, and |x -
+ *                          x'| > 15 or y - y' > 5 (one-sided, as written); else when the same holds against frame f + 1.  del
+ *                          uint8 [R]; n_visit = the frames the reference's walk reaches before its break (:2197-2198).
+ *   rn_label_interpolate   every missing frame between two present frames of a tracklet (:800-828): total int64 [1] = their
+ *                          number; row u, in tracklet order and frame ascending: t1, t2, ti from all_ts fp64 [F, n_cam] at the
+ *                          tracklet's camera, p1 = (t2 - ti) / (t2 - t1), p2 = 1.0 - p1, out fp64 [U,3] = (p1 x' + p2 x, the same
+ *                          for y, ti), out_src int32 [U] = the row BEFORE the gap (-1: left out), out_frame int32 [U].  U = the
+ *                          caller's row count; total > U sets RN_LABEL_BAD_PREFIX and the rows beyond U are left out. */
+#define RN_LABEL_POINTS 5
+#define RN_LABEL_MAX_CAMS 1024
+#define RN_LABEL_GUARD 1              /* flags: the overlap guard passed */
+#define RN_LABEL_FOUND_CUR 2          /* a segment of the camera's tracklet brackets the point */
+#define RN_LABEL_FOUND_PREV 4         /* ... of the partner's */
+#define RN_LABEL_BAD_OFFSETS 1        /* status: tracklet offsets not monotone or outside the R rows */
+#define RN_LABEL_BAD_FRAME 2          /* a frame index outside the F frames or not ascending along its tracklet */
+#define RN_LABEL_BAD_PREFIX 4         /* more missing frames than the U output rows */
+int rn_label_pair_samples(const int64_t *offsets, const double *cols, int64_t R, int n_cam, int64_t n_ids, int key_col, int val0,
+                          int val1, uint8_t *flags, double *values, int32_t *status, void *stream);
+int rn_label_outliers(const int64_t *offsets, const double *cols, const int32_t *frame, int64_t T, int64_t R, int64_t F,
+                      int64_t n_visit, uint8_t *del, int32_t *status, void *stream);
+int64_t rn_label_interpolate_workspace_bytes(int64_t T, int64_t R);
+int rn_label_interpolate(const int64_t *offsets, const double *cols, const int32_t *frame, const double *all_ts, int64_t T,
+                         int64_t R, int64_t F, int n_cam, int64_t U, void *workspace, double *out, int32_t *out_src,
+                         int32_t *out_frame, int64_t *total, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -471,6 +471,15 @@ def gen_datareader():
     subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_datareader.py"), "--out", OUT])
 
 
+def gen_label_audit():
+    """tests/golden/label_audit.npz: the batch passes of the reference's annotator (seems_to_be_working.py) on the scenes of
+    tests/label_audit_cases.py.  Its own script (tools/make_golden_labels.py), in a child process, for the reason
+    gen_datareader gives: the annotator imports the reference's homography, datareader and retinanet under their own names."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_labels.py"), "--out", OUT],
+                          stdout=subprocess.DEVNULL)
+
+
 def gen_replay():
     """tests/golden/replay.npz: the reference's own Data_Reader.plot_in over scripted cameras behind a recording cv2 stand-in.
     Its own script (tools/make_golden_replay.py), in a child process, for the reason gen_datareader gives."""
@@ -1654,7 +1663,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1703,6 +1712,8 @@ def main():
         gen_replay()
     if "tracker_run" in which:
         gen_tracker_run()
+    if "label_audit" in which:
+        gen_label_audit()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
