@@ -447,7 +447,22 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 2 : (TERMS == 2 ? RN_MF16H_OCC :
                                                               const float *__restrict__ scale, const float *__restrict__ shift,
                                                               const float *__restrict__ add, const float *__restrict__ mask,
                                                               const float *__restrict__ add2) {
-    conv_mf16_tile<GENERAL, RAW, TERMS, STG, WV>(d, x, w, y, scale, shift, add, mask, add2, xcd_remap(blockIdx.x, gridDim.x));
+    const int tile = xcd_remap(blockIdx.x, gridDim.x);
+    if constexpr (RAW) {
+        // rn_conv_desc.row_active (the Winograd stage of a sparse gradient): a workgroup none of whose rows is active leaves before its
+        // first load.  (Ho*Wo is a multiple of 256 there: a tile's rows lie in one image, its flags in whole 16-byte units.)
+        if (d.row_active != nullptr && d.w_batch_stride != 0) {
+            constexpr int BM = 32 * WV;
+            const int m0 = (tile / ((d.Cout + 127) / 128)) * BM;
+            int nz = 0;
+            if (threadIdx.x < BM / 16) {
+                const uint4 u = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned char *>(d.row_active) + m0 % (d.Ho * d.Wo))[threadIdx.x];
+                nz = (u.x | u.y | u.z | u.w) != 0u;
+            }
+            if (!__syncthreads_or(nz)) return;
+        }
+    }
+    conv_mf16_tile<GENERAL, RAW, TERMS, STG, WV>(d, x, w, y, scale, shift, add, mask, add2, tile);
 }
 
 template <int TERMS>
@@ -493,6 +508,8 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
     if (!mf16_ok(d) || (variant != 0 && variant != 4 && variant != 5)) return false;
     const int64_t tiles = mf16_tiles(d);
     if (tiles < mf16_min_tiles() || tiles > 0x7fffffff) return false;
+    if (variant == 0 && d->row_active != nullptr && d->w_batch_stride != 0 &&
+        (((uintptr_t)d->row_active & 15) || ((int64_t)d->Ho * d->Wo) % 256 != 0)) { *rc = RN_EINVAL; return true; }
     const dim3 grid((unsigned)tiles), block(256);
 #define RN_MF16_LAUNCH(G, R, T, S) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, T, S>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
     if (d->w_format == 3) {

@@ -79,6 +79,8 @@ struct WgradArgs {
     // operand takes ONE power-of-two scale: that of the largest exponent in any of its tables.
     const void *dy_amax, *x_amax;
     int dy_amax_n, x_amax_n;
+    // Sparse dy (rn_conv_wgrad_batched_flags): one byte per pixel row, 0 = the row of dy is zero in every batch entry; NULL: dense.
+    const unsigned char *k_active;
 };
 
 // scale / inverse scale of an operand (all 64 lanes of the wave active; the result is wave-uniform)
@@ -372,7 +374,11 @@ __device__ __forceinline__ bf16x8 wgs_operand(const char *img, unsigned a0, unsi
 // HALF: the fp16 two-term form (RN_FP32_SPLIT3): two planes per operand (a buffer = dY hi, lo, X hi, lo: 16 KB instead of 24), the
 // operands scaled by their tensors' powers of two inside the split, three v_mfma_f32_32x32x16_f16 per block, the tile multiplied by the
 // two inverse scales before its atomics.
-template <bool RELU, bool HALF = false>
+// SKIP (p.k_active; a flat 1x1 problem: N = Hi = Ho = 1, stride 1, no padding): the slice first lists, in order, its K-steps with an active
+// row -- in the pixel table's memory, which this form does not need: the offset of a pixel of x is its index times Cin -- and the same
+// two-ahead pipeline runs over that list.  Steps left out added exact zeros, so the sums are the dense kernel's.
+#define RN_WG_SKIP_MAX 2040
+template <bool RELU, bool HALF = false, bool SKIP = false>
 __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs p) {
     using G = WgradSplitGeom;
     constexpr int BM = 128, BN = 128, WK = G::WK, TB = G::TB;
@@ -440,10 +446,54 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
         }
         pixtab[j & 1][tid] = e;
     };
+    // SKIP: the list of active K-steps (nks <= RN_WG_SKIP_MAX entries; the four words after them: the waves' counts of a round)
+    unsigned short *klist = reinterpret_cast<unsigned short *>(&pixtab[0][0]);
+    int *wcnt = reinterpret_cast<int *>(klist + RN_WG_SKIP_MAX);
+    int nact = nks;
+    if constexpr (SKIP) {
+        static_assert(RN_WG_SKIP_MAX * 2 + 16 <= (int)sizeof(pixtab), "the list fits the pixel table");
+        nact = 0;
+        for (int k0 = 0; k0 < nks; k0 += 256) {
+            const int ks = k0 + tid;
+            bool on = false;
+            if (ks < nks) {
+                const uint4 u = *reinterpret_cast<const uint4 *>(p.k_active + kbeg + (int64_t)ks * WK);
+                on = (u.x | u.y | u.z | u.w) != 0u;
+            }
+            const unsigned long long b = __ballot(on);
+            if (lane == 0) wcnt[wave] = __popcll(b);
+            __syncthreads();
+            int before = nact, all = 0;
+#pragma unroll
+            for (int w_ = 0; w_ < 4; ++w_) { const int c_ = wcnt[w_]; all += c_; before += w_ < wave ? c_ : 0; }
+            if (on) klist[before + __popcll(b & ((1ull << lane) - 1ull))] = (unsigned short)ks;
+            nact += all;
+            __syncthreads();
+        }
+        if (nact == 0 && p.slab == nullptr) return;          // nothing to add (the fixed-order form still stores its zero slab)
+    }
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     struct Regs { f32x4v a[2], b[2]; };
     // loads of K-step ks (all four; offsets of the X half from the pixel table, the dY half from a scalar advance)
     auto load_step = [&](int ks, Regs &r) {
+        if constexpr (SKIP) {                                // ks: an index into the list
+            if (ks >= nact) {                                // past the list: zeros (what the dense form's loads past the slice give)
+                r.a[0] = r.a[1] = r.b[0] = r.b[1] = f32x4v{0.f, 0.f, 0.f, 0.f};
+                return;
+            }
+            const int kq = klist[ks];
+            const unsigned so = (unsigned)kq * (unsigned)(WK * 4) * (unsigned)p.ldy;
+            r.a[0] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)a_voff, (int)so, 0));
+            r.a[1] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)a_voff, (int)(so + a_half), 0));
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int64_t px = kbeg + (int64_t)kq * WK + G::pixel(tid, h);       // n_first = 0: the pixel's index is its offset in x
+                const bool ok = px < kend && jcol < p.Kflat;
+                const unsigned v = ok ? (unsigned)((int)px * p.Cin * 4 + tap_off) : 0x80000000u;
+                r.b[h] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_b, (int)v, 0, 0));
+            }
+            return;
+        }
         const int2 *tab = pixtab[(ks / TB) & 1];
         const unsigned so = (unsigned)ks * (unsigned)(WK * 4) * (unsigned)p.ldy;
         r.a[0] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_a, (int)a_voff, (int)so, 0));
@@ -523,8 +573,10 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
 #pragma unroll
             for (int e_ = 0; e_ < 16; ++e_) acc[i][j][e_] = 0.f;
 
-    fill_batch(0);
-    __syncthreads();
+    if constexpr (!SKIP) {
+        fill_batch(0);
+        __syncthreads();
+    }
     Regs r0, r1;
     load_step(0, r0);
     split_store(0, r0);
@@ -569,12 +621,14 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
         }
         // table batch b is first read for step b * TB (loaded in iteration b * TB - 2); its slot held batch b - 2, last read in
         // iteration (b - 1) * TB - 3: fill it in iteration (b - 1) * TB + 4
-        if ((ks % TB) == 4 && (ks / TB + 1) * TB < nks + 2) fill_batch(ks / TB + 1);
+        if constexpr (!SKIP) {
+            if ((ks % TB) == 4 && (ks / TB + 1) * TB < nks + 2) fill_batch(ks / TB + 1);
+        }
         __syncthreads();
     };
-    for (int ks = 0; ks < nks; ks += 2) {
+    for (int ks = 0; ks < nact; ks += 2) {                   // (nact = nks unless SKIP)
         k_step(ks, 0, r0, r1);
-        if (ks + 1 < nks) k_step(ks + 1, 1, r1, r0);
+        if (ks + 1 < nact) k_step(ks + 1, 1, r1, r0);
     }
     if (do_cs) {                                             // 8 threads hold partial sums of the same 4 channels: through LDS
         float (*csred)[BM] = reinterpret_cast<float (*)[BM]>(&lds[0][0]);     // (the planes are done with: the loop ended in a barrier)
@@ -637,7 +691,8 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
                         int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
                         int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                         int in_relu, void *stream, bool det, void *workspace, int64_t workspace_bytes, int64_t *need_bytes,
-                        const void *dy_amax = nullptr, int dy_amax_n = 0, const void *x_amax = nullptr, int x_amax_n = 0);
+                        const void *dy_amax = nullptr, int dy_amax_n = 0, const void *x_amax = nullptr, int x_amax_n = 0,
+                        const void *k_active = nullptr);
 
 extern "C" int rn_conv_wgrad_batched(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
                                      int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
@@ -658,6 +713,19 @@ extern "C" int rn_conv_wgrad_batched_det(const float *dy, int ldy, const float *
                         kh, kw, stride, pad, in_relu, stream, true, workspace, workspace_bytes, nullptr, dy_amax, dy_amax_n, x_amax, x_amax_n);
 }
 
+// Sparse dy: the K-steps without an active row are skipped (include/retinanet_mi355x.h); workspace NULL = atomics, else the fixed-order form.
+extern "C" int rn_conv_wgrad_batched_flags(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
+                                           int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
+                                           int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
+                                           int in_relu, const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n,
+                                           const void *k_active, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (k_active == nullptr || ((uintptr_t)k_active & 15)) return RN_EINVAL;
+    if (N != 1 || Hi != 1 || Ho != 1 || Wi != Wo || kh != 1 || kw != 1 || stride != 1 || pad != 0 || in_relu) return RN_EINVAL;
+    return wgrad_launch(dy, ldy, x, dw, colsum, nbatch, dy_bstride, x_bstride, dw_bstride, colsum_batch, N, Hi, Wi, Cin, Ho, Wo, Cout,
+                        kh, kw, stride, pad, in_relu, stream, workspace != nullptr, workspace, workspace_bytes, nullptr, dy_amax, dy_amax_n,
+                        x_amax, x_amax_n, k_active);
+}
+
 // Bytes of workspace rn_conv_wgrad_batched_det needs for this problem (slices x (result image + Cout column sums)).
 extern "C" int64_t rn_conv_wgrad_det_workspace_bytes(int ldy, int nbatch, int64_t dw_bstride, int N, int Hi, int Wi, int Cin, int Ho,
                                                      int Wo, int Cout, int kh, int kw) {
@@ -671,7 +739,7 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
                         int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
                         int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                         int in_relu, void *stream, bool det, void *workspace, int64_t workspace_bytes, int64_t *need_bytes,
-                        const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n) {
+                        const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, const void *k_active) {
     if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin < 4 || (Cin & 3) || (ldy & 3) || ldy < Cout)
         return RN_EINVAL;
     if (nbatch < 1 || nbatch > 4096 || dy_bstride < 0 || x_bstride < 0 || dw_bstride < 0 || colsum_batch < 0 || colsum_batch >= nbatch)
@@ -738,6 +806,7 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
     a.x_amax = x_amax;
     a.dy_amax_n = dy_amax_n;
     a.x_amax_n = x_amax_n;
+    a.k_active = reinterpret_cast<const unsigned char *>(k_active);
 #define RN_WGRAD_LAUNCH(WM_, WN_)                                                                                        \
     do {                                                                                                                 \
         if (half) {                                                                                                      \
@@ -751,7 +820,11 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
     } while (0)
     // RN_OPT_WGRAD_ONCE = 0: the per-wave split for the 128 x 128 tile too (A/B)
     const bool once = split && shape == 2 && rn_get_option(RN_OPT_WGRAD_ONCE) != 0 && Hi + pad < 32000 && Wi + pad < 32000;
-    if (once && half) {
+    if (k_active != nullptr) {                               // only the once-split kernel lists and skips; no quiet dense run
+        if (!once || in_relu || (a.per_split + 15) / 16 > RN_WG_SKIP_MAX) return RN_EINVAL;
+        if (half) hipLaunchKernelGGL((conv_wgrad_once_kernel<false, true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((conv_wgrad_once_kernel<false, false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else if (once && half) {
         if (in_relu) hipLaunchKernelGGL((conv_wgrad_once_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
         else hipLaunchKernelGGL((conv_wgrad_once_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     } else if (once) {

@@ -165,10 +165,15 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const WinoTable g, float *
 
 // ---------------------------------------------------------------------------------------------- output transform
 // mask_mode / add / act as in rn_conv_desc (mask and add have the geometry of y, dense [N,H,W,Cout]).
-template <bool PBITS, bool PADD>
+// FLAGS (tile activity flags): a tile whose flag in `fin` is 0 has M = 0 exactly -- it reads no M and runs the epilogue on
+// zeros; `fout` receives the flags of the STORED tensor for the next layer's transforms: a non-zero pixel sets its own tile and the
+// neighbours whose 6x6 patch contains it (plain byte stores of 1).  Either pointer may be NULL.
+template <bool PBITS, bool PADD, bool FLAGS = false>
 __global__ __launch_bounds__(256, 2) void wino_out_kernel(const WinoTable g, const float *__restrict__ M, int Cout, int64_t t0,
                                                        int64_t Tpad, const float *__restrict__ scale,
-                                                       const float *__restrict__ shift, int mask_mode, int act, int64_t y_bs) {
+                                                       const float *__restrict__ shift, int mask_mode, int act, int64_t y_bs,
+                                                       const unsigned char *__restrict__ fin = nullptr,
+                                                       unsigned char *__restrict__ fout = nullptr) {
     const int cq = Cout >> 2;
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t gt = id / cq;
@@ -197,15 +202,25 @@ __global__ __launch_bounds__(256, 2) void wino_out_kernel(const WinoTable g, con
     const int th = r / TW, tw = r - th * TW;
     const float *mb = M + (t0 + gt) * Cout + c4;
     float4 t[4][6];                                           // t[i][j] = (A^T m)[i][j]
+    bool active = true;                                       // (the same for every thread of a tile)
+    if constexpr (FLAGS) active = fin == nullptr || fin[t0 + gt] != 0;
+    if (active) {
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float4 m[6], o[4];
+        for (int j = 0; j < 6; ++j) {
+            float4 m[6], o[4];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) m[i] = ld_stream(mb + (int64_t)(i * 6 + j) * Tpad * Cout);
-        at6(m, o);
+            for (int i = 0; i < 6; ++i) m[i] = ld_stream(mb + (int64_t)(i * 6 + j) * Tpad * Cout);
+            at6(m, o);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) t[i][j] = o[i];
+            for (int i = 0; i < 4; ++i) t[i][j] = o[i];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t[i][j] = f4(0.f);
     }
+    unsigned wake = 0u;                                       // FLAGS: bit 3 (di + 1) + (dj + 1): tile (th + di, tw + dj) sees a non-zero pixel
     float4 sc = f4(1.f), sh = f4(0.f);
     if (scale) sc = *reinterpret_cast<const float4 *>(scale + c4);
     if (shift) sh = *reinterpret_cast<const float4 *>(shift + c4);
@@ -259,6 +274,27 @@ __global__ __launch_bounds__(256, 2) void wino_out_kernel(const WinoTable g, con
             *reinterpret_cast<float4 *>(y + yoff) = make_float4(v[0], v[1], v[2], v[3]);
             if (sign != nullptr) rn_sign_store(sign, off, v[0], v[1], v[2], v[3]);      // (dense geometry: the 8 lanes of a word share the pixel)
             am = fmaxf(fmaxf(am, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+            if constexpr (FLAGS) {
+                if (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f) {
+                    const unsigned rows = 2u | (i == 0 ? 1u : 0u) | (i == 3 ? 4u : 0u);      // bit di + 1
+                    const unsigned cols = 2u | (j == 0 ? 1u : 0u) | (j == 3 ? 4u : 0u);      // bit dj + 1
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+                        if (rows & (1u << a)) wake |= cols << (3 * a);
+                }
+            }
+        }
+    }
+    if constexpr (FLAGS) {
+        if (fout != nullptr && wake != 0u) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) {
+                    const int th2 = th + a - 1, tw2 = tw + b - 1;
+                    if ((wake & (1u << (3 * a + b))) && (unsigned)th2 < (unsigned)pr.TH && (unsigned)tw2 < (unsigned)TW)
+                        fout[t0 + gt + (int64_t)(a - 1) * TW + (b - 1)] = 1;
+                }
         }
     }
     } while (0);
@@ -370,9 +406,14 @@ __global__ __launch_bounds__(256) void wino_dy_kernel(const WinoTable g, float *
 // Both transforms of an output gradient in ONE pass over it: V = B^T dy B (the data gradient's input transform: 6x6 patches with
 // their halo) and Z = A dy A^T (the weight gradient's: the patch's inner 4x4).  The backward of a Winograd layer needs both and
 // read dy twice; the patch a thread has loaded for V holds the pixels of Z.
+// FLAGS (tile activity flags; one byte per row of V / Z, 16-byte aligned): a tile with flag 0 has an all-zero patch, so
+// V = Z = 0 exactly: it loads nothing and writes no V (the GEMM's rows of such a tile are never read).  Its rows of Z are written -- as
+// zeros -- only where the reduction may read them: it skips whole aligned units of 16 rows, so a unit with any active tile is complete.
+template <bool FLAGS = false>
 __global__ __launch_bounds__(256) void wino_in_both_kernel(const WinoTable g, float *__restrict__ V, float *__restrict__ Z, int C,
                                                            int64_t t0, int64_t Tpad, unsigned *__restrict__ v_row_amax,
-                                                           unsigned *__restrict__ z_tensor_amax) {
+                                                           unsigned *__restrict__ z_tensor_amax,
+                                                           const unsigned char *__restrict__ flags = nullptr) {
     wino_tensor_word(g, z_tensor_amax, WINO_GAIN_A);
     const int cq = C >> 2;
     const int64_t id = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
@@ -395,6 +436,18 @@ __global__ __launch_bounds__(256) void wino_in_both_kernel(const WinoTable g, fl
         if (gt_raw < t_last && c4 == 0) v_row_amax[t0 + gt] = rn_amax_word_of_exp(e_img, WINO_GAIN_BT);
     }
     if (gt_raw >= t_last) return;
+    if constexpr (FLAGS) {
+        const int64_t row = t0 + gt;
+        if (flags[row] == 0) {
+            const uint4 u = *reinterpret_cast<const uint4 *>(flags + (row & ~(int64_t)15));
+            if ((u.x | u.y | u.z | u.w) != 0u) {
+                float *zb0 = Z + row * C + c4;
+#pragma unroll
+                for (int p = 0; p < 36; ++p) st_stream(zb0 + (int64_t)p * Tpad * C, f4(0.f));
+            }
+            return;
+        }
+    }
     float4 t[6][6];                                           // t[i][j] = (B^T d)[i][j]
     float4 tz[6][4];                                          // tz[a][j] = (A dy)[a][j], dy = the patch's rows / columns 1..4
 #pragma unroll
@@ -499,23 +552,35 @@ extern "C" int rn_wino_input_group(const rn_wino_group *g, float *V, int C, int6
     return RN_OK;
 }
 
-extern "C" int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
-                                        void *v_row_amax, void *z_tensor_amax, void *stream) {
+extern "C" int rn_wino_input_both_group_flags(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                              void *v_row_amax, void *z_tensor_amax, const void *flags, void *stream) {
     WinoTable t;
     const int rc = wino_table(g, t);
     if (rc) return rc;
     if (!V || !Z || C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
+    if (flags != nullptr && (((uintptr_t)flags & 15) || (Tpad & 15))) return RN_EINVAL;      // whole 16-byte units of flags
     for (int i = 0; i < t.n; ++i)
         if (!t.src[i]) return RN_EINVAL;
-    hipLaunchKernelGGL(wino_in_both_kernel, dim3(rn_blocks(t.tile_end[t.n - 1] * (C >> 2), 256)), dim3(256), 0, (hipStream_t)stream, t,
-                       V, Z, C, tile_offset, Tpad, reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax));
+    const dim3 grid(rn_blocks(t.tile_end[t.n - 1] * (C >> 2), 256));
+    if (flags != nullptr)
+        hipLaunchKernelGGL(wino_in_both_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad,
+                           reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax),
+                           reinterpret_cast<const unsigned char *>(flags));
+    else
+        hipLaunchKernelGGL(wino_in_both_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad,
+                           reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax),
+                           (const unsigned char *)nullptr);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
+extern "C" int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                        void *v_row_amax, void *z_tensor_amax, void *stream) {
+    return rn_wino_input_both_group_flags(g, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, nullptr, stream);
+}
 
-extern "C" int rn_wino_output_group(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
-                                    const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
-                                    void *stream) {
+extern "C" int rn_wino_output_group_flags(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
+                                          const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
+                                          const void *flags_in, void *flags_out, void *stream) {
     WinoTable t;
     const int rc = wino_table(g, t);
     if (rc) return rc;
@@ -532,15 +597,27 @@ extern "C" int rn_wino_output_group(const rn_wino_group *g, const float *M, int 
     bool padd = true;
     for (int i = 0; i < t.n; ++i) padd = padd && t.add[i] != nullptr;
     const dim3 grid(rn_blocks(t.tile_end[t.n - 1] * (Cout >> 2), 256));
-#define RN_WINO_OUT(B, A) hipLaunchKernelGGL((wino_out_kernel<B, A>), grid, dim3(256), 0, (hipStream_t)stream, t, M, Cout, tile_offset, Tpad, \
-                                             scale, shift, mask_mode, act, y_batch_stride)
-    if (pbits && padd) RN_WINO_OUT(true, true);
-    else if (pbits) RN_WINO_OUT(true, false);
-    else if (padd) RN_WINO_OUT(false, true);
-    else RN_WINO_OUT(false, false);
+    const unsigned char *fin = reinterpret_cast<const unsigned char *>(flags_in);
+    unsigned char *fout = reinterpret_cast<unsigned char *>(flags_out);
+#define RN_WINO_OUT(B, A, F) hipLaunchKernelGGL((wino_out_kernel<B, A, F>), grid, dim3(256), 0, (hipStream_t)stream, t, M, Cout, tile_offset, Tpad, \
+                                                scale, shift, mask_mode, act, y_batch_stride, fin, fout)
+    if (fin != nullptr || fout != nullptr) {
+        if (pbits && padd) RN_WINO_OUT(true, true, true);
+        else if (pbits) RN_WINO_OUT(true, false, true);
+        else if (padd) RN_WINO_OUT(false, true, true);
+        else RN_WINO_OUT(false, false, true);
+    } else if (pbits && padd) RN_WINO_OUT(true, true, false);
+    else if (pbits) RN_WINO_OUT(true, false, false);
+    else if (padd) RN_WINO_OUT(false, true, false);
+    else RN_WINO_OUT(false, false, false);
 #undef RN_WINO_OUT
     RN_LAUNCH_CHECK();
     return RN_OK;
+}
+extern "C" int rn_wino_output_group(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
+                                    const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
+                                    void *stream) {
+    return rn_wino_output_group_flags(g, M, Cout, tile_offset, Tpad, scale, shift, mask_mode, act, y_batch_stride, nullptr, nullptr, stream);
 }
 
 // Single-problem forms.

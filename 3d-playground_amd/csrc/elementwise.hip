@@ -484,6 +484,52 @@ extern "C" int rn_sigmoid_bwd_pad(const float *dy, const float *s, float *out, i
     return RN_OK;
 }
 
+// rn_sigmoid_bwd_pad over [B, H, W, ld] images that also writes the TILE ACTIVITY FLAGS of its result: one byte per 4x4
+// tile, in the tile order of the Winograd transforms (image, tile row, tile column); a non-zero value sets its own tile and the
+// neighbours whose 6x6 patch (the tile plus a one-pixel halo) contains its pixel.  The caller zeroes the flags; plain stores of 1.
+__global__ void sigmoid_bwd_pad_flags_kernel(const float *__restrict__ dy, const float *__restrict__ s, float *__restrict__ out,
+                                             int64_t rows, int H, int W, int C, int ld, int64_t bstride, unsigned *__restrict__ amax,
+                                             unsigned char *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * ld) return;
+    const int64_t rpi = (int64_t)H * W;
+    const int64_t r = i / ld;
+    const int c = (int)(i - r * ld);
+    const int64_t b = r / rpi;
+    const int pix = (int)(r - b * rpi);
+    float v = 0.f;
+    if (c < C) {
+        const int64_t src = b * bstride + (int64_t)pix * C + c;
+        v = dy[src];
+        if (s) { const float p = s[src]; v *= p * (1.0f - p); }
+    }
+    out[i] = v;
+    rn_amax_note(amax, b, fabsf(v));
+    if (v != 0.f) {
+        const int h = pix / W, w = pix - h * W;
+        const int TH = (H + 3) >> 2, TW = (W + 3) >> 2;
+        const int th = h >> 2, tw = w >> 2, hi = h & 3, wi = w & 3;
+        unsigned char *f = flags + (b * TH + th) * TW + tw;
+#pragma unroll
+        for (int a = -1; a <= 1; ++a)
+#pragma unroll
+            for (int e = -1; e <= 1; ++e) {
+                const bool rows_ok = a == 0 || (a < 0 ? hi == 0 && th > 0 : hi == 3 && th + 1 < TH);
+                const bool cols_ok = e == 0 || (e < 0 ? wi == 0 && tw > 0 : wi == 3 && tw + 1 < TW);
+                if (rows_ok && cols_ok) f[a * TW + e] = 1;
+            }
+    }
+}
+extern "C" int rn_sigmoid_bwd_pad_flags(const float *dy, const float *s, float *out, int B, int H, int W, int C, int ld,
+                                        int64_t src_batch_stride, void *amax, void *flags, void *stream) {
+    const int64_t rows = (int64_t)B * H * W;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || ld < C || flags == nullptr || (int64_t)H * W > 0x7fffffff) return RN_EINVAL;
+    hipLaunchKernelGGL(sigmoid_bwd_pad_flags_kernel, dim3(rn_blocks(rows * ld, 256)), dim3(256), 0, (hipStream_t)stream, dy, s, out,
+                       rows, H, W, C, ld, src_batch_stride, reinterpret_cast<unsigned *>(amax), reinterpret_cast<unsigned char *>(flags));
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
 __global__ void add_inplace_kernel(float *__restrict__ dst, const float *__restrict__ src, int64_t n, int64_t per_image, unsigned *__restrict__ amax) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;

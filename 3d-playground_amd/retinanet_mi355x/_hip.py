@@ -122,7 +122,8 @@ class ConvDesc(ctypes.Structure):
                 ("add2_mode", c_i32), ("Ha2", c_i32), ("Wa2", c_i32), ("add2_batch_stride", c_i64),
                 ("x_batch_stride", c_i64), ("y_batch_stride", c_i64), ("add_batch_stride", c_i64),
                 ("w_batch_stride", c_i64), ("w_format", c_i32), ("sign_out", c_vp),
-                ("x_amax", c_vp), ("y_amax", c_vp), ("w_unscale", c_vp), ("x_amax_img_stride", c_i32), ("x_amax_row_stride", c_i32)]
+                ("x_amax", c_vp), ("y_amax", c_vp), ("w_unscale", c_vp), ("x_amax_img_stride", c_i32), ("x_amax_row_stride", c_i32),
+                ("row_active", c_vp)]
 
 
 RN_MAX_GROUP = 5
@@ -162,6 +163,8 @@ SIGNATURES.update({
     "rn_prep_batched": (c_i32, [c_vp, c_vp, c_i32, c_vp]),
     "rn_wino_input_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rn_wino_input_both_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rn_wino_input_both_group_flags": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rn_wino_output_group_flags": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rn_wino_output_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),
     "rn_conv_igemm_grouped": (c_i32, [ctypes.POINTER(ConvGroup), c_vp, c_vp, c_vp, c_vp]),
     "rn_conv_igemm": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -180,6 +183,7 @@ SIGNATURES.update({
     "rn_upsample_add_bwd": (c_i32, [c_vp, c_vp] + [c_i32] * 6 + [c_vp, c_vp]),
     "rn_relu_mask": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "rn_sigmoid_bwd_pad": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp]),
+    "rn_sigmoid_bwd_pad_flags": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rn_add_inplace": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rn_wino_input": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp]),
     "rn_wino_output": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),
@@ -188,6 +192,7 @@ SIGNATURES.update({
     "rn_wino_dw": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp]),
     "rn_conv_wgrad_batched": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32] + [c_i32] * 12 + [c_vp, c_i32, c_vp, c_i32, c_vp]),
     "rn_conv_wgrad_batched_det": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32] + [c_i32] * 12 + [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "rn_conv_wgrad_batched_flags": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32] + [c_i32] * 12 + [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "rn_conv_wgrad_det_workspace_bytes": (c_i64, [c_i32, c_i32, c_i64] + [c_i32] * 9),
     "rn_f32_to_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "rn_bf16_to_f32": (c_i32, [c_vp, c_vp, c_i64, c_vp]),

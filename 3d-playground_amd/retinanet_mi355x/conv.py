@@ -81,7 +81,7 @@ def _mask_operand(mask, mask_mode):
 def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=0, add_hw=(0, 0), mask=None,
                mask_mode=2, act=ACT_NONE, y_batch_stride=None, add_batch_stride=None, in_relu=False, flops=0.0,
                out_map=None, add2=None, w_batch_stride=0, kind=None, sign=False, bf16_products=False, x_amax=None, x_amax_rows=False,
-               amax=None):
+               amax=None, row_active=None):
     """Launch rn_conv_igemm.  x [N,Hi,Wi,Cin]; y a tensor whose storage receives [N,Ho,Wo,Cout] at batch stride
     y_batch_stride; geom = (Ho, Wo, Cout, kh, kw, a, b, p, div_shift) with p an int or (p_rows, p_cols).
     out_map = (os, oo_h, oo_w, Hy, Wy) stores output pixel (oh,ow) at (oh*os+oo_h, ow*os+oo_w) of a [N,Hy,Wy,Cout]
@@ -103,6 +103,8 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
                  mask_mode, int(in_relu), os_, oo_h, oo_w, Hy, Wy,
                  a2[0], a2[1], a2[2], a2[3], Hi * Wi * Cin, ybs, add_batch_stride, w_batch_stride)
     amax_drop(y)                                         # a reused destination: the words of what it held before are stale
+    if row_active is not None:                           # tile flags of the Winograd stage (rn_conv_desc.row_active)
+        d.row_active = row_active.data_ptr()
     bits = _sign_words(y, sign and y_batch_stride is None and out_map is None)
     d.sign_out = None if bits is None else bits.data_ptr()
     yam = None
@@ -362,11 +364,22 @@ def set_deterministic(on=True):
     set_option(OPT_DETERMINISTIC, on)
 
 
-def _wgrad_call(lib, dev, dy_ptr, ldy, x_ptr, dw_ptr, cs_ptr, nbatch, dy_bs, x_bs, dw_bs, cs_batch, geom, amax=(None, None)):
+def _wgrad_call(lib, dev, dy_ptr, ldy, x_ptr, dw_ptr, cs_ptr, nbatch, dy_bs, x_bs, dw_bs, cs_batch, geom, amax=(None, None), flags=None):
     """rn_conv_wgrad_batched, or its fixed-order form with a slab workspace when the deterministic option is on.
-    geom = (N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, in_relu); amax = the amax words of (dy, x) (split3 mode) or Nones."""
+    geom = (N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, in_relu); amax = the amax words of (dy, x) (split3 mode) or Nones.
+    flags: one byte per pixel row of dy (rn_conv_wgrad_batched_flags: K-steps without an active row are skipped), or None."""
     cnt = lambda a: 0 if a is None else (-1 if a.numel() == 1 else a.numel() // AMAX_SUB)      # tables of n images, or one plain word
     am = (_hip.ptr(amax[0]), cnt(amax[0]), _hip.ptr(amax[1]), cnt(amax[1]))
+    if flags is not None:
+        ws, nb = None, 0
+        if lib.rn_get_option(OPT_DETERMINISTIC):
+            N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw = geom[:9]
+            nb = lib.rn_conv_wgrad_det_workspace_bytes(ldy, nbatch, dw_bs, N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw)
+            if nb < 0:
+                return 1
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        return lib.rn_conv_wgrad_batched_flags(dy_ptr, ldy, x_ptr, dw_ptr, cs_ptr, nbatch, dy_bs, x_bs, dw_bs, cs_batch, *geom, *am,
+                                               flags.data_ptr(), _hip.ptr(ws), nb, _hip.stream())
     if not lib.rn_get_option(OPT_DETERMINISTIC):
         return lib.rn_conv_wgrad_batched(dy_ptr, ldy, x_ptr, dw_ptr, cs_ptr, nbatch, dy_bs, x_bs, dw_bs, cs_batch, *geom, *am, _hip.stream())
     N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw = geom[:9]
@@ -458,12 +471,29 @@ def _wino_workspace(device, floats_v, floats_m):
     return ws
 
 
+def tile_flags(device, T):
+    """A zeroed TILE ACTIVITY FLAG array for Winograd-domain tensors of T tiles: one byte per row of V / Z / M
+    (wino_tpad(T) of them); flag 1 = some pixel of the tile's 6x6 patch may be non-zero.  Producers of a gradient set them
+    (sigmoid_bwd_pad(flags=...), wino_conv_group(flags_out=...)); wino_wgrad_group / wino_conv_group skip the tiles left at 0."""
+    return torch.zeros(wino_tpad(T), dtype=torch.uint8, device=device)
+
+
+def wino_flags_ok(T, C, cout):
+    """Can EVERY stage of a Winograd backward (both transforms, the reductions, the GEMM's row blocks, the output transform) honour tile
+    flags for T tiles of a C -> cout layer?  The reductions decide: only the once-split 128 x 128 kernel lists and skips K-steps (the
+    split product modes, more than 64 channels on both sides, at most 2040 K-steps).  Otherwise the whole chain runs dense."""
+    lib = _hip.load()
+    return bool(get_fp32_mfma() != "native" and lib.rn_get_option(OPT_WGRAD_ONCE) and C > 64 and cout > 64 and T < 32000)
+
+
 def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds=None, masks=None, mask_mode=2,
-                    flops=0.0, keep_v=False, y_batch_stride=0, V_in=None, V_ready=None, sign=False):
+                    flops=0.0, keep_v=False, y_batch_stride=0, V_in=None, V_ready=None, sign=False, flags_out=None):
     """3x3 / stride 1 / padding 1 convolution of several inputs [N,H,W,C] with the same (transformed) weights U
     [36, Cout, Kpad]: one grouped input transform into V, ONE batched GEMM launch, one grouped output transform with
     the epilogue (outs: dense tensors, or slices with y_batch_stride).  Returns the outputs (and, with keep_v, the
-    (V, shapes) pair wino_wgrad_group accepts).  flops is informational (the GEMM is priced by its executed FLOPs)."""
+    (V, shapes) pair wino_wgrad_group accepts).  flops is informational (the GEMM is priced by its executed FLOPs).
+    A V_ready that carries tile flags (wino_wgrad_group(flags=...)) makes the GEMM and the output transform skip the inactive tiles;
+    flags_out: a zeroed tile_flags array that receives the flags of the results (the next layer's gradient)."""
     lib = _hip.load()
     dev = xs[0].device
     C = xs[0].shape[3]
@@ -490,6 +520,9 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
         v_am = src[2] if len(src) > 2 and src[2] is not None else (None, None)
     else:
         v_am = _wino_transform_in(xs, V, C, Tpad, 0, want_rows=True, want_tensor=keep_v)
+    flags = V_ready[3] if ready and len(V_ready) > 3 else None      # V holds the ACTIVE tiles only: every later stage must skip the others
+    if flags_out is not None:
+        assert flags_out.dtype == torch.uint8 and flags_out.numel() >= Tpad and len(xs) <= _hip.RN_MAX_GROUP
     # rows past T hold whatever the scratch tensor held: they produce rows of M nobody reads
     Vv = V[:36 * Tpad * C].view(36, 1, Tpad, C)
     Mv = M[:36 * Tpad * cout].view(36, 1, Tpad, cout)
@@ -497,7 +530,7 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
     if want_amax() and v_am[0] is None:              # a V somebody else made without words: the three-term kernels for this launch
         Uv = U.view(36 * cout, U.shape[2])
     conv_igemm(Vv, Uv, Mv, (1, Tpad, cout, 1, 1, 1, 1, 0, 0), flops=2.0 * 36 * T * cout * C, w_batch_stride=cout * U.shape[2],
-               x_amax=v_am[0], x_amax_rows=True)    # executed FLOPs: same kernel, same family
+               x_amax=v_am[0], x_amax_rows=True, row_active=flags)    # executed FLOPs: same kernel, same family (nominal with flags)
     if outs is None:
         outs = [torch.empty((x.shape[0], x.shape[1], x.shape[2], cout), dtype=torch.float32, device=dev) for x in xs]
     off = 0
@@ -517,9 +550,14 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
         nops = 1 + (pa is not None and pa[0] is not None) + (1.0 / 32 if mbits else 1.0) * has_mask + (1.0 / 32 if signs[0] is not None else 0.0)
         nb = 4.0 * (36 * t * cout + nops * sum(x.shape[0] * x.shape[1] * x.shape[2] for x in part) * cout)
         mm = (mask_mode | (MASK_BITS if mbits else 0)) if has_mask else 0
-        _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group(
-            ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
-            act, y_batch_stride, _hip.stream())), "rn_wino_output_group")
+        if flags is not None or flags_out is not None:
+            _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group_flags(
+                ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
+                act, y_batch_stride, _hip.ptr(flags), _hip.ptr(flags_out), _hip.stream())), "rn_wino_output_group_flags")
+        else:
+            _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group(
+                ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
+                act, y_batch_stride, _hip.stream())), "rn_wino_output_group")
         if yams is not None:
             for o, w_ in zip(outs[sl], yams):
                 amax_attach(o, w_)
@@ -555,12 +593,15 @@ def _wino_z_buffer(device, floats):
     return st, k
 
 
-def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_input=False, side=None):
+def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_input=False, side=None, flags=None):
     """Weight gradient of a 3x3 / stride 1 / padding 1 convolution over several problems (gs[i] = dY [N,H,W,Cout],
     xs[i] = its input [N,H,W,Cin]) by Winograd F(4x4,3x3): dw (packed [Cout][Kpad], accumulated into) and colsum.
     Returns None, or with fuse_dgrad_input the (B^T dy B, shapes) pair for wino_conv_group(V_ready=...) of the same layer's data gradient.
     side: a stream for the 36 reductions and the back-transform of dU (the fused form only: the transforms of dy stay on the caller's
-    stream, which goes on to the data gradient while the reductions run beside it)."""
+    stream, which goes on to the data gradient while the reductions run beside it).
+    flags: the tile activity flags of gs (tile_flags), honoured by the fused form when wino_flags_ok says every stage can: the transforms
+    and the reductions skip the inactive tiles, and the returned tuple carries the flags on to wino_conv_group.  Otherwise the call is
+    dense -- never a skipping transform in front of a reduction that reads every row."""
     lib = _hip.load()
     dev = xs[0].device
     C, cout = xs[0].shape[3], gs[0].shape[3]
@@ -592,11 +633,16 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
         vd_rows = torch.zeros(Tpad, dtype=torch.int32, device=dev) if am_on else None
         z_tw = amax_single(dev) if am_on else None
         nb = 4.0 * (sum(t.numel() for t in gs) + 2 * 36 * T * cout)
-        _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group(
-            ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), _hip.stream())),
-            "rn_wino_input_both_group")
-        v_dy = (Vd, tuple(tuple(t.shape) for t in gs), (vd_rows, None))
+        if flags is not None and not wino_flags_ok(T, C, cout):
+            flags = None
+        if flags is not None:
+            assert flags.dtype == torch.uint8 and flags.numel() >= Tpad
+        _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group_flags(
+            ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), _hip.ptr(flags),
+            _hip.stream())), "rn_wino_input_both_group_flags")
+        v_dy = (Vd, tuple(tuple(t.shape) for t in gs), (vd_rows, None)) + ((flags,) if flags is not None else ())
     else:
+        flags = None
         z_tw = _wino_transform_in(gs, Z, cout, Tpad, 1, want_tensor=True)[1]
     # split3: both operands of the 36 reductions are Winograd-domain tensors, one word each (the reduction runs over all images)
     am = (z_tw, v_tw) if (want_amax() and z_tw is not None and v_tw is not None) else (None, None)
@@ -606,7 +652,7 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
     def reductions():
         rc = prof.timed("conv_wgrad" + (" winograd T%d %d->%d" % (T, C, cout) if prof.BY_SHAPE else ""), 2.0 * 36 * T * cout * C, lambda: _wgrad_call(    # executed FLOPs
             lib, dev, Z.data_ptr(), cout, V.data_ptr(), dU.data_ptr(), _hip.ptr(colsum), 36, Tpad * cout, Tpad * C, cout * ku, 7,
-            (1, 1, T, C, 1, T, cout, 1, 1, 1, 0, 0), amax=am))
+            (1, 1, T, C, 1, T, cout, 1, 1, 1, 0, 0), amax=am, flags=flags))
         _hip.check(rc, "rn_conv_wgrad_batched")
         _hip.check(lib.rn_wino_dw(dU.data_ptr(), dw.data_ptr(), cout, C, _hip.stream()), "rn_wino_dw")
     if zst is None:
@@ -621,7 +667,7 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
         # events have not completed are replaced by fresh device allocations -- and the step time bimodal (64 or 90-140 ms from run to
         # run, profiles/r05_wgrad_stream.txt 7).  The tensors are held here instead and released by the caller (side_release) once the
         # stream they were allocated on has waited for the side stream.
-        SIDE_HELD.setdefault(side.cuda_stream, []).append((V, dU) + tuple(am))
+        SIDE_HELD.setdefault(side.cuda_stream, []).append((V, dU, flags) + tuple(am))
     return v_dy                                      # (B^T dy B, shapes) for the data gradient that follows, or None when not fused
 
 
@@ -858,12 +904,23 @@ def relu_mask_(g, z):
     return g                                       # (a mask only lowers magnitudes: an amax word stays a valid bound)
 
 
-def sigmoid_bwd_pad(dy_ptr, s_ptr, B, rows_per_image, C, ld, src_batch_stride, device, bf16=False):
+def sigmoid_bwd_pad(dy_ptr, s_ptr, B, rows_per_image, C, ld, src_batch_stride, device, bf16=False, hw=None, flags=None):
     """Gradient slice of a head output (B images, rows_per_image pixels of C channels each, images
     src_batch_stride floats apart; raw device pointers) -> dense [B*rows_per_image, ld], zero-padded channels,
-    multiplied by s(1-s) when the sigmoid output pointer is given."""
+    multiplied by s(1-s) when the sigmoid output pointer is given.
+    flags (fp32 only, with hw = (H, W), H * W = rows_per_image): a ZEROED uint8 tensor of B * ceil(H/4) * ceil(W/4) bytes that receives
+    the result's tile activity flags (see tile_flags)."""
     lib = _hip.load()
     out = torch.empty((B * rows_per_image, ld), dtype=torch.bfloat16 if bf16 else torch.float32, device=device)
+    if flags is not None:
+        H, W = hw
+        assert not bf16 and H * W == rows_per_image and flags.dtype == torch.uint8 and flags.numel() >= B * ((H + 3) // 4) * ((W + 3) // 4)
+        am = amax_slot(device, B) if want_amax() else None
+        _hip.check(lib.rn_sigmoid_bwd_pad_flags(dy_ptr, s_ptr, out.data_ptr(), B, H, W, C, ld, src_batch_stride, _hip.ptr(am),
+                                                flags.data_ptr(), _hip.stream()), "rn_sigmoid_bwd_pad_flags")
+        if am is not None:
+            out._rn_amax_words = am
+        return out
     if bf16:
         _hip.check(lib.rn_sigmoid_bwd_pad_bf16(dy_ptr, s_ptr, out.data_ptr(), B, rows_per_image, C, ld, src_batch_stride, _hip.stream()),
                    "rn_sigmoid_bwd_pad_bf16")

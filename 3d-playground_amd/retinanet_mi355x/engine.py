@@ -27,6 +27,9 @@ from . import _hip, arch, conv as cv, ops, prof
 # The two input-side transforms of an output gradient (for the weight gradient and for the data gradient of a Winograd layer) in
 # one pass over it; RN_WINO_FUSE_DY=0 keeps the two separate launches (A/B).
 FUSE_DY = os.environ.get("RN_WINO_FUSE_DY", "1") != "0"
+# The regression head's gradient is zero except at the positive anchors (the loss has no regression term elsewhere): its tower's
+# backward carries per-tile activity flags and skips the all-zero tiles.  RN_SPARSE_REG=0: the dense path (A/B).
+SPARSE_REG = os.environ.get("RN_SPARSE_REG", "1") != "0"
 # bf16 engine: the weight gradient of a head layer over its five pyramid levels as ONE launch (rn_conv_wgrad_bf16_grouped); 0: one per level (A/B)
 GROUPED_WGRAD_BF16 = os.environ.get("RN_GROUPED_WGRAD_BF16", "1") != "0"
 # bf16 engine: the data gradient of a 1x1 stride-2 shortcut computed on its output grid and stored at the even input positions; 0: the generic form (A/B)
@@ -309,10 +312,13 @@ class Layer:
                 y._rn_qscale = self.out_scale
         return ys
 
-    def bwd_data_group(self, gs, in_hws, adds=None, masks=None, wino=False):
-        """Stride-1 data gradient of several problems in one launch; adds / masks: per-problem tensors or None."""
+    def bwd_data_group(self, gs, in_hws, adds=None, masks=None, wino=False, flags_out=None):
+        """Stride-1 data gradient of several problems in one launch; adds / masks: per-problem tensors or None.
+        flags_out: a zeroed tile-flag array for the results (cv.tile_flags); self.flags_out_done says whether this call filled it
+        (the Winograd form only)."""
         s = self.spec
         assert s.stride == 1
+        self.flags_out_done = False
         if self.bf16:
             probs, outs, fl = [], [], 0.0
             for i, g in enumerate(gs):
@@ -327,7 +333,9 @@ class Layer:
         if (wino or self.wino_active) and self.wino_ok and all(g.shape[3] == s.cout for g in gs):
             fl = sum(self.flops(g.shape[0], g.shape[1], g.shape[2]) for g in gs)
             ready, self.dy_v = getattr(self, "dy_v", None), None
-            return cv.wino_conv_group(gs, self.wino_weights(1), adds=adds, masks=masks, mask_mode=2, flops=fl, V_ready=ready)
+            self.flags_out_done = flags_out is not None
+            return cv.wino_conv_group(gs, self.wino_weights(1), adds=adds, masks=masks, mask_mode=2, flops=fl, V_ready=ready,
+                                      flags_out=flags_out)
         probs, outs, fl = [], [], 0.0
         for i, g in enumerate(gs):
             N = g.shape[0]
@@ -367,8 +375,9 @@ class Layer:
         cv.wgrad(g, x, self.dw, s.cout, s.k, s.stride, s.pad, kw_pad=self.kw_pad, in_relu=in_relu,
                  flops=self.flops(g.shape[0], g.shape[1], g.shape[2]), colsum=self.cs)
 
-    def bwd_params_group(self, gs, xs, wino=False, side=None):
-        """bwd_params over several problems (pyramid levels); wino: one Winograd weight-gradient pass over all of them."""
+    def bwd_params_group(self, gs, xs, wino=False, side=None, flags=None):
+        """bwd_params over several problems (pyramid levels); wino: one Winograd weight-gradient pass over all of them.
+        flags: the tile activity flags of gs, for the Winograd form (cv.wino_wgrad_group); the other forms are dense."""
         s = self.spec
         if (wino or self.wino_active) and self.wino_ok and all(g.shape[3] == s.cout and g.is_contiguous() for g in gs):
             if self.dw is None:
@@ -376,7 +385,8 @@ class Layer:
                 self.cs = torch.zeros(s.cout, dtype=torch.float32, device=gs[0].device)
             fl = sum(self.flops(g.shape[0], g.shape[1], g.shape[2]) for g in gs)
             du, self.du = getattr(self, "du", None), None
-            self.dy_v = cv.wino_wgrad_group(gs, xs, self.dw, self.cs, flops=fl, V=self.saved_v, dU=du, fuse_dgrad_input=FUSE_DY, side=side)
+            self.dy_v = cv.wino_wgrad_group(gs, xs, self.dw, self.cs, flops=fl, V=self.saved_v, dU=du, fuse_dgrad_input=FUSE_DY, side=side,
+                                            flags=flags)
             self.saved_v = None
             return
         if self.bf16 and GROUPED_WGRAD_BF16 and 1 < len(gs) <= 5 and all(g.is_contiguous() and x.is_contiguous() for g, x in zip(gs, xs)) \
@@ -869,17 +879,20 @@ class Engine:
         for L in layers:
             L.dw = L.cs = L.wd = L.uf = L.ud = L.saved_v = L.dy_v = None
 
-    def _zero_grad_accumulators(self, device):
+    def _zero_grad_accumulators(self, device, flag_bytes=0, flag_arrays=0):
         """Weight-gradient and column-sum accumulators of every layer -- and the Winograd-domain accumulators dU of the layers that
         take that path -- as views of ONE buffer, zeroed by one fill per step (they are atomically accumulated into: ~160 separate
-        zero-fills per step otherwise)."""
+        zero-fills per step otherwise).  flag_arrays tile-flag arrays of flag_bytes each (a multiple of 16; the regression tower's
+        sparse backward, one per layer depth) ride in the same buffer and the same fill -> self._reg_flags."""
         wino = self.use_wino and not self.bwd16
         sizes = []
         for L in self.layers.values():
             s = L.spec
             du = 36 * s.cout * ((s.cin + 31) // 32 * 32) if (wino and L.wino_layer) else 0
             sizes.append((L, L.wf.numel(), (s.cout + 3) // 4 * 4, du))
-        total = sum(a + b + c for _, a, b, c in sizes)
+        total = (sum(a + b + c for _, a, b, c in sizes) + 3) // 4 * 4      # (the flags start at a multiple of 16 bytes)
+        acc_floats = total
+        total += flag_arrays * flag_bytes // 4
         arena = getattr(self, "_arena", None)
         if arena is None or arena.numel() != total or arena.device != device:
             arena = self._arena = torch.empty(total, dtype=torch.float32, device=device)
@@ -890,6 +903,8 @@ class Engine:
             L.cs = arena[o + a:o + a + L.spec.cout]
             L.du = arena[o + a + b:o + a + b + c].view(36, L.spec.cout, -1) if c else None
             o += a + b + c
+        fb = arena[acc_floats:].view(torch.uint8)
+        self._reg_flags = [fb[i * flag_bytes:(i + 1) * flag_bytes] for i in range(flag_arrays)]
 
     # ------------------------------------------------------------------------------------------- fp8 calibration
     def calibrate(self, P, frames, margin=1.0):
@@ -1089,7 +1104,10 @@ class Engine:
         """dreg [B,A,n_reg], dcls [B,A,C] (gradient w.r.t. the post-sigmoid classification) -> {param: grad}."""
         Ls = self.layers
         grads = {}
-        self._zero_grad_accumulators(dreg.device)
+        # sparse regression tower: one flag array per layer depth (output, conv4 .. conv1), each live until that layer's reductions are through
+        sparse_reg = SPARSE_REG and self.use_wino and not self.bwd16 and not self.bf16 and not self.fp8 and dreg.is_cuda
+        reg_tiles = [dreg.shape[0] * ((f.shape[1] + 3) // 4) * ((f.shape[2] + 3) // 4) for f in S["pyramid"]]
+        self._zero_grad_accumulators(dreg.device, cv.wino_tpad(sum(reg_tiles)) if sparse_reg else 0, 5 if sparse_reg else 0)
         for L in Ls.values():
             L.saved_v = L.dy_v = None
         for n, v in S.pop("wino_v", {}).items():          # this call's Winograd input transforms (see forward)
@@ -1148,12 +1166,12 @@ class Engine:
             else:
                 aside(lambda: L.bwd_params(g, x, in_relu=in_relu), (g, x))
 
-        def wg_group(L, gs, xs, wino=False):
+        def wg_group(L, gs, xs, wino=False, flags=None):
             """L.bwd_params_group likewise (the head towers' layers over the pyramid levels)."""
             if wss is None or os.environ.get("RN_WGRAD_TOWERS", "0") == "0":
-                L.bwd_params_group(gs, xs, wino=wino)
+                L.bwd_params_group(gs, xs, wino=wino, flags=flags)
             elif wino or L.wino_active:
-                L.bwd_params_group(gs, xs, wino=wino, side=wss[0])
+                L.bwd_params_group(gs, xs, wino=wino, side=wss[0], flags=flags)
             else:
                 aside(lambda: L.bwd_params_group(gs, xs), tuple(gs) + tuple(xs))
 
@@ -1199,20 +1217,30 @@ class Engine:
                 side[ti].wait_event(fork)
             with torch.cuda.stream(side[ti] if side is not None else main):
                 acts = [[ACT(t) for t in lvl] for lvl in S["towers"][prefix]]   # acts[level][i] (fp8 training: as bf16)
-                gs, off = [], 0
-                for (Hh, Ww), cnt in zip(hws, counts):                    # head-output gradient slices -> dense, padded
+                # tile flags of the gradient at each depth (regression tower): written by the producer of that gradient, read by the layer's
+                # transforms / GEMM / reductions; `fl` turns None for good where a layer does not take the Winograd form
+                F = self._reg_flags if (ti == 0 and sparse_reg and Lout.wino_active) else None
+                fl = F[0] if F else None
+                gs, off, t_off = [], 0, 0
+                for li, ((Hh, Ww), cnt) in enumerate(zip(hws, counts)):   # head-output gradient slices -> dense, padded
                     byte_off = 4 * off * width
                     g = cv.sigmoid_bwd_pad(dout.data_ptr() + byte_off, None if sig is None else sig.data_ptr() + byte_off,
                                            B, Hh * Ww, arch.NUM_ANCHORS * width, Lout.cout_pad, A * width, dout.device,
-                                           bf16=self.bwd16)
+                                           bf16=self.bwd16, hw=(Hh, Ww), flags=None if fl is None else fl[t_off:t_off + reg_tiles[li]])
                     gs.append(cv.amax_carry(g.view(B, Hh, Ww, Lout.cout_pad), g))
                     off += cnt
-                wg_group(Lout, gs, [acts[li][3] for li in range(5)])          # direct: one launch per level (K slices fill the GPU)
-                gs = Lout.bwd_data_group(gs, hws, masks=[acts[li][3] for li in range(5)])
+                    t_off += reg_tiles[li]
+                wg_group(Lout, gs, [acts[li][3] for li in range(5)], flags=fl)          # direct: one launch per level (K slices fill the GPU)
+                nxt = F[1] if fl is not None else None
+                gs = Lout.bwd_data_group(gs, hws, masks=[acts[li][3] for li in range(5)], flags_out=nxt)
+                fl = nxt if Lout.flags_out_done else None
                 for i in (3, 2, 1):
-                    wg_group(tower[i], gs, [acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16)
-                    gs = tower[i].bwd_data_group(gs, hws, masks=[acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16)
-                wg_group(tower[0], gs, pyramid, wino=self.use_wino and not self.bwd16)
+                    wg_group(tower[i], gs, [acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16, flags=fl)
+                    nxt = F[5 - i] if fl is not None else None
+                    gs = tower[i].bwd_data_group(gs, hws, masks=[acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16,
+                                                 flags_out=nxt)
+                    fl = nxt if tower[i].flags_out_done else None
+                wg_group(tower[0], gs, pyramid, wino=self.use_wino and not self.bwd16, flags=fl)
                 first = dpyr[0] is None
                 if side is not None and not first:
                     side[ti].wait_stream(side[0])                         # the other tower's pyramid gradient is complete

@@ -557,6 +557,11 @@ typedef struct rn_conv_desc {
     const float *w_unscale;        /* w_format == 3: per weight row the inverse 2^-s of the power-of-two scale its fp16 terms were
                                       written with (rn_split_weights_f16); [batch * Cout] when w_batch_stride != 0 */
     int x_amax_img_stride, x_amax_row_stride;
+    const void *row_active;        /* NULL, or TILE ACTIVITY FLAGS for the Winograd-stage GEMM (w_batch_stride != 0) of a sparse gradient: one
+                                      byte per row of an image (Ho*Wo of them, 16-byte aligned), 0 = the row of x is zero in every image and
+                                      nobody reads that row of y.  A workgroup whose rows are all inactive computes nothing; rows of
+                                      inactive tiles inside an active workgroup are computed from whatever x holds.  A kernel without the
+                                      test ignores the flags (a dense result is always right). */
 } rn_conv_desc;
 #define RN_MASK_BITS 4
 
@@ -693,6 +698,18 @@ int rn_conv_wgrad_batched_det(const float *dy, int ldy, const float *x, float *d
                               int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int in_relu,
                               const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, void *workspace, int64_t workspace_bytes,
                               void *stream);
+/* The batched 1x1 reductions of a SPARSE gradient (the Winograd weight gradient of the regression tower): k_active holds one byte per
+ * pixel row of dy (N = Hi = Ho = 1, Wi = Wo pixels, 1x1, stride 1, no padding; 16-byte aligned, readable up to the next multiple of
+ * 16), 0 = that row of dy is zero in every batch entry.  A K slice runs only the 16-row K-steps that hold an active row, in their
+ * order; a slice without one adds nothing (fixed-order form: its slab is zero).  Skipped rows of dy and x are never read.  The result
+ * equals the dense call's (the fixed-order form bit for bit, up to the sign of a zero).  workspace NULL: fp32 atomics
+ * (rn_conv_wgrad_batched); else the fixed-order form (rn_conv_wgrad_batched_det).  RN_EINVAL where the flags cannot be honoured: another
+ * geometry, the native product mode, a tile shape other than 128 x 128, more than 2040 K-steps per slice. */
+int rn_conv_wgrad_batched_flags(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
+                                int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi, int Wi,
+                                int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int in_relu,
+                                const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, const void *k_active,
+                                void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------- bf16 convolution engine -----------------
  * The reduced-precision form of rn_conv_igemm / rn_conv_wgrad for BASELINE configs[2] (bf16 MFMA,
@@ -814,6 +831,17 @@ int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, 
                              void *v_row_amax, void *z_tensor_amax, void *stream);
 int rn_wino_output_group(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
                          const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride, void *stream);
+/* The same two with TILE ACTIVITY FLAGS: one byte per tile row of V / Z / M ([Tpad], 16-byte aligned, zeroed by the
+ * caller, set by the producers of the gradient), 1 = some pixel of the tile's 6x6 patch may be non-zero.
+ *   rn_wino_input_both_group_flags: a tile with flag 0 loads nothing and writes no V; its rows of Z are zeroed where the 16-row unit
+ *       they lie in holds an active tile (what a reduction that skips whole inactive units reads).  flags NULL: the dense form.
+ *   rn_wino_output_group_flags: a tile with flags_in 0 reads no M and runs the epilogue on zeros (the result is dense); flags_out receives
+ *       the flags of the STORED tensors, in the same tile order, for the next layer.  Either may be NULL. */
+int rn_wino_input_both_group_flags(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                   void *v_row_amax, void *z_tensor_amax, const void *flags, void *stream);
+int rn_wino_output_group_flags(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
+                               const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
+                               const void *flags_in, void *flags_out, void *stream);
 int rn_wino_input(const float *x, float *V, int N, int H, int W, int C, int64_t tile_offset, int64_t Tpad, void *stream);
 int rn_wino_output(const float *M, float *y, int N, int H, int W, int Cout, int64_t tile_offset, int64_t Tpad,
                    const float *scale, const float *shift, const float *add, const float *mask, int mask_mode, int act,
@@ -909,6 +937,10 @@ int rn_upsample_add_bwd(const float *src, float *dst, int N, int Hs, int Ws, int
 int rn_relu_mask(float *g, const float *z, int64_t n, void *stream);
 int rn_sigmoid_bwd_pad(const float *dy, const float *s, float *out, int B, int64_t rows_per_image, int C, int ld,
                        int64_t src_batch_stride, void *amax, void *stream);
+/* rn_sigmoid_bwd_pad for images of H x W pixels that also sets the tile activity flags of its result (one byte per 4x4 tile of the
+ * B images, zeroed by the caller): a non-zero value sets its tile and the neighbours whose 6x6 patch contains its pixel. */
+int rn_sigmoid_bwd_pad_flags(const float *dy, const float *s, float *out, int B, int H, int W, int C, int ld,
+                             int64_t src_batch_stride, void *amax, void *flags, void *stream);
 int rn_add_inplace(float *dst, const float *src, int64_t n, int64_t per_image, void *amax, void *stream);
 /* `amax` of rn_nchw_to_nhwc4 / rn_maxpool_bwd / rn_upsample_add_bwd / rn_sigmoid_bwd_pad / rn_add_inplace (round 5): NULL, or the amax
  * words of the tensor the call produces, one per image (rn_conv_desc.y_amax: raised by atomic max; the caller zeroes them first).
