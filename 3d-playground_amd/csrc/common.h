@@ -49,6 +49,17 @@ static inline int rn_env_int(const char *name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
+// Compute units of the current device (256 where the runtime will not say), read once: the grids of the kernels that walk a device-side
+// work list are sized by it, never by the list.
+static inline int rn_device_cus() {
+    static const int cus = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 8) v = 256;
+        return v;
+    }();
+    return cus;
+}
+
 // Sum over the 64 lanes of a wave; every lane gets the total.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

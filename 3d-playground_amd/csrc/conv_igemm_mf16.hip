@@ -465,6 +465,16 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 2 : (TERMS == 2 ? RN_MF16H_OCC :
     conv_mf16_tile<GENERAL, RAW, TERMS, STG, WV>(d, x, w, y, scale, shift, add, mask, add2, tile);
 }
 
+// rn_conv_desc.row_list: the RAW batched instance over a device-side work list instead of the dense grid with early exits (of which three
+// quarters left after reading their flags, and the active quarter sat wherever the tiles' XCD bands put it).  Same tile, same arithmetic.
+template <int TERMS, bool STG>
+__global__ __launch_bounds__(256, TERMS == 2 ? RN_MF16H_OCC : 3) void conv_igemm_mf16_list_kernel(const rn_conv_desc d, const float *__restrict__ x,
+                                                                   const float *__restrict__ w, float *__restrict__ y) {
+    rn_row_list_walk(d, [&](int tile) {
+        conv_mf16_tile<false, true, TERMS, STG, 4>(d, x, w, y, nullptr, nullptr, nullptr, nullptr, nullptr, tile);
+    });
+}
+
 template <int TERMS>
 __global__ __launch_bounds__(256, TERMS == 2 ? RN_MF16H_OCC : 3) void conv_igemm_mf16_grouped_kernel(const rn_conv_group g, const float *__restrict__ w,
                                                                       const float *__restrict__ scale,
@@ -511,6 +521,20 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
     if (variant == 0 && d->row_active != nullptr && d->w_batch_stride != 0 &&
         (((uintptr_t)d->row_active & 15) || ((int64_t)d->Ho * d->Wo) % 256 != 0)) { *rc = RN_EINVAL; return true; }
     const dim3 grid((unsigned)tiles), block(256);
+    if (variant == 0) {                                      // the work-list form: a grid sized by the device, three workgroups per CU
+        const int lst = rn_row_list_ok(d);
+        if (lst < 0) { *rc = RN_EINVAL; return true; }
+        if (lst > 0) {
+            const dim3 gl(rn_row_list_grid(d, 3));
+            static const int stg_min_k_l = rn_env_int("RN_MF16_STG_MIN_K", 256);
+            if (d->w_format != 3) hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<3, false>), gl, block, 0, s, *d, x, w, y);
+            else if (RN_MF16_STG != 0 && d->kh * d->kw * d->Cin >= stg_min_k_l) hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<2, true>), gl, block, 0, s, *d, x, w, y);
+            else hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<2, false>), gl, block, 0, s, *d, x, w, y);
+            const hipError_t e = hipGetLastError();
+            *rc = e == hipSuccess ? RN_OK : (int)e;
+            return true;
+        }
+    }
 #define RN_MF16_LAUNCH(G, R, T, S) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, T, S>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
     if (d->w_format == 3) {
         // staged activations (row-coalesced direct-to-LDS loads) where the K loop is long enough to pay for the longer prologue: measured

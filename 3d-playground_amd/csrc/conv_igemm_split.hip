@@ -25,6 +25,16 @@ __global__ __launch_bounds__(256, BK == 32 ? 2 : 3) void conv_igemm_split_kernel
     conv_igemm_tile<WM, WN, GENERAL, BK, RELU, RAW, SPLIT, TERMS>(d, x, w, y, scale, shift, add, mask, add2, xcd_remap(blockIdx.x, gridDim.x));
 }
 
+// rn_conv_desc.row_list for the Winograd-stage GEMMs that land here in RN_FP32_SPLIT3 mode (a channel count that is no multiple of 32:
+// the padded gradient of a head's output layer, which ran this kernel DENSE over tiles of which a fiftieth were active): the raw two-term
+// 128 x 128 tile over the device-side work list (conv_igemm_tile.h: rn_row_list_walk).
+__global__ __launch_bounds__(256, 3) void conv_igemm_split_list_kernel(const rn_conv_desc d, const float *__restrict__ x,
+                                                                       const float *__restrict__ w, float *__restrict__ y) {
+    rn_row_list_walk(d, [&](int tile) {
+        conv_igemm_tile<2, 2, false, 16, false, true, 2, 2>(d, x, w, y, nullptr, nullptr, nullptr, nullptr, nullptr, tile);
+    });
+}
+
 template <int WM, int WN, int SPLIT, int BK = 16, int TERMS = 3>
 __global__ __launch_bounds__(256, BK == 32 ? 2 : 3) void conv_igemm_split_grouped_kernel(const rn_conv_group g, const float *__restrict__ w,
                                                                           const float *__restrict__ scale,
@@ -82,6 +92,15 @@ int rn_igemm_split_launch(int variant, unsigned tiles, const rn_conv_desc *d, co
         // no multiple of 32, the input-ReLU form): the tile of conv_igemm_tile.h with two-term fp16 products (TERMS 2)
         if (d->x_amax == nullptr || d->w_unscale == nullptr) return RN_EINVAL;
         const dim3 grid2(tiles), block2(256);
+        if (variant == 0) {
+            const int lst = rn_row_list_ok(d);
+            if (lst < 0) return RN_EINVAL;
+            if (lst > 0) {
+                hipLaunchKernelGGL(conv_igemm_split_list_kernel, dim3(rn_row_list_grid(d, 3)), block2, 0, s, *d, x, w, y);
+                RN_LAUNCH_CHECK();
+                return RN_OK;
+            }
+        }
 #define RN_HALF_LAUNCH(WM, WN, G, R, RAW) \
         hipLaunchKernelGGL((conv_igemm_split_kernel<WM, WN, G, R, RAW, 2, 16, 2>), grid2, block2, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
         switch (variant) {

@@ -781,6 +781,37 @@ __device__ __forceinline__ void conv_igemm_tile(const rn_conv_desc &d, const flo
     if (partial == nullptr && !rn_span) rn_amax_note(d.y_amax, m0 / HoWo, rn_am);
 }
 
+// rn_conv_desc.row_list (the Winograd-stage GEMM of a sparse gradient, 128 x 128 tiles): the workgroup's share of the work list.  Item i =
+// (image p, listed block b, column tile nt), nt fastest and p slowest, so that workgroups running side by side share an image's weights and
+// the two column tiles of a block sit on one XCD; run(tile) gets the tile index the dense launch would have given that workgroup.  The grid
+// is whatever the launcher chose; nobody waits for anybody, a count of zero returns at once.  Between two items every store has left and
+// the workgroup meets at a barrier: the next tile's prologue writes the LDS the last one's epilogue read.
+template <typename F>
+__device__ __forceinline__ void rn_row_list_walk(const rn_conv_desc &d, F &&run) {
+    const int *__restrict__ list = reinterpret_cast<const int *>(d.row_list);
+    const int ntn = (d.Cout + 127) / 128, bpi = d.Ho * d.Wo / 128;
+    const int n_raw = *reinterpret_cast<const int *>(d.row_list_n);
+    const int nblk = n_raw < 0 ? 0 : (n_raw < bpi ? n_raw : bpi);      // (a list never holds more blocks than the image has)
+    const int per = nblk * ntn;
+    const int64_t items = (int64_t)per * d.N;
+    for (int64_t it = xcd_remap(blockIdx.x, gridDim.x); it < items; it += gridDim.x) {
+        const int p = (int)(it / per), r = (int)(it - (int64_t)p * per);
+        const int b = list[r / ntn];
+        if ((unsigned)b < (unsigned)bpi) run((p * bpi + b) * ntn + r % ntn);      // (uniform in the workgroup)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+}
+// Host side: may a launch walk d->row_list?  -> 0 no list, 1 yes, -1 a list the launch cannot honour (RN_EINVAL).
+static inline int rn_row_list_ok(const rn_conv_desc *d) {
+    if (d->row_list == nullptr || d->w_batch_stride == 0) return 0;
+    if (d->row_list_n == nullptr || d->row_list_grid < 0 || ((int64_t)d->Ho * d->Wo) % 256 != 0 || ((uintptr_t)d->row_list & 3)) return -1;
+    return 1;
+}
+static inline unsigned rn_row_list_grid(const rn_conv_desc *d, int per_cu) {
+    return (unsigned)(d->row_list_grid > 0 ? d->row_list_grid : rn_device_cus() * per_cu);
+}
+
 // What the fp32 launchers accept (conv_launch.h has the rules every form shares): 4-byte elements, tiles of up to 256 rows.
 static inline int check_desc(const rn_conv_desc *d) {
     if (rn_check_desc_core(d, 4, 256, 32) || rn_check_desc_mask(d)) return RN_EINVAL;

@@ -409,17 +409,33 @@ __global__ __launch_bounds__(256) void wino_dy_kernel(const WinoTable g, float *
 // FLAGS (tile activity flags; one byte per row of V / Z, 16-byte aligned): a tile with flag 0 has an all-zero patch, so
 // V = Z = 0 exactly: it loads nothing and writes no V (the GEMM's rows of such a tile are never read).  Its rows of Z are written -- as
 // zeros -- only where the reduction may read them: it skips whole aligned units of 16 rows, so a unit with any active tile is complete.
-template <bool FLAGS = false>
+// LIST (with FLAGS; rn_tile_lists): thread id -> entry of the list of 16-row units that hold an active tile -> tile, instead of thread id ->
+// tile: the listed units' tiles are treated exactly as above, the others are never visited.  The launch keeps the dense grid (the list's
+// length is known on the device only); a workgroup past the end of the list leaves after one scalar load.  Row words of V are written for
+// the listed units only (the caller zeroes the others: rows of the GEMM nobody reads).
+template <bool FLAGS = false, bool LIST = false>
 __global__ __launch_bounds__(256) void wino_in_both_kernel(const WinoTable g, float *__restrict__ V, float *__restrict__ Z, int C,
                                                            int64_t t0, int64_t Tpad, unsigned *__restrict__ v_row_amax,
                                                            unsigned *__restrict__ z_tensor_amax,
-                                                           const unsigned char *__restrict__ flags = nullptr) {
+                                                           const unsigned char *__restrict__ flags = nullptr,
+                                                           const int *__restrict__ units = nullptr,
+                                                           const int *__restrict__ n_units = nullptr) {
     wino_tensor_word(g, z_tensor_amax, WINO_GAIN_A);
     const int cq = C >> 2;
-    const int64_t id = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
-    const int64_t gt_raw = id / cq, t_last = g.tile_end[g.n - 1];
-    const int64_t gt = gt_raw < t_last ? gt_raw : t_last - 1;   // (threads past the end still help with the table read below)
+    // (LIST: the plain id -- the list's entries fill the first workgroups only, which the XCD bands would put on one XCD)
+    const int64_t id = (int64_t)(LIST ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x)) * 256 + threadIdx.x;
+    const int64_t t_last = g.tile_end[g.n - 1];
+    int64_t gt_raw = id / cq;
     const int c4 = (int)(id - gt_raw * cq) * 4;
+    if constexpr (LIST) {
+        const int nu_raw = *n_units, nu_max = (int)(Tpad >> 4);
+        const int64_t rows = 16 * (int64_t)(nu_raw < 0 ? 0 : (nu_raw < nu_max ? nu_raw : nu_max));
+        if ((id - threadIdx.x) >= rows * cq) return;          // (the whole workgroup)
+        const int64_t it = gt_raw;
+        gt_raw = it < rows ? (int64_t)units[it >> 4] * 16 + (it & 15) - t0 : t_last;
+        if (gt_raw < 0) gt_raw = t_last;
+    }
+    const int64_t gt = gt_raw < t_last ? gt_raw : t_last - 1;   // (threads past the end still help with the table read below)
     int64_t tile;
     const int q = wino_locate(g, gt, tile);
     const float *x = g.src[0];
@@ -485,6 +501,64 @@ __global__ __launch_bounds__(256) void wino_in_both_kernel(const WinoTable g, fl
         bt6(t[i], o);
 #pragma unroll
         for (int j = 0; j < 6; ++j) st_stream(vb + (int64_t)(i * 6 + j) * Tpad * C, o[j]);
+    }
+}
+
+// The work lists of one flag array, by ONE workgroup: the active tile rows, the aligned 16-row units and the 128-row blocks
+// that hold an active row, each ascending, and the three counts (counts[0..2] = tiles, units, blocks).  Thread t owns 128-row block t (at
+// most 256 of them: the launcher's check) as eight 16-bit masks of its non-zero flag bytes; one exclusive prefix sum over the threads'
+// three counts, packed 20 bits each into one word, places every thread's entries in order.  Entries past a count keep what they held.
+__device__ __forceinline__ unsigned nz_bytes(unsigned w) {      // bit i = byte i of w is non-zero
+    const unsigned t = (w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
+    return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u);
+}
+__global__ __launch_bounds__(256) void tile_lists_kernel(const unsigned char *__restrict__ flags, int Tpad, int *__restrict__ counts,
+                                                         int *__restrict__ tiles, int *__restrict__ units, int *__restrict__ blocks) {
+    __shared__ unsigned long long wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = Tpad >> 7;
+    unsigned m[8];
+    unsigned long long c = 0ull;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = 0u;
+    if (tid < nb) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(flags) + 8 * tid;
+        int ct = 0, cu = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint4 v = p[j];
+            m[j] = nz_bytes(v.x) | (nz_bytes(v.y) << 4) | (nz_bytes(v.z) << 8) | (nz_bytes(v.w) << 12);
+            ct += __builtin_popcount(m[j]);
+            cu += m[j] != 0u;
+        }
+        c = (unsigned long long)ct | ((unsigned long long)cu << 20) | ((unsigned long long)(cu != 0) << 40);
+    }
+    unsigned long long s = c;                                // inclusive prefix sum in the wave, then over the four waves
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long t = __shfl_up(s, off, 64);
+        if (lane >= off) s += t;
+    }
+    if (lane == 63) wsum[wave] = s;
+    __syncthreads();
+    unsigned long long base = 0ull, total = 0ull;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { base += w < wave ? wsum[w] : 0ull; total += wsum[w]; }
+    s = s - c + base;
+    if (tid == 0) {
+        counts[0] = (int)(total & 0xfffffu); counts[1] = (int)((total >> 20) & 0xfffffu); counts[2] = (int)((total >> 40) & 0xfffffu);
+    }
+    int ot = (int)(s & 0xfffffu), ou = (int)((s >> 20) & 0xfffffu);
+    const int ob = (int)((s >> 40) & 0xfffffu);
+    if ((c >> 40) != 0ull) blocks[ob] = tid;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        unsigned mm = m[j];
+        if (mm != 0u) units[ou++] = 8 * tid + j;
+        while (mm != 0u) {
+            tiles[ot++] = 128 * tid + 16 * j + __builtin_ctz(mm);
+            mm &= mm - 1u;
+        }
     }
 }
 
@@ -573,6 +647,36 @@ extern "C" int rn_wino_input_both_group_flags(const rn_wino_group *g, float *V, 
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
+extern "C" int rn_tile_lists(const void *flags, int64_t Tpad, void *counts, void *tiles, void *units, void *blocks, void *stream) {
+    if (!flags || !counts || !tiles || !units || !blocks || Tpad <= 0 || (Tpad & 255) || Tpad > 256 * 128) return RN_EINVAL;      // one thread per block
+    if (((uintptr_t)flags & 15) || (((uintptr_t)counts | (uintptr_t)tiles | (uintptr_t)units | (uintptr_t)blocks) & 3)) return RN_EINVAL;
+    hipLaunchKernelGGL(tile_lists_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const unsigned char *>(flags), (int)Tpad,
+                       reinterpret_cast<int *>(counts), reinterpret_cast<int *>(tiles), reinterpret_cast<int *>(units),
+                       reinterpret_cast<int *>(blocks));
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
+// rn_wino_input_both_group_flags over the work list of `flags` (rn_tile_lists: units / n_units on the device).
+extern "C" int rn_wino_input_both_group_lists(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                              void *v_row_amax, void *z_tensor_amax, const void *flags, const void *units,
+                                              const void *n_units, void *stream) {
+    WinoTable t;
+    const int rc = wino_table(g, t);
+    if (rc) return rc;
+    if (!V || !Z || C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
+    if (!flags || !units || !n_units || ((uintptr_t)flags & 15) || ((uintptr_t)units & 3) || (Tpad & 15)) return RN_EINVAL;
+    for (int i = 0; i < t.n; ++i)
+        if (!t.src[i]) return RN_EINVAL;
+    const dim3 gl(rn_blocks(t.tile_end[t.n - 1] * (C >> 2), 256));
+    hipLaunchKernelGGL((wino_in_both_kernel<true, true>), gl, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad,
+                       reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax),
+                       reinterpret_cast<const unsigned char *>(flags), reinterpret_cast<const int *>(units),
+                       reinterpret_cast<const int *>(n_units));
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
 extern "C" int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
                                         void *v_row_amax, void *z_tensor_amax, void *stream) {
     return rn_wino_input_both_group_flags(g, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, nullptr, stream);

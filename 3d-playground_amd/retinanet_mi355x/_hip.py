@@ -123,7 +123,7 @@ class ConvDesc(ctypes.Structure):
                 ("x_batch_stride", c_i64), ("y_batch_stride", c_i64), ("add_batch_stride", c_i64),
                 ("w_batch_stride", c_i64), ("w_format", c_i32), ("sign_out", c_vp),
                 ("x_amax", c_vp), ("y_amax", c_vp), ("w_unscale", c_vp), ("x_amax_img_stride", c_i32), ("x_amax_row_stride", c_i32),
-                ("row_active", c_vp)]
+                ("row_active", c_vp), ("row_list", c_vp), ("row_list_n", c_vp), ("row_list_grid", c_i32)]
 
 
 RN_MAX_GROUP = 5
@@ -164,6 +164,8 @@ SIGNATURES.update({
     "rn_wino_input_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "rn_wino_input_both_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "rn_wino_input_both_group_flags": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rn_tile_lists": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rn_wino_input_both_group_lists": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rn_wino_output_group_flags": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rn_wino_output_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),
     "rn_conv_igemm_grouped": (c_i32, [ctypes.POINTER(ConvGroup), c_vp, c_vp, c_vp, c_vp]),

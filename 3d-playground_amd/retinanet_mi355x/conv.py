@@ -81,7 +81,7 @@ def _mask_operand(mask, mask_mode):
 def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=0, add_hw=(0, 0), mask=None,
                mask_mode=2, act=ACT_NONE, y_batch_stride=None, add_batch_stride=None, in_relu=False, flops=0.0,
                out_map=None, add2=None, w_batch_stride=0, kind=None, sign=False, bf16_products=False, x_amax=None, x_amax_rows=False,
-               amax=None, row_active=None):
+               amax=None, row_active=None, row_list=None):
     """Launch rn_conv_igemm.  x [N,Hi,Wi,Cin]; y a tensor whose storage receives [N,Ho,Wo,Cout] at batch stride
     y_batch_stride; geom = (Ho, Wo, Cout, kh, kw, a, b, p, div_shift) with p an int or (p_rows, p_cols).
     out_map = (os, oo_h, oo_w, Hy, Wy) stores output pixel (oh,ow) at (oh*os+oo_h, ow*os+oo_w) of a [N,Hy,Wy,Cout]
@@ -105,6 +105,8 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
     amax_drop(y)                                         # a reused destination: the words of what it held before are stale
     if row_active is not None:                           # tile flags of the Winograd stage (rn_conv_desc.row_active)
         d.row_active = row_active.data_ptr()
+    if row_list is not None:                             # ... and their work list (rn_conv_desc.row_list: a TileLists)
+        d.row_list, d.row_list_n, d.row_list_grid = row_list.blocks.data_ptr(), row_list.counts.data_ptr() + 8, row_list.grid
     bits = _sign_words(y, sign and y_batch_stride is None and out_map is None)
     d.sign_out = None if bits is None else bits.data_ptr()
     yam = None
@@ -478,6 +480,42 @@ def tile_flags(device, T):
     return torch.zeros(wino_tpad(T), dtype=torch.uint8, device=device)
 
 
+class TileLists:
+    """The device-side work lists of one tile-flag array (rn_tile_lists): counts = int32 [tiles, units, blocks, -],
+    tiles / units / blocks = the ascending indices of the active tile rows, of the aligned 16-row units and of the 128-row blocks that
+    hold one.  Nothing here is read by the host in the hot path.  grid: workgroups of the launches that walk a list (0: sized by the
+    device; the tests cap it to run lists longer than the grid)."""
+    __slots__ = ("flags", "buf", "counts", "tiles", "units", "blocks", "grid")
+
+    def lengths(self):
+        """(tiles, units, blocks) -- a host read, for tools and tests."""
+        return tuple(int(v) for v in self.counts[:3].tolist())
+
+
+def tile_lists_numel(Tpad):
+    return 4 + Tpad + Tpad // 16 + Tpad // 128
+
+
+def tile_lists(flags, Tpad=None, buf=None, grid=0):
+    """Build the work lists of `flags` (its first Tpad bytes; a tile_flags array) on the current stream, after whatever set the flags
+    there.  buf: an int32 tensor of tile_lists_numel(Tpad) elements to build them in (the engine's, one per layer depth, so that a
+    captured graph replays into the same memory)."""
+    lib = _hip.load()
+    Tpad = flags.numel() if Tpad is None else Tpad
+    assert flags.dtype == torch.uint8 and flags.numel() >= Tpad and Tpad % 256 == 0
+    n = tile_lists_numel(Tpad)
+    if buf is None:
+        buf = torch.empty(n, dtype=torch.int32, device=flags.device)
+    assert buf.dtype == torch.int32 and buf.numel() >= n and buf.is_contiguous()
+    tl = TileLists()
+    tl.flags, tl.buf, tl.grid = flags, buf, int(grid)
+    nb, nu = Tpad // 128, Tpad // 16
+    tl.counts, tl.blocks, tl.units, tl.tiles = buf[:4], buf[4:4 + nb], buf[4 + nb:4 + nb + nu], buf[4 + nb + nu:n]
+    _hip.check(lib.rn_tile_lists(flags.data_ptr(), Tpad, tl.counts.data_ptr(), tl.tiles.data_ptr(), tl.units.data_ptr(),
+                                 tl.blocks.data_ptr(), _hip.stream()), "rn_tile_lists")
+    return tl
+
+
 def wino_flags_ok(T, C, cout):
     """Can EVERY stage of a Winograd backward (both transforms, the reductions, the GEMM's row blocks, the output transform) honour tile
     flags for T tiles of a C -> cout layer?  The reductions decide: only the once-split 128 x 128 kernel lists and skips K-steps (the
@@ -521,6 +559,7 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
     else:
         v_am = _wino_transform_in(xs, V, C, Tpad, 0, want_rows=True, want_tensor=keep_v)
     flags = V_ready[3] if ready and len(V_ready) > 3 else None      # V holds the ACTIVE tiles only: every later stage must skip the others
+    lists = V_ready[4] if ready and len(V_ready) > 4 else None      # ... and the GEMM walks their work list instead of the dense grid
     if flags_out is not None:
         assert flags_out.dtype == torch.uint8 and flags_out.numel() >= Tpad and len(xs) <= _hip.RN_MAX_GROUP
     # rows past T hold whatever the scratch tensor held: they produce rows of M nobody reads
@@ -530,7 +569,7 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
     if want_amax() and v_am[0] is None:              # a V somebody else made without words: the three-term kernels for this launch
         Uv = U.view(36 * cout, U.shape[2])
     conv_igemm(Vv, Uv, Mv, (1, Tpad, cout, 1, 1, 1, 1, 0, 0), flops=2.0 * 36 * T * cout * C, w_batch_stride=cout * U.shape[2],
-               x_amax=v_am[0], x_amax_rows=True, row_active=flags)    # executed FLOPs: same kernel, same family (nominal with flags)
+               x_amax=v_am[0], x_amax_rows=True, row_active=flags, row_list=lists)    # executed FLOPs: same kernel, same family (nominal with flags)
     if outs is None:
         outs = [torch.empty((x.shape[0], x.shape[1], x.shape[2], cout), dtype=torch.float32, device=dev) for x in xs]
     off = 0
@@ -593,7 +632,7 @@ def _wino_z_buffer(device, floats):
     return st, k
 
 
-def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_input=False, side=None, flags=None):
+def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_input=False, side=None, flags=None, lists=None):
     """Weight gradient of a 3x3 / stride 1 / padding 1 convolution over several problems (gs[i] = dY [N,H,W,Cout],
     xs[i] = its input [N,H,W,Cin]) by Winograd F(4x4,3x3): dw (packed [Cout][Kpad], accumulated into) and colsum.
     Returns None, or with fuse_dgrad_input the (B^T dy B, shapes) pair for wino_conv_group(V_ready=...) of the same layer's data gradient.
@@ -601,7 +640,10 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
     stream, which goes on to the data gradient while the reductions run beside it).
     flags: the tile activity flags of gs (tile_flags), honoured by the fused form when wino_flags_ok says every stage can: the transforms
     and the reductions skip the inactive tiles, and the returned tuple carries the flags on to wino_conv_group.  Otherwise the call is
-    dense -- never a skipping transform in front of a reduction that reads every row."""
+    dense -- never a skipping transform in front of a reduction that reads every row.
+    lists: with honoured flags, walk work lists instead of visiting every tile (TileLists): True builds them here, an int32 tensor is the
+    buffer to build them in, a TileLists of these flags is taken as it is.  The transforms walk the unit list, the data gradient's GEMM the
+    block list (the tuple carries them on); the reductions keep their own K-step grouping."""
     lib = _hip.load()
     dev = xs[0].device
     C, cout = xs[0].shape[3], gs[0].shape[3]
@@ -637,10 +679,21 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
             flags = None
         if flags is not None:
             assert flags.dtype == torch.uint8 and flags.numel() >= Tpad
-        _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group_flags(
-            ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), _hip.ptr(flags),
-            _hip.stream())), "rn_wino_input_both_group_flags")
-        v_dy = (Vd, tuple(tuple(t.shape) for t in gs), (vd_rows, None)) + ((flags,) if flags is not None else ())
+        if flags is None or lists is None or lists is False:
+            lists = None
+        elif not isinstance(lists, TileLists):
+            lists = tile_lists(flags, Tpad, buf=None if lists is True else lists)
+        if lists is not None:
+            assert lists.flags.data_ptr() == flags.data_ptr()
+            _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group_lists(
+                ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), flags.data_ptr(),
+                lists.units.data_ptr(), lists.counts.data_ptr() + 4, _hip.stream())), "rn_wino_input_both_group_lists")
+        else:
+            _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group_flags(
+                ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), _hip.ptr(flags),
+                _hip.stream())), "rn_wino_input_both_group_flags")
+        v_dy = (Vd, tuple(tuple(t.shape) for t in gs), (vd_rows, None)) + ((flags,) if flags is not None else ()) \
+            + ((lists,) if lists is not None else ())
     else:
         flags = None
         z_tw = _wino_transform_in(gs, Z, cout, Tpad, 1, want_tensor=True)[1]
@@ -667,7 +720,7 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
         # events have not completed are replaced by fresh device allocations -- and the step time bimodal (64 or 90-140 ms from run to
         # run, profiles/r05_wgrad_stream.txt 7).  The tensors are held here instead and released by the caller (side_release) once the
         # stream they were allocated on has waited for the side stream.
-        SIDE_HELD.setdefault(side.cuda_stream, []).append((V, dU, flags) + tuple(am))
+        SIDE_HELD.setdefault(side.cuda_stream, []).append((V, dU, flags, lists) + tuple(am))
     return v_dy                                      # (B^T dy B, shapes) for the data gradient that follows, or None when not fused
 
 

@@ -30,6 +30,9 @@ FUSE_DY = os.environ.get("RN_WINO_FUSE_DY", "1") != "0"
 # The regression head's gradient is zero except at the positive anchors (the loss has no regression term elsewhere): its tower's
 # backward carries per-tile activity flags and skips the all-zero tiles.  RN_SPARSE_REG=0: the dense path (A/B).
 SPARSE_REG = os.environ.get("RN_SPARSE_REG", "1") != "0"
+# ... and its flagged stages walk device-side work lists (cv.tile_lists) instead of launching dense grids whose workgroups test their
+# flags and leave.  RN_SPARSE_REG_LISTS=0: the early-exit instances (A/B); inert when RN_SPARSE_REG=0.
+SPARSE_REG_LISTS = os.environ.get("RN_SPARSE_REG_LISTS", "1") != "0"
 # bf16 engine: the weight gradient of a head layer over its five pyramid levels as ONE launch (rn_conv_wgrad_bf16_grouped); 0: one per level (A/B)
 GROUPED_WGRAD_BF16 = os.environ.get("RN_GROUPED_WGRAD_BF16", "1") != "0"
 # bf16 engine: the data gradient of a 1x1 stride-2 shortcut computed on its output grid and stored at the even input positions; 0: the generic form (A/B)
@@ -375,9 +378,10 @@ class Layer:
         cv.wgrad(g, x, self.dw, s.cout, s.k, s.stride, s.pad, kw_pad=self.kw_pad, in_relu=in_relu,
                  flops=self.flops(g.shape[0], g.shape[1], g.shape[2]), colsum=self.cs)
 
-    def bwd_params_group(self, gs, xs, wino=False, side=None, flags=None):
+    def bwd_params_group(self, gs, xs, wino=False, side=None, flags=None, lists=None):
         """bwd_params over several problems (pyramid levels); wino: one Winograd weight-gradient pass over all of them.
-        flags: the tile activity flags of gs, for the Winograd form (cv.wino_wgrad_group); the other forms are dense."""
+        flags: the tile activity flags of gs, for the Winograd form (cv.wino_wgrad_group); the other forms are dense.
+        lists: the buffer their work lists are built in (cv.wino_wgrad_group), or None: the flagged stages visit every tile."""
         s = self.spec
         if (wino or self.wino_active) and self.wino_ok and all(g.shape[3] == s.cout and g.is_contiguous() for g in gs):
             if self.dw is None:
@@ -386,7 +390,7 @@ class Layer:
             fl = sum(self.flops(g.shape[0], g.shape[1], g.shape[2]) for g in gs)
             du, self.du = getattr(self, "du", None), None
             self.dy_v = cv.wino_wgrad_group(gs, xs, self.dw, self.cs, flops=fl, V=self.saved_v, dU=du, fuse_dgrad_input=FUSE_DY, side=side,
-                                            flags=flags)
+                                            flags=flags, lists=lists)
             self.saved_v = None
             return
         if self.bf16 and GROUPED_WGRAD_BF16 and 1 < len(gs) <= 5 and all(g.is_contiguous() and x.is_contiguous() for g, x in zip(gs, xs)) \
@@ -905,6 +909,13 @@ class Engine:
             o += a + b + c
         fb = arena[acc_floats:].view(torch.uint8)
         self._reg_flags = [fb[i * flag_bytes:(i + 1) * flag_bytes] for i in range(flag_arrays)]
+        # the work lists of those arrays (cv.tile_lists), one buffer per depth: written whole by the builder where anybody reads them, so
+        # never zeroed; kept across steps so that a captured graph replays into the same memory
+        n = cv.tile_lists_numel(flag_bytes) if flag_arrays else 0
+        bufs = getattr(self, "_reg_list_bufs", None)
+        if flag_arrays and (bufs is None or len(bufs) != flag_arrays or bufs[0].numel() != n or bufs[0].device != device):
+            bufs = self._reg_list_bufs = [torch.empty(n, dtype=torch.int32, device=device) for _ in range(flag_arrays)]
+        self._reg_lists = bufs if flag_arrays else []
 
     # ------------------------------------------------------------------------------------------- fp8 calibration
     def calibrate(self, P, frames, margin=1.0):
@@ -1166,12 +1177,12 @@ class Engine:
             else:
                 aside(lambda: L.bwd_params(g, x, in_relu=in_relu), (g, x))
 
-        def wg_group(L, gs, xs, wino=False, flags=None):
+        def wg_group(L, gs, xs, wino=False, flags=None, lists=None):
             """L.bwd_params_group likewise (the head towers' layers over the pyramid levels)."""
             if wss is None or os.environ.get("RN_WGRAD_TOWERS", "0") == "0":
-                L.bwd_params_group(gs, xs, wino=wino, flags=flags)
+                L.bwd_params_group(gs, xs, wino=wino, flags=flags, lists=lists)
             elif wino or L.wino_active:
-                L.bwd_params_group(gs, xs, wino=wino, side=wss[0], flags=flags)
+                L.bwd_params_group(gs, xs, wino=wino, side=wss[0], flags=flags, lists=lists)
             else:
                 aside(lambda: L.bwd_params_group(gs, xs), tuple(gs) + tuple(xs))
 
@@ -1221,6 +1232,10 @@ class Engine:
                 # transforms / GEMM / reductions; `fl` turns None for good where a layer does not take the Winograd form
                 F = self._reg_flags if (ti == 0 and sparse_reg and Lout.wino_active) else None
                 fl = F[0] if F else None
+                # the work lists of each depth's flags, built where the layer's transform is about to read them (after their producer, on
+                # this stream): LB[k] is depth k's buffer
+                LB = self._reg_lists if (F and SPARSE_REG_LISTS) else None
+                lb = lambda k, fl_: LB[k] if (LB and fl_ is not None) else None
                 gs, off, t_off = [], 0, 0
                 for li, ((Hh, Ww), cnt) in enumerate(zip(hws, counts)):   # head-output gradient slices -> dense, padded
                     byte_off = 4 * off * width
@@ -1230,17 +1245,18 @@ class Engine:
                     gs.append(cv.amax_carry(g.view(B, Hh, Ww, Lout.cout_pad), g))
                     off += cnt
                     t_off += reg_tiles[li]
-                wg_group(Lout, gs, [acts[li][3] for li in range(5)], flags=fl)          # direct: one launch per level (K slices fill the GPU)
+                wg_group(Lout, gs, [acts[li][3] for li in range(5)], flags=fl, lists=lb(0, fl))          # direct: one launch per level (K slices fill the GPU)
                 nxt = F[1] if fl is not None else None
                 gs = Lout.bwd_data_group(gs, hws, masks=[acts[li][3] for li in range(5)], flags_out=nxt)
                 fl = nxt if Lout.flags_out_done else None
                 for i in (3, 2, 1):
-                    wg_group(tower[i], gs, [acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16, flags=fl)
+                    wg_group(tower[i], gs, [acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16, flags=fl,
+                             lists=lb(4 - i, fl))
                     nxt = F[5 - i] if fl is not None else None
                     gs = tower[i].bwd_data_group(gs, hws, masks=[acts[li][i - 1] for li in range(5)], wino=self.use_wino and not self.bwd16,
                                                  flags_out=nxt)
                     fl = nxt if tower[i].flags_out_done else None
-                wg_group(tower[0], gs, pyramid, wino=self.use_wino and not self.bwd16, flags=fl)
+                wg_group(tower[0], gs, pyramid, wino=self.use_wino and not self.bwd16, flags=fl, lists=lb(4, fl))
                 first = dpyr[0] is None
                 if side is not None and not first:
                     side[ti].wait_stream(side[0])                         # the other tower's pyramid gradient is complete

@@ -562,6 +562,13 @@ typedef struct rn_conv_desc {
                                       nobody reads that row of y.  A workgroup whose rows are all inactive computes nothing; rows of
                                       inactive tiles inside an active workgroup are computed from whatever x holds.  A kernel without the
                                       test ignores the flags (a dense result is always right). */
+    const void *row_list;          /* NULL, or the same activity as a WORK LIST on the device (rn_tile_lists): int32 indices of the 128-row
+                                      blocks of an image that hold an active row, ascending; row_list_n points to their int32 count.  The
+                                      Winograd-stage GEMM then launches a grid fixed by the device's size -- row_list_grid workgroups, 0:
+                                      a few per compute unit -- whose workgroups walk listed block x column tile x image with stride
+                                      gridDim.x and visit nothing else.  Kernels without the list form fall back to row_active / dense. */
+    const void *row_list_n;
+    int row_list_grid;
 } rn_conv_desc;
 #define RN_MASK_BITS 4
 
@@ -842,6 +849,17 @@ int rn_wino_input_both_group_flags(const rn_wino_group *g, float *V, float *Z, i
 int rn_wino_output_group_flags(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
                                const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
                                const void *flags_in, void *flags_out, void *stream);
+/* WORK LISTS of one flag array (Tpad bytes, a multiple of 256 and at most 32 768, 16-byte aligned), built on the device by one workgroup and never read by
+ * the host: tiles = the rows with a non-zero flag, units = the aligned 16-row units and blocks = the 128-row blocks that hold one, each
+ * ascending int32 (room for Tpad, Tpad / 16 and Tpad / 128 entries; entries past the count keep what they held), counts[0..2] = their
+ * lengths.  Stages that take a list visit nothing else, so an inactive tile costs nothing:
+ *   rn_wino_input_both_group_lists: what rn_wino_input_both_group_flags stores, thread -> entry of `units` -> tile; row words of V are
+ *       written for the listed units only, the caller zeroes the others.
+ *   rn_conv_desc.row_list / row_list_n (= blocks, counts + 2): the Winograd-stage GEMM. */
+int rn_tile_lists(const void *flags, int64_t Tpad, void *counts, void *tiles, void *units, void *blocks, void *stream);
+int rn_wino_input_both_group_lists(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                   void *v_row_amax, void *z_tensor_amax, const void *flags, const void *units, const void *n_units,
+                                   void *stream);
 int rn_wino_input(const float *x, float *V, int N, int H, int W, int C, int64_t tile_offset, int64_t Tpad, void *stream);
 int rn_wino_output(const float *M, float *y, int N, int H, int W, int Cout, int64_t tile_offset, int64_t Tpad,
                    const float *scale, const float *shift, const float *add, const float *mask, int mask_mode, int act,

@@ -49,7 +49,7 @@ def main():
             off += n
     print("labels: synth.labels_dir(%d, %d, %d, %d, 8, seed=1); anchors per image %d" % (B, a.boxes, H, W, anc.shape[0]))
     print("positives per image: %s" % positives)
-    print("%-6s %-14s %-12s %-12s %-12s" % ("depth", "active tiles", "32-row", "128-row", "256-row"))
+    print("%-6s %-14s %-12s %-12s %-12s %s" % ("depth", "active tiles", "32-row", "128-row", "256-row", "work lists: tiles / 16-row units / 128-row blocks"))
     cur = [torch.stack(m).float()[:, None] for m in maps]       # [B,1,gh,gw] per level: pixels that can be non-zero
     for depth in range(5):
         flags = []
@@ -66,6 +66,8 @@ def main():
             g = np.zeros(n * rows_)
             g[:f.size] = f
             line += " %-12s" % ("%.1f %%" % (100.0 * g.reshape(n, rows_).max(axis=1).mean()))
+        cnt = lambda r: int(np.pad(f, (0, -f.size % r)).reshape(-1, r).max(axis=1).sum())
+        line += " %d / %d / %d" % (cnt(1), cnt(16), cnt(128))       # the lengths of cv.tile_lists' lists for these flags
         print(line)
         cur = [F.max_pool2d(m, 3, 1, 1) for m in cur]           # a 3x3 data gradient: one pixel wider
     print("tiles: %d" % f.size)
