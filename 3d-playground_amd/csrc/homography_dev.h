@@ -18,6 +18,24 @@ __device__ __forceinline__ void state_corners(const float *__restrict__ s, float
     }
 }
 
+// The same corners from an fp64 state: torch.tensor of a list that holds np.float64 scalars is float64, so the sums of
+// homography.py:310-318 run in fp64, and each result is rounded once on assignment into the float32 torch.zeros of :307
+// (seems_to_be_working.py:1690-1695, the candidates of Annotator.replace_homgraphy).  s = (x, y, l, w, h, direction).
+__device__ __forceinline__ void state_corners_mixed(const double s[6], float x[8], float y[8], float z[8]) {
+    const double xr = s[0], yc = s[1], l = s[2], w = s[3], h = s[4], dir = s[5];
+    const float xf32 = (float)(xr + dir * l), xr32 = (float)xr;                 // homography.py:310-311
+    const double half = dir * w / 2.0;                                          // homography.py:314-315
+    const float ylo = (float)(yc - half), yhi = (float)(yc + half);
+    const float zt = (float)(-h);                                               // homography.py:318
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int q = k & 3;
+        x[k] = (q < 2) ? xf32 : xr32;
+        y[k] = (k & 1) ? yhi : ylo;
+        z[k] = (k >= 4) ? zt : 0.f;
+    }
+}
+
 template <typename T>
 __device__ __forceinline__ void corners_to_state(const T x[8], const T y[8], const T z[8], float *__restrict__ o) {
     const T fx = x[0] + x[1], rx = x[2] + x[3];

@@ -108,6 +108,8 @@ SIGNATURES = {
     "rn_label_outliers": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "rn_label_interpolate_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rn_label_interpolate": (c_i32, [c_vp] * 4 + [c_i64] * 3 + [c_i32, c_i64] + [c_vp] * 7),
+    "rn_label_rebase": (c_i32, [c_vp, c_vp, c_i64] + [c_vp] * 4 + [c_i32, c_vp, c_i32, c_i32] + [c_vp] * 5),
+    "rn_label_offset_y": (c_i32, [c_vp] * 4 + [c_i64, c_i32, c_vp, c_vp]),
 }
 
 class ConvDesc(ctypes.Structure):

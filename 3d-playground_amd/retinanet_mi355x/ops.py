@@ -1878,9 +1878,12 @@ LABEL_POINTS = 5                   # RN_LABEL_POINTS
 LABEL_MAX_CAMS = 1024              # RN_LABEL_MAX_CAMS
 LABEL_GUARD, LABEL_FOUND_CUR, LABEL_FOUND_PREV = 1, 2, 4
 LABEL_BAD_OFFSETS, LABEL_BAD_FRAME, LABEL_BAD_PREFIX = 1, 2, 4
+LABEL_BAD_CAMERA, LABEL_BAD_ERROR = 8, 16                      # of label_rebase
 _LABEL_BITS = ((LABEL_BAD_OFFSETS, "tracklet offsets out of order or outside the rows"),
                (LABEL_BAD_FRAME, "a frame index outside the frames or not ascending along its tracklet"),
-               (LABEL_BAD_PREFIX, "more missing frames than output rows"))
+               (LABEL_BAD_PREFIX, "more missing frames than output rows"),
+               (LABEL_BAD_CAMERA, "a camera index outside the cameras"),
+               (LABEL_BAD_ERROR, "a reprojection error that is not finite at a round's winning candidate"))
 
 
 def label_status(device, status=None):
@@ -1986,3 +1989,67 @@ def label_interpolate(offsets, cols, frame, all_ts, rows, status=None):
                                             rows, ws.data_ptr(), _hip.ptr(out), _hip.ptr(out_src), _hip.ptr(out_frame),
                                             total.data_ptr(), status.data_ptr(), _hip.stream()), "rn_label_interpolate")
     return out, out_src, out_frame, total, status
+
+
+# ------------------------------------------------------------------------------------------------ re-basing labels
+LABEL_REBASE_MAX_GRID = 16         # RN_LABEL_REBASE_MAX_GRID
+LABEL_REBASE_MAX_ROUNDS = 8        # RN_LABEL_REBASE_MAX_ROUNDS
+
+
+def label_rebase_radii(search_rad=50, stop=1):
+    """The radii of seems_to_be_working.py:1682-1706, by the reference's own ``search_rad /= 5``: [50, 10.0, 2.0]."""
+    radii = []
+    while search_rad > stop:
+        radii.append(search_rad)
+        search_rad /= 5
+    return radii
+
+
+def label_rebase(state6, cam, P1_old, P2_old, P1_new, P2_new, radii, grid=11, status=None):
+    """seems_to_be_working.py:1677-1709 for every box, one wave each: state6 fp64 [n,6] = (x, y, l, w, h, direction), cam int32
+    [n], P1_* fp64 [n_cam,3,4] (or [n_cam,12]), P2_* alike or None (no wrapper switch), radii fp64 [rounds] on the device,
+    2 <= grid <= 16 -> (centre fp64 [n,2], err fp64 [n], idx int32 [n, rounds], status).  A box the kernel leaves out (its
+    status bit is set) keeps NaN / -1."""
+    lib = _hip.load()
+    _hip.need_gpu(state6, cam, P1_old, P2_old, P1_new, P2_new, radii)
+    specs = [("state6", state6, torch.float64), ("cam", cam, torch.int32), ("P1_old", P1_old, torch.float64),
+             ("P1_new", P1_new, torch.float64), ("radii", radii, torch.float64)]
+    specs += [(k, v, torch.float64) for k, v in (("P2_old", P2_old), ("P2_new", P2_new)) if v is not None]
+    _mot_typed("label_rebase", *specs)
+    n, n_cam, rounds, grid = state6.shape[0], P1_old.shape[0], radii.numel(), int(grid)
+    if state6.dim() != 2 or state6.shape[1] != 6 or tuple(cam.shape) != (n,) or radii.dim() != 1 or n >= 2 ** 31:
+        raise RuntimeError("label_rebase: state6 is fp64 [n,6], cam int32 [n], radii fp64 [rounds]")
+    for k, v in (("P1_old", P1_old), ("P2_old", P2_old), ("P1_new", P1_new), ("P2_new", P2_new)):
+        if v is not None and (v.numel() != n_cam * 12 or v.shape[0] != n_cam):
+            raise RuntimeError("label_rebase: %s is fp64 [n_cam,3,4] for the %d cameras of P1_old" % (k, n_cam))
+    if not 2 <= grid <= LABEL_REBASE_MAX_GRID or not 1 <= rounds <= LABEL_REBASE_MAX_ROUNDS or n_cam > LABEL_MAX_CAMS:
+        raise RuntimeError("label_rebase: 2 <= grid <= %d, 1 <= rounds <= %d, at most %d cameras"
+                           % (LABEL_REBASE_MAX_GRID, LABEL_REBASE_MAX_ROUNDS, LABEL_MAX_CAMS))
+    dev = state6.device
+    status = label_status(dev, status)
+    centre = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    err = torch.empty(n, dtype=torch.float64, device=dev)
+    idx = torch.empty((n, rounds), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_rebase(_hip.ptr(state6), _hip.ptr(cam), n, _hip.ptr(P1_old), _hip.ptr(P2_old), _hip.ptr(P1_new),
+                                       _hip.ptr(P2_new), n_cam, radii.data_ptr(), rounds, grid, _hip.ptr(centre), _hip.ptr(err),
+                                       _hip.ptr(idx), status.data_ptr(), _hip.stream()), "rn_label_rebase")
+    return centre, err, idx, status
+
+
+def label_offset_y(xy, coef, y_straight, direction, reverse=False):
+    """seems_to_be_working.py:1792-1802 for every box: xy fp64 [n,2], coef fp64 [n,3] = (p2, p1, p0), y_straight fp64 [n]
+    (subtracted from the offset where direction is -1), direction int32 [n] -> y fp64 [n], y - offset or, reverse, y + offset."""
+    lib = _hip.load()
+    _hip.need_gpu(xy, coef, y_straight, direction)
+    _mot_typed("label_offset_y", ("xy", xy, torch.float64), ("coef", coef, torch.float64), ("y_straight", y_straight, torch.float64),
+               ("direction", direction, torch.int32))
+    n = xy.shape[0]
+    if xy.dim() != 2 or xy.shape[1] != 2 or tuple(coef.shape) != (n, 3) or tuple(y_straight.shape) != (n,) or \
+            tuple(direction.shape) != (n,):
+        raise RuntimeError("label_offset_y: xy is fp64 [n,2], coef fp64 [n,3], y_straight fp64 [n], direction int32 [n]")
+    out = torch.empty(n, dtype=torch.float64, device=xy.device)
+    with torch.cuda.device(xy.device):
+        _hip.check(lib.rn_label_offset_y(_hip.ptr(xy), _hip.ptr(coef), _hip.ptr(y_straight), _hip.ptr(direction), n,
+                                         int(bool(reverse)), _hip.ptr(out), _hip.stream()), "rn_label_offset_y")
+    return out

@@ -47,6 +47,8 @@ Operator                                         reference code it stands for
                                                  estimate_projection_error (the samples)    2249-2357
   label_outliers(offsets, cols, frame, F, visit) Annotator.remove_outliers             seems_to_be_working.py:2192-2233
   label_interpolate(offsets, cols, frame, ts, n) Annotator.interpolate, every object   seems_to_be_working.py:780-836
+  label_rebase(state6, cam, 4 x P, radii, grid)  Annotator.replace_homgraphy's search  seems_to_be_working.py:1677-1709
+  label_offset_y(xy, coef, y_straight, dir, rev) Annotator.offset_box_y, every box     seems_to_be_working.py:1779-1805
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -640,3 +642,32 @@ def _(offsets, cols, frame, all_ts, rows):
     e = cols.new_empty
     return (e((rows, 3), dtype=torch.float64), e((rows,), dtype=torch.int32), e((rows,), dtype=torch.int32),
             e((1,), dtype=torch.int64), e((1,), dtype=torch.int32))
+
+
+# ---- re-basing labels (csrc/label_rebase.hip): label_rebase returns the status word last, like the audit's ops
+OPERATORS += ("label_rebase", "label_offset_y")
+
+
+@_lib.custom_op(NS + "::label_rebase", mutates_args=(), device_types="cuda")
+def label_rebase(state6: torch.Tensor, cam: torch.Tensor, P1_old: torch.Tensor, P2_old: Optional[torch.Tensor],
+                 P1_new: torch.Tensor, P2_new: Optional[torch.Tensor], radii: torch.Tensor,
+                 grid: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_rebase(state6, cam, P1_old, P2_old, P1_new, P2_new, radii, grid)
+
+
+@label_rebase.register_fake
+def _(state6, cam, P1_old, P2_old, P1_new, P2_new, radii, grid):
+    n, e = state6.shape[0], state6.new_empty
+    return (e((n, 2), dtype=torch.float64), e((n,), dtype=torch.float64), e((n, radii.shape[0]), dtype=torch.int32),
+            e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::label_offset_y", mutates_args=(), device_types="cuda")
+def label_offset_y(xy: torch.Tensor, coef: torch.Tensor, y_straight: torch.Tensor, direction: torch.Tensor,
+                   reverse: bool) -> torch.Tensor:
+    return ops.label_offset_y(xy, coef, y_straight, direction, reverse)
+
+
+@label_offset_y.register_fake
+def _(xy, coef, y_straight, direction, reverse):
+    return xy.new_empty((xy.shape[0],), dtype=torch.float64)

@@ -1264,6 +1264,37 @@ int rn_label_interpolate(const int64_t *offsets, const double *cols, const int32
                          int64_t R, int64_t F, int n_cam, int64_t U, void *workspace, double *out, int32_t *out_src,
                          int32_t *out_frame, int64_t *total, int32_t *status, void *stream);
 
+/* ---- re-basing multi-camera labels (csrc/label_rebase.hip): the passes of the annotator that act on the audit ---------------
+ * Annotator.replace_homgraphy (seems_to_be_working.py:1629-1730) and offset_box_y (:1779-1805, the arithmetic of replace_y,
+ * :1733-1776).  fp64 with one rounding per operation.  rn_label_rebase ORs its bits into the status word of the audit (int32,
+ * zeroed by the caller): a bad item is left out, its centre and err stay NaN and its idx -1.
+ *   rn_label_rebase    one wave per box.  state6 fp64 [n,6] = (x, y, l, w, h, direction), cam int32 [n]; P1_old, P2_old, P1_new,
+ *                      P2_new fp64 [n_cam,12], a P2 of NULL: no Homography_Wrapper switch.  The old box's image footprint
+ *                      (:1677-1678): the six values rounded to fp32, the fp32 corners of homography.py:305-320, projected
+ *                      with the old matrices (homography.py:438-476, 849-856).  Per round r < rounds, around the centre (the
+ *                      box's x, y at first): x = np.linspace(cx - radii[r], cx + radii[r], grid), element k = k * step + start
+ *                      with step = (stop - start) / (grid - 1), the last element stop itself; y alike; candidate ix * grid + iy
+ *                      is the fp64 state (x[ix], y[iy], l, w, h, direction) (:1685-1691), its corners computed in fp64 and each
+ *                      rounded once to fp32 (homography.py:307-318 writes them into a float32 tensor), the wrapper switch taken
+ *                      per candidate on that corner-0 y > 60, projected with the new matrices.  Its error (:1701): m_k = (dx *
+ *                      dx + dy * dy) / 2 over the bottom corners k < 4, err = (((m0 + m1) + m2) + m3) / 4.  The first smallest
+ *                      index wins, as torch.argmin picks it (:1704), and the centre moves to (x[idx / grid], y[idx % grid])
+ *                      (:1705).  centre fp64 [n,2], err fp64 [n] = the last round's minimum (:1709), idx int32 [n, rounds].
+ *                      2 <= grid <= RN_LABEL_REBASE_MAX_GRID, 1 <= rounds <= RN_LABEL_REBASE_MAX_ROUNDS; the caller computes
+ *                      radii with the reference's own `search_rad /= 5` (:1682, :1706).
+ *   rn_label_offset_y  one thread per box (:1792-1802): xy fp64 [n,2], coef fp64 [n,3] = the (p2, p1, p0) the host looked up
+ *                      under camera + "_EB" | "_WB", y_offset = ((x * x) * p2 + x * p1) + p0, minus y_straight[i] where
+ *                      direction[i] == -1; out fp64 [n] = y - y_offset, or y + y_offset with reverse. */
+#define RN_LABEL_REBASE_MAX_GRID 16
+#define RN_LABEL_REBASE_MAX_ROUNDS 8
+#define RN_LABEL_BAD_CAMERA 8         /* status: a camera index outside the n_cam cameras */
+#define RN_LABEL_BAD_ERROR 16         /* the error at a round's winning candidate is not finite */
+int rn_label_rebase(const double *state6, const int32_t *cam, int64_t n, const double *P1_old, const double *P2_old,
+                    const double *P1_new, const double *P2_new, int n_cam, const double *radii, int rounds, int grid,
+                    double *centre, double *err, int32_t *idx, int32_t *status, void *stream);
+int rn_label_offset_y(const double *xy, const double *coef, const double *y_straight, const int32_t *direction, int64_t n,
+                      int reverse, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
