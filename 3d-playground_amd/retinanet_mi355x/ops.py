@@ -1879,11 +1879,13 @@ LABEL_MAX_CAMS = 1024              # RN_LABEL_MAX_CAMS
 LABEL_GUARD, LABEL_FOUND_CUR, LABEL_FOUND_PREV = 1, 2, 4
 LABEL_BAD_OFFSETS, LABEL_BAD_FRAME, LABEL_BAD_PREFIX = 1, 2, 4
 LABEL_BAD_CAMERA, LABEL_BAD_ERROR = 8, 16                      # of label_rebase
+LABEL_BAD_TABLE = 32                                           # of the spline kernels
 _LABEL_BITS = ((LABEL_BAD_OFFSETS, "tracklet offsets out of order or outside the rows"),
                (LABEL_BAD_FRAME, "a frame index outside the frames or not ascending along its tracklet"),
                (LABEL_BAD_PREFIX, "more missing frames than output rows"),
                (LABEL_BAD_CAMERA, "a camera index outside the cameras"),
-               (LABEL_BAD_ERROR, "a reprojection error that is not finite at a round's winning candidate"))
+               (LABEL_BAD_ERROR, "a reprojection error that is not finite at a round's winning candidate"),
+               (LABEL_BAD_TABLE, "a spline group, wave, spline index or row range outside its table"))
 
 
 def label_status(device, status=None):
@@ -2053,3 +2055,175 @@ def label_offset_y(xy, coef, y_straight, direction, reverse=False):
         _hip.check(lib.rn_label_offset_y(_hip.ptr(xy), _hip.ptr(coef), _hip.ptr(y_straight), _hip.ptr(direction), n,
                                          int(bool(reverse)), _hip.ptr(out), _hip.stream()), "rn_label_offset_y")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ spline trajectories
+SPLINE_GRP, SPLINE_WS_COLS, SPLINE_FIGS, SPLINE_MAX_NCAP = 8, 19, 5, 4096     # RN_SPLINE_*
+SPLINE_UNUSED, SPLINE_STUCK, SPLINE_REJECTED = 97, 98, 99
+SPLINE_METRICS = {"ape": 0}                                    # any other metric: the reference's ``else`` branch (1)
+
+
+def spline_metric(metric):
+    return SPLINE_METRICS.get(metric, 1) if isinstance(metric, str) else int(metric)
+
+
+def spline_waves(grp):
+    """Host side of ``spline_fit``: grp int32 [G, 8] (numpy) = (row0, m, k, ncap, cand0, ncand, -, axis) -> waves int32 [NW, 2] =
+    (group, first candidate); column 6 of grp is filled with each group's first wave.  The 64 lanes of a wave are consecutive
+    candidates of one group."""
+    import numpy as np
+    waves, w = [], 0
+    for g in range(len(grp)):
+        grp[g, 6] = w
+        for c0 in range(0, int(grp[g, 5]), 64):
+            waves.append((g, c0))
+            w += 1
+    return np.array(waves, np.int32).reshape(-1, 2)
+
+
+def label_box_weights(state6, cam, P1, P2=None, status=None):
+    """seems_to_be_working.py:1186-1196 for every box: state6 fp64 [n,6] = (x, y, l, w, h, direction), cam int32 [n], P1 / P2 fp64
+    [n_cam,12] (P2 None: no wrapper switch) -> (out fp64 [n,4] = (x_weight, y_weight, x_diff, y_diff), status)."""
+    lib = _hip.load()
+    _hip.need_gpu(state6, cam, P1, P2)
+    specs = [("state6", state6, torch.float64), ("cam", cam, torch.int32), ("P1", P1, torch.float64)]
+    _mot_typed("label_box_weights", *(specs + ([("P2", P2, torch.float64)] if P2 is not None else [])))
+    n, n_cam = state6.shape[0], P1.shape[0]
+    if state6.dim() != 2 or state6.shape[1] != 6 or tuple(cam.shape) != (n,) or P1.numel() != n_cam * 12 or n >= 2 ** 31 or \
+            not 1 <= n_cam <= LABEL_MAX_CAMS or (P2 is not None and tuple(P2.shape) != tuple(P1.shape)):
+        raise RuntimeError("label_box_weights: state6 is fp64 [n,6], cam int32 [n], P1 and P2 fp64 [n_cam,12]")
+    dev = state6.device
+    status = label_status(dev, status)
+    out = torch.empty((n, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_box_weights(_hip.ptr(state6), _hip.ptr(cam), n, _hip.ptr(P1), _hip.ptr(P2), n_cam, _hip.ptr(out),
+                                            status.data_ptr(), _hip.stream()), "rn_label_box_weights")
+    return out, status
+
+
+def _spline_rows(what, grp, tx, *cols):
+    _mot_typed(what, ("grp", grp, torch.int32), ("tx", tx, torch.float64), *[("column", c, torch.float64) for c in cols])
+    if grp.dim() != 2 or grp.shape[1] != SPLINE_GRP or tx.dim() != 1 or any(tuple(c.shape) != tuple(tx.shape) for c in cols) or \
+            grp.shape[0] >= 2 ** 31 or tx.numel() >= 2 ** 31:
+        raise RuntimeError("%s: grp is int32 [G,%d], tx and the other columns fp64 [R]" % (what, SPLINE_GRP))
+    return grp.shape[0], tx.numel()
+
+
+def _spline_ncap(what, ncap):
+    ncap = int(ncap)
+    if not 6 <= ncap <= SPLINE_MAX_NCAP:
+        raise RuntimeError("%s: 6 <= ncap <= %d" % (what, SPLINE_MAX_NCAP))
+    return ncap
+
+
+def spline_workspace_bytes(n_waves, ncap):
+    return int(_hip.load().rn_spline_fit_workspace_bytes(int(n_waves), int(ncap)))
+
+
+def spline_fit(grp, waves, tx, val, wt, s, ncap, workspace=None, status=None):
+    """FITPACK curfit (iopt = 0) for every candidate smoothing factor, one lane each: grp int32 [G,8] and waves int32 [NW,2] from
+    ``spline_waves``, tx / val / wt fp64 [R], s fp64 [NC], ncap = the largest knot count any lane may reach -> (workspace fp64
+    [19 * ncap, NW * 64] (row 0.. the knots t, row ncap.. the coefficients c of every lane), n int32 [NW * 64], ier int32,
+    fp fp64, iterations int32, status).  ``workspace``: a tensor of a former call to reuse (at least as large)."""
+    lib = _hip.load()
+    _hip.need_gpu(grp, waves, tx, val, wt, s, workspace)
+    G, R = _spline_rows("spline_fit", grp, tx, val, wt)
+    _mot_typed("spline_fit", ("waves", waves, torch.int32), ("s", s, torch.float64))
+    ncap = _spline_ncap("spline_fit", ncap)
+    if waves.dim() != 2 or waves.shape[1] != 2 or s.dim() != 1 or waves.shape[0] >= 2 ** 25 or s.numel() >= 2 ** 31:
+        raise RuntimeError("spline_fit: waves is int32 [NW,2], s fp64 [NC]")
+    NW, dev = waves.shape[0], tx.device
+    NL = NW * 64
+    status = label_status(dev, status)
+    need = SPLINE_WS_COLS * ncap * NL
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise RuntimeError("spline_fit: the workspace is a contiguous fp64 tensor of at least %d elements" % need)
+    n = torch.empty(NL, dtype=torch.int32, device=dev)
+    ier = torch.empty(NL, dtype=torch.int32, device=dev)
+    fp = torch.empty(NL, dtype=torch.float64, device=dev)
+    iters = torch.empty(NL, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_spline_fit(_hip.ptr(grp), G, _hip.ptr(waves), NW, _hip.ptr(tx), _hip.ptr(val), _hip.ptr(wt), R, _hip.ptr(s),
+                                     s.numel(), ncap, workspace.data_ptr(), _hip.ptr(n), _hip.ptr(ier), _hip.ptr(fp), _hip.ptr(iters),
+                                     status.data_ptr(), _hip.stream()), "rn_spline_fit")
+    return workspace.reshape(-1)[:need].view(SPLINE_WS_COLS * ncap, NL), n, ier, fp, iters, status
+
+
+def spline_select(grp, tx, val, wt, wscore, n_cand, ncap, workspace, n, ier, fp, metric="ape", status=None):
+    """seems_to_be_working.py:1238-1294 for every group, one workgroup each, on the output of ``spline_fit`` -> (scores fp64 [NC]
+    (NaN: skipped), win int32 [G,3] = (candidate or -1, n, ier), figures fp64 [G,5] = (fp, score, sqrt(mean r^2), sqrt(mean (w
+    r)^2), sqrt(max (w r)^2)), t fp64 [G, ncap], c fp64 [G, ncap], status)."""
+    lib = _hip.load()
+    _hip.need_gpu(grp, tx, val, wt, wscore, workspace, n, ier, fp)
+    G, R = _spline_rows("spline_select", grp, tx, val, wt, wscore)
+    _mot_typed("spline_select", ("workspace", workspace, torch.float64), ("n", n, torch.int32), ("ier", ier, torch.int32),
+               ("fp", fp, torch.float64))
+    ncap, NC, NL = _spline_ncap("spline_select", ncap), int(n_cand), n.numel()
+    if NL % 64 or tuple(ier.shape) != (NL,) or tuple(fp.shape) != (NL,) or workspace.numel() < SPLINE_WS_COLS * ncap * NL or \
+            not 0 <= NC < 2 ** 31:
+        raise RuntimeError("spline_select: n, ier, fp are [NW * 64] and the workspace is spline_fit's for the same ncap")
+    dev = tx.device
+    status = label_status(dev, status)
+    scores = torch.empty(NC, dtype=torch.float64, device=dev)
+    win = torch.empty((G, 3), dtype=torch.int32, device=dev)
+    fig = torch.empty((G, SPLINE_FIGS), dtype=torch.float64, device=dev)
+    t = torch.empty((G, ncap), dtype=torch.float64, device=dev)
+    c = torch.empty((G, ncap), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_spline_select(_hip.ptr(grp), G, _hip.ptr(tx), _hip.ptr(val), _hip.ptr(wt), _hip.ptr(wscore), R, NC, NL // 64,
+                                        ncap, workspace.data_ptr(), _hip.ptr(n), _hip.ptr(ier), _hip.ptr(fp), spline_metric(metric),
+                                        _hip.ptr(scores), _hip.ptr(win), _hip.ptr(fig), _hip.ptr(t), _hip.ptr(c), status.data_ptr(),
+                                        _hip.stream()), "rn_spline_select")
+    return scores, win, fig, t, c, status
+
+
+def _spline_pack(what, st, sc, snk):
+    _mot_typed(what, ("st", st, torch.float64), ("sc", sc, torch.float64), ("snk", snk, torch.int32))
+    if st.dim() != 2 or tuple(sc.shape) != tuple(st.shape) or tuple(snk.shape) != (st.shape[0], 2) or st.shape[0] >= 2 ** 31:
+        raise RuntimeError("%s: st and sc are fp64 [S, ncap], snk int32 [S,2] = (n, k)" % what)
+    return st.shape[0], _spline_ncap(what, st.shape[1])
+
+
+def spline_eval(st, sc, snk, qs, qt):
+    """FITPACK splev with extrapolation, one thread per query: st / sc fp64 [S, ncap] the knots and coefficients, snk int32 [S,2] =
+    (n, k) (n = 0: no spline), qs int32 [Q] the spline of every query, qt fp64 [Q] -> fp64 [Q] (NaN without a spline)."""
+    lib = _hip.load()
+    _hip.need_gpu(st, sc, snk, qs, qt)
+    S, ncap = _spline_pack("spline_eval", st, sc, snk)
+    _mot_typed("spline_eval", ("qs", qs, torch.int32), ("qt", qt, torch.float64))
+    if qs.dim() != 1 or tuple(qt.shape) != tuple(qs.shape):
+        raise RuntimeError("spline_eval: qs is int32 [Q], qt fp64 [Q]")
+    out = torch.empty(qs.numel(), dtype=torch.float64, device=st.device)
+    with torch.cuda.device(st.device):
+        _hip.check(lib.rn_spline_eval(_hip.ptr(st), _hip.ptr(sc), _hip.ptr(snk), S, ncap, _hip.ptr(qs), _hip.ptr(qt), qs.numel(),
+                                      _hip.ptr(out), _hip.stream()), "rn_spline_eval")
+    return out
+
+
+def label_ts_shift(st, sc, snk, off, rs, rx, base, run, shifts, use_run=True, metric="ape", status=None):
+    """seems_to_be_working.py:1416-1442 for every (frame, camera) entry, one wave each: the packed splines of ``spline_eval``, off
+    int64 [E+1] the rows of every entry, rs int32 [Rr] / rx fp64 [Rr] the spline and the label x of its kept objects, base / run
+    fp64 [E] the camera's time stamp and running error, shifts fp64 [trials < 64] -> (best_t fp64 [E], errs fp64 [E,2] = (best,
+    initial), best_i int32 [E], status)."""
+    lib = _hip.load()
+    _hip.need_gpu(st, sc, snk, off, rs, rx, base, run, shifts)
+    S, ncap = _spline_pack("label_ts_shift", st, sc, snk)
+    _mot_typed("label_ts_shift", ("off", off, torch.int64), ("rs", rs, torch.int32), ("rx", rx, torch.float64),
+               ("base", base, torch.float64), ("run", run, torch.float64), ("shifts", shifts, torch.float64))
+    E, Rr, trials = off.numel() - 1, rs.numel(), shifts.numel()
+    if off.dim() != 1 or E < 0 or rs.dim() != 1 or tuple(rx.shape) != (Rr,) or tuple(base.shape) != (E,) or tuple(run.shape) != (E,) \
+            or shifts.dim() != 1 or not 1 <= trials < 64 or E >= 2 ** 31 or Rr >= 2 ** 31:
+        raise RuntimeError("label_ts_shift: off is int64 [E+1], rs int32 [Rr], rx fp64 [Rr], base and run fp64 [E], 1 <= trials < 64")
+    dev = st.device
+    status = label_status(dev, status)
+    best_t = torch.empty(E, dtype=torch.float64, device=dev)
+    errs = torch.empty((E, 2), dtype=torch.float64, device=dev)
+    best_i = torch.empty(E, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_ts_shift(_hip.ptr(st), _hip.ptr(sc), _hip.ptr(snk), S, ncap, _hip.ptr(off), _hip.ptr(rs), _hip.ptr(rx), E,
+                                         Rr, _hip.ptr(base), _hip.ptr(run), _hip.ptr(shifts), trials, int(bool(use_run)),
+                                         spline_metric(metric), _hip.ptr(best_t), _hip.ptr(errs), _hip.ptr(best_i), status.data_ptr(),
+                                         _hip.stream()), "rn_label_ts_shift")
+    return best_t, errs, best_i, status

@@ -49,6 +49,10 @@ Operator                                         reference code it stands for
   label_interpolate(offsets, cols, frame, ts, n) Annotator.interpolate, every object   seems_to_be_working.py:780-836
   label_rebase(state6, cam, 4 x P, radii, grid)  Annotator.replace_homgraphy's search  seems_to_be_working.py:1677-1709
   label_offset_y(xy, coef, y_straight, dir, rev) Annotator.offset_box_y, every box     seems_to_be_working.py:1779-1805
+  label_box_weights(state6, cam, P1, P2)         Annotator.create_trajectory's weights seems_to_be_working.py:1186-1196
+  spline_fit / spline_select / spline_eval       ... its UnivariateSpline fits (FITPACK     seems_to_be_working.py:1233-1294
+                                                 curfit), scores and winner; splev
+  label_ts_shift(splines, entries, shifts, ..)   Annotator.adjust_ts_with_trajectories seems_to_be_working.py:1416-1442
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -671,3 +675,68 @@ def label_offset_y(xy: torch.Tensor, coef: torch.Tensor, y_straight: torch.Tenso
 @label_offset_y.register_fake
 def _(xy, coef, y_straight, direction, reverse):
     return xy.new_empty((xy.shape[0],), dtype=torch.float64)
+
+
+# ---- spline trajectories (csrc/label_spline.hip): the status word of the audit comes last where an op has one
+OPERATORS += ("label_box_weights", "spline_fit", "spline_select", "spline_eval", "label_ts_shift")
+
+
+@_lib.custom_op(NS + "::label_box_weights", mutates_args=(), device_types="cuda")
+def label_box_weights(state6: torch.Tensor, cam: torch.Tensor, P1: torch.Tensor,
+                      P2: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.label_box_weights(state6, cam, P1, P2)
+
+
+@label_box_weights.register_fake
+def _(state6, cam, P1, P2):
+    return state6.new_empty((state6.shape[0], 4), dtype=torch.float64), state6.new_empty((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::spline_fit", mutates_args=(), device_types="cuda")
+def spline_fit(grp: torch.Tensor, waves: torch.Tensor, tx: torch.Tensor, val: torch.Tensor, wt: torch.Tensor, s: torch.Tensor,
+               ncap: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.spline_fit(grp, waves, tx, val, wt, s, ncap)
+
+
+@spline_fit.register_fake
+def _(grp, waves, tx, val, wt, s, ncap):
+    NL, e = waves.shape[0] * 64, tx.new_empty
+    return (e((ops.SPLINE_WS_COLS * ncap, NL), dtype=torch.float64), e((NL,), dtype=torch.int32), e((NL,), dtype=torch.int32),
+            e((NL,), dtype=torch.float64), e((NL,), dtype=torch.int32), e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::spline_select", mutates_args=(), device_types="cuda")
+def spline_select(grp: torch.Tensor, tx: torch.Tensor, val: torch.Tensor, wt: torch.Tensor, wscore: torch.Tensor, n_cand: int,
+                  ncap: int, workspace: torch.Tensor, n: torch.Tensor, ier: torch.Tensor, fp: torch.Tensor,
+                  metric: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.spline_select(grp, tx, val, wt, wscore, n_cand, ncap, workspace, n, ier, fp, metric)
+
+
+@spline_select.register_fake
+def _(grp, tx, val, wt, wscore, n_cand, ncap, workspace, n, ier, fp, metric):
+    G, e = grp.shape[0], tx.new_empty
+    return (e((n_cand,), dtype=torch.float64), e((G, 3), dtype=torch.int32), e((G, ops.SPLINE_FIGS), dtype=torch.float64),
+            e((G, ncap), dtype=torch.float64), e((G, ncap), dtype=torch.float64), e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::spline_eval", mutates_args=(), device_types="cuda")
+def spline_eval(st: torch.Tensor, sc: torch.Tensor, snk: torch.Tensor, qs: torch.Tensor, qt: torch.Tensor) -> torch.Tensor:
+    return ops.spline_eval(st, sc, snk, qs, qt)
+
+
+@spline_eval.register_fake
+def _(st, sc, snk, qs, qt):
+    return qt.new_empty((qs.shape[0],), dtype=torch.float64)
+
+
+@_lib.custom_op(NS + "::label_ts_shift", mutates_args=(), device_types="cuda")
+def label_ts_shift(st: torch.Tensor, sc: torch.Tensor, snk: torch.Tensor, off: torch.Tensor, rs: torch.Tensor, rx: torch.Tensor,
+                   base: torch.Tensor, run: torch.Tensor, shifts: torch.Tensor, use_run: bool,
+                   metric: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_ts_shift(st, sc, snk, off, rs, rx, base, run, shifts, use_run, metric)
+
+
+@label_ts_shift.register_fake
+def _(st, sc, snk, off, rs, rx, base, run, shifts, use_run, metric):
+    E, e = base.shape[0], base.new_empty
+    return (e((E,), dtype=torch.float64), e((E, 2), dtype=torch.float64), e((E,), dtype=torch.int32), e((1,), dtype=torch.int32))

@@ -1295,6 +1295,63 @@ int rn_label_rebase(const double *state6, const int32_t *cam, int64_t n, const d
 int rn_label_offset_y(const double *xy, const double *coef, const double *y_straight, const int32_t *direction, int64_t n,
                       int reverse, double *out, void *stream);
 
+/* ---- smoothing-spline trajectories of multi-camera labels (csrc/label_spline.hip) -------------------------------------------
+ * Annotator.create_trajectory (seems_to_be_working.py:1137-1314), get_splines (:1338-1350), gen_trajectories (:1317-1336),
+ * adjust_ts_with_trajectories (:1353-1458).  fp64 with one rounding per operation, in FITPACK's order.  The status word is the
+ * audit's (int32, zeroed by the caller, bits OR-ed in); a bad item is left out.
+ *   rn_label_box_weights  one thread per box (:1186-1196): state6 fp64 [n,6] rounded to fp32, the fp32 corners of
+ *                         homography.py:305-320 projected in fp64 with the box's own camera (P2 of NULL: no wrapper switch);
+ *                         out fp64 [n,4] = (x_weight, y_weight, x_diff, y_diff): diff = the norm of the mean of the two corner
+ *                         differences (corners 0,1 - 2,3 along the length, 0,2 - 1,3 across), weight = diff / l or / w.
+ *   rn_spline_fit         FITPACK curfit (fpcurf, iopt = 0, xb = x[0], xe = x[m-1], tol = 1e-3, maxit = 20, nest = max(m + k + 1,
+ *                         2k + 3)), one lane per candidate smoothing factor.  grp int32 [G, RN_SPLINE_GRP] = (row0, m, k, ncap,
+ *                         cand0, ncand, wave0, axis) per (object, axis): rows [row0, row0 + m) of tx / val / wt fp64 [R] (abscissae
+ *                         ascending, ordinates, weights), k in {2, 3}, candidates s[cand0 .. cand0 + ncand), lanes [wave0 * 64,
+ *                         ...).  waves int32 [NW, 2] = (group, first candidate) of every wave.  A lane whose knot count n would
+ *                         pass ncap (<= the launch's ncap <= RN_SPLINE_MAX_NCAP; the caller sets it to the reference's knot limit
+ *                         + 2k, at most m + k + 1) stops with ier RN_SPLINE_REJECTED; RN_SPLINE_STUCK where FITPACK's fpknot
+ *                         finds no interval to split (it reads an unset index there); RN_SPLINE_UNUSED on a padding lane.
+ *                         workspace: RN_SPLINE_WS_COLS columns of ncap doubles per lane, element e of lane L at [e * NW * 64 + L],
+ *                         columns t, c, z, fpint, nrdata, a (4), g (5), b (5).  out_n / out_ier / out_iter int32 [NW * 64], out_fp
+ *                         fp64 [NW * 64]; out_iter = least-squares rounds + iterations on p.
+ *   rn_spline_select      one workgroup per group: a candidate survives with ier <= 3 and a value at 0 that is not NaN (:1238);
+ *                         its score over the group's rows with the weights wscore, summed in ascending row order: metric 0
+ *                         sqrt(sum / m), metric 1 sqrt(max) on axis 0 and max on axis 1 (:1246-1255, :1269-1278); the first
+ *                         smallest below +inf wins.  scores fp64 [NC] (NaN: skipped), win int32 [G,3] = (candidate or -1, n, ier),
+ *                         wfig fp64 [G, RN_SPLINE_FIGS] = (fp, score, sqrt(mean r^2), sqrt(mean (wt r)^2), sqrt(max (wt r)^2)) of the
+ *                         winner (:1282-1294), wt_out / wc_out fp64 [G, ncap] = its knots and coefficients, zero-filled.
+ *   rn_spline_eval        one thread per query: FITPACK splev with extrapolation; st / sc fp64 [S, ncap], snk int32 [S,2] = (n, k),
+ *                         qs int32 [Q] (outside [0, S) or n = 0: NaN), qt fp64 [Q] -> out fp64 [Q].
+ *   rn_label_ts_shift     one wave per (frame, camera) entry e < E (:1416-1442): rows [off[e], off[e+1]) = its kept objects, rs
+ *                         int32 the spline, rx fp64 the label x.  Trial j < trials: time = (base[e] + shifts[j]) + run[e] (without
+ *                         use_run: base[e] + shifts[j]), error = sqrt(mean d^2) (metric 1: sqrt(max d^2)), d = fp32(spline(time)) -
+ *                         x in fp64, ascending rows; the first smallest below +inf wins.  best_t fp64 [E] (no winner: base[e]), errs
+ *                         fp64 [E,2] = (best, initial: sqrt(mean d^2) at base[e]), best_i int32 [E] (-1: none).  trials < 64. */
+#define RN_SPLINE_GRP 8
+#define RN_SPLINE_WS_COLS 19
+#define RN_SPLINE_FIGS 5
+#define RN_SPLINE_MAX_NCAP 4096
+#define RN_SPLINE_UNUSED 97           /* ier of a lane without a candidate */
+#define RN_SPLINE_STUCK 98            /* ... whose knot insertion found no interval */
+#define RN_SPLINE_REJECTED 99         /* ... stopped at the knot limit */
+#define RN_SPLINE_BAD_TABLE 32        /* status: a group, wave or row range outside its table */
+int64_t rn_spline_fit_workspace_bytes(int64_t n_waves, int ncap);
+int rn_label_box_weights(const double *state6, const int32_t *cam, int64_t n, const double *P1, const double *P2, int n_cam,
+                         double *out, int32_t *status, void *stream);
+int rn_spline_fit(const int32_t *grp, int64_t G, const int32_t *waves, int64_t NW, const double *tx, const double *val,
+                  const double *wt, int64_t R, const double *s, int64_t NC, int ncap, void *workspace, int32_t *out_n,
+                  int32_t *out_ier, double *out_fp, int32_t *out_iter, int32_t *status, void *stream);
+int rn_spline_select(const int32_t *grp, int64_t G, const double *tx, const double *val, const double *wt, const double *wscore,
+                     int64_t R, int64_t NC, int64_t NW, int ncap, const void *workspace, const int32_t *out_n,
+                     const int32_t *out_ier, const double *out_fp, int metric, double *scores, int32_t *win, double *wfig,
+                     double *wt_out, double *wc_out, int32_t *status, void *stream);
+int rn_spline_eval(const double *st, const double *sc, const int32_t *snk, int64_t S, int ncap, const int32_t *qs,
+                   const double *qt, int64_t Q, double *out, void *stream);
+int rn_label_ts_shift(const double *st, const double *sc, const int32_t *snk, int64_t S, int ncap, const int64_t *off,
+                      const int32_t *rs, const double *rx, int64_t E, int64_t Rr, const double *base, const double *run,
+                      const double *shifts, int trials, int use_run, int metric, double *best_t, double *errs, int32_t *best_i,
+                      int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
