@@ -117,6 +117,9 @@ SIGNATURES = {
     "rn_spline_eval": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "rn_label_ts_shift": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32,
                                   c_i32] + [c_vp] * 5),
+    "rn_label_series_workspace_bytes": (c_i64, [c_i64]),
+    "rn_label_series": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, c_f64, c_f64, c_i32] + [c_vp] * 8),
+    "rn_label_group_rmse": (c_i32, [c_vp, c_vp, c_i64, c_i64] + [c_vp] * 5),
 }
 
 class ConvDesc(ctypes.Structure):

@@ -1880,12 +1880,14 @@ LABEL_GUARD, LABEL_FOUND_CUR, LABEL_FOUND_PREV = 1, 2, 4
 LABEL_BAD_OFFSETS, LABEL_BAD_FRAME, LABEL_BAD_PREFIX = 1, 2, 4
 LABEL_BAD_CAMERA, LABEL_BAD_ERROR = 8, 16                      # of label_rebase
 LABEL_BAD_TABLE = 32                                           # of the spline kernels
+LABEL_BAD_GROUP = 64                                           # of label_group_rmse
 _LABEL_BITS = ((LABEL_BAD_OFFSETS, "tracklet offsets out of order or outside the rows"),
                (LABEL_BAD_FRAME, "a frame index outside the frames or not ascending along its tracklet"),
                (LABEL_BAD_PREFIX, "more missing frames than output rows"),
                (LABEL_BAD_CAMERA, "a camera index outside the cameras"),
                (LABEL_BAD_ERROR, "a reprojection error that is not finite at a round's winning candidate"),
-               (LABEL_BAD_TABLE, "a spline group, wave, spline index or row range outside its table"))
+               (LABEL_BAD_TABLE, "a spline group, wave, spline index or row range outside its table"),
+               (LABEL_BAD_GROUP, "group ids that do not ascend or lie outside the groups"))
 
 
 def label_status(device, status=None):
@@ -2227,3 +2229,59 @@ def label_ts_shift(st, sc, snk, off, rs, rx, base, run, shifts, use_run=True, me
                                          spline_metric(metric), _hip.ptr(best_t), _hip.ptr(errs), _hip.ptr(best_i), status.data_ptr(),
                                          _hip.stream()), "rn_label_ts_shift")
     return best_t, errs, best_i, status
+
+
+# ------------------------------------------------------------------------------------------------ label quality
+LABEL_SERIES_PLANES, LABEL_SERIES_MAX_LDS_ROWS = 7, 4096       # RN_LABEL_SERIES_*
+
+
+def label_series(offsets, cols, n_cam, lane=None, lds_rows=None, status=None):
+    """manual_annotator_state_v3.py:3847-3958 for every object, one workgroup each: the audit's table (offsets int64 [n_ids *
+    n_cam + 1], cols fp64 [R,3] = (x, y, timestamp)); lane (lo, hi) keeps the rows with lo < y < hi only; lds_rows, a power of
+    two in 2 .. 4096 (the default), is the largest object sorted in LDS, a longer one goes through a global workspace with the
+    same result -> (order int32 [R], keep uint8 [R], series fp64 [7, R] = t, x, y, v, vy, a, theta, counts int32 [n_ids,3] = (n,
+    m, feasible segments), figs fp64 [n_ids,2] = (range, variation), status): include/retinanet_mi355x.h."""
+    lib = _hip.load()
+    _hip.need_gpu(offsets, cols)
+    T, R = _label_table("label_series", offsets, cols)
+    n_cam = int(n_cam)
+    lds_rows = LABEL_SERIES_MAX_LDS_ROWS if lds_rows is None else int(lds_rows)
+    if not 1 <= n_cam <= LABEL_MAX_CAMS or T % n_cam:
+        raise RuntimeError("label_series: 1 <= n_cam <= %d divides the tracklet count" % LABEL_MAX_CAMS)
+    if not 2 <= lds_rows <= LABEL_SERIES_MAX_LDS_ROWS or lds_rows & (lds_rows - 1):
+        raise RuntimeError("label_series: lds_rows is a power of two, 2 .. %d" % LABEL_SERIES_MAX_LDS_ROWS)
+    lo, hi = (0.0, 0.0) if lane is None else (float(lane[0]), float(lane[1]))
+    n_ids, dev = T // n_cam, cols.device
+    status = label_status(dev, status)
+    ws = torch.empty(max(16, lib.rn_label_series_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+    order = torch.empty(R, dtype=torch.int32, device=dev)
+    keep = torch.empty(R, dtype=torch.uint8, device=dev)
+    series = torch.empty((LABEL_SERIES_PLANES, R), dtype=torch.float64, device=dev)
+    counts = torch.empty((n_ids, 3), dtype=torch.int32, device=dev)
+    figs = torch.empty((n_ids, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_series(offsets.data_ptr(), _hip.ptr(cols), R, n_cam, n_ids, int(lane is not None), lo, hi, lds_rows,
+                                       ws.data_ptr(), _hip.ptr(order), _hip.ptr(keep), _hip.ptr(series), _hip.ptr(counts),
+                                       _hip.ptr(figs), status.data_ptr(), _hip.stream()), "rn_label_series")
+    return order, keep, series, counts, figs, status
+
+
+def label_group_rmse(im, group, n_groups, status=None):
+    """manual_annotator_state_v3.py:3997-4000 for every group, one workgroup each: im fp64 [n,8,2] (``hg_to_im``), group int32
+    [n], ascending ids in [0, n_groups) -> (rmse fp64 [n_groups], mean fp64 [n_groups,2], count int32 [n_groups], status); an
+    empty group gives NaN, NaN, 0."""
+    lib = _hip.load()
+    _hip.need_gpu(im, group)
+    _mot_typed("label_group_rmse", ("im", im, torch.float64), ("group", group, torch.int32))
+    n, G = group.numel(), int(n_groups)
+    if group.dim() != 1 or tuple(im.shape) != (n, 8, 2) or n >= 2 ** 31 or not 0 <= G < 2 ** 31:
+        raise RuntimeError("label_group_rmse: im is fp64 [n,8,2], group int32 [n], 0 <= n_groups < 2^31")
+    dev = im.device
+    status = label_status(dev, status)
+    rmse = torch.empty(G, dtype=torch.float64, device=dev)
+    mean = torch.empty((G, 2), dtype=torch.float64, device=dev)
+    count = torch.empty(G, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_group_rmse(_hip.ptr(im), _hip.ptr(group), n, G, _hip.ptr(rmse), _hip.ptr(mean), _hip.ptr(count),
+                                           status.data_ptr(), _hip.stream()), "rn_label_group_rmse")
+    return rmse, mean, count, status

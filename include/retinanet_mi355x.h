@@ -1352,6 +1352,39 @@ int rn_label_ts_shift(const double *st, const double *sc, const int32_t *snk, in
                       const double *shifts, int trials, int use_run, int metric, double *best_t, double *errs, int32_t *best_i,
                       int32_t *status, void *stream);
 
+/* ---- scoring a multi-camera label set (csrc/label_quality.hip): the metrics of the later annotator --------------------------
+ * manual_annotator_state_v3.py: calculate_total_variation (:3843-3889), calculate_feasibility (:3891-3979), the data half of
+ * plot_trajectories_unified (:3634-3711, smooth = 1), the reduction of annotator_rmse (:3981-4007).  fp64 with one rounding per
+ * operation (atan2 aside).  The status word is the audit's (int32, zeroed by the caller, bits OR-ed in).
+ *   rn_label_series      one workgroup per object on the audit's table (offsets int64 [n_ids * n_cam + 1], cols fp64 [R,3] = (x, y,
+ *                        timestamp)): the rows of object j are [offsets[j * n_cam], offsets[(j + 1) * n_cam]), camera outer, frame
+ *                        inner.  With lane_on only rows with lane_lo < y < lane_hi take part (:3645-3646).  The n rows that do are
+ *                        sorted by (timestamp, position in the object's rows) -- the stable sort by time -- in LDS when the
+ *                        object's row count, rounded up to a power of two, is at most lds_rows (a power of two, 2 ..
+ *                        RN_LABEL_SERIES_MAX_LDS_ROWS), else in the workspace.  order int32 [R]: at [offsets[j * n_cam] + i], i <
+ *                        n, the row of the i-th sorted box, -1 behind; keep uint8 [R]: 1 for i = 0 and where t[i] >= t[i-1] +
+ *                        0.01 against the previous SORTED row (:3875-3878), 0 behind n.  series fp64 [RN_LABEL_SERIES_PLANES, R]:
+ *                        planes t, x, y, v, vy, a, theta of the m kept rows from the same first position, 0.0 behind: dt[i] =
+ *                        (t[i+1] - t[i]) + 1e-08, v[i] = -((x[i+1] - x[i]) / dt[i]), vy[i] = (y[i+1] - y[i]) / dt[i], a[i] =
+ *                        (v[i+1] - v[i]) / dt[i] on the extended v, the last value of each repeated (all 0.0 for m = 1); theta =
+ *                        atan2(vy, v) * 180 / pi.  counts int32 [n_ids,3] = (n, m, feasible segments: of the m - 1, those with v
+ *                        in (0, 140) and theta in (-25, 25) at both ends -- the reference's acceleration mask never enters, :3975);
+ *                        figs fp64 [n_ids,2] = (max(x) - min(x), sum |x[i] - x[i-1]| in ascending order) over the kept rows.
+ *                        offsets[0] != 0, offsets[n_ids * n_cam] != R or an object's range out of order: RN_LABEL_BAD_OFFSETS.
+ *   rn_label_group_rmse  one workgroup per group: im fp64 [n,8,2] image corners, group int32 [n] ascending ids in [0, n_groups)
+ *                        (else RN_LABEL_BAD_GROUP).  im_pos = (corner 2 + corner 3) / 2 (:3997); mean fp64 [n_groups,2] = sum /
+ *                        count, rmse fp64 [n_groups] = sqrt(sum(dx * dx + dy * dy) / count), sums in ascending row order; count
+ *                        int32 [n_groups]; an empty group: NaN, NaN, 0. */
+#define RN_LABEL_SERIES_PLANES 7
+#define RN_LABEL_SERIES_MAX_LDS_ROWS 4096   /* 48 KiB of keys and indices: three workgroups share the 160 KiB of a CU */
+#define RN_LABEL_BAD_GROUP 64         /* status: group ids that do not ascend or lie outside the groups */
+int64_t rn_label_series_workspace_bytes(int64_t R);
+int rn_label_series(const int64_t *offsets, const double *cols, int64_t R, int n_cam, int64_t n_ids, int lane_on, double lane_lo,
+                    double lane_hi, int lds_rows, void *workspace, int32_t *order, uint8_t *keep, double *series, int32_t *counts,
+                    double *figs, int32_t *status, void *stream);
+int rn_label_group_rmse(const double *im, const int32_t *group, int64_t n, int64_t n_groups, double *rmse, double *mean,
+                        int32_t *count, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

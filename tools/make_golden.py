@@ -498,6 +498,15 @@ def gen_label_trajectory():
                           stdout=subprocess.DEVNULL)
 
 
+def gen_label_quality():
+    """tests/golden/label_quality.npz: calculate_total_variation, calculate_feasibility and annotator_rmse of the reference's
+    later annotator on the scenes of tests/label_quality_cases.py.  Its own script (tools/make_golden_label_quality.py), in a
+    child process, for the reason gen_label_audit gives."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_label_quality.py"), "--out", OUT],
+                          stdout=subprocess.DEVNULL)
+
+
 def gen_replay():
     """tests/golden/replay.npz: the reference's own Data_Reader.plot_in over scripted cameras behind a recording cv2 stand-in.
     Its own script (tools/make_golden_replay.py), in a child process, for the reason gen_datareader gives."""
@@ -1681,7 +1690,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit", "label_rewrite", "label_trajectory"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit", "label_rewrite", "label_trajectory", "label_quality"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1736,6 +1745,8 @@ def main():
         gen_label_rewrite()
     if "label_trajectory" in which:
         gen_label_trajectory()
+    if "label_quality" in which:
+        gen_label_quality()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
