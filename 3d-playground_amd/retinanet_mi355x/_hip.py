@@ -110,6 +110,9 @@ SIGNATURES = {
     "rn_label_interpolate": (c_i32, [c_vp] * 4 + [c_i64] * 3 + [c_i32, c_i64] + [c_vp] * 7),
     "rn_label_rebase": (c_i32, [c_vp, c_vp, c_i64] + [c_vp] * 4 + [c_i32, c_vp, c_i32, c_i32] + [c_vp] * 5),
     "rn_label_offset_y": (c_i32, [c_vp] * 4 + [c_i64, c_i32, c_vp, c_vp]),
+    "rn_label_crop_windows": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_f32, c_f32, c_f32] + [c_vp] * 6),
+    "rn_label_best_anchor": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32] + [c_vp] * 5),
+    "rn_label_fit_box2d": (c_i32, [c_vp] * 5 + [c_i64, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32] + [c_vp] * 5),
     "rn_spline_fit_workspace_bytes": (c_i64, [c_i64, c_i32]),
     "rn_label_box_weights": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "rn_spline_fit": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32] + [c_vp] * 7),

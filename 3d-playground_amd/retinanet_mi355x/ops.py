@@ -2059,6 +2059,103 @@ def label_offset_y(xy, coef, y_straight, direction, reverse=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ detector-assisted labelling
+def _label_cameras(what, n, cam, P1, P2):
+    specs = [("cam", cam, torch.int32), ("P1", P1, torch.float64)] + ([] if P2 is None else [("P2", P2, torch.float64)])
+    _mot_typed(what, *specs)
+    n_cam = P1.shape[0] if P1.dim() else -1
+    if tuple(cam.shape) != (n,) or n >= 2 ** 31:
+        raise RuntimeError("%s: cam is int32 [n] for the n = %d boxes" % (what, n))
+    for k, v in (("P1", P1), ("P2", P2)):
+        if v is not None and (v.dim() < 2 or v.numel() != n_cam * 12 or v.shape[0] != n_cam):
+            raise RuntimeError("%s: %s is fp64 [n_cam,3,4] for the cameras of P1" % (what, k))
+    if n_cam > LABEL_MAX_CAMS:
+        raise RuntimeError("%s: at most %d cameras" % (what, LABEL_MAX_CAMS))
+    return n_cam
+
+
+def label_crop_windows(state6, cam, P1, P2, ber=1.2, width=1920, height=1080, status=None):
+    """manual_annotator_state_v3.py:662-673 and :707-717 for every box, one thread each: state6 fp32 [n,6] = (x, y, l, w, h,
+    direction), cam int32 [n], P1 fp64 [n_cam,3,4] (or [n_cam,12]), P2 alike or None (no wrapper switch) -> (crop_box fp32 [n,4],
+    rois fp32 [n,5] = (camera, window), win fp32 [n,3] = (minx, miny, scale), skipped uint8 [n], status).  A box whose crop box
+    leaves the frame is flagged in ``skipped`` and keeps NaN in rois and win, as the reference returns silently."""
+    lib = _hip.load()
+    _hip.need_gpu(state6, cam, P1, P2)
+    _mot_typed("label_crop_windows", ("state6", state6, torch.float32))
+    if state6.dim() != 2 or state6.shape[1] != 6:
+        raise RuntimeError("label_crop_windows: state6 is fp32 [n,6]")
+    n = state6.shape[0]
+    n_cam = _label_cameras("label_crop_windows", n, cam, P1, P2)
+    dev = state6.device
+    status = label_status(dev, status)
+    crop_box = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    rois = torch.empty((n, 5), dtype=torch.float32, device=dev)
+    win = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    skipped = torch.empty(n, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_crop_windows(_hip.ptr(state6), _hip.ptr(cam), n, _hip.ptr(P1), _hip.ptr(P2), n_cam, float(ber),
+                                             float(width), float(height), _hip.ptr(crop_box), _hip.ptr(rois), _hip.ptr(win),
+                                             _hip.ptr(skipped), status.data_ptr(), _hip.stream()), "rn_label_crop_windows")
+    return crop_box, rois, win, skipped, status
+
+
+def label_best_anchor(cls, reg, win, cs=112):
+    """manual_annotator_state_v3.py:731-740 for every crop, one wave each: cls fp32 [n,A,C] and reg fp32 [n,A,4] (the 2D
+    localiser's LOCALIZE outputs), win fp32 [n,3] = (minx, miny, scale) -> (box fp32 [n,4] in frame coordinates, anchor int32
+    [n], confidence fp32 [n], class int32 [n]).  torch.max / torch.argmax: a NaN counts as largest, equal values go to the
+    lower index."""
+    lib = _hip.load()
+    _hip.need_gpu(cls, reg, win)
+    _mot_typed("label_best_anchor", ("cls", cls, torch.float32), ("reg", reg, torch.float32), ("win", win, torch.float32))
+    if cls.dim() != 3 or cls.shape[1] < 1 or cls.shape[2] < 1 or tuple(reg.shape) != (cls.shape[0], cls.shape[1], 4) or \
+            tuple(win.shape) != (cls.shape[0], 3) or cls.shape[0] >= 2 ** 31 or cls.shape[1] * cls.shape[2] >= 2 ** 31:
+        raise RuntimeError("label_best_anchor: cls is fp32 [n,A,C] with A, C >= 1, reg fp32 [n,A,4], win fp32 [n,3]")
+    n, A, C = cls.shape
+    dev = cls.device
+    box = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    anchor = torch.empty(n, dtype=torch.int32, device=dev)
+    conf = torch.empty(n, dtype=torch.float32, device=dev)
+    klass = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_best_anchor(_hip.ptr(cls), _hip.ptr(reg), _hip.ptr(win), n, A, C, float(cs), _hip.ptr(box),
+                                            _hip.ptr(anchor), _hip.ptr(conf), _hip.ptr(klass), _hip.stream()),
+                   "rn_label_best_anchor")
+    return box, anchor, conf, klass
+
+
+def label_fit_box2d(tmpl, cam, centre, target, P1, P2, radii, grid=11, skip=None, status=None):
+    """manual_annotator_state_v3.py:603-632 for every box, one wave each: tmpl fp32 [n,4] = (l, w, h, direction), cam int32 [n],
+    centre fp32 [n,2] (where the search starts), target fp32 [n,4] = (x1, y1, x2, y2), P1 fp64 [n_cam,3,4] (or [n_cam,12]), P2
+    alike or None (no wrapper switch), radii fp64 [rounds] on the device (``label_rebase_radii``), 2 <= grid <= 16 -> (centre
+    fp32 [n,2], err fp32 [n], idx int32 [n, rounds], status).  A box the kernel leaves out (its status bit is set) keeps
+    NaN / -1, and so does, without a status bit, a box whose byte of ``skip`` (uint8 [n], ``label_crop_windows``' skipped) is
+    set."""
+    lib = _hip.load()
+    _hip.need_gpu(tmpl, cam, centre, target, P1, P2, radii, skip)
+    _mot_typed("label_fit_box2d", ("tmpl", tmpl, torch.float32), ("centre", centre, torch.float32),
+               ("target", target, torch.float32), ("radii", radii, torch.float64))
+    n, rounds, grid = tmpl.shape[0] if tmpl.dim() else -1, radii.numel(), int(grid)
+    if tuple(tmpl.shape) != (n, 4) or tuple(centre.shape) != (n, 2) or tuple(target.shape) != (n, 4) or radii.dim() != 1:
+        raise RuntimeError("label_fit_box2d: tmpl is fp32 [n,4], centre fp32 [n,2], target fp32 [n,4], radii fp64 [rounds]")
+    if skip is not None:
+        _mot_typed("label_fit_box2d", ("skip", skip, torch.uint8))
+        if tuple(skip.shape) != (n,):
+            raise RuntimeError("label_fit_box2d: skip is uint8 [n]")
+    n_cam = _label_cameras("label_fit_box2d", n, cam, P1, P2)
+    if not 2 <= grid <= LABEL_REBASE_MAX_GRID or not 1 <= rounds <= LABEL_REBASE_MAX_ROUNDS:
+        raise RuntimeError("label_fit_box2d: 2 <= grid <= %d, 1 <= rounds <= %d" % (LABEL_REBASE_MAX_GRID, LABEL_REBASE_MAX_ROUNDS))
+    dev = tmpl.device
+    status = label_status(dev, status)
+    out = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    err = torch.empty(n, dtype=torch.float32, device=dev)
+    idx = torch.empty((n, rounds), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_label_fit_box2d(_hip.ptr(tmpl), _hip.ptr(cam), _hip.ptr(centre), _hip.ptr(target), _hip.ptr(skip), n, _hip.ptr(P1),
+                                          _hip.ptr(P2), n_cam, radii.data_ptr(), rounds, grid, _hip.ptr(out), _hip.ptr(err),
+                                          _hip.ptr(idx), status.data_ptr(), _hip.stream()), "rn_label_fit_box2d")
+    return out, err, idx, status
+
+
 # ------------------------------------------------------------------------------------------------ spline trajectories
 SPLINE_GRP, SPLINE_WS_COLS, SPLINE_FIGS, SPLINE_MAX_NCAP = 8, 19, 5, 4096     # RN_SPLINE_*
 SPLINE_UNUSED, SPLINE_STUCK, SPLINE_REJECTED = 97, 98, 99

@@ -49,6 +49,10 @@ Operator                                         reference code it stands for
   label_interpolate(offsets, cols, frame, ts, n) Annotator.interpolate, every object   seems_to_be_working.py:780-836
   label_rebase(state6, cam, 4 x P, radii, grid)  Annotator.replace_homgraphy's search  seems_to_be_working.py:1677-1709
   label_offset_y(xy, coef, y_straight, dir, rev) Annotator.offset_box_y, every box     seems_to_be_working.py:1779-1805
+  label_crop_windows(state6, cam, P1, P2, ..)    Annotator.automate's crop box and edge     manual_annotator_state_v3.py:662-673,
+                                                 test, crop_detect's square window          707-717
+  label_best_anchor(cls, reg, win, cs)           Annotator.crop_detect's best anchor   manual_annotator_state_v3.py:731-740
+  label_fit_box2d(tmpl, cam, centre, target, ..) Annotator.paste_in_2D_bbox's search   manual_annotator_state_v3.py:603-632
   label_box_weights(state6, cam, P1, P2)         Annotator.create_trajectory's weights seems_to_be_working.py:1186-1196
   spline_fit / spline_select / spline_eval       ... its UnivariateSpline fits (FITPACK     seems_to_be_working.py:1233-1294
                                                  curfit), scores and winner; splev
@@ -675,6 +679,49 @@ def label_offset_y(xy: torch.Tensor, coef: torch.Tensor, y_straight: torch.Tenso
 @label_offset_y.register_fake
 def _(xy, coef, y_straight, direction, reverse):
     return xy.new_empty((xy.shape[0],), dtype=torch.float64)
+
+
+# ---- detector-assisted labelling (csrc/label_assist.hip): the status word of the audit comes last where an op has one
+OPERATORS += ("label_crop_windows", "label_best_anchor", "label_fit_box2d")
+
+
+@_lib.custom_op(NS + "::label_crop_windows", mutates_args=(), device_types="cuda")
+def label_crop_windows(state6: torch.Tensor, cam: torch.Tensor, P1: torch.Tensor, P2: Optional[torch.Tensor], ber: float,
+                       width: float, height: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_crop_windows(state6, cam, P1, P2, ber, width, height)
+
+
+@label_crop_windows.register_fake
+def _(state6, cam, P1, P2, ber, width, height):
+    n, e = state6.shape[0], state6.new_empty
+    return (e((n, 4), dtype=torch.float32), e((n, 5), dtype=torch.float32), e((n, 3), dtype=torch.float32),
+            e((n,), dtype=torch.uint8), e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::label_best_anchor", mutates_args=(), device_types="cuda")
+def label_best_anchor(cls: torch.Tensor, reg: torch.Tensor, win: torch.Tensor,
+                      cs: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_best_anchor(cls, reg, win, cs)
+
+
+@label_best_anchor.register_fake
+def _(cls, reg, win, cs):
+    n, e = cls.shape[0], cls.new_empty
+    return (e((n, 4), dtype=torch.float32), e((n,), dtype=torch.int32), e((n,), dtype=torch.float32), e((n,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::label_fit_box2d", mutates_args=(), device_types="cuda")
+def label_fit_box2d(tmpl: torch.Tensor, cam: torch.Tensor, centre: torch.Tensor, target: torch.Tensor, P1: torch.Tensor,
+                    P2: Optional[torch.Tensor], radii: torch.Tensor, grid: int,
+                    skip: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.label_fit_box2d(tmpl, cam, centre, target, P1, P2, radii, grid, skip)
+
+
+@label_fit_box2d.register_fake
+def _(tmpl, cam, centre, target, P1, P2, radii, grid, skip):
+    n, e = tmpl.shape[0], tmpl.new_empty
+    return (e((n, 2), dtype=torch.float32), e((n,), dtype=torch.float32), e((n, radii.shape[0]), dtype=torch.int32),
+            e((1,), dtype=torch.int32))
 
 
 # ---- spline trajectories (csrc/label_spline.hip): the status word of the audit comes last where an op has one

@@ -1295,6 +1295,44 @@ int rn_label_rebase(const double *state6, const int32_t *cam, int64_t n, const d
 int rn_label_offset_y(const double *xy, const double *coef, const double *y_straight, const int32_t *direction, int64_t n,
                       int reverse, double *out, void *stream);
 
+/* ---- detector-assisted labelling (csrc/label_assist.hip): the annotator's path that MAKES labels -----------------------------
+ * Annotator.automate, crop_detect and paste_in_2D_bbox of manual_annotator_state_v3.py (seems_to_be_working.py holds the same
+ * code at other line numbers), for n boxes at once.  float32 throughout, one rounding per operation, except inside state_to_im,
+ * whose camera matrices are float64.  The status word is the audit's (int32, zeroed by the caller).
+ *   rn_label_crop_windows  one thread per box (automate :662-673, crop_detect :707-717).  state6 fp32 [n,6] = (x, y, l, w, h,
+ *                          direction), cam int32 [n], P1 / P2 fp64 [n_cam,12] (P2 NULL: no wrapper switch).  The fp32 corners of
+ *                          homography.py:305-320 go through P (homography.py:438-476, 849-856); crop_box fp32 [n,4] = min / max
+ *                          over the eight fp64 image points, rounded once.  skipped uint8 [n] = 1 where x1 < 0, y1 < 0, x2 >
+ *                          width or y2 > height (:672; the reference's 1920 and 1080) or the camera is bad
+ *                          (RN_LABEL_BAD_CAMERA); such a box keeps NaN in rois and win.  Otherwise scale = max(w, h) * ber (h
+ *                          only where h > w), the window is (cx - scale / 2, cy - scale / 2, cx + scale / 2, cy + scale / 2)
+ *                          about cx = (x2 + x1) / 2, cy = (y2 + y1) / 2; rois fp32 [n,5] = (camera, window), win fp32 [n,3] =
+ *                          (minx, miny, scale).
+ *   rn_label_best_anchor   one wave per crop (crop_detect :731-740).  cls fp32 [n,A,C], reg fp32 [n,A,4] = the LOCALIZE outputs,
+ *                          win as above.  conf = the maximum over the C classes (torch.max: a NaN counts as largest, equal
+ *                          values go to the lower index), the anchor is torch.argmax of conf by the same rule; box fp32 [n,4] =
+ *                          reg[anchor] * scale / cs, x plus minx, y plus miny; anchor int32 [n], conf fp32 [n], klass int32 [n].
+ *   rn_label_fit_box2d     one wave per box (paste_in_2D_bbox :603-632).  tmpl fp32 [n,4] = (l, w, h, direction), centre0 fp32
+ *                          [n,2], target fp32 [n,4] = (x1, y1, x2, y2).  Per round r < rounds around the centre: x = np.linspace
+ *                          (cx - radii[r], cx + radii[r], grid) in fp32 (element k = k * step + start, step = (stop - start) /
+ *                          (grid - 1), the last element stop), y alike; candidate ix * grid + iy is the fp32 state (x[ix], y[iy],
+ *                          tmpl), its 2D extent as in rn_label_crop_windows with the wrapper switch per candidate; err = (((d0 *
+ *                          d0 + d1 * d1) + d2 * d2) + d3 * d3) / 4 with d = extent - target in fp32.  The first smallest index
+ *                          wins (torch.argmin: a NaN counts as smallest) and the centre moves to (x[idx / grid], y[idx % grid]).
+ *                          centre fp32 [n,2], err fp32 [n] = the last round's minimum, idx int32 [n, rounds].  A bad camera
+ *                          (RN_LABEL_BAD_CAMERA) or a winning error that is not finite (RN_LABEL_BAD_ERROR) leaves the box out:
+ *                          NaN, NaN, -1.  Limits as rn_label_rebase's: 2 <= grid <= RN_LABEL_REBASE_MAX_GRID, 1 <= rounds <=
+ *                          RN_LABEL_REBASE_MAX_ROUNDS; radii fp64 [rounds], each rounded to fp32 first.  skip uint8 [n] or NULL:
+ *                          a box whose byte is set (rn_label_crop_windows' skipped) is left out too, without a status bit. */
+int rn_label_crop_windows(const float *state6, const int32_t *cam, int64_t n, const double *P1, const double *P2, int n_cam,
+                          float ber, float width, float height, float *crop_box, float *rois, float *win, uint8_t *skipped,
+                          int32_t *status, void *stream);
+int rn_label_best_anchor(const float *cls, const float *reg, const float *win, int64_t n, int A, int C, float cs, float *box,
+                         int32_t *anchor, float *conf, int32_t *klass, void *stream);
+int rn_label_fit_box2d(const float *tmpl, const int32_t *cam, const float *centre0, const float *target, const uint8_t *skip,
+                       int64_t n, const double *P1, const double *P2, int n_cam, const double *radii, int rounds, int grid, float *centre,
+                       float *err, int32_t *idx, int32_t *status, void *stream);
+
 /* ---- smoothing-spline trajectories of multi-camera labels (csrc/label_spline.hip) -------------------------------------------
  * Annotator.create_trajectory (seems_to_be_working.py:1137-1314), get_splines (:1338-1350), gen_trajectories (:1317-1336),
  * adjust_ts_with_trajectories (:1353-1458).  fp64 with one rounding per operation, in FITPACK's order.  The status word is the

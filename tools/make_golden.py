@@ -507,6 +507,15 @@ def gen_label_quality():
                           stdout=subprocess.DEVNULL)
 
 
+def gen_label_assist():
+    """tests/golden/label_assist.npz: box_to_state, find_box, copy_paste, paste_in_2D_bbox and automate of the reference's v3
+    annotator on the scripts of tests/label_assist_cases.py.  Its own script (tools/make_golden_label_assist.py), in a child
+    process, for the reason gen_label_audit gives."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_label_assist.py"), "--out", OUT],
+                          stdout=subprocess.DEVNULL)
+
+
 def gen_replay():
     """tests/golden/replay.npz: the reference's own Data_Reader.plot_in over scripted cameras behind a recording cv2 stand-in.
     Its own script (tools/make_golden_replay.py), in a child process, for the reason gen_datareader gives."""
@@ -1690,7 +1699,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit", "label_rewrite", "label_trajectory", "label_quality"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit", "label_rewrite", "label_trajectory", "label_quality", "label_assist"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1747,6 +1756,8 @@ def main():
         gen_label_trajectory()
     if "label_quality" in which:
         gen_label_quality()
+    if "label_assist" in which:
+        gen_label_assist()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
