@@ -10,6 +10,7 @@
 // reduction has a fixed order, restated in tests/calib_cases.py.
 #include "common.h"
 #include "homography_dev.h"
+#include "wave_dev.h"
 
 #define CAL_BLOCK 256
 #define VP_LEVELS 16
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(CAL_BLOCK) void vanishing_points_kernel(const doubl
         }
         const int cells = ax.n * ay.n;                                          // <= 1024; scan index = ix * ny + iy
         double bd = __builtin_inf();
-        int bi = 0x7fffffff;
+        int bi = RN_NO_INDEX;
         for (int cell = t; cell < cells; cell += CAL_BLOCK) {
             const int ix = cell / ay.n, iy = cell - ix * ay.n;
             const double x = vp_elem(ax, ix), y = vp_elem(ay, iy);
@@ -93,22 +94,7 @@ __global__ __launch_bounds__(CAL_BLOCK) void vanishing_points_kernel(const doubl
             }
             if (acc < bd) { bd = acc; bi = cell; }                              // ascending cells: the first minimum; NaN never
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_xor(bd, off, RN_WAVE);
-            const int oi = __shfl_xor(bi, off, RN_WAVE);
-            if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-        }
-        if ((t & 63) == 0) { sh_d[t >> 6] = bd; sh_i[t >> 6] = bi; }
-        __syncthreads();
-        bd = sh_d[0]; bi = sh_i[0];
-#pragma unroll
-        for (int w = 1; w < CAL_BLOCK / RN_WAVE; ++w) {
-            const double od = sh_d[w];
-            const int oi = sh_i[w];
-            if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-        }
-        __syncthreads();
+        block_arg_first<CAL_BLOCK / RN_WAVE>(bd, bi, rn_lt_first<double>(), sh_d, sh_i);
         if (bd < best) {                                                        // strict, against the best carried across levels
             const int ix = bi / ay.n, iy = bi - ix * ay.n;
             px = vp_elem(ax, ix);

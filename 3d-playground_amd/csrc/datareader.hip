@@ -18,11 +18,10 @@
 // sets a bit of *status and the item is left out; it is never used as an index.
 #include "common.h"
 #include "homography_dev.h"
+#include "wave_dev.h"
 
 #define DR_THREADS 256
 #define DR_WAVES (DR_THREADS / RN_WAVE)
-
-__device__ __forceinline__ void dr_flag(int32_t *status, int bit) { atomicOr(status, bit); }
 
 // rows [lo, hi) of frame f; the caller guarantees 0 <= f < F (offsets holds F + 1 entries)
 __device__ __forceinline__ bool dr_frame(const int64_t *__restrict__ off, int64_t f, int64_t R, int64_t &lo, int64_t &hi) {
@@ -39,7 +38,7 @@ __global__ void __launch_bounds__(DR_THREADS) dr_mate_kernel(const int64_t *__re
     int64_t a0, a1, b0, b1;
     const bool ok_a = dr_frame(off, f, R, a0, a1), ok_b = dr_frame(off, f + 1, R, b0, b1);
     if (!ok_a || !ok_b) {                                                       // uniform over the workgroup
-        if (threadIdx.x == 0) dr_flag(status, RN_REINTERP_BAD_OFFSETS);
+        if (threadIdx.x == 0) rn_flag(status, RN_REINTERP_BAD_OFFSETS);
         return;
     }
     for (int64_t t0 = b0; t0 < b1; t0 += RN_REINTERP_TILE) {
@@ -60,7 +59,7 @@ __global__ void __launch_bounds__(DR_THREADS) dr_mate_kernel(const int64_t *__re
 __device__ __forceinline__ bool dr_mated(int32_t m, int64_t b0, int64_t b1, int32_t *status) {
     if (m < 0) return false;
     if ((int64_t)m >= b0 && (int64_t)m < b1) return true;
-    dr_flag(status, RN_REINTERP_BAD_MATE);
+    rn_flag(status, RN_REINTERP_BAD_MATE);
     return false;
 }
 
@@ -75,7 +74,7 @@ __global__ void __launch_bounds__(DR_THREADS) dr_frame_count_kernel(const int64_
         int64_t a0, a1, b0, b1;
         const bool ok_a = dr_frame(off, f, R, a0, a1), ok_b = dr_frame(off, f + 1, R, b0, b1);
         if (!ok_a || !ok_b) {
-            if (threadIdx.x == 0) dr_flag(status, RN_REINTERP_BAD_OFFSETS);
+            if (threadIdx.x == 0) rn_flag(status, RN_REINTERP_BAD_OFFSETS);
         } else {
             for (int64_t r = a0 + threadIdx.x; r < a1; r += DR_THREADS) n += dr_mated(mate[r], b0, b1, status) ? 1 : 0;
         }
@@ -90,28 +89,6 @@ __global__ void __launch_bounds__(DR_THREADS) dr_frame_count_kernel(const int64_
     }
 }
 
-// inclusive scan of v over the workgroup; `part` holds DR_WAVES values; total = the workgroup's sum
-template <typename V>
-__device__ __forceinline__ V dr_block_scan(V v, V *part, V &total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < RN_WAVE; d <<= 1) {
-        const V o = __shfl_up(v, d, RN_WAVE);
-        if (lane >= d) v += o;
-    }
-    if (lane == RN_WAVE - 1) part[w] = v;
-    __syncthreads();
-    V before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < DR_WAVES; ++k) {
-        if (k < w) before += part[k];
-        total += part[k];
-    }
-    __syncthreads();                                                            // part is free for the next call
-    return v + before;
-}
-
 // ---- per instant: the count of its frame a, and the exclusive prefix.  One workgroup walks the instants in chunks.
 __global__ void __launch_bounds__(DR_THREADS) dr_prefix_kernel(const int32_t *__restrict__ frame_count, const int32_t *__restrict__ inst_a,
                                                                int64_t F, int64_t T, int32_t *__restrict__ count,
@@ -123,13 +100,13 @@ __global__ void __launch_bounds__(DR_THREADS) dr_prefix_kernel(const int32_t *__
         int c = 0;
         if (t < T) {
             const int64_t a = inst_a[t];
-            if (a < 0 || a + 1 >= F) dr_flag(status, RN_REINTERP_BAD_PAIR);
+            if (a < 0 || a + 1 >= F) rn_flag(status, RN_REINTERP_BAD_PAIR);
             else c = frame_count[a];
             if (c < 0) c = 0;
             count[t] = c;
         }
         long long total;
-        const long long incl = dr_block_scan<long long>(c, part, total);                // 256 frame counts can pass 2^31
+        const long long incl = block_scan_incl<DR_WAVES, long long>(c, part, total);    // 256 frame counts can pass 2^31
         if (t < T) prefix[t] = carry + (int64_t)(incl - c);
         carry += (int64_t)total;
     }
@@ -147,18 +124,18 @@ __global__ void __launch_bounds__(DR_THREADS) dr_rows_kernel(const int64_t *__re
     const int64_t t = blockIdx.x;
     const int64_t a = inst_a[t];
     if (a < 0 || a + 1 >= F) {                                                  // every exit below is uniform over the workgroup
-        if (threadIdx.x == 0) dr_flag(status, RN_REINTERP_BAD_PAIR);
+        if (threadIdx.x == 0) rn_flag(status, RN_REINTERP_BAD_PAIR);
         return;
     }
     int64_t a0, a1, b0, b1;
     const bool ok_a = dr_frame(off, a, R, a0, a1), ok_b = dr_frame(off, a + 1, R, b0, b1);
     if (!ok_a || !ok_b) {
-        if (threadIdx.x == 0) dr_flag(status, RN_REINTERP_BAD_OFFSETS);
+        if (threadIdx.x == 0) rn_flag(status, RN_REINTERP_BAD_OFFSETS);
         return;
     }
     const int64_t p0 = prefix[t], p1 = prefix[t + 1];
     if (p0 < 0 || p1 < p0 || p1 > U) {
-        if (threadIdx.x == 0) dr_flag(status, RN_REINTERP_BAD_PREFIX);
+        if (threadIdx.x == 0) rn_flag(status, RN_REINTERP_BAD_PREFIX);
         return;
     }
     const double ts = frame_ts[a], next_ts = frame_ts[a + 1], out_t = inst_time[t];
@@ -174,7 +151,7 @@ __global__ void __launch_bounds__(DR_THREADS) dr_rows_kernel(const int64_t *__re
             on = dr_mated(m, b0, b1, status);
         }
         int total;
-        const int incl = dr_block_scan(on ? 1 : 0, part, total);
+        const int incl = block_scan_incl<DR_WAVES>(on ? 1 : 0, part, total);
         if (on) {
             const int64_t dst = p0 + carry + (int64_t)(incl - 1);
             if (dst < p1) {
@@ -184,7 +161,7 @@ __global__ void __launch_bounds__(DR_THREADS) dr_rows_kernel(const int64_t *__re
                 out_src[dst] = (int32_t)r;
                 out_inst[dst] = (int32_t)t;
             } else {
-                dr_flag(status, RN_REINTERP_BAD_PREFIX);
+                rn_flag(status, RN_REINTERP_BAD_PREFIX);
             }
         }
         carry += total;
@@ -215,7 +192,7 @@ __global__ void __launch_bounds__(DR_THREADS) dr_track_rows_kernel(const double 
     float *sp = space + i * 8;
     double *o = im + i * 16, *b = box + i * 4;
     if (m < 0 || (int64_t)m >= n_mats) {
-        dr_flag(status, RN_REINTERP_BAD_MAT_INDEX);
+        rn_flag(status, RN_REINTERP_BAD_MAT_INDEX);
         keep[i] = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) sp[k] = 0.f;

@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave_dev.h"
 
 #define EV_TILE RN_EVAL_SORT_TILE
 #define EV_SPAN RN_EVAL_SORT_SPAN
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void eval_match_kernel(const EvRow *__restrict
         const double dx1 = d.x1, dy1 = d.y1, dx2 = d.x2, dy2 = d.y2;            // fp32 -> fp64 (:115)
         const double area_d = (dx2 - dx1) * (dy2 - dy1);
         double best = -INFINITY;
-        int best_j = 0x7fffffff;
+        int best_j = RN_NO_INDEX;
         bool nan = false;
         for (int j = lane; j < n; j += 64) {
             const double *b = ann + (a0 + j) * 4;
@@ -198,12 +199,7 @@ __global__ __launch_bounds__(256) void eval_match_kernel(const EvRow *__restrict
             if (ov != ov) nan = true;
             else if (ov > best) { best = ov; best_j = j; }                      // j ascending: the first maximum of this lane
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {                                // np.argmax: the first maximum (:204)
-            const double ob = __shfl_xor(best, off, 64);
-            const int oj = __shfl_xor(best_j, off, 64);
-            if (ob > best || (ob == best && oj < best_j)) { best = ob; best_j = oj; }
-        }
+        wave_arg_first(best, best_j, rn_gt_first<double>());                    // np.argmax: the first maximum (:204)
         int hit = 0;
         if (!__any(nan) && best >= iou_thr && best_j < n) {                     // a NaN overlap is argmax's pick and fails >= (:207)
             const int owner = best_j & 63;
@@ -265,21 +261,13 @@ __global__ __launch_bounds__(64) void eval_hist_kernel(const uint64_t *__restric
 // one workgroup: exclusive scan of hist[0 .. n) in place, thread t owns a contiguous piece
 __global__ __launch_bounds__(1024) void eval_scan_kernel(int32_t *__restrict__ hist, int64_t n) {
     __shared__ int wave_tot[16];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x;
     const int64_t per = (n + 1023) / 1024;
     const int64_t lo = (int64_t)t * per, hi = lo + per < n ? lo + per : n;
     int sum = 0;
     for (int64_t q = lo; q < hi; ++q) sum += hist[q];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wv] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int k = 0; k < 16; ++k) run += k < wv ? wave_tot[k] : 0;
+    int total;
+    int run = block_scan_incl<16>(sum, wave_tot, total) - sum;
     for (int64_t q = lo; q < hi; ++q) { const int v = hist[q]; hist[q] = run; run += v; }
 }
 

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "homography_dev.h"
+#include "wave_dev.h"
 
 #define FIT_WAVES 4
 
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(64 * FIT_WAVES) void fit_nearest_kernel(const float
     for (int q = 0; q < 6; ++q) g[q] = gt[(int64_t)b * 6 + q];
     const float4 fg = hg_footprint(g);
     float best = INFINITY;                                                      // min_dist = np.inf (:363)
-    int arg = 0x7fffffff;
+    int arg = RN_NO_INDEX;
     for (int j = lo + lane; j < hi; j += 64) {
         float s[6];
 #pragma unroll
@@ -72,13 +73,8 @@ __global__ __launch_bounds__(64 * FIT_WAVES) void fit_nearest_kernel(const float
         const float dist = 1.0f - fit_iou(hg_footprint(s), fg);                 // :367
         if (dist < best) { best = dist; arg = j; }                              // :370-372
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64);
-        const int oa = __shfl_xor(arg, off, 64);
-        if (ob < best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (lane == 0) rows[b] = arg == 0x7fffffff ? -1 : arg;
+    wave_arg_first(best, arg, rn_lt_first<float>());
+    if (lane == 0) rows[b] = arg == RN_NO_INDEX ? -1 : arg;
 }
 
 // one workgroup of 1024; the frames are taken 1024 at a time, in order
@@ -101,24 +97,14 @@ __global__ __launch_bounds__(1024) void fit_compact_kernel(const float *__restri
             else if (row < 0) ++n_bad;                                          // no distance compared below infinity
         }
         const int has = row >= 0;
-        int incl = has;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) wave_tot[wv] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { const int v = wave_tot[k]; before += k < wv ? v : 0; total += v; }
+        int total;
+        const int incl = block_scan_incl<16>(has, wave_tot, total);
         if (has) {
-            const int k = base + before + incl - 1;                             // k <= b < B: inside resid [B,5]
+            const int k = base + incl - 1;                                      // k <= b < B: inside resid [B,5]
 #pragma unroll
             for (int q = 0; q < 5; ++q) resid[(int64_t)k * 5 + q] = det[(int64_t)row * 6 + q] - gt[(int64_t)b * 6 + q];   // :374-375
         }
         base += total;
-        __syncthreads();
     }
     n_empty = wave_sum(n_empty);
     n_bad = wave_sum(n_bad);

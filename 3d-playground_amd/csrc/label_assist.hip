@@ -5,13 +5,12 @@
 //   fits the detected 2D box.
 //
 // The reference does this for one box per key press.  Here, for n boxes at once:
-//   la_windows_kernel  one thread per box: state -> image corners -> 2D extent, the edge test of :672, the square crop window.
-//   la_anchor_kernel   one wave per crop: lanes stride the anchors, a wave reduction on (confidence, anchor) picks torch.argmax's
+//   as_windows_kernel  one thread per box: state -> image corners -> 2D extent, the edge test of :672, the square crop window.
+//   as_anchor_kernel   one wave per crop: lanes stride the anchors, a wave reduction on (confidence, anchor) picks torch.argmax's
 //                      winner (a NaN counts as largest, equal values go to the lower index), lane 0 moves the winner's box into
 //                      frame coordinates.
-//   la_fit_kernel      one wave per box, the structure of lr_rebase_kernel (label_rebase.hip): per round the lanes take candidates
-//                      l, l + 64, ... of the grid, a wave reduction on (error, index) picks the first smallest as torch.argmin
-//                      does, and the centre moves there.
+//   as_fit_kernel      one wave per box: label_grid_search (label_search_dev.h) in fp32; the kernel's own part is the error of one
+//                      candidate centre.
 //
 // Arithmetic (this file is in the Makefile's EXACT list: no fma contraction, one rounding per operation).  With today's numpy and
 // torch the reference's search runs in float32 throughout, unlike replace_homgraphy's: the centre is a float32 tensor,
@@ -23,7 +22,7 @@
 // arrive as float64 (ops.label_rebase_radii) and are rounded to float32 first, as torch does with a Python scalar beside a
 // float32 tensor.  tests/golden/label_assist.npz, written by the reference's own methods, agrees with every statement here.
 //
-// A box whose byte of the optional `skip` array is set (the edge test of la_windows_kernel) is left out of the fit without a
+// A box whose byte of the optional `skip` array is set (the edge test of as_windows_kernel) is left out of the fit without a
 // status bit, as the reference returns silently.
 //
 // Indices read from memory: the camera index, checked before use; a bad one sets a bit of *status and the box is left out (its
@@ -32,33 +31,14 @@
 
 #include "common.h"
 #include "homography_dev.h"
+#include "label_search_dev.h"
 
-#define LA_THREADS 256
-#define LA_WAVES (LA_THREADS / RN_WAVE)
-#define LA_MAX ((int64_t)1 << 31)
-#define LA_NO_INDEX 0x7fffffff
-
-// torch.argmin's order: a NaN is smaller than every number, equal values go to the lower index
-__device__ __forceinline__ bool la_before(float ea, int ia, float eb, int ib) {
-    if (ea != ea) return (eb != eb) ? ia < ib : true;
-    if (eb != eb) return false;
-    return ea == eb ? ia < ib : ea < eb;
-}
-
-// torch.argmax's order: a NaN is larger than every number, equal values go to the lower index
-__device__ __forceinline__ bool la_above(float va, int ia, float vb, int ib) {
-    if (va != va) return (vb != vb) ? ia < ib : true;
-    if (vb != vb) return false;
-    return va == vb ? ia < ib : va > vb;
-}
-
-// element k of np.linspace(start, stop, grid) in float32: arange * step + start, the last element is stop itself
-__device__ __forceinline__ float la_linspace(float start, float stop, float step, int k, int grid) {
-    return k == grid - 1 ? stop : (float)k * step + start;
-}
+#define AS_THREADS 256
+#define AS_WAVES (AS_THREADS / RN_WAVE)
+#define AS_MAX ((int64_t)1 << 31)
 
 // :620-623 / :665-668: torch.min / torch.max over the eight float64 image points (a NaN wins both), then one rounding to float32
-__device__ __forceinline__ void la_extent(const float s[6], const double *__restrict__ P1, const double *__restrict__ P2, int m,
+__device__ __forceinline__ void as_extent(const float s[6], const double *__restrict__ P1, const double *__restrict__ P2, int m,
                                           float ext[4]) {
     float fx[8], fy[8], fz[8];
     double2 im[8];
@@ -79,7 +59,7 @@ __device__ __forceinline__ void la_extent(const float s[6], const double *__rest
     ext[3] = (float)y2;
 }
 
-__global__ void __launch_bounds__(LA_THREADS) la_fit_kernel(const float *__restrict__ tmpl, const int32_t *__restrict__ cam,
+__global__ void __launch_bounds__(AS_THREADS) as_fit_kernel(const float *__restrict__ tmpl, const int32_t *__restrict__ cam,
                                                             const float *__restrict__ centre0, const float *__restrict__ target,
                                                             const uint8_t *__restrict__ skip, int64_t n,
                                                             const double *__restrict__ P1, const double *__restrict__ P2, int n_cam,
@@ -87,12 +67,12 @@ __global__ void __launch_bounds__(LA_THREADS) la_fit_kernel(const float *__restr
                                                             float *__restrict__ centre, float *__restrict__ err_out,
                                                             int32_t *__restrict__ idx_out, int32_t *status) {
     const int lane = threadIdx.x & 63;
-    const int64_t b = (int64_t)blockIdx.x * LA_WAVES + (threadIdx.x >> 6);     // wave-uniform, like every exit below
+    const int64_t b = (int64_t)blockIdx.x * AS_WAVES + (threadIdx.x >> 6);     // wave-uniform, like every exit below
     if (b >= n) return;
-    if (skip != nullptr && skip[b]) return;                                     // la_windows_kernel's edge test: no status bit
+    if (skip != nullptr && skip[b]) return;                                     // as_windows_kernel's edge test: no status bit
     const int m = cam[b];
     if (m < 0 || m >= n_cam) {
-        if (lane == 0) atomicOr(status, RN_LABEL_BAD_CAMERA);
+        if (lane == 0) rn_flag(status, RN_LABEL_BAD_CAMERA);
         return;
     }
     float s[6], t[4];
@@ -101,45 +81,20 @@ __global__ void __launch_bounds__(LA_THREADS) la_fit_kernel(const float *__restr
         s[2 + k] = tmpl[b * 4 + k];                                            // :611: (l, w, h, direction)
         t[k] = target[b * 4 + k];
     }
-    const int cells = grid * grid;
     float cx = centre0[b * 2], cy = centre0[b * 2 + 1], win_err = 0.f;
-    for (int r = 0; r < rounds; ++r) {
-        const float rad = (float)radii[r];
-        const float x0 = cx - rad, x1 = cx + rad, y0 = cy - rad, y1 = cy + rad;   // :606-607
-        const float sx = (x1 - x0) / (float)(grid - 1), sy = (y1 - y0) / (float)(grid - 1);
-        float best = INFINITY;
-        int best_i = LA_NO_INDEX;
-        for (int c = lane; c < cells; c += RN_WAVE) {                           // ascending per lane
-            s[0] = la_linspace(x0, x1, sx, c / grid, grid);                     // :609-612: index = ix * grid + iy
-            s[1] = la_linspace(y0, y1, sy, c % grid, grid);
-            float ext[4], sq[4];
-            la_extent(s, P1, P2, m, ext);                                       // :616-623, the wrapper switch is per candidate
+    const auto score = [&](float x, float y) {                                  // :606-627: one shifted template
+        s[0] = x;
+        s[1] = y;
+        float ext[4], sq[4];
+        as_extent(s, P1, P2, m, ext);                                           // :616-623, the wrapper switch is per candidate
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {                                       // :627
-                const float d = ext[k] - t[k];
-                sq[k] = d * d;
-            }
-            const float e = (((sq[0] + sq[1]) + sq[2]) + sq[3]) / 4.0f;
-            if (la_before(e, c, best, best_i)) { best = e; best_i = c; }
+        for (int k = 0; k < 4; ++k) {                                           // :627
+            const float d = ext[k] - t[k];
+            sq[k] = d * d;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {                                      // (error, index) is a total order: all lanes agree
-            const float oe = __shfl_xor(best, o, RN_WAVE);
-            const int oi = __shfl_xor(best_i, o, RN_WAVE);
-            if (la_before(oe, oi, best, best_i)) { best = oe; best_i = oi; }
-        }
-        if (!isfinite(best) || best_i >= cells) {                               // wave-uniform
-            if (lane == 0) {
-                atomicOr(status, RN_LABEL_BAD_ERROR);
-                for (int q = 0; q < r; ++q) idx_out[b * rounds + q] = -1;       // the box is left out as a whole
-            }
-            return;
-        }
-        cx = la_linspace(x0, x1, sx, best_i / grid, grid);                      // :631
-        cy = la_linspace(y0, y1, sy, best_i % grid, grid);
-        win_err = best;
-        if (lane == 0) idx_out[b * rounds + r] = best_i;
-    }
+        return (((sq[0] + sq[1]) + sq[2]) + sq[3]) / 4.0f;
+    };
+    if (!label_grid_search<float>(cx, cy, win_err, radii, rounds, grid, idx_out + b * rounds, status, score)) return;
     if (lane == 0) {
         centre[b * 2] = cx;
         centre[b * 2 + 1] = cy;
@@ -147,32 +102,35 @@ __global__ void __launch_bounds__(LA_THREADS) la_fit_kernel(const float *__restr
     }
 }
 
-__global__ void __launch_bounds__(LA_THREADS) la_anchor_kernel(const float *__restrict__ cls, const float *__restrict__ reg,
+__global__ void __launch_bounds__(AS_THREADS) as_anchor_kernel(const float *__restrict__ cls, const float *__restrict__ reg,
                                                                const float *__restrict__ win, int64_t n, int A, int C, float cs,
                                                                float *__restrict__ box, int32_t *__restrict__ anchor,
                                                                float *__restrict__ conf, int32_t *__restrict__ klass) {
     const int lane = threadIdx.x & 63;
-    const int64_t b = (int64_t)blockIdx.x * LA_WAVES + (threadIdx.x >> 6);     // wave-uniform
+    const int64_t b = (int64_t)blockIdx.x * AS_WAVES + (threadIdx.x >> 6);     // wave-uniform
     if (b >= n) return;
     const float *cb = cls + b * A * C;
+    const torch_argmax_before<float> above;
     float best = -INFINITY;
-    int best_a = LA_NO_INDEX, best_k = 0;
+    int best_a = RN_NO_INDEX, best_k = 0;
     for (int a = lane; a < A; a += RN_WAVE) {                                   // ascending per lane
         const float *row = cb + (int64_t)a * C;
         float v = row[0];                                                       // :731: torch.max over the classes
         int vk = 0;
         for (int k = 1; k < C; ++k) {
             const float w = row[k];
-            if (la_above(w, k, v, vk)) { v = w; vk = k; }
+            if (above(w, k, v, vk)) { v = w; vk = k; }
         }
-        if (la_above(v, a, best, best_a)) { best = v; best_a = a; best_k = vk; }
+        if (above(v, a, best, best_a)) { best = v; best_a = a; best_k = vk; }
     }
+    // Written in place, not wave_arg_first: the winner's class index travels along as a third value, and behind a helper that
+    // carries it this launch measured 1 us slower than before (profiles/wave_primitives_refactor.txt).  As is: the same code.
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {                                          // :734: torch.argmax over the anchors
         const float ov = __shfl_xor(best, o, RN_WAVE);
         const int oa = __shfl_xor(best_a, o, RN_WAVE);
         const int ok = __shfl_xor(best_k, o, RN_WAVE);
-        if (la_above(ov, oa, best, best_a)) { best = ov; best_a = oa; best_k = ok; }
+        if (above(ov, oa, best, best_a)) { best = ov; best_a = oa; best_k = ok; }
     }
     if (lane != 0 || best_a >= A) return;                                       // A >= 1: lane 0 always holds an anchor
     const float minx = win[b * 3], miny = win[b * 3 + 1], scale = win[b * 3 + 2];
@@ -184,24 +142,24 @@ __global__ void __launch_bounds__(LA_THREADS) la_anchor_kernel(const float *__re
     klass[b] = best_k;
 }
 
-__global__ void __launch_bounds__(LA_THREADS) la_windows_kernel(const float *__restrict__ state6, const int32_t *__restrict__ cam,
+__global__ void __launch_bounds__(AS_THREADS) as_windows_kernel(const float *__restrict__ state6, const int32_t *__restrict__ cam,
                                                                 int64_t n, const double *__restrict__ P1,
                                                                 const double *__restrict__ P2, int n_cam, float ber, float width,
                                                                 float height, float *__restrict__ crop_box,
                                                                 float *__restrict__ rois, float *__restrict__ win,
                                                                 uint8_t *__restrict__ skipped, int32_t *status) {
-    const int64_t b = (int64_t)blockIdx.x * LA_THREADS + threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * AS_THREADS + threadIdx.x;
     if (b >= n) return;
     skipped[b] = 1;
     const int m = cam[b];
     if (m < 0 || m >= n_cam) {
-        atomicOr(status, RN_LABEL_BAD_CAMERA);
+        rn_flag(status, RN_LABEL_BAD_CAMERA);
         return;
     }
     float s[6], ext[4];
 #pragma unroll
     for (int k = 0; k < 6; ++k) s[k] = state6[b * 6 + k];                       // :662
-    la_extent(s, P1, P2, m, ext);
+    as_extent(s, P1, P2, m, ext);
 #pragma unroll
     for (int k = 0; k < 4; ++k) crop_box[b * 4 + k] = ext[k];
     if (ext[0] < 0.f || ext[1] < 0.f || ext[2] > width || ext[3] > height) return;      // :672
@@ -226,7 +184,7 @@ extern "C" int rn_label_fit_box2d(const float *tmpl, const int32_t *cam, const f
                                   const uint8_t *skip, int64_t n, const double *P1, const double *P2, int n_cam,
                                   const double *radii, int rounds, int grid,
                                   float *centre, float *err, int32_t *idx, int32_t *status, void *stream) {
-    if (n < 0 || n >= LA_MAX || n_cam < 0 || n_cam > RN_LABEL_MAX_CAMS || rounds < 1 || rounds > RN_LABEL_REBASE_MAX_ROUNDS ||
+    if (n < 0 || n >= AS_MAX || n_cam < 0 || n_cam > RN_LABEL_MAX_CAMS || rounds < 1 || rounds > RN_LABEL_REBASE_MAX_ROUNDS ||
         grid < 2 || grid > RN_LABEL_REBASE_MAX_GRID || !status)
         return RN_EINVAL;
     if (n == 0) return RN_OK;
@@ -236,7 +194,7 @@ extern "C" int rn_label_fit_box2d(const float *tmpl, const int32_t *cam, const f
     if (e == hipSuccess) e = hipMemsetAsync(err, 0xFF, (size_t)n * sizeof(float), s);
     if (e == hipSuccess) e = hipMemsetAsync(idx, 0xFF, (size_t)n * rounds * sizeof(int32_t), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(la_fit_kernel, dim3(rn_blocks(n, LA_WAVES)), dim3(LA_THREADS), 0, s, tmpl, cam, centre0, target, skip, n, P1,
+    hipLaunchKernelGGL(as_fit_kernel, dim3(rn_blocks(n, AS_WAVES)), dim3(AS_THREADS), 0, s, tmpl, cam, centre0, target, skip, n, P1,
                        P2, n_cam, radii, rounds, grid, centre, err, idx, status);
     RN_LAUNCH_CHECK();
     return RN_OK;
@@ -244,10 +202,10 @@ extern "C" int rn_label_fit_box2d(const float *tmpl, const int32_t *cam, const f
 
 extern "C" int rn_label_best_anchor(const float *cls, const float *reg, const float *win, int64_t n, int A, int C, float cs,
                                     float *box, int32_t *anchor, float *conf, int32_t *klass, void *stream) {
-    if (n < 0 || n >= LA_MAX || A < 1 || C < 1 || (int64_t)A * C >= LA_MAX) return RN_EINVAL;
+    if (n < 0 || n >= AS_MAX || A < 1 || C < 1 || (int64_t)A * C >= AS_MAX) return RN_EINVAL;
     if (n == 0) return RN_OK;
     if (!cls || !reg || !win || !box || !anchor || !conf || !klass) return RN_EINVAL;
-    hipLaunchKernelGGL(la_anchor_kernel, dim3(rn_blocks(n, LA_WAVES)), dim3(LA_THREADS), 0, (hipStream_t)stream, cls, reg, win, n,
+    hipLaunchKernelGGL(as_anchor_kernel, dim3(rn_blocks(n, AS_WAVES)), dim3(AS_THREADS), 0, (hipStream_t)stream, cls, reg, win, n,
                        A, C, cs, box, anchor, conf, klass);
     RN_LAUNCH_CHECK();
     return RN_OK;
@@ -256,7 +214,7 @@ extern "C" int rn_label_best_anchor(const float *cls, const float *reg, const fl
 extern "C" int rn_label_crop_windows(const float *state6, const int32_t *cam, int64_t n, const double *P1, const double *P2,
                                      int n_cam, float ber, float width, float height, float *crop_box, float *rois, float *win,
                                      uint8_t *skipped, int32_t *status, void *stream) {
-    if (n < 0 || n >= LA_MAX || n_cam < 0 || n_cam > RN_LABEL_MAX_CAMS || !status) return RN_EINVAL;
+    if (n < 0 || n >= AS_MAX || n_cam < 0 || n_cam > RN_LABEL_MAX_CAMS || !status) return RN_EINVAL;
     if (n == 0) return RN_OK;
     if (!state6 || !cam || !crop_box || !rois || !win || !skipped || (n_cam > 0 && !P1)) return RN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -264,7 +222,7 @@ extern "C" int rn_label_crop_windows(const float *state6, const int32_t *cam, in
     if (e == hipSuccess) e = hipMemsetAsync(rois, 0xFF, (size_t)n * 5 * sizeof(float), s);
     if (e == hipSuccess) e = hipMemsetAsync(win, 0xFF, (size_t)n * 3 * sizeof(float), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(la_windows_kernel, dim3(rn_blocks(n, LA_THREADS)), dim3(LA_THREADS), 0, s, state6, cam, n, P1, P2, n_cam, ber,
+    hipLaunchKernelGGL(as_windows_kernel, dim3(rn_blocks(n, AS_THREADS)), dim3(AS_THREADS), 0, s, state6, cam, n, P1, P2, n_cam, ber,
                        width, height, crop_box, rois, win, skipped, status);
     RN_LAUNCH_CHECK();
     return RN_OK;

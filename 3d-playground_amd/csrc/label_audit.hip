@@ -27,37 +27,17 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave_dev.h"
 
 #define LA_THREADS 256
 #define LA_WAVES (LA_THREADS / RN_WAVE)
 #define LA_MAX ((int64_t)1 << 31)
-
-__device__ __forceinline__ void la_flag(int32_t *status, int bit) { atomicOr(status, bit); }
 
 // rows [lo, hi) of tracklet t; the caller guarantees 0 <= t < T (offsets holds T + 1 entries)
 __device__ __forceinline__ bool la_rows(const int64_t *__restrict__ off, int64_t t, int64_t R, int64_t &lo, int64_t &hi) {
     lo = off[t];
     hi = off[t + 1];
     return lo >= 0 && lo <= hi && hi <= R;
-}
-
-__device__ __forceinline__ double la_wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, RN_WAVE));
-    return v;
-}
-__device__ __forceinline__ double la_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, RN_WAVE));
-    return v;
-}
-__device__ __forceinline__ int la_wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int w = __shfl_xor(v, o, RN_WAVE);
-        v = w > v ? w : v;
-    }
-    return v;
 }
 
 // min and max of column kc over rows [lo, hi), wave-uniform
@@ -70,8 +50,8 @@ __device__ __forceinline__ void la_minmax(const double *__restrict__ cols, int k
         mn = fmin(mn, k);
         mx = fmax(mx, k);
     }
-    mn = la_wave_min(mn);
-    mx = la_wave_max(mx);
+    mn = wave_min(mn);
+    mx = wave_max(mx);
 }
 
 // for each of the five points, the last i in [1, n) with (K[i] - pt) * (K[i-1] - pt) <= 0 (0: none), wave-uniform
@@ -86,7 +66,7 @@ __device__ __forceinline__ void la_last_crossing(const double *__restrict__ cols
             if ((ka - pt[q]) * (kb - pt[q]) <= 0.0) best[q] = (int)i;           // :1908 (NaN compares false, as in Python)
     }
 #pragma unroll
-    for (int q = 0; q < RN_LABEL_POINTS; ++q) best[q] = la_wave_max(best[q]);
+    for (int q = 0; q < RN_LABEL_POINTS; ++q) best[q] = wave_max(best[q]);
 }
 
 // value of column vc at key `pt` on segment (i - 1, i) of the tracklet at row lo (:1909-1910)
@@ -121,7 +101,7 @@ __global__ void __launch_bounds__(LA_THREADS) la_pair_kernel(const int64_t *__re
     int64_t a0, a1, b0, b1;                                                     // c1 = the camera's tracklet, c0 = the partner's
     const bool ok_a = la_rows(off, obj * C + cam, R, a0, a1), ok_b = la_rows(off, obj * C + prev, R, b0, b1);
     if (!ok_a || !ok_b) {
-        if (lane == 0) la_flag(status, RN_LABEL_BAD_OFFSETS);
+        if (lane == 0) rn_flag(status, RN_LABEL_BAD_OFFSETS);
         la_no_samples(fl, o, lane);
         return;
     }
@@ -170,7 +150,7 @@ __global__ void __launch_bounds__(LA_THREADS) la_outliers_kernel(const int64_t *
     if (t >= T) return;
     int64_t lo, hi;
     if (!la_rows(off, t, R, lo, hi)) {
-        la_flag(status, RN_LABEL_BAD_OFFSETS);
+        rn_flag(status, RN_LABEL_BAD_OFFSETS);
         return;
     }
     bool prev_deleted = false;
@@ -178,7 +158,7 @@ __global__ void __launch_bounds__(LA_THREADS) la_outliers_kernel(const int64_t *
     for (int64_t r = lo; r < hi; ++r) {
         const int64_t f = frame[r];
         if (f <= f_before || f >= F) {                                          // also f < 0
-            la_flag(status, RN_LABEL_BAD_FRAME);
+            rn_flag(status, RN_LABEL_BAD_FRAME);
             return;
         }
         if (f >= n_visit) return;                                               // :2197-2198: the walk has ended
@@ -227,7 +207,7 @@ __global__ void __launch_bounds__(LA_THREADS) la_gap_kernel(const int64_t *__res
     if (t >= T) return;
     int64_t lo, hi;
     if (!la_rows(off, t, R, lo, hi)) {
-        if (lane == 0) { la_flag(status, RN_LABEL_BAD_OFFSETS); w.count[t] = 0; }
+        if (lane == 0) { rn_flag(status, RN_LABEL_BAD_OFFSETS); w.count[t] = 0; }
         return;
     }
     int carry = 0;
@@ -236,52 +216,33 @@ __global__ void __launch_bounds__(LA_THREADS) la_gap_kernel(const int64_t *__res
         int g = 0;
         if (r + 1 < hi) {
             const int64_t f0 = frame[r], f1 = frame[r + 1];
-            if (f0 < 0 || f1 <= f0 || f1 >= F) la_flag(status, RN_LABEL_BAD_FRAME);
+            if (f0 < 0 || f1 <= f0 || f1 >= F) rn_flag(status, RN_LABEL_BAD_FRAME);
             else g = (int)(f1 - f0 - 1);
         }
-        int incl = g;
-#pragma unroll
-        for (int d = 1; d < RN_WAVE; d <<= 1) {
-            const int o = __shfl_up(incl, d, RN_WAVE);
-            if (lane >= d) incl += o;
-        }
+        const int incl = wave_scan_incl(g);                                     // the waves leave on their own: no block scan
         if (r < hi) w.row_pre[r] = carry + incl - g;
         carry += __shfl(incl, RN_WAVE - 1, RN_WAVE);                            // every gap lies inside the F frames: no overflow
     }
     if (lane == 0) w.count[t] = carry;
 }
 
-// one workgroup walks the tracklets in chunks (the scan of dr_prefix_kernel)
+// one workgroup walks the tracklets in chunks
 __global__ void __launch_bounds__(LA_THREADS) la_prefix_kernel(int64_t T, int64_t U, LaWs w, int64_t *__restrict__ total,
                                                                int32_t *status) {
     __shared__ long long part[LA_WAVES];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     long long carry = 0;
     for (int64_t base = 0; base < T; base += LA_THREADS) {
         const int64_t t = base + threadIdx.x;
         const long long c = t < T ? (long long)w.count[t] : 0;
-        long long v = c;
-#pragma unroll
-        for (int d = 1; d < RN_WAVE; d <<= 1) {
-            const long long o = __shfl_up(v, d, RN_WAVE);
-            if (lane >= d) v += o;
-        }
-        if (lane == RN_WAVE - 1) part[wv] = v;
-        __syncthreads();
-        long long before = 0, sum = 0;
-#pragma unroll
-        for (int k = 0; k < LA_WAVES; ++k) {
-            if (k < wv) before += part[k];
-            sum += part[k];
-        }
-        __syncthreads();                                                        // part is free for the next chunk
-        if (t < T) w.prefix[t] = carry + before + v - c;
+        long long sum;
+        const long long incl = block_scan_incl<LA_WAVES>(c, part, sum);
+        if (t < T) w.prefix[t] = carry + incl - c;
         carry += sum;
     }
     if (threadIdx.x == 0) {
         w.prefix[T] = carry;
         total[0] = carry;
-        if (carry > U) la_flag(status, RN_LABEL_BAD_PREFIX);                    // the fill leaves the rows beyond U out
+        if (carry > U) rn_flag(status, RN_LABEL_BAD_PREFIX);                    // the fill leaves the rows beyond U out
     }
 }
 
@@ -300,7 +261,7 @@ __global__ void __launch_bounds__(LA_THREADS) la_fill_kernel(const int64_t *__re
     const int64_t k = u - w.prefix[t];
     int64_t lo, hi;
     if (!la_rows(off, t, R, lo, hi) || hi - lo < 2 || k < 0 || k >= (int64_t)w.count[t]) {
-        la_flag(status, RN_LABEL_BAD_OFFSETS);
+        rn_flag(status, RN_LABEL_BAD_OFFSETS);
         return;
     }
     int64_t r = lo, r_hi = hi - 1;                                              // the last row with row_pre <= k that has a successor
@@ -310,7 +271,7 @@ __global__ void __launch_bounds__(LA_THREADS) la_fill_kernel(const int64_t *__re
     }
     const int64_t f0 = frame[r], f1 = frame[r + 1], fi = f0 + 1 + (k - (int64_t)w.row_pre[r]);
     if (f0 < 0 || fi <= f0 || fi >= f1 || f1 >= F) {
-        la_flag(status, RN_LABEL_BAD_FRAME);
+        rn_flag(status, RN_LABEL_BAD_FRAME);
         return;
     }
     const int c = (int)(t % C);

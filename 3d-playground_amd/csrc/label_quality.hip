@@ -28,13 +28,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave_dev.h"
 
 #define LQ_THREADS 256
 #define LQ_WAVES (LQ_THREADS / RN_WAVE)
 #define LQ_MAX ((int64_t)1 << 31)
 #define LQ_PLANES 7                     // t, x, y, v, vy, a, theta
-
-__device__ __forceinline__ void lq_flag(int32_t *status, int bit) { atomicOr(status, bit); }
 
 __device__ __forceinline__ int64_t lq_pow2(int64_t n) {
     int64_t p = 1;
@@ -44,24 +43,7 @@ __device__ __forceinline__ int64_t lq_pow2(int64_t n) {
 
 // exclusive position of this thread's flag among the workgroup's; total = their number (workgroup-uniform).  part: LQ_WAVES ints.
 __device__ __forceinline__ int lq_scan(int flag, int *part, int &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int incl = flag;
-#pragma unroll
-    for (int d = 1; d < RN_WAVE; d <<= 1) {
-        const int o = __shfl_up(incl, d, RN_WAVE);
-        if (lane >= d) incl += o;
-    }
-    if (lane == RN_WAVE - 1) part[wv] = incl;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < LQ_WAVES; ++k) {
-        if (k < wv) before += part[k];
-        sum += part[k];
-    }
-    __syncthreads();                                                            // part is free for the next call
-    total = sum;
-    return before + incl - flag;
+    return block_scan_incl<LQ_WAVES>(flag, part, total) - flag;
 }
 
 // The sums of a(i) and b(i) over i < count in ascending order, started from 0.0, on every thread.  buf: 2 * LQ_THREADS doubles.
@@ -149,7 +131,7 @@ __device__ __forceinline__ void lq_object(const double *__restrict__ cols, int64
     const int64_t P = lq_pow2(n);
     for (int64_t i = n + tid; i < P; i += LQ_THREADS) {
         key[i] = INFINITY;
-        idx[i] = 0x7fffffff;
+        idx[i] = RN_NO_INDEX;
     }
     __syncthreads();
     lq_sort(key, idx, P);
@@ -163,7 +145,7 @@ __device__ __forceinline__ void lq_object(const double *__restrict__ cols, int64
         if (i < n) {
             int64_t ii = idx[i];
             if (ii < 0 || ii >= L) {
-                lq_flag(status, RN_LABEL_BAD_OFFSETS);
+                rn_flag(status, RN_LABEL_BAD_OFFSETS);
                 ii = 0;
             }
             r = s0 + ii;
@@ -224,11 +206,8 @@ __device__ __forceinline__ void lq_object(const double *__restrict__ cols, int64
             feas += v0 < 140.0 && v1 < 140.0 && v0 > 0.0 && v1 > 0.0 && h0 < 25.0 && h1 < 25.0 && h0 > -25.0 && h1 > -25.0;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, d, RN_WAVE));
-        mx = fmax(mx, __shfl_xor(mx, d, RN_WAVE));
-    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
     feas = wave_sum(feas);
     if ((tid & 63) == 0) {
         buf[tid >> 6] = mn;
@@ -269,11 +248,11 @@ __global__ void __launch_bounds__(LQ_THREADS) lq_series_kernel(const int64_t *__
     __shared__ int part[LQ_WAVES];
     __shared__ double buf[2 * LQ_THREADS];
     const int64_t obj = blockIdx.x;
-    if (obj == 0 && threadIdx.x == 0 && (off[0] != 0 || off[N * C] != R)) lq_flag(status, RN_LABEL_BAD_OFFSETS);
+    if (obj == 0 && threadIdx.x == 0 && (off[0] != 0 || off[N * C] != R)) rn_flag(status, RN_LABEL_BAD_OFFSETS);
     const int64_t s0 = off[obj * C], s1 = off[(obj + 1) * C];
     if (s0 < 0 || s0 > s1 || s1 > R) {                                          // workgroup-uniform
         if (threadIdx.x == 0) {
-            lq_flag(status, RN_LABEL_BAD_OFFSETS);
+            rn_flag(status, RN_LABEL_BAD_OFFSETS);
             o.counts[obj * 3] = o.counts[obj * 3 + 1] = o.counts[obj * 3 + 2] = 0;
             o.figs[obj * 2] = o.figs[obj * 2 + 1] = 0.0;
         }
@@ -293,7 +272,7 @@ __global__ void __launch_bounds__(LQ_THREADS) lq_group_check_kernel(const int32_
     const int64_t r = (int64_t)blockIdx.x * LQ_THREADS + threadIdx.x;
     if (r >= n) return;
     const int64_t g = group[r];
-    if (g < 0 || g >= G || (r > 0 && (int64_t)group[r - 1] > g)) lq_flag(status, RN_LABEL_BAD_GROUP);
+    if (g < 0 || g >= G || (r > 0 && (int64_t)group[r - 1] > g)) rn_flag(status, RN_LABEL_BAD_GROUP);
 }
 
 // the first row in [0, n] whose group is not below g

@@ -6,8 +6,8 @@
 // through the NEW homography, and the centre whose bottom footprint lands nearest the old box's image footprint starts the next
 // round at a fifth of the radius.  Here:
 //   lr_rebase_kernel    one wave per box.  Every lane projects the old box once (fp32 state, state_corners, the old matrices),
-//                       then lanes take candidates l, l + 64, ... of the grid, a wave reduction on (error, index) picks the first
-//                       smallest as torch.argmin does, and the centre moves there.
+//                       then the wave runs label_grid_search (label_search_dev.h) in fp64: the kernel's own part is the error
+//                       of one candidate centre.
 //   lr_offset_y_kernel  one thread per box.
 //
 // Arithmetic: fp64, one rounding per operation in the reference's order (this file is in the Makefile's EXACT list: no fma
@@ -19,23 +19,11 @@
 
 #include "common.h"
 #include "homography_dev.h"
+#include "label_search_dev.h"
 
 #define LR_THREADS 256
 #define LR_WAVES (LR_THREADS / RN_WAVE)
 #define LR_MAX ((int64_t)1 << 31)
-#define LR_NO_INDEX 0x7fffffff
-
-// torch.argmin's order: a NaN is smaller than every number, equal values go to the lower index
-__device__ __forceinline__ bool lr_before(double ea, int ia, double eb, int ib) {
-    if (ea != ea) return (eb != eb) ? ia < ib : true;
-    if (eb != eb) return false;
-    return ea == eb ? ia < ib : ea < eb;
-}
-
-// element k of np.linspace(start, stop, grid): arange * step + start, the last element is stop itself
-__device__ __forceinline__ double lr_linspace(double start, double stop, double step, int k, int grid) {
-    return k == grid - 1 ? stop : (double)k * step + start;
-}
 
 __global__ void __launch_bounds__(LR_THREADS) lr_rebase_kernel(const double *__restrict__ state6, const int32_t *__restrict__ cam,
                                                                int64_t n, const double *__restrict__ P1_old,
@@ -49,7 +37,7 @@ __global__ void __launch_bounds__(LR_THREADS) lr_rebase_kernel(const double *__r
     if (b >= n) return;
     const int m = cam[b];
     if (m < 0 || m >= n_cam) {
-        if (lane == 0) atomicOr(status, RN_LABEL_BAD_CAMERA);
+        if (lane == 0) rn_flag(status, RN_LABEL_BAD_CAMERA);
         return;
     }
     double s[6];
@@ -64,46 +52,21 @@ __global__ void __launch_bounds__(LR_THREADS) lr_rebase_kernel(const double *__r
         state_corners(s32, fx, fy, fz);
         hg_project_to_im(fx, fy, fz, P1_old, P2_old, m, old_im);
     }
-    const int cells = grid * grid;
     double cx = s[0], cy = s[1], win_err = 0.0;
-    for (int r = 0; r < rounds; ++r) {
-        const double rad = radii[r];
-        const double x0 = cx - rad, x1 = cx + rad, y0 = cy - rad, y1 = cy + rad;    // :1685-1686
-        const double sx = (x1 - x0) / (double)(grid - 1), sy = (y1 - y0) / (double)(grid - 1);
-        double best = INFINITY;
-        int best_i = LR_NO_INDEX;
-        for (int c = lane; c < cells; c += RN_WAVE) {                           // ascending per lane
-            s[0] = lr_linspace(x0, x1, sx, c / grid, grid);                     // :1688-1691: index = ix * grid + iy
-            s[1] = lr_linspace(y0, y1, sy, c % grid, grid);
-            state_corners_mixed(s, fx, fy, fz);
-            hg_project_to_im(fx, fy, fz, P1_new, P2_new, m, im);                // the wrapper switch is per candidate
-            double mk[4];
+    const auto score = [&](double x, double y) {                                // :1685-1701: one shifted box
+        s[0] = x;
+        s[1] = y;
+        state_corners_mixed(s, fx, fy, fz);
+        hg_project_to_im(fx, fy, fz, P1_new, P2_new, m, im);                    // the wrapper switch is per candidate
+        double mk[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {                                       // :1701: the four bottom corners
-                const double dx = im[k].x - old_im[k].x, dy = im[k].y - old_im[k].y;
-                mk[k] = (dx * dx + dy * dy) / 2.0;
-            }
-            const double e = (((mk[0] + mk[1]) + mk[2]) + mk[3]) / 4.0;
-            if (lr_before(e, c, best, best_i)) { best = e; best_i = c; }
+        for (int k = 0; k < 4; ++k) {                                           // :1701: the four bottom corners
+            const double dx = im[k].x - old_im[k].x, dy = im[k].y - old_im[k].y;
+            mk[k] = (dx * dx + dy * dy) / 2.0;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {                                      // (error, index) is a total order: all lanes agree
-            const double oe = __shfl_xor(best, o, RN_WAVE);
-            const int oi = __shfl_xor(best_i, o, RN_WAVE);
-            if (lr_before(oe, oi, best, best_i)) { best = oe; best_i = oi; }
-        }
-        if (!isfinite(best) || best_i >= cells) {                               // wave-uniform
-            if (lane == 0) {
-                atomicOr(status, RN_LABEL_BAD_ERROR);
-                for (int q = 0; q < r; ++q) idx_out[b * rounds + q] = -1;       // the box is left out as a whole
-            }
-            return;
-        }
-        cx = lr_linspace(x0, x1, sx, best_i / grid, grid);                      // :1705
-        cy = lr_linspace(y0, y1, sy, best_i % grid, grid);
-        win_err = best;
-        if (lane == 0) idx_out[b * rounds + r] = best_i;
-    }
+        return (((mk[0] + mk[1]) + mk[2]) + mk[3]) / 4.0;
+    };
+    if (!label_grid_search<double>(cx, cy, win_err, radii, rounds, grid, idx_out + b * rounds, status, score)) return;
     if (lane == 0) {
         centre[b * 2] = cx;
         centre[b * 2 + 1] = cy;

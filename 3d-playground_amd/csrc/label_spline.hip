@@ -29,12 +29,11 @@
 
 #include "common.h"
 #include "homography_dev.h"
+#include "wave_dev.h"
 
 #define SP_THREADS 256
 #define SP_MAX ((int64_t)1 << 31)
 #define SP_MAXIT 20
-
-__device__ __forceinline__ void sp_flag(int32_t *status, int bit) { atomicOr(status, bit); }
 
 // a 1-based array with a stride: a lane's slice of the interleaved workspace (stride NL) or a packed row (stride 1)
 struct SpArr {
@@ -449,7 +448,7 @@ __global__ void __launch_bounds__(RN_WAVE) sp_fit_kernel(const int32_t *__restri
     out_iter[lane] = 0;
     SpGroup q;
     if (g < 0 || g >= G || !sp_group(grp, g, R, NC, NW, N, q) || c0 < 0 || c0 % RN_WAVE || q.wave0 + c0 / RN_WAVE != wv) {
-        if (threadIdx.x == 0) sp_flag(status, RN_SPLINE_BAD_TABLE);
+        if (threadIdx.x == 0) rn_flag(status, RN_SPLINE_BAD_TABLE);
         return;
     }
     const int c = c0 + (int)threadIdx.x;
@@ -485,21 +484,21 @@ __global__ void __launch_bounds__(SP_THREADS) sp_select_kernel(const int32_t *__
                                                                int metric, double *__restrict__ scores, int32_t *__restrict__ win,
                                                                double *__restrict__ wfig, double *__restrict__ wt_out,
                                                                double *__restrict__ wc_out, int32_t *__restrict__ status) {
-    __shared__ double s_best[SP_THREADS];
-    __shared__ int s_idx[SP_THREADS];
+    __shared__ double s_best[SP_THREADS / RN_WAVE];
+    __shared__ int s_idx[SP_THREADS / RN_WAVE];
     const int64_t g = blockIdx.x, NL = NW * RN_WAVE;
     const int tid = threadIdx.x;
     SpGroup q;
     if (!sp_group(grp, g, R, NC, NW, N, q)) {
         if (tid == 0) {
-            sp_flag(status, RN_SPLINE_BAD_TABLE);
+            rn_flag(status, RN_SPLINE_BAD_TABLE);
             win[g * 3] = -1; win[g * 3 + 1] = 0; win[g * 3 + 2] = RN_SPLINE_UNUSED;
         }
         return;
     }
     const double *x = tx + q.row0, *y = val + q.row0, *w2 = wsc + q.row0, *w = wt + q.row0;
     double best = INFINITY;
-    int bidx = INT32_MAX;
+    int bidx = RN_NO_INDEX;
     for (int c = tid; c < q.ncand; c += SP_THREADS) {
         const int64_t lane = (int64_t)q.wave0 * RN_WAVE + c;
         const int n = out_n[lane], ier = out_ier[lane];
@@ -524,22 +523,9 @@ __global__ void __launch_bounds__(SP_THREADS) sp_select_kernel(const int32_t *__
             bidx = c;
         }
     }
-    s_best[tid] = best;
-    s_idx[tid] = bidx;
-    __syncthreads();
-    for (int o = SP_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double b2 = s_best[tid + o];
-            const int i2 = s_idx[tid + o];
-            if (b2 < s_best[tid] || (b2 == s_best[tid] && i2 < s_idx[tid])) {
-                s_best[tid] = b2;
-                s_idx[tid] = i2;
-            }
-        }
-        __syncthreads();
-    }
-    const int wi = s_idx[0];
-    const bool found = wi != INT32_MAX;
+    block_arg_first<SP_THREADS / RN_WAVE>(best, bidx, rn_lt_first<double>(), s_best, s_idx);
+    const int wi = bidx;
+    const bool found = wi != RN_NO_INDEX;
     const int64_t lane = (int64_t)q.wave0 * RN_WAVE + (found ? wi : 0);
     const int n = found ? out_n[lane] : 0;
     for (int i = tid; i < N; i += SP_THREADS) {
@@ -552,7 +538,7 @@ __global__ void __launch_bounds__(SP_THREADS) sp_select_kernel(const int32_t *__
         win[g * 3 + 2] = found ? out_ier[lane] : RN_SPLINE_UNUSED;
         double *f = wfig + g * RN_SPLINE_FIGS;
         f[0] = found ? out_fp[lane] : NAN;
-        f[1] = found ? s_best[0] : NAN;
+        f[1] = found ? best : NAN;
         double se = 0.0, pe = 0.0, mx = -INFINITY;
         if (found) {
             const SpCArr T{ws + lane, NL}, C{ws + (int64_t)N * NL + lane, NL};
@@ -604,7 +590,7 @@ __global__ void __launch_bounds__(SP_THREADS) sp_shift_kernel(const double *__re
     const int64_t lo = off[e], hi = off[e + 1];
     if (!(lo >= 0 && lo < hi && hi <= Rr)) {
         if (lane == 0) {
-            sp_flag(status, RN_SPLINE_BAD_TABLE);
+            rn_flag(status, RN_SPLINE_BAD_TABLE);
             best_t[e] = NAN; errs[e * 2] = NAN; errs[e * 2 + 1] = NAN; best_i[e] = -1;
         }
         return;
@@ -627,27 +613,19 @@ __global__ void __launch_bounds__(SP_THREADS) sp_shift_kernel(const double *__re
             sum = sum + q;
             mx = (q > mx || isnan(q)) ? q : mx;
         }
-        if (bad) sp_flag(status, RN_SPLINE_BAD_TABLE);
+        if (bad) rn_flag(status, RN_SPLINE_BAD_TABLE);
         else err = (metric == 0 || lane == trials) ? sqrt(sum / (double)(hi - lo)) : sqrt(mx);
     }
     const double init = __shfl(err, trials, RN_WAVE);
     double best = (lane < trials && err < INFINITY) ? err : INFINITY;
-    int bi = (lane < trials && err < INFINITY) ? lane : INT32_MAX;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double b2 = __shfl_xor(best, o, RN_WAVE);
-        const int i2 = __shfl_xor(bi, o, RN_WAVE);
-        if (b2 < best || (b2 == best && i2 < bi)) {
-            best = b2;
-            bi = i2;
-        }
-    }
-    const double tbest = __shfl(time, bi == INT32_MAX ? trials : bi, RN_WAVE);
+    int bi = (lane < trials && err < INFINITY) ? lane : RN_NO_INDEX;
+    wave_arg_first(best, bi, rn_lt_first<double>());
+    const double tbest = __shfl(time, bi == RN_NO_INDEX ? trials : bi, RN_WAVE);
     if (lane == 0) {
         best_t[e] = tbest;
         errs[e * 2] = best;
         errs[e * 2 + 1] = init;
-        best_i[e] = bi == INT32_MAX ? -1 : bi;
+        best_i[e] = bi == RN_NO_INDEX ? -1 : bi;
     }
 }
 
@@ -659,7 +637,7 @@ __global__ void sp_weights_kernel(const double *__restrict__ state6, const int32
     if (i >= n) return;
     const int m = cam[i];
     if (m < 0 || m >= n_cam) {
-        sp_flag(status, RN_LABEL_BAD_CAMERA);
+        rn_flag(status, RN_LABEL_BAD_CAMERA);
 #pragma unroll
         for (int k = 0; k < 4; ++k) out[i * 4 + k] = NAN;
         return;

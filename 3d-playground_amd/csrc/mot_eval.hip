@@ -257,8 +257,8 @@ __global__ __launch_bounds__(64) void mot_frame_kernel(
             edge += (x0 < 0 || x2 < 0 || x0 > 1920 || x2 > 1920 || y0 < 0 || y2 < 0 || y0 > 1080 || y2 > 1080);   // :286-290
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { edge += __shfl_xor(edge, off, 64); nmatch += __shfl_xor(nmatch, off, 64); }
+    edge = wave_sum(edge);
+    nmatch = wave_sum(nmatch);
     if (lane == 0) { frame_edge[f] = edge; frame_match[f] = nmatch; }
 }
 

@@ -114,8 +114,7 @@ __global__ __launch_bounds__(64) void lsap_solve_kernel(const double *__restrict
             cnt += keep;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    cnt = wave_sum(cnt);
     if (lane == 0) { n_matched[0] = cnt; status[0] = 0; }
 }
 

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "homography_dev.h"
+#include "wave_dev.h"
 
 struct TsPair { int32_t cam_i, cam_j; float te_ij, te_ji; };      // one 16-byte record per pair: its two entries
 
@@ -179,12 +180,7 @@ __global__ __launch_bounds__(1024) void ts_scan_kernel(const int64_t *__restrict
         sum += cnt[q];
         if (r < dd) { const int64_t c = cams[r]; bad |= (c < 0 || c >= n_cam); }
     }
-    int incl = sum;                                                             // inclusive scan inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    const int incl = wave_scan_incl(sum);
     if (lane == 63) wave_tot[wv] = incl;
     bad = __syncthreads_or(bad);
     int before = 0, total = 0;

@@ -106,6 +106,26 @@ def test_mates_counts_and_rows_at_the_edges(dev, edges):
     assert torch.equal(t_mate, mate)
 
 
+def test_offsets_carry_across_a_chunk_of_instants(dev):
+    """dr_prefix_kernel walks the instants 256 at a time: 257 of them over five small frames, so the prefix of the last
+    instant and the total hold the carry out of the first chunk."""
+    from retinanet_mi355x import ops
+    frames = [np.array([1, 2, 3]), np.array([3, 9, 1, 2]), np.array([9, 4]), np.array([5, 4, 6, 7, 9]), np.array([7])]
+    offsets = np.concatenate(([0], np.cumsum([len(f) for f in frames]))).astype(np.int64)
+    ids = np.concatenate(frames).astype(np.int64)
+    inst_a = ((np.arange(257) * 7) % 4).astype(np.int32)                                       # inst_a[256] = 0, a frame of 3 mates
+    none = np.zeros(0)
+    want_mate = brute_force(offsets, ids, np.zeros((len(ids), 6)), np.arange(5.0), none, none)[3]
+    per_frame = np.array([(want_mate[offsets[f]:offsets[f + 1]] >= 0).sum() for f in range(len(frames))])
+    assert list(per_frame) == [3, 1, 2, 1, 0]
+    up = lambda a: torch.from_numpy(a).to(dev)     # noqa: E731
+    mate, status = ops.reinterp_mate(up(offsets), up(ids))
+    assert np.array_equal(mate.cpu().numpy(), want_mate)
+    count, prefix, status = ops.reinterp_offsets(up(offsets), mate, up(inst_a), status=status)
+    assert int(status) == 0 and np.array_equal(count.cpu().numpy(), per_frame[inst_a])
+    assert prefix.dtype == torch.int64 and np.array_equal(prefix.cpu().numpy(), np.concatenate(([0], np.cumsum(per_frame[inst_a]))))
+
+
 def test_empty_and_single_frame_inputs(dev):
     import datareader
     none = np.zeros(0)

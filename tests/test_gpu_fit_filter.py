@@ -122,6 +122,31 @@ def test_fit_nearest(ops, dev, golden, name):
         assert list(n(rows)) == [0, 73, 141]
 
 
+@pytest.mark.parametrize("last", [2, 0])
+def test_fit_nearest_compaction_carries_across_a_chunk_of_frames(ops, dev, last):
+    """fit_compact_kernel takes the frames 1024 at a time: 1025 frames of 0 .. 2 detections.  Frames without a match (empty,
+    or NaN distances only) lie all over the first chunk, frame 1023 among them; frame 1024, alone in the second chunk, has a
+    match (its residual's row is the carry) or is empty (the carry is the count)."""
+    from retinanet_mi355x import synth
+    B = 1025
+    d_per = (np.arange(B) * 5 + 1) % 3
+    d_per[[0, 1022, 1023, 1024]] = (1, 2, 0, last)
+    off = np.concatenate(([0], np.cumsum(d_per))).astype(np.int64)
+    gt = synth.vehicle_states(B, seed=541).numpy()
+    gt[[6, 1020], 3] = 0                                           # zero area: NaN distances, no match
+    frame = np.repeat(np.arange(B), d_per)
+    det = gt[frame].copy()
+    det[:, 0] += synth.uniform((len(det),), 542, -20, 20)
+    det[:, 1] += synth.uniform((len(det),), 543, -3, 3)
+    assert d_per[6] and d_per[1020]
+    w_rows, w_resid, w_counts = fc.nearest(gt, det, off)
+    assert w_counts[1] == int((d_per == 0).sum()) > 300 and w_counts[2] == 2 and (w_rows[1024] >= 0) == (last > 0)
+    rows, resid, info = ops.fit_nearest(torch.from_numpy(gt).to(dev), torch.from_numpy(det).to(dev), torch.from_numpy(off).to(dev))
+    assert np.array_equal(n(rows), w_rows) and tuple(n(info)) == w_counts
+    k = int(info[0])
+    assert np.array_equal(n(resid)[:k].view(np.int32), w_resid.view(np.int32)) and not n(resid)[k:].any()
+
+
 def test_fit_nearest_operator_and_edges(ops, dev):
     gt, det, off = fc.nearest_cases()["sizes"]
     g, d, o = torch.from_numpy(gt).to(dev), torch.from_numpy(det).to(dev), torch.from_numpy(off).to(dev)

@@ -120,6 +120,22 @@ def test_fuzz_scenes_equal_the_restatement_bit_for_bit(Me, part):
         check_against(audited(Me, scene), want, seed)
 
 
+def test_interpolation_prefix_carries_across_a_chunk_of_tracklets(Me):
+    """la_prefix_kernel walks the tracklets 256 at a time: 257 tracklets (one camera), most of one row, with gaps in tracklets
+    3, 254 and 255 (the first chunk) and 256 (alone in the second), so the fill's rows depend on the carry between the chunks."""
+    scene = lc.empty_scene(1, 12, seed=9)
+    gaps = {3: (0, 4), 254: (1, 3, 9), 255: (2, 5), 256: (0, 7, 8, 11)}
+    for oid in range(257):
+        for f in gaps.get(oid, (oid % 12,)):
+            lc.put(scene, f, 0, oid, 3.0 * f + 0.25 * oid, 20.0 + 0.5 * f + 0.01 * oid, cls=oid)
+    want = lc.Labels(scene)
+    assert lc.ref_interpolate(want) == 3 + 6 + 2 + 8
+    me = Me(scene)
+    assert me.interpolate_all() == 19
+    for got_a, want_a in zip(lc.dump(me.data, scene["names"]), lc.dump(want.data, scene["names"])):
+        assert bit_equal(got_a, want_a)
+
+
 @pytest.mark.parametrize("name", sorted(SCENES))
 @pytest.mark.parametrize("cols", [(0, 2, -1), (0, 1, -1), (2, 0, 1)])
 def test_sample_block_equals_the_restatement(dev, name, cols):
