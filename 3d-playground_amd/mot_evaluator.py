@@ -10,6 +10,10 @@ result block of ops.MOT_RESULT doubles comes back.  The per-match lists of ``sel
 (``evaluate(collect=True)`` / ``evaluate_tracks(..., collect=True)``); ``evaluate`` goes through ``evaluate_tracks``.
 There is no CPU path.
 
+Beyond the reference: ``evaluate_association`` / ``params["association"]`` add the identity scores (IDF1 / IDP / IDR) and
+the HOTA family from the same packed frames (csrc/mot_assoc.hip, ops.mot_id_* / ops.mot_hota_*); with the key absent or
+False ``evaluate`` is unchanged.
+
 Differences a caller can see, all stated in INTEGRATION.md: ``params["sequence"]`` (plotting through cv2) raises
 NotImplementedError; the (mean, deviation) figures are summed in fp64 in a fixed order, where the reference sums the fp32
 stack in fp32 -- they agree to the reference's own summation error; a frame with more than ops.MOT_MAX objects on a side
@@ -141,11 +145,12 @@ def metrics_from_result(res, match_iou):
     return m, res[52:152].astype(np.int64).reshape(10, 10)
 
 
-def evaluate_tracks(gt_rows, pred_rows, homography, match_iou=0, cutoff_frame=10000, collect=False, m=None):
+def evaluate_tracks(gt_rows, pred_rows, homography, match_iou=0, cutoff_frame=10000, collect=False, m=None, pk=None):
     """For callers that already hold the per-frame dicts of load_i24_csv: -> (metrics, confusion), and with collect=True a
     third value, the per-pair arrays (IoU matrices, assignment slots, per-match vectors).  m: the evaluator's running dict;
     its counters and confusion matrix are set before the ratios are formed, so they outlive TP = 0 as in the reference."""
-    pk = pack_tracks(gt_rows, pred_rows, homography, cutoff_frame)
+    if pk is None:                                                       # pk: pack_tracks' result, for a caller that packs once
+        pk = pack_tracks(gt_rows, pred_rows, homography, cutoff_frame)
     out = run_packed(pk, homography, match_iou, getattr(homography, "device", "cuda:0"), collect=collect)
     res = out["result"]
     if m is not None and res[11] == 0:
@@ -159,11 +164,106 @@ def evaluate_tracks(gt_rows, pred_rows, homography, match_iou=0, cutoff_frame=10
     return metrics, confusion
 
 
+# ------------------------------------------------------------------------------------------------ identity and association
+ASSOC_SCALARS = ("IDF1", "IDP", "IDR", "IDTP", "IDFP", "IDFN", "HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA",
+                 "HOTA(0)")
+ASSOC_FIGURES = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
+ASSOC_TAIL = 6                                                           # IDTP, its status, the two (code, where) status pairs
+
+
+def run_association(pk, hg, id_iou, device, ious=None, collect=False):
+    """Upload once, the five stages of csrc/mot_assoc.hip, one block back: ops.MOT_ASSOC_RESULT doubles of rn_mot_hota_reduce,
+    then IDTP, the identity assignment's status, and (code, where) of rn_mot_id_counts and of rn_mot_hota_align."""
+    dev = torch.device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)     # noqa: E731
+    n_gid, n_pid = len(pk["gid"]), len(pk["pid"])
+    offsets, totals = ops.mot_offsets(pk["n_gt"], pk["n_pred"], dev)      # raises above ops.MOT_MAX, before any launch
+    ops.mot_assoc_dims("evaluate_association", n_gid, n_pid)              # ... and above the dense storage's cap
+    gt_id, pred_id = up(pk["gt_id"]), up(pk["pred_id"])
+    if ious is None:
+        cor = hg.correspondence[hg.default_correspondence]
+        H, P = up(np.asarray(cor["H"], np.float64)), up(np.asarray(cor["P"], np.float64))
+        _, gt_box, pred_box, _ = ops.mot_prepare(up(pk["gt_im"]), up(pk["gt_h0"]), up(pk["gt_vel"]), up(pk["pred_state"]), H, P)
+        ious = ops.mot_iou(gt_box, pred_box, offsets, totals)
+    csr = tuple(up(a) for a in ops.mot_id_csr(pk["n_gt"], pk["n_pred"], pk["gt_id"], n_gid))
+    alphas = up(ops.mot_alphas())
+    gc, pc, C, st_counts = ops.mot_id_counts(ious, offsets, totals, gt_id, pred_id, n_gid, n_pid, id_iou)
+    match, info = ops.mot_id_assign(C)
+    pot, st_align = ops.mot_hota_align(ious, offsets, totals, gt_id, pred_id, csr, n_gid, n_pid)
+    assigned = ops.mot_hota_assign(ious, offsets, totals, gt_id, pred_id, gc, pc, pot, alphas)
+    result = ops.mot_hota_reduce(offsets, totals, assigned, gt_id, pred_id, gc, pc)
+    block = torch.cat((result, info.double(), st_counts.double(), st_align.double()))
+    out = dict(result=block.cpu().numpy())
+    if collect:
+        out.update(iou=ious.cpu().numpy(), gc=gc.cpu().numpy(), pc=pc.cpu().numpy(), C=C.cpu().numpy(), id_match=match.cpu().numpy(),
+                   pot=pot.cpu().numpy(), slot_row=assigned[0].cpu().numpy(), slot_col=assigned[1].cpu().numpy(),
+                   slot_s=assigned[2].cpu().numpy(), slot_n=assigned[3].cpu().numpy())
+    return out
+
+
+def association_from_result(res, n_gt_objects, n_pred_objects, alphas=None):
+    """The identity and HOTA figures from run_association's block.  The ratios and the means over alpha are formed here."""
+    R = ops.MOT_ASSOC_RESULT
+    idtp, id_status, c_code, c_where, a_code, a_where = (int(v) for v in res[R:R + ASSOC_TAIL])
+    for code, where, what in ((c_code, c_where, "frame slot"), (a_code, a_where, "ground-truth id index")):
+        if code == ops.MOT_DUPLICATE_ID:
+            raise ValueError("an id occurs twice in one frame on one side (%s %d); the identity and association scores need "
+                             "ids that are unique within a frame" % (what, where))
+        if code != 0:
+            raise RuntimeError("association scores: an index outside the packed layout (code %d, %s %d)" % (code, what, where))
+    status, frame = int(res[R - 2]), int(res[R - 1])
+    if status == ops.MOT_INVALID:
+        raise ValueError("matrix contains invalid numeric entries (frame slot %d)" % frame)
+    if status == ops.MOT_INFEASIBLE or id_status == ops.MOT_INFEASIBLE:
+        raise ValueError("cost matrix is infeasible (frame slot %d)" % frame)
+    if status != 0:
+        raise RuntimeError("association scores: frame slot %d has status %d" % (frame, status))
+    idfn, idfp = n_gt_objects - idtp, n_pred_objects - idtp
+    m = {"IDF1": idtp / max(1, idtp + 0.5 * idfp + 0.5 * idfn), "IDP": idtp / max(1, idtp + idfp), "IDR": idtp / max(1, idtp + idfn),
+         "IDTP": idtp, "IDFP": idfp, "IDFN": idfn}
+    blk = np.asarray(res[:ops.MOT_ALPHAS * 7], np.float64).reshape(ops.MOT_ALPHAS, 7)
+    TP, FN, FP, loc, a_sum, re_sum, pr_sum = (blk[:, k] for k in range(7))
+    per = {"TP": TP.astype(np.int64), "FN": FN.astype(np.int64), "FP": FP.astype(np.int64)}
+    per["AssA"] = a_sum / np.maximum(1, TP)
+    per["AssRe"] = re_sum / np.maximum(1, TP)
+    per["AssPr"] = pr_sum / np.maximum(1, TP)
+    per["DetRe"] = TP / np.maximum(1, TP + FN)
+    per["DetPr"] = TP / np.maximum(1, TP + FP)
+    per["DetA"] = TP / np.maximum(1, TP + FN + FP)
+    per["HOTA"] = np.sqrt(per["DetA"] * per["AssA"])
+    per["LocA"] = np.maximum(1e-10, loc) / np.maximum(1e-10, TP)
+    for name in ASSOC_FIGURES:
+        m[name] = float(np.mean(per[name]))
+    m["HOTA(0)"] = float(per["HOTA"][0])
+    m["alphas"] = ops.mot_alphas() if alphas is None else np.asarray(alphas, np.float64)
+    m["per_alpha"] = per
+    return m
+
+
+def evaluate_association(gt_rows, pred_rows, homography, cutoff_frame=10000, id_iou=0.5, collect=False, ious=None):
+    """IDF1 / IDP / IDR (Ristani et al. 2016) and the HOTA family (Luiten et al. 2021) of a tracking output, on the device.
+    These go beyond the reference's evaluator.  -> a dict with IDF1, IDP, IDR, IDTP, IDFP, IDFN; HOTA, DetA, AssA, DetRe, DetPr,
+    AssRe, AssPr, LocA (means over alpha); "HOTA(0)"; "alphas" and "per_alpha" (the arrays).  ious: a flat fp64 device tensor
+    replacing rn_mot_iou's output, as in run_packed.  collect=True returns (dict, the per-stage arrays)."""
+    return _association(pack_tracks(gt_rows, pred_rows, homography, cutoff_frame), homography, id_iou, collect, ious)
+
+
+def _association(pk, homography, id_iou, collect=False, ious=None):
+    out = run_association(pk, homography, id_iou, getattr(homography, "device", "cuda:0"), ious=ious, collect=collect)
+    m = association_from_result(out["result"], int(np.sum(pk["n_gt"])), int(np.sum(pk["n_pred"])))
+    if collect:
+        out["packed"] = pk
+        return m, out
+    return m
+
+
 class MOT_Evaluator():
     def __init__(self, gt_path, pred_path, homography, params=None):
         self.match_iou = 0
         self.cutoff_frame = 10000
         self.sequence = None
+        self.association = False
+        self.id_iou = 0.5
         self.gt_mode = "im"
         self.hg = homography
         _, self.gt = load_i24_csv(gt_path)
@@ -172,6 +272,8 @@ class MOT_Evaluator():
             self.match_iou = params.get("match_iou", self.match_iou)
             self.cutoff_frame = params.get("cutoff_frame", self.cutoff_frame)
             self.sequence = params.get("sequence", self.sequence)
+            self.association = bool(params.get("association", self.association))
+            self.id_iou = params.get("id_iou", self.id_iou)
         if self.sequence is not None:
             raise NotImplementedError("params['sequence'] plots every frame through cv2 (mot_evaluator.py:242-277); "
                                       "this evaluator scores only")
@@ -185,11 +287,23 @@ class MOT_Evaluator():
 
     def evaluate(self, collect=False):
         """collect=True also fills the per-match lists of ``self.m`` (one more copy from the device)."""
-        got = evaluate_tracks(self.gt, self.pred, self.hg, self.match_iou, self.cutoff_frame, collect=collect, m=self.m)
+        pk = pack_tracks(self.gt, self.pred, self.hg, self.cutoff_frame) if self.association else None   # packed once for both
+        got = evaluate_tracks(self.gt, self.pred, self.hg, self.match_iou, self.cutoff_frame, collect=collect, m=self.m, pk=pk)
         self.metrics, self.confusion = got[0], got[1]
         if collect:
             self._collect(got[2]["packed"], got[2])
+        if self.association:                                             # after the reference's keys; absent or False: nothing changes
+            assoc = self.association_metrics = _association(pk, self.hg, self.id_iou)
+            for key in ASSOC_SCALARS:
+                self.metrics[key] = assoc[key]
         self.print_metrics()
+
+    def evaluate_association(self, collect=False):
+        """Only the identity and association figures (IDF1, HOTA, ...): the dict of the module's evaluate_association, kept in
+        ``self.association_metrics``."""
+        got = evaluate_association(self.gt, self.pred, self.hg, self.cutoff_frame, self.id_iou, collect=collect)
+        self.association_metrics = got[0] if collect else got
+        return got
 
     def _collect(self, pk, out):
         """The reference's per-match lists, in its order: frames in increasing order, matches by ascending row."""

@@ -88,6 +88,12 @@ SIGNATURES = {
     "rn_mot_frame_metrics": (c_i32, [c_vp] * 5 + [c_i64, c_i64, c_vp, c_vp, c_vp, c_f64] + [c_vp] * 19),
     "rn_mot_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "rn_mot_reduce": (c_i32, [c_i64, c_i64] + [c_vp] * 16 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "rn_mot_assoc_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rn_mot_id_counts": (c_i32, [c_vp] * 5 + [c_i64] * 6 + [c_vp, c_vp, c_i64, c_i64, c_f64] + [c_vp] * 5),
+    "rn_mot_id_assign": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "rn_mot_hota_align": (c_i32, [c_vp] * 5 + [c_i64] * 6 + [c_vp] * 5 + [c_i64] * 3 + [c_vp] * 5),
+    "rn_mot_hota_assign": (c_i32, [c_vp] * 5 + [c_i64] * 6 + [c_vp, c_vp, c_i64, c_i64] + [c_vp] * 11),
+    "rn_mot_hota_reduce": (c_i32, [c_vp] * 4 + [c_i64] * 6 + [c_vp] * 9 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
     "rn_vanishing_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rn_hg_reproj_error": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "rn_hg_scale_z": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),

@@ -810,6 +810,176 @@ def mot_reduce(offsets, totals, assigned, per_slot, gt_id, pred_id, n_gid, n_pid
     return result
 
 
+# ------------------------------------------------------------------------------------------------ identity and association scores
+MOT_ALPHAS = 19                    # RN_MOT_ALPHAS
+MOT_ASSOC_RESULT = 135             # RN_MOT_ASSOC_RESULT
+MOT_ASSOC_MAX_CELLS = 1 << 20      # RN_MOT_ASSOC_MAX_CELLS: n_gid * n_pid of the dense id x id storage
+MOT_DUPLICATE_ID, MOT_BAD_INDEX = 4, 5
+
+
+def mot_alphas():
+    """The HOTA thresholds: what np.arange(0.05, 0.99, 0.05) holds, 0.05 + k * 0.05 in fp64."""
+    return np.arange(0.05, 0.99, 0.05)
+
+
+def mot_assoc_dims(what, n_gid, n_pid):
+    """The documented cap of the dense storage: raises before any launch."""
+    if n_gid < 0 or n_pid < 0 or n_gid > MOT_MAX_IDS or n_pid > MOT_MAX_IDS or n_gid * n_pid > MOT_ASSOC_MAX_CELLS:
+        raise RuntimeError("%s: %d ground-truth ids x %d predicted ids = %d cells; the dense id x id storage takes at most %d cells "
+                           "and %d ids per side" % (what, n_gid, n_pid, n_gid * n_pid, MOT_ASSOC_MAX_CELLS, MOT_MAX_IDS))
+
+
+def _assoc_layout(what, offsets, totals, gt_id, pred_id, iou=None):
+    """The frame layout as the rn_mot_id_* / rn_mot_hota_* entries take it: (pointers, sizes)."""
+    gt_off, pr_off, iou_off, slot_off = offsets
+    max_n, _, cells, S = totals
+    _hip.need_gpu(gt_id, pred_id, iou, *offsets)
+    _mot_typed(what, ("gt_id", gt_id, torch.int32), ("pred_id", pred_id, torch.int32), ("gt_off", gt_off, torch.int32),
+               ("pr_off", pr_off, torch.int32), ("iou_off", iou_off, torch.int64), ("slot_off", slot_off, torch.int32))
+    if max_n > MOT_MAX:
+        raise RuntimeError("a frame holds %d objects; the assignment takes at most MOT_MAX = %d per side" % (max_n, MOT_MAX))
+    F = gt_off.numel() - 1
+    if F < 0 or pr_off.numel() != F + 1 or iou_off.numel() != F + 1 or slot_off.numel() != F + 1:
+        raise RuntimeError("%s: the four offset arrays hold F + 1 entries each" % what)
+    if iou is not None:
+        _mot_typed(what, ("iou", iou, torch.float64))
+        if iou.numel() != cells:
+            raise RuntimeError("%s: iou holds %d cells, the offsets describe %d" % (what, iou.numel(), cells))
+    return ((gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(), slot_off.data_ptr()),
+            (F, max_n, gt_id.numel(), pred_id.numel(), cells, S))
+
+
+def mot_id_counts(iou, offsets, totals, gt_id, pred_id, n_gid, n_pid, id_iou=0.5):
+    """-> (gc int32 [n_gid], pc int32 [n_pid]: frames holding each id; C int32 [n_gid, n_pid]: frames with S_t[g,p] >= id_iou;
+    status int32 [2] = (code, first frame): MOT_DUPLICATE_ID where an id occurs twice in a frame on one side)."""
+    lib = _hip.load()
+    mot_assoc_dims("mot_id_counts", n_gid, n_pid)
+    ptrs, sizes = _assoc_layout("mot_id_counts", offsets, totals, gt_id, pred_id, iou)
+    dev = gt_id.device
+    gc = torch.empty(n_gid, dtype=torch.int32, device=dev)
+    pc = torch.empty(n_pid, dtype=torch.int32, device=dev)
+    C = torch.empty((n_gid, n_pid), dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_id_counts(_hip.ptr(iou), *ptrs, *sizes, _hip.ptr(gt_id), _hip.ptr(pred_id), n_gid, n_pid, float(id_iou),
+                                        _hip.ptr(gc), _hip.ptr(pc), _hip.ptr(C), status.data_ptr(), _hip.stream()), "rn_mot_id_counts")
+    return gc, pc, C, status
+
+
+def _assoc_workspace(lib, n_gid, n_pid, dev):
+    return torch.empty(max(16, lib.rn_mot_assoc_workspace_bytes(n_gid, n_pid)), dtype=torch.uint8, device=dev)
+
+
+def mot_id_assign(C):
+    """linear_sum_assignment(C, maximize=True) on the id x id counts, one wave -> (match int32 [n_gid]: the prediction id matched
+    to each ground-truth id or -1; info int64 [2] = (IDTP, status))."""
+    lib = _hip.load()
+    _hip.need_gpu(C)
+    _mot_typed("mot_id_assign", ("C", C, torch.int32))
+    if C.dim() != 2:
+        raise RuntimeError("mot_id_assign: C is [n_gid, n_pid]")
+    n_gid, n_pid = C.shape
+    mot_assoc_dims("mot_id_assign", n_gid, n_pid)
+    dev = C.device
+    ws = _assoc_workspace(lib, n_gid, n_pid, dev)
+    match = torch.empty(n_gid, dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_id_assign(_hip.ptr(C), n_gid, n_pid, ws.data_ptr(), _hip.ptr(match), info.data_ptr(), _hip.stream()),
+                   "rn_mot_id_assign")
+    return match, info
+
+
+def mot_id_csr(n_gt, n_pred, gt_id, n_gid):
+    """Host: per ground-truth id its appearances over the scored frames (both sides present) as a CSR in ascending frame order
+    -> (csr_off int32 [n_gid + 1], csr_frame, csr_row int32 [n]) numpy arrays.  gt_id: the packed dense ids, a host array."""
+    ng, npr = np.asarray(n_gt, np.int64).reshape(-1), np.asarray(n_pred, np.int64).reshape(-1)
+    gid = np.asarray(gt_id, np.int64).reshape(-1)
+    frame = np.repeat(np.arange(len(ng)), ng)
+    row = np.arange(len(gid)) - np.repeat(np.cumsum(ng) - ng, ng)
+    keep = (npr[frame] > 0) & (gid >= 0) & (gid < n_gid) if len(gid) else np.zeros(0, bool)
+    frame, row, gid = frame[keep], row[keep], gid[keep]
+    order = np.argsort(gid, kind="stable")                                  # objects are in frame order already
+    off = np.concatenate(([0], np.cumsum(np.bincount(gid, minlength=n_gid)))) if n_gid else np.zeros(1)
+    return off.astype(np.int32), frame[order].astype(np.int32), row[order].astype(np.int32)
+
+
+def mot_hota_align(iou, offsets, totals, gt_id, pred_id, csr, n_gid, n_pid):
+    """The potential-match sums of HOTA's global alignment -> (pot fp64 [n_gid, n_pid], status int32 [2]).  csr = (csr_off,
+    csr_frame, csr_row) int32 device tensors (mot_id_csr); row g of pot is summed by one workgroup in ascending frame order."""
+    lib = _hip.load()
+    mot_assoc_dims("mot_hota_align", n_gid, n_pid)
+    ptrs, sizes = _assoc_layout("mot_hota_align", offsets, totals, gt_id, pred_id, iou)
+    csr_off, csr_frame, csr_row = csr
+    _hip.need_gpu(*csr)
+    _mot_typed("mot_hota_align", ("csr_off", csr_off, torch.int32), ("csr_frame", csr_frame, torch.int32), ("csr_row", csr_row, torch.int32))
+    if csr_off.numel() != n_gid + 1 or csr_frame.numel() != csr_row.numel():
+        raise RuntimeError("mot_hota_align: csr_off [n_gid + 1], csr_frame and csr_row of one length")
+    dev = gt_id.device
+    rowsum = torch.empty(gt_id.numel(), dtype=torch.float64, device=dev)
+    colsum = torch.empty(pred_id.numel(), dtype=torch.float64, device=dev)
+    pot = torch.empty((n_gid, n_pid), dtype=torch.float64, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_hota_align(_hip.ptr(iou), *ptrs, *sizes, _hip.ptr(gt_id), _hip.ptr(pred_id), csr_off.data_ptr(),
+                                         _hip.ptr(csr_frame), _hip.ptr(csr_row), csr_frame.numel(), n_gid, n_pid, _hip.ptr(rowsum),
+                                         _hip.ptr(colsum), _hip.ptr(pot), status.data_ptr(), _hip.stream()), "rn_mot_hota_align")
+    return pot, status
+
+
+def mot_hota_assign(iou, offsets, totals, gt_id, pred_id, gc, pc, pot, alphas):
+    """Per scored frame linear_sum_assignment(-(ga * S)), ga = pot / ((gc + pc) - pot) -> (slot_row, slot_col int32 [S], slot_s
+    fp64 [S]: the pair's S, slot_n int32 [S]: how many of the ascending alphas pass S >= alpha - 2^-52, frame_status int32 [F])."""
+    lib = _hip.load()
+    _hip.need_gpu(gc, pc, pot, alphas)
+    _mot_typed("mot_hota_assign", ("gc", gc, torch.int32), ("pc", pc, torch.int32), ("pot", pot, torch.float64),
+               ("alphas", alphas, torch.float64))
+    n_gid, n_pid = gc.numel(), pc.numel()
+    mot_assoc_dims("mot_hota_assign", n_gid, n_pid)
+    if pot.numel() != n_gid * n_pid or alphas.numel() != MOT_ALPHAS:
+        raise RuntimeError("mot_hota_assign: pot [n_gid, n_pid], alphas [%d]" % MOT_ALPHAS)
+    ptrs, sizes = _assoc_layout("mot_hota_assign", offsets, totals, gt_id, pred_id, iou)
+    dev, F, S = gt_id.device, sizes[0], sizes[5]
+    score = torch.empty(sizes[4], dtype=torch.float64, device=dev)
+    slot_row = torch.empty(S, dtype=torch.int32, device=dev)
+    slot_col = torch.empty(S, dtype=torch.int32, device=dev)
+    slot_s = torch.empty(S, dtype=torch.float64, device=dev)
+    slot_n = torch.empty(S, dtype=torch.int32, device=dev)
+    frame_status = torch.zeros(F, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_hota_assign(_hip.ptr(iou), *ptrs, *sizes, _hip.ptr(gt_id), _hip.ptr(pred_id), n_gid, n_pid, _hip.ptr(gc),
+                                          _hip.ptr(pc), _hip.ptr(pot), alphas.data_ptr(), _hip.ptr(score), _hip.ptr(slot_row),
+                                          _hip.ptr(slot_col), _hip.ptr(slot_s), _hip.ptr(slot_n), _hip.ptr(frame_status),
+                                          _hip.stream()), "rn_mot_hota_assign")
+    return slot_row, slot_col, slot_s, slot_n, frame_status
+
+
+def mot_hota_reduce(offsets, totals, assigned, gt_id, pred_id, gc, pc):
+    """assigned = what mot_hota_assign returns -> result fp64 [MOT_ASSOC_RESULT] on the device: per alpha (TP, FN, FP, Loc,
+    AssA-sum, AssRe-sum, AssPr-sum), then the status and the first frame with one (layout: include/retinanet_mi355x.h)."""
+    lib = _hip.load()
+    slot_row, slot_col, slot_s, slot_n, frame_status = assigned
+    _hip.need_gpu(gc, pc, *assigned)
+    _mot_typed("mot_hota_reduce", ("gc", gc, torch.int32), ("pc", pc, torch.int32), ("slot_row", slot_row, torch.int32),
+               ("slot_col", slot_col, torch.int32), ("slot_s", slot_s, torch.float64), ("slot_n", slot_n, torch.int32),
+               ("frame_status", frame_status, torch.int32))
+    n_gid, n_pid = gc.numel(), pc.numel()
+    mot_assoc_dims("mot_hota_reduce", n_gid, n_pid)
+    ptrs, sizes = _assoc_layout("mot_hota_reduce", offsets, totals, gt_id, pred_id)
+    F, S = sizes[0], sizes[5]
+    if frame_status.numel() != F or any(t.numel() != S for t in (slot_row, slot_col, slot_s, slot_n)):
+        raise RuntimeError("mot_hota_reduce: frame_status [F = %d] and the four slot arrays [S = %d]" % (F, S))
+    dev = gt_id.device
+    ws = _assoc_workspace(lib, n_gid, n_pid, dev)
+    result = torch.empty(MOT_ASSOC_RESULT, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_mot_hota_reduce(*ptrs, *sizes, _hip.ptr(frame_status), _hip.ptr(slot_row), _hip.ptr(slot_col),
+                                          _hip.ptr(slot_s), _hip.ptr(slot_n), _hip.ptr(gt_id), _hip.ptr(pred_id), _hip.ptr(gc),
+                                          _hip.ptr(pc), n_gid, n_pid, ws.data_ptr(), result.data_ptr(), _hip.stream()),
+                   "rn_mot_hota_reduce")
+    return result
+
+
 # ------------------------------------------------------------------------------------------------ tracking CSV resampling
 REINTERP_TILE = 1024               # RN_REINTERP_TILE: ids of the next frame per LDS tile
 REINTERP_BAD_OFFSETS, REINTERP_BAD_PAIR, REINTERP_BAD_MATE, REINTERP_BAD_PREFIX, REINTERP_BAD_MAT_INDEX = 1, 2, 4, 8, 16

@@ -32,6 +32,9 @@ Operator                                         reference code it stands for
   eval_ap(table, state, tp, num_annotations)     per-class sort + _compute_ap           R/csv_eval.py:216-235, 38-62
   mot_prepare / mot_iou / mot_assign /           MOT_Evaluator.evaluate, all frames    mot_evaluator.py:120-412
   mot_frame_metrics / mot_reduce
+  mot_id_counts / mot_id_assign /                IDF1 and HOTA of the same frames      beyond the reference (csrc/mot_assoc.hip)
+  mot_hota_align / mot_hota_assign /
+  mot_hota_reduce
   vanishing_points(lines, offsets)               find_vanishing_point, many sets       homography.py:96-154
   hg_reproj_error(boxes, heights, H, P, C)       test_transformation's arithmetic      homography.py:581-587
   hg_scale_z(boxes, heights, H, P, gran, max)    scale_Z's search                      homography.py:607-666
@@ -443,6 +446,72 @@ def _(n_gt, n_pred, slot_row, slot_col, pred_assigned, frame_status, per_slot, g
     return gt_id.new_empty((ops.MOT_RESULT,), dtype=torch.float64)
 
 
+# ---- identity and association scores (IDF1, HOTA): the same host int lists for the layout
+@_lib.custom_op(NS + "::mot_id_counts", mutates_args=(), device_types="cuda")
+def mot_id_counts(iou: torch.Tensor, n_gt: List[int], n_pred: List[int], gt_id: torch.Tensor, pred_id: torch.Tensor, n_gid: int,
+                  n_pid: int, id_iou: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    offsets, totals = _mot_layout(n_gt, n_pred, iou.device)
+    return ops.mot_id_counts(iou, offsets, totals, gt_id, pred_id, n_gid, n_pid, id_iou)
+
+
+@mot_id_counts.register_fake
+def _(iou, n_gt, n_pred, gt_id, pred_id, n_gid, n_pid, id_iou):
+    e = iou.new_empty
+    return (e((n_gid,), dtype=torch.int32), e((n_pid,), dtype=torch.int32), e((n_gid, n_pid), dtype=torch.int32),
+            e((2,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::mot_id_assign", mutates_args=(), device_types="cuda")
+def mot_id_assign(C: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.mot_id_assign(C)
+
+
+@mot_id_assign.register_fake
+def _(C):
+    return C.new_empty((C.shape[0],), dtype=torch.int32), C.new_empty((2,), dtype=torch.int64)
+
+
+@_lib.custom_op(NS + "::mot_hota_align", mutates_args=(), device_types="cuda")
+def mot_hota_align(iou: torch.Tensor, n_gt: List[int], n_pred: List[int], gt_id: torch.Tensor, pred_id: torch.Tensor,
+                   csr_off: torch.Tensor, csr_frame: torch.Tensor, csr_row: torch.Tensor, n_gid: int,
+                   n_pid: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    offsets, totals = _mot_layout(n_gt, n_pred, iou.device)
+    return ops.mot_hota_align(iou, offsets, totals, gt_id, pred_id, (csr_off, csr_frame, csr_row), n_gid, n_pid)
+
+
+@mot_hota_align.register_fake
+def _(iou, n_gt, n_pred, gt_id, pred_id, csr_off, csr_frame, csr_row, n_gid, n_pid):
+    return iou.new_empty((n_gid, n_pid), dtype=torch.float64), iou.new_empty((2,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::mot_hota_assign", mutates_args=(), device_types="cuda")
+def mot_hota_assign(iou: torch.Tensor, n_gt: List[int], n_pred: List[int], gt_id: torch.Tensor, pred_id: torch.Tensor,
+                    gc: torch.Tensor, pc: torch.Tensor, pot: torch.Tensor,
+                    alphas: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    offsets, totals = _mot_layout(n_gt, n_pred, iou.device)
+    return ops.mot_hota_assign(iou, offsets, totals, gt_id, pred_id, gc, pc, pot, alphas)
+
+
+@mot_hota_assign.register_fake
+def _(iou, n_gt, n_pred, gt_id, pred_id, gc, pc, pot, alphas):
+    S, e = sum(min(a, b) for a, b in zip(n_gt, n_pred)), iou.new_empty
+    return (e((S,), dtype=torch.int32), e((S,), dtype=torch.int32), e((S,), dtype=torch.float64), e((S,), dtype=torch.int32),
+            e((len(n_gt),), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::mot_hota_reduce", mutates_args=(), device_types="cuda")
+def mot_hota_reduce(n_gt: List[int], n_pred: List[int], slot_row: torch.Tensor, slot_col: torch.Tensor, slot_s: torch.Tensor,
+                    slot_n: torch.Tensor, frame_status: torch.Tensor, gt_id: torch.Tensor, pred_id: torch.Tensor, gc: torch.Tensor,
+                    pc: torch.Tensor) -> torch.Tensor:
+    offsets, totals = _mot_layout(n_gt, n_pred, gt_id.device)
+    return ops.mot_hota_reduce(offsets, totals, (slot_row, slot_col, slot_s, slot_n, frame_status), gt_id, pred_id, gc, pc)
+
+
+@mot_hota_reduce.register_fake
+def _(n_gt, n_pred, slot_row, slot_col, slot_s, slot_n, frame_status, gt_id, pred_id, gc, pc):
+    return gt_id.new_empty((ops.MOT_ASSOC_RESULT,), dtype=torch.float64)
+
+
 # ---- camera calibration
 @_lib.custom_op(NS + "::vanishing_points", mutates_args=(), device_types="cuda")
 def vanishing_points(lines: torch.Tensor, offsets: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -541,6 +610,7 @@ OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "dec
              "eval_select", "eval_match", "eval_ap", "mot_prepare", "mot_iou", "mot_assign", "mot_frame_metrics", "mot_reduce",
              "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography", "reinterp_mate", "reinterp_offsets", "reinterp_rows",
              "track_rows", "render_edges", "render_rects", "render_text", "render_compose")
+OPERATORS += ("mot_id_counts", "mot_id_assign", "mot_hota_align", "mot_hota_assign", "mot_hota_reduce")
 
 
 # ---- output frames: the painters OR into the mask plane in place

@@ -1044,6 +1044,63 @@ int rn_mot_reduce(int64_t F, int64_t S, const int32_t *gt_off, const int32_t *pr
                   const int32_t *gt_id, const int32_t *pred_id, int64_t n_gid, int64_t n_pid, void *workspace,
                   double *result, void *stream);
 
+/* ---------------------------------------------------------------- identity and association scores (IDF1, HOTA) --------
+ * Beyond the reference, whose evaluator stops at the CLEAR-MOT figures above: the identity scores of Ristani et al. (ECCV-W
+ * 2016) and the HOTA family of Luiten et al. (IJCV 2021), from the same packed frames, fp64 IoU matrices (rn_mot_iou) and dense
+ * ids (csrc/mot_assoc.hip states the definitions).  Every entry takes the frame layout: the four offset arrays, F, max_n (the
+ * largest n_gt or n_pred of a frame; above RN_MOT_MAX -> RN_EINVAL, no launch) and the totals n_gt / n_pr (objects), cells, S
+ * (slots) that the offsets are checked against on the device.  n_gid * n_pid <= RN_MOT_ASSOC_MAX_CELLS (dense id x id
+ * storage), else RN_EINVAL before any launch.  No synchronisation.
+ *   rn_mot_id_counts    gc int32 [n_gid] / pc int32 [n_pid]: frames holding each id; C int32 [n_gid, n_pid]: frames with
+ *                       S_t[g,p] >= id_iou.  status int32 [2] = (highest code, first frame with one or -1): RN_MOT_TOO_LARGE
+ *                       (a frame outside the layout), RN_MOT_DUPLICATE_ID (an id twice in one frame on one side),
+ *                       RN_MOT_BAD_INDEX (an id outside the dense range; it is left out)
+ *   rn_mot_id_assign    scipy's linear_sum_assignment(C, maximize=True) on one wave64: match int32 [n_gid] (the prediction id
+ *                       or -1), info int64 [2] = (IDTP = sum of C over the matching, status)
+ *   rn_mot_hota_align   pot fp64 [n_gid, n_pid] = sum over scored frames of S / ((colsum[p] + rowsum[g]) - S) (0 where the
+ *                       denominator is <= 2^-52).  rowsum fp64 [n_gt] / colsum fp64 [n_pr] are scratch the call fills: each a
+ *                       sequential ascending sum.  csr_off int32 [n_gid + 1], csr_frame / csr_row int32 [n_csr]: per
+ *                       ground-truth id its (frame slot, row in the frame) over the scored frames, frames strictly ascending --
+ *                       workgroup g walks them in that order and owns row g of pot, so there is no fp64 atomic and the
+ *                       result is the same bits every time.  status int32 [2] as above (second word: the first id)
+ *   rn_mot_hota_assign  per scored frame linear_sum_assignment(-(ga * S)) with ga = pot / ((gc + pc) - pot); score fp64 [cells]
+ *                       is scratch.  Per slot (ground-truth row ascending): slot_row / slot_col (-1 = no pair), slot_s (the
+ *                       pair's S), slot_n (how many of the ascending alphas fp64 [RN_MOT_ALPHAS] pass S >= alpha - 2^-52: a
+ *                       prefix).  frame_status int32 [F] as rn_mot_assign, and RN_MOT_BAD_INDEX
+ *   rn_mot_hota_reduce  result fp64 [RN_MOT_ASSOC_RESULT]: per alpha k seven values at [7 k]: TP FN FP (exact integers), Loc
+ *                       (sum of S of the counted pairs), AssA-sum = sum M (M / max(1, gc + pc - M)), AssRe-sum (max(1, gc)),
+ *                       AssPr-sum (max(1, pc)) over the cells of M_k -- each fp64 sum in one fixed order (entry e to partial
+ *                       e % 256 in ascending e, the partials in increasing order); [133] status, [134] the first frame with
+ *                       one (then nothing else is reported).  workspace: rn_mot_assoc_workspace_bytes(n_gid, n_pid) bytes
+ *                       (0 = above a limit), shared with rn_mot_id_assign. */
+#define RN_MOT_ALPHAS 19
+#define RN_MOT_ASSOC_RESULT 135
+#define RN_MOT_ASSOC_MAX_CELLS 1048576   /* n_gid * n_pid: 100 bytes of workspace per cell */
+#define RN_MOT_DUPLICATE_ID 4
+#define RN_MOT_BAD_INDEX 5
+int64_t rn_mot_assoc_workspace_bytes(int64_t n_gid, int64_t n_pid);
+int rn_mot_id_counts(const double *iou, const int32_t *gt_off, const int32_t *pr_off, const int64_t *iou_off,
+                     const int32_t *slot_off, int64_t F, int64_t max_n, int64_t n_gt, int64_t n_pr, int64_t cells, int64_t S,
+                     const int32_t *gt_id, const int32_t *pred_id, int64_t n_gid, int64_t n_pid, double id_iou, int32_t *gc,
+                     int32_t *pc, int32_t *C, int32_t *status, void *stream);
+int rn_mot_id_assign(const int32_t *C, int64_t n_gid, int64_t n_pid, void *workspace, int32_t *match, int64_t *info,
+                     void *stream);
+int rn_mot_hota_align(const double *iou, const int32_t *gt_off, const int32_t *pr_off, const int64_t *iou_off,
+                      const int32_t *slot_off, int64_t F, int64_t max_n, int64_t n_gt, int64_t n_pr, int64_t cells, int64_t S,
+                      const int32_t *gt_id, const int32_t *pred_id, const int32_t *csr_off, const int32_t *csr_frame,
+                      const int32_t *csr_row, int64_t n_csr, int64_t n_gid, int64_t n_pid, double *rowsum, double *colsum,
+                      double *pot, int32_t *status, void *stream);
+int rn_mot_hota_assign(const double *iou, const int32_t *gt_off, const int32_t *pr_off, const int64_t *iou_off,
+                       const int32_t *slot_off, int64_t F, int64_t max_n, int64_t n_gt, int64_t n_pr, int64_t cells, int64_t S,
+                       const int32_t *gt_id, const int32_t *pred_id, int64_t n_gid, int64_t n_pid, const int32_t *gc,
+                       const int32_t *pc, const double *pot, const double *alphas, double *score, int32_t *slot_row,
+                       int32_t *slot_col, double *slot_s, int32_t *slot_n, int32_t *frame_status, void *stream);
+int rn_mot_hota_reduce(const int32_t *gt_off, const int32_t *pr_off, const int64_t *iou_off, const int32_t *slot_off,
+                       int64_t F, int64_t max_n, int64_t n_gt, int64_t n_pr, int64_t cells, int64_t S,
+                       const int32_t *frame_status, const int32_t *slot_row, const int32_t *slot_col, const double *slot_s,
+                       const int32_t *slot_n, const int32_t *gt_id, const int32_t *pred_id, const int32_t *gc,
+                       const int32_t *pc, int64_t n_gid, int64_t n_pid, void *workspace, double *result, void *stream);
+
 /* ---- camera calibration (csrc/calibrate.hip): the set-up half of homography.py, fp64 in the reference's order --------
  * rn_vanishing_points  replaces find_vanishing_point (homography.py:96-154) for `sets` line sets in one launch, one
  *                      workgroup per set: lines fp64 [N,4] (x0, y0, x1, y1), offsets int64 [sets+1] (CSR rows into
