@@ -692,7 +692,7 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
                         int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                         int in_relu, void *stream, bool det, void *workspace, int64_t workspace_bytes, int64_t *need_bytes,
                         const void *dy_amax = nullptr, int dy_amax_n = 0, const void *x_amax = nullptr, int x_amax_n = 0,
-                        const void *k_active = nullptr);
+                        const void *k_active = nullptr, int32_t *plan = nullptr);
 
 extern "C" int rn_conv_wgrad_batched(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
                                      int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
@@ -735,11 +735,25 @@ extern "C" int64_t rn_conv_wgrad_det_workspace_bytes(int ldy, int nbatch, int64_
     return rc == RN_OK ? need : -1;
 }
 
+// The path wgrad_launch would take for this problem in the current product mode and options (tests name their cases by it), nothing launched:
+// out = {tile shape 0 = 64 x 256 / 1 = 256 x 64 / 2 = 128 x 128, tiles, K slices, pixels per slice, xcd_map, workgroups,
+//        kernel 0 = conv_wgrad_kernel / 1 = conv_wgrad_once_kernel, arithmetic 0 = fp32 MFMA / 1 = three bf16 terms / 2 = two fp16 terms}.
+extern "C" int rn_conv_wgrad_plan(int ldy, int nbatch, int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N,
+                                  int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int in_relu,
+                                  int have_amax, int have_flags, int det, int32_t *out) {
+    if (out == nullptr) return RN_EINVAL;
+    static const int word = 0;                               // stands for operands that are only tested against NULL here
+    const void *am = have_amax ? &word : nullptr;
+    return wgrad_launch(nullptr, ldy, nullptr, nullptr, nullptr, nbatch, dy_bstride, x_bstride, dw_bstride, colsum_batch, N, Hi, Wi, Cin, Ho,
+                        Wo, Cout, kh, kw, stride, pad, in_relu, nullptr, det != 0, nullptr, 0, nullptr, am, have_amax ? 1 : 0, am,
+                        have_amax ? 1 : 0, have_flags ? &word : nullptr, out);
+}
+
 static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
                         int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
                         int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                         int in_relu, void *stream, bool det, void *workspace, int64_t workspace_bytes, int64_t *need_bytes,
-                        const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, const void *k_active) {
+                        const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, const void *k_active, int32_t *plan) {
     if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin < 4 || (Cin & 3) || (ldy & 3) || ldy < Cout)
         return RN_EINVAL;
     if (nbatch < 1 || nbatch > 4096 || dy_bstride < 0 || x_bstride < 0 || dw_bstride < 0 || colsum_batch < 0 || colsum_batch >= nbatch)
@@ -788,6 +802,21 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
     a.splits = (int)splits;
     a.slab = a.cs_slab = nullptr;
     a.slab_stride = 0;
+    // 16-pixel K-steps: 40-48 KiB of LDS, four / three workgroups per CU (measured: +2..4 % over 32-pixel steps at two per CU
+    // on the mid-size layers, equal on the largest; the 64 x 256 tile does not fit twice at 32).
+    const bool split = rn_get_fp32_mfma() != RN_FP32_NATIVE;
+    // RN_FP32_SPLIT3 with both amax words: the fp16 two-term kernels; without them (a caller of the plain entry point) the three-term ones
+    const bool half = rn_get_fp32_mfma() == RN_FP32_SPLIT3 && dy_amax != nullptr && x_amax != nullptr && dy_amax_n != 0 && x_amax_n != 0;
+    // RN_OPT_WGRAD_ONCE = 0: the per-wave split for the 128 x 128 tile too (A/B)
+    const bool once = split && shape == 2 && rn_get_option(RN_OPT_WGRAD_ONCE) != 0 && Hi + pad < 32000 && Wi + pad < 32000;
+    // only the once-split kernel lists and skips; no quiet dense run
+    if (k_active != nullptr && (!once || in_relu || (a.per_split + 15) / 16 > RN_WG_SKIP_MAX)) return RN_EINVAL;
+    const int64_t grid_wgs = (int64_t)tiles * (a.xcd_map ? (splits + 7) / 8 * 8 : splits);
+    if (plan != nullptr) {                                   // rn_conv_wgrad_plan: the numbers above, nothing launched
+        plan[0] = shape; plan[1] = tiles; plan[2] = a.splits; plan[3] = (int32_t)a.per_split; plan[4] = a.xcd_map;
+        plan[5] = (int32_t)grid_wgs; plan[6] = once ? 1 : 0; plan[7] = half ? 2 : (split ? 1 : 0);
+        return RN_OK;
+    }
     if (det) {
         a.slab_stride = nbatch > 1 ? (int64_t)nbatch * dw_bstride : (int64_t)Cout * a.Kpad;
         const int64_t need = splits * (a.slab_stride + Cout) * (int64_t)sizeof(float);
@@ -796,12 +825,7 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
         a.slab = reinterpret_cast<float *>(workspace);
         a.cs_slab = a.slab + splits * a.slab_stride;
     }
-    const dim3 grid((unsigned)(tiles * (a.xcd_map ? (splits + 7) / 8 * 8 : splits)));
-    // 16-pixel K-steps: 40-48 KiB of LDS, four / three workgroups per CU (measured: +2..4 % over 32-pixel steps at two per CU
-    // on the mid-size layers, equal on the largest; the 64 x 256 tile does not fit twice at 32).
-    const bool split = rn_get_fp32_mfma() != RN_FP32_NATIVE;
-    // RN_FP32_SPLIT3 with both amax words: the fp16 two-term kernels; without them (a caller of the plain entry point) the three-term ones
-    const bool half = rn_get_fp32_mfma() == RN_FP32_SPLIT3 && dy_amax != nullptr && x_amax != nullptr && dy_amax_n != 0 && x_amax_n != 0;
+    const dim3 grid((unsigned)grid_wgs);
     a.dy_amax = dy_amax;
     a.x_amax = x_amax;
     a.dy_amax_n = dy_amax_n;
@@ -818,10 +842,7 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
         } else if (in_relu) hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, true, 16, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
         else hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, false, 16, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);         \
     } while (0)
-    // RN_OPT_WGRAD_ONCE = 0: the per-wave split for the 128 x 128 tile too (A/B)
-    const bool once = split && shape == 2 && rn_get_option(RN_OPT_WGRAD_ONCE) != 0 && Hi + pad < 32000 && Wi + pad < 32000;
-    if (k_active != nullptr) {                               // only the once-split kernel lists and skips; no quiet dense run
-        if (!once || in_relu || (a.per_split + 15) / 16 > RN_WG_SKIP_MAX) return RN_EINVAL;
+    if (k_active != nullptr) {
         if (half) hipLaunchKernelGGL((conv_wgrad_once_kernel<false, true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
         else hipLaunchKernelGGL((conv_wgrad_once_kernel<false, false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     } else if (once && half) {

@@ -393,6 +393,17 @@ def _wgrad_call(lib, dev, dy_ptr, ldy, x_ptr, dw_ptr, cs_ptr, nbatch, dy_bs, x_b
                                          ws.data_ptr(), nb, _hip.stream())
 
 
+WGRAD_PLAN_FIELDS = ("shape", "tiles", "splits", "per_split", "xcd_map", "grid", "kernel", "arith")
+
+
+def wgrad_plan(ldy, nbatch, dy_bs, x_bs, dw_bs, cs_batch, geom, have_amax=False, have_flags=False, det=None):
+    """rn_conv_wgrad_plan: the path _wgrad_call's launch of the same arguments takes, as a dict of WGRAD_PLAN_FIELDS (None: refused)."""
+    out = (ctypes.c_int32 * 8)()
+    det = get_option(OPT_DETERMINISTIC) if det is None else det
+    rc = _hip.load().rn_conv_wgrad_plan(ldy, nbatch, dy_bs, x_bs, dw_bs, cs_batch, *geom, int(have_amax), int(have_flags), int(det), out)
+    return dict(zip(WGRAD_PLAN_FIELDS, out)) if rc == 0 else None
+
+
 def wino_weights(weight, mode=0, scale=None):
     """OIHW 3x3 parameter -> U [36, rows, Kpad] (mode 0: forward; mode 1: data gradient, batch-norm scale folded in)."""
     lib = _hip.load()

@@ -717,6 +717,14 @@ int rn_conv_wgrad_batched_flags(const float *dy, int ldy, const float *x, float 
                                 int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int in_relu,
                                 const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, const void *k_active,
                                 void *workspace, int64_t workspace_bytes, void *stream);
+/* Which path the calls above would take for a problem in the current product mode and options -- nothing is launched (host code).  The
+ * geometry arguments of rn_conv_wgrad_batched; have_amax: both amax operands given; have_flags: the rn_conv_wgrad_batched_flags form;
+ * det: a fixed-order form.  out[0] tile shape (0: 64 x 256, 1: 256 x 64, 2: 128 x 128), out[1] tiles, out[2] K slices, out[3] pixels
+ * per slice, out[4] whole slices per XCD (0/1), out[5] workgroups of the grid, out[6] kernel (0: per-wave operands, 1: operands split
+ * once per workgroup), out[7] arithmetic (0: fp32 MFMA, 1: three bf16 terms, 2: two fp16 terms).  RN_EINVAL where the call would be. */
+int rn_conv_wgrad_plan(int ldy, int nbatch, int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
+                       int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int in_relu, int have_amax,
+                       int have_flags, int det, int32_t *out);
 
 /* ---------------------------------------------------------------- bf16 convolution engine -----------------
  * The reduced-precision form of rn_conv_igemm / rn_conv_wgrad for BASELINE configs[2] (bf16 MFMA,
