@@ -74,6 +74,12 @@ SIGNATURES = {
     "rn_eval_match": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_f64, c_vp, c_vp, c_vp, c_vp]),
     "rn_eval_ap_workspace_bytes": (c_i64, [c_i64]),
     "rn_eval_ap": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rn_eval_corners": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "rn_eval_cuboid_overlap": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "rn_eval_cuboid_assign": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp]),
+    "rn_eval_cuboid_errors": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp]),
     "rn_frame_ingest": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp]),
     "rn_frame_ingest_half": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32] + [c_f32] * 6 + [c_i32, c_vp, c_vp, c_vp]),
     "rn_parse_frame_timestamps": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_vp, c_i32] + [c_vp] * 9),

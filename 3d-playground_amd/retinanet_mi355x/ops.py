@@ -1400,6 +1400,144 @@ def eval_ap(table, state, tp, num_annotations, ap=None):
     return ap, order
 
 
+# ------------------------------------------------------------------------------------------------ detector validation in 3D
+EVAL_CUBOID_OVERLAPS = {"silhouette": 0, "base": 1, "top": 2}      # RN_EVAL_CUBOID_*: all 8 corners / corners 0..3 / corners 4..7
+EVAL_CUBOID_MAX_VERTS = 16         # RN_EVAL_CUBOID_MAX_VERTS
+EVAL_CUBOID_MAX_THRESHOLDS = 8     # RN_EVAL_CUBOID_MAX_THRESHOLDS
+EVAL_CUBOID_TERMS = ("iou", "corner_px", "corner_rel", "corner_px_reversed")        # columns of eval_cuboid_errors' terms
+EVAL_CUBOID_SUMS = ("tp", "iou", "corner_px", "corner_rel", "reversed")             # columns of its per-class sums
+
+
+def _eval_cuboid_check(name, table, img_rows, ann_corners, ann_offsets, num_classes):
+    I, C, M = img_rows.shape[0], int(num_classes), ann_corners.shape[0]
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous():
+        raise RuntimeError(name + ": the table comes from ops.eval_table")
+    if ann_corners.dtype != torch.float64 or (M and tuple(ann_corners.shape) != (M, 16)) or ann_offsets.dtype != torch.int32 or \
+            ann_offsets.numel() != I * C + 1 or not 0 < C <= EVAL_MAX_CLASSES or not ann_corners.is_contiguous() or \
+            not ann_offsets.is_contiguous() or not img_rows.is_contiguous() or img_rows.dtype != torch.int32:
+        raise RuntimeError("%s: contiguous ann_corners [M,16] float64, ann_offsets int32 [%d * %d + 1], got %s %s and %s %s"
+                           % (name, I, C, ann_corners.dtype, tuple(ann_corners.shape), ann_offsets.dtype, tuple(ann_offsets.shape)))
+    return I, C, M
+
+
+def _eval_cuboid_rows(name, rows, **tensors):
+    """Every tensor is contiguous, of the dtype given and has `rows` leading entries."""
+    for what, (t, dtype, shape) in tensors.items():
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("%s: %s is a contiguous %s %s tensor, got %s %s" % (name, what, dtype, list(shape), t.dtype, tuple(t.shape)))
+
+
+def eval_corners(boxes, table, img_rows, image, corners):
+    """The 16 corner coordinates (columns 0:16 of the directional model's boxes [K, >=16]) of the rows eval_select has just
+    appended for `image`, into corners float32 [rows, 16] in place, at the rows' positions.  Same stream as eval_select.
+    No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(boxes, table, img_rows, corners)
+    rows, K = table.shape[0], boxes.shape[0]
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous():
+        raise RuntimeError("eval_corners: the table comes from ops.eval_table")
+    if K and (boxes.dim() != 2 or boxes.shape[1] < 16):
+        raise RuntimeError("eval_corners: boxes [K, >=16] with the corners in columns 0:16, got %s" % (tuple(boxes.shape),))
+    if K > EVAL_MAX_K or not 0 <= int(image) < img_rows.shape[0]:
+        raise RuntimeError("eval_corners: image %d of %d, %d detections (at most %d)" % (image, img_rows.shape[0], K, EVAL_MAX_K))
+    _eval_cuboid_rows("eval_corners", rows, corners=(corners, torch.float32, (rows, 16)))
+    if K:
+        boxes = _hip.f32c(boxes)
+    with torch.cuda.device(table.device):
+        _hip.check(lib.rn_eval_corners(boxes.data_ptr() if K else None, boxes.shape[1] if K else 16, K, int(image), img_rows.shape[0],
+                                       img_rows.data_ptr(), table.data_ptr() if rows else None, rows,
+                                       corners.data_ptr() if rows else None, _hip.stream()), "rn_eval_corners")
+
+
+def eval_cuboid_overlap(table, img_rows, corners, ann_corners, ann_offsets, num_classes, overlap="silhouette"):
+    """Per table row the first maximum, over all annotations of its (image, class) group, of the IoU of the convex hulls of
+    the chosen corners (overlap: "silhouette" all 8, "base" 0..3, "top" 4..7; exact clipping in fp64).  ann_corners [M,16]
+    fp64, ann_offsets int32 [num_images * num_classes + 1] in (image, class) order.  -> (best_iou float64 [rows], best_ann
+    int32 [rows]: the index inside the group, -1 with 0.0 for a group without annotations).  No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(table, img_rows, corners, ann_corners, ann_offsets)
+    if overlap not in EVAL_CUBOID_OVERLAPS:
+        raise RuntimeError("eval_cuboid_overlap: overlap is one of %s, got %r" % (sorted(EVAL_CUBOID_OVERLAPS), overlap))
+    I, C, M = _eval_cuboid_check("eval_cuboid_overlap", table, img_rows, ann_corners, ann_offsets, num_classes)
+    rows, dev = table.shape[0], table.device
+    _eval_cuboid_rows("eval_cuboid_overlap", rows, corners=(corners, torch.float32, (rows, 16)))
+    best_iou = torch.zeros(rows, dtype=torch.float64, device=dev)
+    best_ann = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_eval_cuboid_overlap(table.data_ptr() if rows else None, rows, img_rows.data_ptr() if I else None, I, C,
+                                              corners.data_ptr() if rows else None, ann_corners.data_ptr() if M else None,
+                                              ann_offsets.data_ptr(), M, EVAL_CUBOID_OVERLAPS[overlap],
+                                              best_iou.data_ptr() if rows else None, best_ann.data_ptr() if rows else None,
+                                              _hip.stream()), "rn_eval_cuboid_overlap")
+    return best_iou, best_ann
+
+
+def eval_cuboid_assign(table, img_rows, best_iou, best_ann, ann_offsets, num_annotated, num_classes, thresholds,
+                       num_annotations=None):
+    """The serial walk of csv_eval.py:189-213 per (image, class, threshold) on eval_cuboid_overlap's candidates: a row is a
+    true positive at t iff best_iou >= t and its candidate is not yet taken at t.  thresholds: 1..8 floats, or a float64
+    device tensor; num_annotated = M, the number of packed annotations.  -> (tp uint8 [T, rows], num_annotations int32
+    [num_classes] (written into the tensor given, if one is), matched int32 [rows]: the annotation of the true positives at
+    thresholds[0], else -1).  No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(table, img_rows, best_iou, best_ann, ann_offsets, num_annotations)
+    dev, rows, I, C, M = table.device, table.shape[0], img_rows.shape[0], int(num_classes), int(num_annotated)
+    if not torch.is_tensor(thresholds):
+        thresholds = torch.tensor([float(t) for t in thresholds], dtype=torch.float64, device=dev)
+    T = thresholds.numel()
+    if thresholds.dtype != torch.float64 or not thresholds.is_cuda or not thresholds.is_contiguous() or \
+            not 1 <= T <= EVAL_CUBOID_MAX_THRESHOLDS:
+        raise RuntimeError("eval_cuboid_assign: 1 to %d float64 thresholds, got %s %s"
+                           % (EVAL_CUBOID_MAX_THRESHOLDS, thresholds.dtype, tuple(thresholds.shape)))
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous():
+        raise RuntimeError("eval_cuboid_assign: the table comes from ops.eval_table")
+    if ann_offsets.dtype != torch.int32 or ann_offsets.numel() != I * C + 1 or not ann_offsets.is_contiguous() or \
+            not 0 < C <= EVAL_MAX_CLASSES or M < 0 or img_rows.dtype != torch.int32 or not img_rows.is_contiguous():
+        raise RuntimeError("eval_cuboid_assign: ann_offsets int32 [%d * %d + 1], got %s %s" % (I, C, ann_offsets.dtype, tuple(ann_offsets.shape)))
+    _eval_cuboid_rows("eval_cuboid_assign", rows, best_iou=(best_iou, torch.float64, (rows,)), best_ann=(best_ann, torch.int32, (rows,)))
+    if num_annotations is None:
+        num_annotations = torch.zeros(C, dtype=torch.int32, device=dev)
+    elif num_annotations.dtype != torch.int32 or num_annotations.numel() != C or not num_annotations.is_contiguous():
+        raise RuntimeError("eval_cuboid_assign: num_annotations is a contiguous int32 [num_classes] tensor")
+    tp = torch.zeros((T, rows), dtype=torch.uint8, device=dev)
+    matched = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    taken = torch.empty(M * T, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_eval_cuboid_assign(table.data_ptr() if rows else None, rows, img_rows.data_ptr() if I else None, I, C,
+                                             ann_offsets.data_ptr(), M, best_iou.data_ptr() if rows else None,
+                                             best_ann.data_ptr() if rows else None, thresholds.data_ptr(), T,
+                                             taken.data_ptr() if M else None, tp.data_ptr() if rows else None,
+                                             num_annotations.data_ptr(), matched.data_ptr() if rows else None, _hip.stream()),
+                   "rn_eval_cuboid_assign")
+    return tp, num_annotations, matched
+
+
+def eval_cuboid_errors(table, state, img_rows, corners, ann_corners, ann_offsets, num_classes, tp, matched, best_iou, sums=None):
+    """The error figures of the true positives at thresholds[0] (tp: that threshold's flags, uint8 [rows]).  -> (terms
+    float64 [rows, 4]: EVAL_CUBOID_TERMS, zeros for every other row; sums float64 [num_classes, 5]: EVAL_CUBOID_SUMS per class,
+    added in table order (written into the tensor given, if one is)).  Bit-identical from run to run.  No synchronisation."""
+    lib = _hip.load()
+    _hip.need_gpu(table, state, img_rows, corners, ann_corners, ann_offsets, tp, matched, best_iou, sums)
+    _eval_check_table(table, state)
+    I, C, M = _eval_cuboid_check("eval_cuboid_errors", table, img_rows, ann_corners, ann_offsets, num_classes)
+    rows, dev = table.shape[0], table.device
+    _eval_cuboid_rows("eval_cuboid_errors", rows, corners=(corners, torch.float32, (rows, 16)), tp=(tp, torch.uint8, (rows,)),
+                      matched=(matched, torch.int32, (rows,)), best_iou=(best_iou, torch.float64, (rows,)))
+    if sums is None:
+        sums = torch.zeros((C, 5), dtype=torch.float64, device=dev)
+    elif sums.dtype != torch.float64 or sums.numel() != 5 * C or not sums.is_contiguous():
+        raise RuntimeError("eval_cuboid_errors: sums is a contiguous float64 [num_classes, 5] tensor")
+    terms = torch.zeros((rows, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.rn_eval_cuboid_errors(table.data_ptr() if rows else None, rows, state.data_ptr(), I, C,
+                                             corners.data_ptr() if rows else None, ann_corners.data_ptr() if M else None,
+                                             ann_offsets.data_ptr(), M, tp.data_ptr() if rows else None,
+                                             matched.data_ptr() if rows else None, best_iou.data_ptr() if rows else None,
+                                             terms.data_ptr() if rows else None, sums.data_ptr(), _hip.stream()),
+                   "rn_eval_cuboid_errors")
+    return terms, sums
+
+
 # ------------------------------------------------------------------------------------------------ frame ingest
 IMAGENET_MEAN = (0.485, 0.456, 0.406)     # util_track/mp_loader.py:241
 IMAGENET_STD = (0.229, 0.224, 0.225)

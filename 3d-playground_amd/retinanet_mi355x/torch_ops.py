@@ -30,6 +30,8 @@ Operator                                         reference code it stands for
   eval_select(scores, labels, boxes, table, ..)  _get_detections' selection (in place)  R/csv_eval.py:102-123
   eval_match(table, img_rows, ann_box, off, ..)  evaluate's greedy matching             R/csv_eval.py:189-213, 21-35
   eval_ap(table, state, tp, num_annotations)     per-class sort + _compute_ap           R/csv_eval.py:216-235, 38-62
+  eval_corners / eval_cuboid_overlap / eval_cuboid_assign / eval_cuboid_errors          (no counterpart: eval3d.py)
+                                                 3D validation: cuboid IoU, matching, corner errors
   mot_prepare / mot_iou / mot_assign /           MOT_Evaluator.evaluate, all frames    mot_evaluator.py:120-412
   mot_frame_metrics / mot_reduce
   mot_id_counts / mot_id_assign /                IDF1 and HOTA of the same frames      beyond the reference (csrc/mot_assoc.hip)
@@ -370,6 +372,49 @@ def _(table, state, tp, num_annotations):
     return (table.new_empty((num_annotations.shape[0],), dtype=torch.float64), table.new_empty((table.shape[0],), dtype=torch.int32))
 
 
+# ---- detector validation in 3D (cuboid AP, corner errors)
+@_lib.custom_op(NS + "::eval_corners", mutates_args=("corners",), device_types="cuda")
+def eval_corners(boxes: torch.Tensor, table: torch.Tensor, img_rows: torch.Tensor, image: int, corners: torch.Tensor) -> None:
+    ops.eval_corners(boxes, table, img_rows, image, corners)
+
+
+@_lib.custom_op(NS + "::eval_cuboid_overlap", mutates_args=(), device_types="cuda")
+def eval_cuboid_overlap(table: torch.Tensor, img_rows: torch.Tensor, corners: torch.Tensor, ann_corners: torch.Tensor,
+                        ann_offsets: torch.Tensor, num_classes: int, overlap: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.eval_cuboid_overlap(table, img_rows, corners, ann_corners, ann_offsets, num_classes, overlap)
+
+
+@eval_cuboid_overlap.register_fake
+def _(table, img_rows, corners, ann_corners, ann_offsets, num_classes, overlap):
+    return table.new_empty((table.shape[0],), dtype=torch.float64), table.new_empty((table.shape[0],), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::eval_cuboid_assign", mutates_args=(), device_types="cuda")
+def eval_cuboid_assign(table: torch.Tensor, img_rows: torch.Tensor, best_iou: torch.Tensor, best_ann: torch.Tensor,
+                       ann_offsets: torch.Tensor, num_annotated: int, num_classes: int,
+                       thresholds: List[float]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.eval_cuboid_assign(table, img_rows, best_iou, best_ann, ann_offsets, num_annotated, num_classes, thresholds)
+
+
+@eval_cuboid_assign.register_fake
+def _(table, img_rows, best_iou, best_ann, ann_offsets, num_annotated, num_classes, thresholds):
+    rows = table.shape[0]
+    return (table.new_empty((len(thresholds), rows), dtype=torch.uint8), table.new_empty((num_classes,), dtype=torch.int32),
+            table.new_empty((rows,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::eval_cuboid_errors", mutates_args=(), device_types="cuda")
+def eval_cuboid_errors(table: torch.Tensor, state: torch.Tensor, img_rows: torch.Tensor, corners: torch.Tensor,
+                       ann_corners: torch.Tensor, ann_offsets: torch.Tensor, num_classes: int, tp: torch.Tensor,
+                       matched: torch.Tensor, best_iou: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.eval_cuboid_errors(table, state, img_rows, corners, ann_corners, ann_offsets, num_classes, tp, matched, best_iou)
+
+
+@eval_cuboid_errors.register_fake
+def _(table, state, img_rows, corners, ann_corners, ann_offsets, num_classes, tp, matched, best_iou):
+    return table.new_empty((table.shape[0], 4), dtype=torch.float64), table.new_empty((num_classes, 5), dtype=torch.float64)
+
+
 # ---- tracking evaluation (MOT metrics): the per-frame counts travel as host int lists, as ops.mot_offsets takes them
 def _mot_layout(n_gt, n_pred, device):
     return ops.mot_offsets(n_gt, n_pred, device)
@@ -611,6 +656,7 @@ OPERATORS = ("anchors", "pairwise_iou", "focal_loss_fwd", "focal_loss_bwd", "dec
              "vanishing_points", "hg_reproj_error", "hg_scale_z", "fit_homography", "reinterp_mate", "reinterp_offsets", "reinterp_rows",
              "track_rows", "render_edges", "render_rects", "render_text", "render_compose")
 OPERATORS += ("mot_id_counts", "mot_id_assign", "mot_hota_align", "mot_hota_assign", "mot_hota_reduce")
+OPERATORS += ("eval_corners", "eval_cuboid_overlap", "eval_cuboid_assign", "eval_cuboid_errors")
 
 
 # ---- output frames: the painters OR into the mask plane in place

@@ -334,6 +334,52 @@ int rn_eval_ap(const void *table, int64_t table_rows, const int32_t *state, cons
                const int32_t *num_annotations, int num_classes, void *workspace, double *ap, int32_t *order,
                void *stream);
 
+/* ---------------------------------------------------------------- detector validation in 3D: cuboid AP, corner errors
+ * Beyond the reference (its csv_eval.py scores four columns; on the directional model's rows it would read two corner
+ * points as a box).  Detections are the directional model's [K,20] rows, columns 0:16 the corners fbl fbr bbl bbr ftl ftr
+ * btl btr as (x, y); annotations are ann_corners [M,16] fp64 with ann_offsets [num_images * num_classes + 1] i32 in
+ * (image, class) order, as rn_eval_match takes its boxes.  Table, img_rows and state are rn_eval_select's, unchanged.
+ * No entry synchronises; all take any stream.  All arithmetic is fp64, one rounding per operation; no floating-point atomics.
+ * rn_eval_corners, once per image right after its rn_eval_select on the same stream: corners [table_rows,16] fp32 gets
+ *   columns 0:16 of boxes[row.index] for the rows img_rows[image] names (none after a status).  box_stride >= 16.
+ * rn_eval_cuboid_overlap: per row the first maximum over ALL annotations of its (image, class) group of the IoU of two
+ *   convex polygons -- the hull of the chosen corners of the detection and of the annotation: RN_EVAL_CUBOID_SILHOUETTE all 8,
+ *   _BASE corners 0..3, _TOP corners 4..7.  Hull: points sorted by (x, y), exact duplicates dropped, monotone chain in which
+ *   a cross product <= 0 pops (collinear points go); fewer than 3 vertices or a non-finite coordinate on either side gives 0.
+ *   Intersection: the detection's hull cut by each edge of the annotation's (Sutherland-Hodgman, on the edge is inside, at
+ *   most RN_EVAL_CUBOID_MAX_VERTS vertices), shoelace area clipped to [0, min(area_a, area_b)]; iou = inter /
+ *   max(area_a + area_b - inter, DBL_EPSILON).  best_iou [table_rows] fp64, best_ann [table_rows] i32: the index inside the
+ *   group, or -1 with 0.0 for a group without annotations and for rows behind the cursor.
+ * rn_eval_cuboid_assign: thresholds [num_thresholds <= RN_EVAL_CUBOID_MAX_THRESHOLDS] fp64 ON THE DEVICE.  Per (group,
+ *   threshold) the rows in table order: tp[t * table_rows + row] = 1 iff best_iou >= thresholds[t] and best_ann has not been
+ *   taken at t (csv_eval.py:189-213: the candidate is the argmax over all annotations, taken or not), else 0.  matched
+ *   [table_rows] i32: best_ann of the true positives at thresholds[0], else -1.  num_annotations [num_classes] i32 as
+ *   rn_eval_match counts them.  taken: M * num_thresholds bytes of workspace.
+ * rn_eval_cuboid_errors, for the true positives at thresholds[0] (tp: that threshold's table_rows flags): terms
+ *   [table_rows,4] fp64 = best_iou, corner_px (the mean over the 8 corners of the distance in pixels, label order),
+ *   corner_px / max(diag, DBL_EPSILON) with diag the diagonal of the min / max envelope of the annotation's 8 corners,
+ *   corner_px with the detection's corners taken in the order 3 2 1 0 7 6 5 4 (turned by 180 degrees); zeros for every other
+ *   row.  sums [num_classes,5] fp64 = n_tp, sum best_iou, sum corner_px, sum corner_px / diag, n_reversed (rows whose
+ *   turned corner_px is strictly smaller), each added in table order. */
+#define RN_EVAL_CUBOID_SILHOUETTE 0
+#define RN_EVAL_CUBOID_BASE 1
+#define RN_EVAL_CUBOID_TOP 2
+#define RN_EVAL_CUBOID_MAX_VERTS 16
+#define RN_EVAL_CUBOID_MAX_THRESHOLDS 8
+int rn_eval_corners(const float *boxes, int64_t box_stride, int64_t K, int image, int64_t num_images,
+                    const int32_t *img_rows, const void *table, int64_t table_rows, float *corners, void *stream);
+int rn_eval_cuboid_overlap(const void *table, int64_t table_rows, const int32_t *img_rows, int64_t num_images,
+                           int num_classes, const float *corners, const double *ann_corners, const int32_t *ann_offsets,
+                           int64_t M, int overlap, double *best_iou, int32_t *best_ann, void *stream);
+int rn_eval_cuboid_assign(const void *table, int64_t table_rows, const int32_t *img_rows, int64_t num_images,
+                          int num_classes, const int32_t *ann_offsets, int64_t M, const double *best_iou,
+                          const int32_t *best_ann, const double *thresholds, int num_thresholds, void *taken, uint8_t *tp,
+                          int32_t *num_annotations, int32_t *matched, void *stream);
+int rn_eval_cuboid_errors(const void *table, int64_t table_rows, const int32_t *state, int64_t num_images, int num_classes,
+                          const float *corners, const double *ann_corners, const int32_t *ann_offsets, int64_t M,
+                          const uint8_t *tp, const int32_t *matched, const double *best_iou, double *terms, double *sums,
+                          void *stream);
+
 /* ---------------------------------------------------------------- frame ingest ----------------------------
  * Replaces F.to_tensor + F.normalize of the reference's loaders (util_track/mp_loader.py:239-243,
  * perform_3D_detection_on_video_sequences.py:51-58) on device: frames uint8 [B,H,W,3] (as the decoder / cv2.resize

@@ -3,6 +3,7 @@
 
   python tools/train_ddp.py --gpus N [--epochs 3] [--iters 4] [--batch 8] [--height 1080 --width 1920] [--arch resnet50]
                             [--dtype fp32|bf16] [--out gpurun_out/train_ddp] [--resume PATH]
+                            [--validate-3d BATCHES]
 
   * model: the drop-in ``resnet50(num_classes=8)`` (directional 3D-RetinaNet), same random-init weights on every rank, heads
     re-initialised as the reference does (:290-291); ``--resume`` loads a checkpoint first -- also one written by the
@@ -48,6 +49,9 @@ def parse():
     ap.add_argument("--augment", action="store_true",
                     help="feed the step from augment.AugmentedBatches (the reference loader's augmentation, on the device) over "
                          "synth.frames quantised to uint8, instead of from ready-made tensors")
+    ap.add_argument("--validate-3d", type=int, default=0, metavar="BATCHES",
+                    help="after every epoch score the model's 3D boxes on this many held-out synthetic batches (eval3d.validator: "
+                         "cuboid AP at IoU 0.5 / 0.7 and the corner errors of the matched boxes); the result is the epoch's 'validation'")
     return ap.parse_args()
 
 
@@ -111,9 +115,17 @@ def main():
         batches = augment.AugmentedBatches(u8, labels, ["p1c1"] * n, {"p1c1": [[-310.5, 12.25], [2100.75, -55.5], [48.0, 3000.5]]},
                                            B, dev, seed=rank)
 
+    validate = None
+    if args.validate_3d:
+        from retinanet_mi355x import eval3d
+        held_out = [(synth.frames(B, H, W, seed=900000 + 10 * it), synth.labels_dir(B, 10, H, W, 8, seed=900005 + 10 * it))
+                    for it in range(args.validate_3d)]                             # the same on every rank, never trained on
+        validate = eval3d.validator(held_out, num_classes=8)
+
     t0 = time.time()
     hist = trainer.train(net, opt, sched, batches, args.epochs, checkpoint=os.path.join(args.out, "corrected_data_e{}.pt"),
-                         rank=rank, log=lambda m: print(m, flush=True), dataparallel_keys=args.dataparallel_keys)
+                         rank=rank, log=lambda m: print(m, flush=True), dataparallel_keys=args.dataparallel_keys,
+                         validate=validate)
     torch.cuda.synchronize()
     dt = time.time() - t0
     # every rank holds the same weights: compare a checksum across ranks
