@@ -3,6 +3,10 @@
 The library is built in-tree by ``csrc/Makefile`` (``__graft_entry__.build()``).  There is no fallback: if the
 shared object is missing or a tensor is not on a HIP device every op raises -- the product path never runs on
 the CPU and never touches ``oracle/``.
+
+``call`` is how the operator wrappers (``ops.py``, ``util_track/kf.py``) reach an entry point that ends in the stream: it turns
+tensors into pointers, reads the current stream inside the device guard, appends it and checks the return code.  The training
+path (``conv.py``, ``engine.py``, ``optim.py``) passes structures by reference and takes no guard: it uses ``load`` / ``check``.
 """
 import ctypes
 import os
@@ -293,6 +297,19 @@ def ptr(t):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def call(name, *args, device=None):
+    """Run entry point ``name``, whose last parameter is the stream, on the current stream and check its return code.
+    A tensor argument passes its ``data_ptr()``, ``None`` passes NULL, anything else goes as given.  With ``device`` the
+    call runs under that device's guard and the stream is read inside it; a caller that makes several calls holds one
+    guard of its own and gives none."""
+    fn = getattr(load(), name)
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    if device is None:
+        return check(fn(*args, stream()), name)
+    with torch.cuda.device(device):
+        check(fn(*args, stream()), name)
 
 
 def f32c(t):

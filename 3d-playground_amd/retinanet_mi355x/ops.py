@@ -25,8 +25,7 @@ def anchors(height, width, device):
         raise RuntimeError("anchors are generated on the MI355X (no CPU fallback); got device %s" % device)
     n = lib.rn_anchor_count(int(height), int(width))
     out = torch.empty((1, n, 4), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _hip.check(lib.rn_anchors_fwd(out.data_ptr(), int(height), int(width), _hip.stream()), "rn_anchors_fwd")
+    _hip.call("rn_anchors_fwd", out, int(height), int(width), device=device)
     return out
 
 
@@ -36,20 +35,16 @@ def anchor_count(height, width):
 
 def pairwise_iou(a, b):
     """calc_iou (D/losses.py:5-22): [A,4] x [N,4] -> [A,N]."""
-    lib = _hip.load()
     _hip.need_gpu(a, b)
     a, b = _hip.f32c(a), _hip.f32c(b)
     out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
     if out.numel():
-        with torch.cuda.device(a.device):
-            _hip.check(lib.rn_pairwise_iou(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.shape[0], b.shape[0],
-                                           _hip.stream()), "rn_pairwise_iou")
+        _hip.call("rn_pairwise_iou", a, b, out, a.shape[0], b.shape[0], device=a.device)
     return out
 
 
 def assign(anchor_boxes, ann, directional=True):
     """(iou_max [B,A] f32, argmax [B,A] i32 among valid rows, state [B,A] i32 in {-1,0,1}) -- D/losses.py:109-124."""
-    lib = _hip.load()
     _hip.need_gpu(anchor_boxes, ann)
     anc = _hip.f32c(anchor_boxes.reshape(-1, 4))
     ann = _hip.f32c(ann)
@@ -58,9 +53,7 @@ def assign(anchor_boxes, ann, directional=True):
     iou = torch.empty((B, A), dtype=torch.float32, device=anc.device)
     arg = torch.empty((B, A), dtype=torch.int32, device=anc.device)
     st = torch.empty((B, A), dtype=torch.int32, device=anc.device)
-    with torch.cuda.device(anc.device):
-        _hip.check(lib.rn_assign(anc.data_ptr(), ann.data_ptr(), B, A, N, int(directional), iou.data_ptr(),
-                                 arg.data_ptr(), st.data_ptr(), _hip.stream()), "rn_assign")
+    _hip.call("rn_assign", anc, ann, B, A, N, int(directional), iou, arg, st, device=anc.device)
     return iou, arg, st
 
 
@@ -80,7 +73,6 @@ def focal_workspace_bytes(B, A):
 
 def focal_loss_forward_raw(cls, reg, anchor_boxes, ann, directional):
     """rn_focal_loss_fwd: -> (losses [3] fp32, workspace for the backward).  No autograd, no label check."""
-    lib = _hip.load()
     _hip.need_gpu(cls, reg, anchor_boxes, ann)
     cls_c, reg_c = _hip.f32c(cls), _hip.f32c(reg)
     anc = _hip.f32c(anchor_boxes.reshape(-1, 4))
@@ -94,26 +86,20 @@ def focal_loss_forward_raw(cls, reg, anchor_boxes, ann, directional):
                               "directional" if directional else "2D"))
     ws = focal_workspace(B, A, cls_c.device)
     losses = torch.empty(3, dtype=torch.float32, device=cls_c.device)
-    with torch.cuda.device(cls_c.device):
-        _hip.check(lib.rn_focal_loss_fwd(cls_c.data_ptr(), reg_c.data_ptr(), anc.data_ptr(), _hip.ptr(ann_c),
-                                         B, A, C, N, int(directional), ws.data_ptr(), losses.data_ptr(),
-                                         _hip.stream()), "rn_focal_loss_fwd")
+    _hip.call("rn_focal_loss_fwd", cls_c, reg_c, anc, ann_c, B, A, C, N, int(directional), ws, losses, device=cls_c.device)
     return losses, ws
 
 
 def focal_loss_backward_raw(cls, reg, anchor_boxes, ann, directional, ws, grad_losses):
     """rn_focal_loss_bwd: grad_losses [3] device floats -> (dcls, dreg)."""
-    lib = _hip.load()
     cls_c, reg_c = _hip.f32c(cls), _hip.f32c(reg)
     anc = _hip.f32c(anchor_boxes.reshape(-1, 4))
     ann_c = _hip.f32c(ann)
     B, A, C = cls_c.shape
     g = _hip.f32c(grad_losses.reshape(3))
     dcls, dreg = torch.empty_like(cls_c), torch.empty_like(reg_c)
-    with torch.cuda.device(cls_c.device):
-        _hip.check(lib.rn_focal_loss_bwd(cls_c.data_ptr(), reg_c.data_ptr(), anc.data_ptr(), _hip.ptr(ann_c),
-                                         B, A, C, ann_c.shape[1], int(directional), ws.data_ptr(),
-                                         g.data_ptr(), dcls.data_ptr(), dreg.data_ptr(), _hip.stream()), "rn_focal_loss_bwd")
+    _hip.call("rn_focal_loss_bwd", cls_c, reg_c, anc, ann_c, B, A, C, ann_c.shape[1], int(directional), ws, g, dcls, dreg,
+              device=cls_c.device)
     return dcls, dreg
 
 
@@ -203,27 +189,22 @@ def focal_loss(cls, reg, anchor_boxes, ann, directional=True, check_labels=True)
 # ------------------------------------------------------------------------------------------------ decode
 def decode_dir(anchor_boxes, reg):
     """BBoxTransform.forward, directional (D/utils.py:102-149): [1,A,4],[B,A,12] -> [B,A,20]."""
-    lib = _hip.load()
     _hip.need_gpu(anchor_boxes, reg)
     anc, reg_c = _hip.f32c(anchor_boxes.reshape(-1, 4)), _hip.f32c(reg)
     B, A, _ = reg_c.shape
     out = torch.empty((B, A, 20), dtype=torch.float32, device=reg_c.device)
-    with torch.cuda.device(reg_c.device):
-        _hip.check(lib.rn_decode_dir(anc.data_ptr(), reg_c.data_ptr(), out.data_ptr(), B, A, _hip.stream()), "rn_decode_dir")
+    _hip.call("rn_decode_dir", anc, reg_c, out, B, A, device=reg_c.device)
     return out
 
 
 def decode_2d(anchor_boxes, deltas, clip_hw=None):
     """BBoxTransform.forward, 2D (R/utils.py:102-126), optionally with ClipBoxes fused (R/utils.py:134-144)."""
-    lib = _hip.load()
     _hip.need_gpu(anchor_boxes, deltas)
     anc, d = _hip.f32c(anchor_boxes.reshape(-1, 4)), _hip.f32c(deltas)
     B, A, _ = d.shape
     out = torch.empty((B, A, 4), dtype=torch.float32, device=d.device)
     h, w = clip_hw if clip_hw is not None else (0.0, 0.0)
-    with torch.cuda.device(d.device):
-        _hip.check(lib.rn_decode_2d(anc.data_ptr(), d.data_ptr(), out.data_ptr(), B, A, int(clip_hw is not None),
-                                    float(w), float(h), _hip.stream()), "rn_decode_2d")
+    _hip.call("rn_decode_2d", anc, d, out, B, A, int(clip_hw is not None), float(w), float(h), device=d.device)
     return out
 
 
@@ -235,12 +216,9 @@ def clip_boxes_check(boxes):
 
 def clip_boxes_(boxes, height, width):
     """ClipBoxes.forward (R/utils.py:134-144): in place on a contiguous [..,4] fp32 tensor; returns it."""
-    lib = _hip.load()
     clip_boxes_check(boxes)
     if boxes.numel():
-        with torch.cuda.device(boxes.device):
-            _hip.check(lib.rn_clip_boxes(boxes.data_ptr(), boxes.numel() // 4, float(width), float(height),
-                                         _hip.stream()), "rn_clip_boxes")
+        _hip.call("rn_clip_boxes", boxes, boxes.numel() // 4, float(width), float(height), device=boxes.device)
     return boxes
 
 
@@ -256,22 +234,19 @@ class _PostBuffers:
         self.keep = torch.empty((n_problems, NMS_MAX), dtype=torch.int32, device=device)
 
 
-def _select(lib, scores_ptr, n, stride, start, fixed, buf, p):
-    _hip.check(lib.rn_threshold_select(scores_ptr, n, stride, float(start), KEEP, float(fixed), buf.ws.data_ptr(),
-                                       buf.count[p, 0:1].data_ptr(), buf.sel[p].data_ptr(), _hip.stream()),
-               "rn_threshold_select")
+def _select(scores_ptr, n, stride, start, fixed, buf, p):
+    """Under the caller's device guard, as every call of the post-process below."""
+    _hip.call("rn_threshold_select", scores_ptr, n, stride, float(start), KEEP, float(fixed), buf.ws, buf.count[p, 0:1], buf.sel[p])
 
 
-def _nms(lib, boxes, box_col, scores_ptr, score_stride, category, buf, p, max_cand):
-    _hip.check(lib.rn_nms(boxes.data_ptr(), boxes.shape[-1], box_col, scores_ptr, score_stride, buf.sel[p].data_ptr(),
-                          _hip.ptr(category), buf.count[p, 0:1].data_ptr(), max_cand, 0.5, buf.ws.data_ptr(),
-                          buf.keep[p].data_ptr(), buf.count[p, 1:2].data_ptr(), _hip.stream()), "rn_nms")
+def _nms(boxes, box_col, scores_ptr, score_stride, category, buf, p, max_cand):
+    _hip.call("rn_nms", boxes, boxes.shape[-1], box_col, scores_ptr, score_stride, buf.sel[p], category, buf.count[p, 0:1],
+              max_cand, 0.5, buf.ws, buf.keep[p], buf.count[p, 1:2])
 
 
 def postprocess_single(cls, boxes20):
     """Single-frame eval branch (D/model.py:346-397): per class, adaptive threshold from 1e-25 until <= 10 000
     survive, NMS(0.5) on cols 16:20.  cls [1,A,C], boxes [1,A,20] -> [scores[K], class_idx[K] i64, boxes[K,20]]."""
-    lib = _hip.load()
     _hip.need_gpu(cls, boxes20)
     if cls.shape[0] != 1:
         raise RuntimeError("single-frame post-process assumes batch 1 (D/model.py:366 squeezes the batch away); "
@@ -282,8 +257,8 @@ def postprocess_single(cls, boxes20):
     with torch.cuda.device(cls.device):
         for c in range(C):
             sp = cls.data_ptr() + 4 * c
-            _select(lib, sp, A, C, 1e-25, -1.0, buf, c)
-            _nms(lib, boxes20, 16, sp, C, None, buf, c, KEEP)
+            _select(sp, A, C, 1e-25, -1.0, buf, c)
+            _nms(boxes20, 16, sp, C, None, buf, c, KEEP)
     counts = buf.count.cpu().numpy()
     out_s, out_c, out_b = [], [], []
     for c in range(C):
@@ -302,7 +277,6 @@ def postprocess_single(cls, boxes20):
 def postprocess_multi(cls, boxes20):
     """MULTI_FRAME eval branch (D/model.py:311-344): flatten B*A, max over classes, adaptive threshold from 1e-7,
     batched NMS keyed by image.  -> (scores[K], classes[K] i64, boxes[K,20], im_index[K] i64)."""
-    lib = _hip.load()
     _hip.need_gpu(cls, boxes20)
     cls, boxes20 = _hip.f32c(cls), _hip.f32c(boxes20)
     B, A, C = cls.shape
@@ -312,11 +286,11 @@ def postprocess_multi(cls, boxes20):
     classes = torch.empty(n, dtype=torch.int64, device=dev)
     buf = _PostBuffers(n, 1, KEEP, dev)
     with torch.cuda.device(dev):
-        _hip.check(lib.rn_rowmax(cls.data_ptr(), n, C, scores.data_ptr(), classes.data_ptr(), _hip.stream()), "rn_rowmax")
-        _select(lib, scores.data_ptr(), n, 1, 1e-7, -1.0, buf, 0)
+        _hip.call("rn_rowmax", cls, n, C, scores, classes)
+        _select(scores, n, 1, 1e-7, -1.0, buf, 0)
         # image index of each candidate = flat index // A   (D/model.py:314-316)
         cat = torch.div(buf.sel[0], A, rounding_mode="floor").to(torch.int32)
-        _nms(lib, boxes20.reshape(n, 20), 16, scores.data_ptr(), 1, cat, buf, 0, KEEP)
+        _nms(boxes20.reshape(n, 20), 16, scores, 1, cat, buf, 0, KEEP)
     counts = buf.count.cpu().numpy()
     idx = buf.sel[0].long()[buf.keep[0, :counts[0, 1]].long()]
     return scores[idx], classes[idx], boxes20.reshape(n, 20)[idx], torch.div(idx, A, rounding_mode="floor")
@@ -334,7 +308,6 @@ def detect_multi(cls, reg, anchor_boxes):
     filter: row max over classes -> adaptive threshold (<= 10 000 candidates) -> decode those (rn_decode_dir_select; the
     reference decodes all B*A anchors first, :347) -> batched NMS keyed by image on the compact boxes.  Same survivors,
     bit-identical boxes.  -> (scores[K], classes[K] i64, boxes[K,20], im_index[K] i64)."""
-    lib = _hip.load()
     _hip.need_gpu(cls, reg, anchor_boxes)
     cls, reg = _hip.f32c(cls), _hip.f32c(reg)
     anc = _hip.f32c(anchor_boxes.reshape(-1, 4))
@@ -348,14 +321,11 @@ def detect_multi(cls, reg, anchor_boxes):
     cscore = torch.empty(KEEP, dtype=torch.float32, device=dev)
     cimage = torch.empty(KEEP, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _hip.check(lib.rn_rowmax(cls.data_ptr(), n, C, scores.data_ptr(), classes.data_ptr(), _hip.stream()), "rn_rowmax")
-        _select(lib, scores.data_ptr(), n, 1, 1e-7, -1.0, buf, 0)
-        _hip.check(lib.rn_decode_dir_select(anc.data_ptr(), reg.data_ptr(), A, scores.data_ptr(), 1, buf.sel[0].data_ptr(),
-                                            buf.count[0, 0:1].data_ptr(), KEEP, cboxes.data_ptr(), cscore.data_ptr(),
-                                            cimage.data_ptr(), _hip.stream()), "rn_decode_dir_select")
-        _hip.check(lib.rn_nms(cboxes.data_ptr(), 20, 16, cscore.data_ptr(), 1, _arange_i32(KEEP, dev).data_ptr(),
-                              cimage.data_ptr(), buf.count[0, 0:1].data_ptr(), KEEP, 0.5, buf.ws.data_ptr(),
-                              buf.keep[0].data_ptr(), buf.count[0, 1:2].data_ptr(), _hip.stream()), "rn_nms")
+        _hip.call("rn_rowmax", cls, n, C, scores, classes)
+        _select(scores, n, 1, 1e-7, -1.0, buf, 0)
+        _hip.call("rn_decode_dir_select", anc, reg, A, scores, 1, buf.sel[0], buf.count[0, 0:1], KEEP, cboxes, cscore, cimage)
+        _hip.call("rn_nms", cboxes, 20, 16, cscore, 1, _arange_i32(KEEP, dev), cimage, buf.count[0, 0:1], KEEP, 0.5, buf.ws,
+                  buf.keep[0], buf.count[0, 1:2])
     counts = buf.count.cpu().numpy()
     kept = buf.keep[0, :counts[0, 1]].long()                              # candidate positions, decreasing score
     return cscore[kept], classes[buf.sel[0].long()[kept]], cboxes[kept], cimage[kept].long()
@@ -364,7 +334,6 @@ def detect_multi(cls, reg, anchor_boxes):
 def detect_single(cls, reg, anchor_boxes):
     """Single-frame eval branch (D/model.py:346-397) from the head outputs, decoding only each class's survivors.
     cls [1,A,C], reg [1,A,12] -> [scores[K], class_idx[K] i64, boxes[K,20]]."""
-    lib = _hip.load()
     _hip.need_gpu(cls, reg, anchor_boxes)
     if cls.shape[0] != 1:
         raise RuntimeError("single-frame post-process assumes batch 1 (D/model.py:366 squeezes the batch away); "
@@ -380,13 +349,10 @@ def detect_single(cls, reg, anchor_boxes):
     with torch.cuda.device(dev):
         for c in range(C):
             sp = cls.data_ptr() + 4 * c
-            _select(lib, sp, A, C, 1e-25, -1.0, buf, c)
-            _hip.check(lib.rn_decode_dir_select(anc.data_ptr(), reg.data_ptr(), A, sp, C, buf.sel[c].data_ptr(),
-                                                buf.count[c, 0:1].data_ptr(), KEEP, cboxes[c].data_ptr(), cscore[c].data_ptr(),
-                                                None, _hip.stream()), "rn_decode_dir_select")
-            _hip.check(lib.rn_nms(cboxes[c].data_ptr(), 20, 16, cscore[c].data_ptr(), 1, ar.data_ptr(), None,
-                                  buf.count[c, 0:1].data_ptr(), KEEP, 0.5, buf.ws.data_ptr(), buf.keep[c].data_ptr(),
-                                  buf.count[c, 1:2].data_ptr(), _hip.stream()), "rn_nms")
+            _select(sp, A, C, 1e-25, -1.0, buf, c)
+            _hip.call("rn_decode_dir_select", anc, reg, A, sp, C, buf.sel[c], buf.count[c, 0:1], KEEP, cboxes[c], cscore[c], None)
+            _hip.call("rn_nms", cboxes[c], 20, 16, cscore[c], 1, ar, None, buf.count[c, 0:1], KEEP, 0.5, buf.ws, buf.keep[c],
+                      buf.count[c, 1:2])
     counts = buf.count.cpu().numpy()
     out_s, out_c, out_b = [], [], []
     for c in range(C):
@@ -404,7 +370,6 @@ def detect_single(cls, reg, anchor_boxes):
 
 def postprocess_2d(cls, boxes4):
     """2D eval branch (R/model.py:283-311): per class score > 0.05, NMS(0.5)."""
-    lib = _hip.load()
     _hip.need_gpu(cls, boxes4)
     if cls.shape[0] != 1:
         raise RuntimeError("the 2D post-process assumes batch 1 (R/model.py:288 squeezes the batch away)")
@@ -414,14 +379,14 @@ def postprocess_2d(cls, boxes4):
     with torch.cuda.device(cls.device):
         for c in range(C):
             sp = cls.data_ptr() + 4 * c
-            _select(lib, sp, A, C, 0.0, 0.05, buf, c)
+            _select(sp, A, C, 0.0, 0.05, buf, c)
         counts = buf.count.cpu().numpy()
         if counts[:, 0].max() > NMS_MAX:
             raise RuntimeError("more than %d boxes above 0.05 in one class (%d): the on-device NMS orders its "
                                "candidates in LDS and does not take more" % (NMS_MAX, counts[:, 0].max()))
         for c in range(C):
             if counts[c, 0]:
-                _nms(lib, boxes4, 0, cls.data_ptr() + 4 * c, C, None, buf, c, NMS_MAX)
+                _nms(boxes4, 0, cls.data_ptr() + 4 * c, C, None, buf, c, NMS_MAX)
     counts = buf.count.cpu().numpy()
     out_s, out_c, out_b = [], [], []
     for c in range(C):
@@ -453,10 +418,8 @@ def nms(boxes, scores, iou_threshold, idxs=None):
     count = torch.tensor([n, 0], dtype=torch.int32, device=dev)
     keep = torch.empty(n, dtype=torch.int32, device=dev)
     cat = None if idxs is None else idxs.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_nms(boxes.data_ptr(), boxes.shape[1], 0, scores.data_ptr(), 1, cand.data_ptr(), _hip.ptr(cat),
-                              count[0:1].data_ptr(), n, float(iou_threshold), ws.data_ptr(), keep.data_ptr(),
-                              count[1:2].data_ptr(), _hip.stream()), "rn_nms")
+    _hip.call("rn_nms", boxes, boxes.shape[1], 0, scores, 1, cand, cat, count[0:1], n, float(iou_threshold), ws, keep, count[1:2],
+              device=dev)
     return keep[:int(count[1])].long()
 
 
@@ -476,45 +439,36 @@ def _state6(state):
 
 
 def hg_state_to_space(state):
-    lib = _hip.load()
     _hip.need_gpu(state)
     s = _state6(state)
     out = torch.empty((s.shape[0], 8, 3), dtype=torch.float32, device=s.device)
     if s.shape[0]:
-        with torch.cuda.device(s.device):
-            _hip.check(lib.rn_state_to_space(s.data_ptr(), out.data_ptr(), s.shape[0], _hip.stream()), "rn_state_to_space")
+        _hip.call("rn_state_to_space", s, out, s.shape[0], device=s.device)
     return out
 
 
 def hg_space_to_state(space):
-    lib = _hip.load()
     _hip.need_gpu(space)
     sp = space.double().contiguous()
     out = torch.empty((sp.shape[0], 6), dtype=torch.float32, device=sp.device)
     if sp.shape[0]:
-        with torch.cuda.device(sp.device):
-            _hip.check(lib.rn_space_to_state(sp.data_ptr(), out.data_ptr(), sp.shape[0], _hip.stream()), "rn_space_to_state")
+        _hip.call("rn_space_to_state", sp, out, sp.shape[0], device=sp.device)
     return out
 
 
 def hg_to_im(points, P, P2=None, mat_index=None, from_state=True):
     """state [d,6] (from_state) or space [d,8,3] fp32 -> image [d,8,2] fp64.  P: device fp64 [n,3,4]."""
-    lib = _hip.load()
     _hip.need_gpu(points, P, P2, mat_index)
     p = _state6(points) if from_state else _hip.f32c(points)
     d = p.shape[0]
     out = torch.empty((d, 8, 2), dtype=torch.float64, device=p.device)
     if d:
-        fn = lib.rn_state_to_im if from_state else lib.rn_space_to_im
-        with torch.cuda.device(p.device):
-            _hip.check(fn(p.data_ptr(), P.data_ptr(), _hip.ptr(P2), _hip.ptr(mat_index), out.data_ptr(), d,
-                          _hip.stream()), "rn_state_to_im")
+        _hip.call("rn_state_to_im" if from_state else "rn_space_to_im", p, P, P2, mat_index, out, d, device=p.device)
     return out
 
 
 def hg_from_im(im, heights, H, H2=None, mat_index=None, to_state=True):
     """image [d,8,2] fp64 + heights [d] -> state [d,6] fp32 (to_state) or space [d,8,3] fp64."""
-    lib = _hip.load()
     _hip.need_gpu(im, heights, H, H2, mat_index)
     im = im.double().contiguous()
     hts = _hip.f32c(heights)
@@ -524,10 +478,7 @@ def hg_from_im(im, heights, H, H2=None, mat_index=None, to_state=True):
     else:
         out = torch.empty((d, 8, 3), dtype=torch.float64, device=im.device)
     if d:
-        fn = lib.rn_im_to_state if to_state else lib.rn_im_to_space
-        with torch.cuda.device(im.device):
-            _hip.check(fn(im.data_ptr(), hts.data_ptr(), H.data_ptr(), _hip.ptr(H2), _hip.ptr(mat_index),
-                          out.data_ptr(), d, _hip.stream()), "rn_im_to_state")
+        _hip.call("rn_im_to_state" if to_state else "rn_im_to_space", im, hts, H, H2, mat_index, out, d, device=im.device)
     return out
 
 
@@ -560,27 +511,21 @@ def parse_detections(scores, labels, boxes20, camera_idxs, H1, H2, P1, P2, sigma
     out_scores = torch.empty(d, dtype=torch.float32, device=dev)
     out_cams = torch.empty(d, dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_parse_detections(scores.data_ptr(), labels.data_ptr(), boxes20.data_ptr(), camera_idxs.data_ptr(), d,
-                                           H1.data_ptr(), _hip.ptr(H2), _hip.ptr(P1), _hip.ptr(P2), H1.shape[0],
-                                           _hip.ptr(hts), float(sigma_d), float(phi_nms_im), float(phi_nms_space),
-                                           int(nms_flags), int(bool(refine_height)), ws.data_ptr(), out_state.data_ptr(),
-                                           out_labels.data_ptr(), out_scores.data_ptr(), out_cams.data_ptr(),
-                                           count.data_ptr(), _hip.stream()), "rn_parse_detections")
+    _hip.call("rn_parse_detections", scores, labels, boxes20, camera_idxs, d, H1, H2, P1, P2, H1.shape[0], hts, float(sigma_d),
+              float(phi_nms_im), float(phi_nms_space), int(nms_flags), int(bool(refine_height)), ws, out_state, out_labels,
+              out_scores, out_cams, count, device=dev)
     return out_state, out_labels, out_scores, out_cams, count
 
 
 def md_iou(a, b):
     """MC_Crop_Tracker.md_iou (MC3D_crop_tracker.py:1030-1049): [B,N,4] x [B,N,4] -> [B,N] fp64."""
-    lib = _hip.load()
     _hip.need_gpu(a, b)
     if a.shape != b.shape or a.shape[-1] != 4:
         raise RuntimeError("md_iou: shapes %s and %s" % (tuple(a.shape), tuple(b.shape)))
     a, b = a.double().contiguous(), b.double().contiguous()
     out = torch.empty(a.shape[:-1], dtype=torch.float64, device=a.device)
     if out.numel():
-        with torch.cuda.device(a.device):
-            _hip.check(lib.rn_md_iou(a.data_ptr(), b.data_ptr(), out.data_ptr(), out.numel(), _hip.stream()), "rn_md_iou")
+        _hip.call("rn_md_iou", a, b, out, out.numel(), device=a.device)
     return out
 
 
@@ -593,7 +538,6 @@ LSAP_OK, LSAP_INVALID, LSAP_INFEASIBLE = 0, 1, 2
 def track_cost(pre, det):
     """The cost of MC_Crop_Tracker.match_hungarian (MC3D_crop_tracker.py:680-701): priors [n, >=6] and detections
     [m, >=6] fp32 states (direction at column 5) -> [n,m] fp64 ``1 - md_iou`` of their road-plane footprints."""
-    lib = _hip.load()
     _hip.need_gpu(pre, det)
     if pre.dim() != 2 or det.dim() != 2 or pre.shape[1] < 6 or det.shape[1] < 6:
         raise RuntimeError("track_cost: states are [n, >= 6], got %s and %s" % (tuple(pre.shape), tuple(det.shape)))
@@ -601,9 +545,7 @@ def track_cost(pre, det):
     n, m = pre.shape[0], det.shape[0]
     cost = torch.empty((n, m), dtype=torch.float64, device=pre.device)
     if n and m:
-        with torch.cuda.device(pre.device):
-            _hip.check(lib.rn_track_cost(pre.data_ptr(), pre.shape[1], det.data_ptr(), det.shape[1], n, m, cost.data_ptr(),
-                                         _hip.stream()), "rn_track_cost")
+        _hip.call("rn_track_cost", pre, pre.shape[1], det, det.shape[1], n, m, cost, device=pre.device)
     return cost
 
 
@@ -624,10 +566,7 @@ def _lsap(cost, max_cost):
                            % (LSAP_MAX_MIN, LSAP_MAX, nr, nc))
     c = cost.double().contiguous()
     ws = torch.empty(lib.rn_lsap_workspace_bytes(nr, nc), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_linear_sum_assignment(c.data_ptr(), nr, nc, float(max_cost), ws.data_ptr(), row_match.data_ptr(),
-                                                info[0:1].data_ptr(), info[1:2].data_ptr(), _hip.stream()),
-                   "rn_linear_sum_assignment")
+    _hip.call("rn_linear_sum_assignment", c, nr, nc, float(max_cost), ws, row_match, info[0:1], info[1:2], device=dev)
     return row_match, info
 
 
@@ -665,19 +604,41 @@ MOT_RESULT = 152                   # RN_MOT_RESULT
 MOT_OK, MOT_INVALID, MOT_INFEASIBLE, MOT_TOO_LARGE = 0, 1, 2, 3
 
 
-def _mot_typed(what, *specs):
+def _typed(what, *specs):
+    """The dtype and contiguity check of every domain below: specs are (name, tensor, dtype)."""
     for name, t, dtype in specs:
         if t.dtype != dtype or not t.is_contiguous():
             raise RuntimeError("%s: %s is a contiguous %s tensor, got %s" % (what, name, dtype, t.dtype))
 
 
+def _status_word(what, device, status):
+    """The status word a family of entry points ORs its bits into: a zeroed int32 [1] unless one is handed on."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    _hip.need_gpu(status)
+    _typed(what, ("status", status, torch.int32))
+    if status.numel() != 1:
+        raise RuntimeError("%s: status is one int32" % what)
+    return status
+
+
+def _refused(prefix, bits_table, status):
+    """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
+    bits = int(status)
+    if bits:
+        raise RuntimeError(prefix + _bits_text(bits_table, bits) + " (status %d)" % bits)
+
+
+def _bits_text(bits_table, bits):
+    return "; ".join(t for b, t in bits_table if bits & b)
+
+
 def mot_prepare(gt_im, gt_h0, gt_vel, pred_state, H, P):
     """mot_evaluator.py:155-215 for all objects of a sequence: gt_im fp64 [G,8,2], gt_h0 / gt_vel fp32 [G], pred_state fp32
     [M,7], H fp64 [3,3], P fp64 [3,4] -> (gt_state fp32 [G,7], gt_box fp32 [G,4], pred_box fp32 [M,4], pred_im fp64 [M,8,2])."""
-    lib = _hip.load()
     _hip.need_gpu(gt_im, gt_h0, gt_vel, pred_state, H, P)
-    _mot_typed("mot_prepare", ("gt_im", gt_im, torch.float64), ("gt_h0", gt_h0, torch.float32), ("gt_vel", gt_vel, torch.float32),
-               ("pred_state", pred_state, torch.float32), ("H", H, torch.float64), ("P", P, torch.float64))
+    _typed("mot_prepare", ("gt_im", gt_im, torch.float64), ("gt_h0", gt_h0, torch.float32), ("gt_vel", gt_vel, torch.float32),
+           ("pred_state", pred_state, torch.float32), ("H", H, torch.float64), ("P", P, torch.float64))
     G, M, dev = gt_im.shape[0], pred_state.shape[0], gt_im.device
     if gt_im.numel() != G * 16 or gt_h0.numel() != G or gt_vel.numel() != G or pred_state.numel() != M * 7 or H.numel() != 9 \
             or P.numel() != 12:
@@ -686,10 +647,7 @@ def mot_prepare(gt_im, gt_h0, gt_vel, pred_state, H, P):
     gt_box = torch.empty((G, 4), dtype=torch.float32, device=dev)
     pred_box = torch.empty((M, 4), dtype=torch.float32, device=dev)
     pred_im = torch.empty((M, 8, 2), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_prepare(_hip.ptr(gt_im), _hip.ptr(gt_h0), _hip.ptr(gt_vel), G, _hip.ptr(pred_state), M, H.data_ptr(),
-                                      P.data_ptr(), gt_state.data_ptr(), gt_box.data_ptr(), pred_box.data_ptr(), pred_im.data_ptr(),
-                                      _hip.stream()), "rn_mot_prepare")
+    _hip.call("rn_mot_prepare", gt_im, gt_h0, gt_vel, G, pred_state, M, H, P, gt_state, gt_box, pred_box, pred_im, device=dev)
     return gt_state, gt_box, pred_box, pred_im
 
 
@@ -714,24 +672,20 @@ def mot_offsets(n_gt, n_pred, device):
 
 def mot_iou(gt_box, pred_box, offsets, totals):
     """Every frame's IoU matrix in self.iou's fp32 arithmetic (mot_evaluator.py:87-118, 219-222) -> flat fp64 [cells]."""
-    lib = _hip.load()
     _hip.need_gpu(gt_box, pred_box, *offsets)
-    _mot_typed("mot_iou", ("gt_box", gt_box, torch.float32), ("pred_box", pred_box, torch.float32))
+    _typed("mot_iou", ("gt_box", gt_box, torch.float32), ("pred_box", pred_box, torch.float32))
     gt_off, pr_off, iou_off, _ = offsets
     max_n, max_cells, cells, _ = totals
     iou = torch.empty(cells, dtype=torch.float64, device=gt_box.device)
-    with torch.cuda.device(gt_box.device):
-        _hip.check(lib.rn_mot_iou(_hip.ptr(gt_box), _hip.ptr(pred_box), gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(),
-                                  gt_off.numel() - 1, max_cells, _hip.ptr(iou), _hip.stream()), "rn_mot_iou")
+    _hip.call("rn_mot_iou", gt_box, pred_box, gt_off, pr_off, iou_off, gt_off.numel() - 1, max_cells, iou, device=gt_box.device)
     return iou
 
 
 def mot_assign(iou, offsets, totals, M):
     """linear_sum_assignment(ious, maximize=True) of every frame (mot_evaluator.py:225) ->
     (slot_row, slot_col int32 [S], pred_assigned uint8 [M], frame_status int32 [F])."""
-    lib = _hip.load()
     _hip.need_gpu(iou, *offsets)
-    _mot_typed("mot_assign", ("iou", iou, torch.float64))
+    _typed("mot_assign", ("iou", iou, torch.float64))
     gt_off, pr_off, iou_off, slot_off = offsets
     max_n, _, cells, S = totals
     if iou.numel() != cells:
@@ -743,10 +697,8 @@ def mot_assign(iou, offsets, totals, M):
     slot_col = torch.empty(S, dtype=torch.int32, device=dev)
     pred_assigned = torch.empty(M, dtype=torch.uint8, device=dev)
     frame_status = torch.zeros(F, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_assign(_hip.ptr(iou), gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(), slot_off.data_ptr(), F,
-                                     max_n, S, M, _hip.ptr(slot_row), _hip.ptr(slot_col), _hip.ptr(pred_assigned),
-                                     _hip.ptr(frame_status), _hip.stream()), "rn_mot_assign")
+    _hip.call("rn_mot_assign", iou, gt_off, pr_off, iou_off, slot_off, F, max_n, S, M, slot_row, slot_col, pred_assigned,
+              frame_status, device=dev)
     return slot_row, slot_col, pred_assigned, frame_status
 
 
@@ -754,14 +706,13 @@ def mot_frame_metrics(iou, offsets, totals, assigned, match_iou, gt_state, pred_
     """mot_evaluator.py:229-238, 283-290, 301-341 per frame.  assigned = what mot_assign returns.  ->
     (slot_iou fp64 [S], slot_gid, slot_pid int32 [S] (-1 below match_iou), state_err fp32 [S,7], bot, top fp64 [S], cell uint8
     [S], frame_edge, frame_match int32 [F])."""
-    lib = _hip.load()
     slot_row, slot_col, pred_assigned, frame_status = assigned
     gt_off, pr_off, iou_off, slot_off = offsets
     _hip.need_gpu(iou, gt_state, pred_state, gt_im, pred_im, gt_cls, pred_cls, gt_id, pred_id, *assigned)
-    _mot_typed("mot_frame_metrics", ("iou", iou, torch.float64), ("gt_state", gt_state, torch.float32),
-               ("pred_state", pred_state, torch.float32), ("gt_im", gt_im, torch.float64), ("pred_im", pred_im, torch.float64),
-               ("gt_cls", gt_cls, torch.int32), ("pred_cls", pred_cls, torch.int32), ("gt_id", gt_id, torch.int32),
-               ("pred_id", pred_id, torch.int32))
+    _typed("mot_frame_metrics", ("iou", iou, torch.float64), ("gt_state", gt_state, torch.float32),
+           ("pred_state", pred_state, torch.float32), ("gt_im", gt_im, torch.float64), ("pred_im", pred_im, torch.float64),
+           ("gt_cls", gt_cls, torch.int32), ("pred_cls", pred_cls, torch.int32), ("gt_id", gt_id, torch.int32),
+           ("pred_id", pred_id, torch.int32))
     G, M = gt_id.numel(), pred_id.numel()
     if gt_state.numel() != G * 7 or pred_state.numel() != M * 7 or gt_im.numel() != G * 16 or pred_im.numel() != M * 16 \
             or gt_cls.numel() != G or pred_cls.numel() != M or pred_assigned.numel() != M:
@@ -776,13 +727,9 @@ def mot_frame_metrics(iou, offsets, totals, assigned, match_iou, gt_state, pred_
     cell = torch.empty(S, dtype=torch.uint8, device=dev)
     frame_edge = torch.zeros(F, dtype=torch.int32, device=dev)
     frame_match = torch.zeros(F, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_frame_metrics(
-            _hip.ptr(iou), gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(), slot_off.data_ptr(), F, S, _hip.ptr(slot_row),
-            _hip.ptr(slot_col), _hip.ptr(frame_status), float(match_iou), _hip.ptr(gt_state), _hip.ptr(pred_state), _hip.ptr(gt_im),
-            _hip.ptr(pred_im), _hip.ptr(gt_cls), _hip.ptr(pred_cls), _hip.ptr(gt_id), _hip.ptr(pred_id), _hip.ptr(pred_assigned),
-            _hip.ptr(slot_iou), _hip.ptr(slot_gid), _hip.ptr(slot_pid), _hip.ptr(state_err), _hip.ptr(bot), _hip.ptr(top),
-            _hip.ptr(cell), _hip.ptr(frame_edge), _hip.ptr(frame_match), _hip.stream()), "rn_mot_frame_metrics")
+    _hip.call("rn_mot_frame_metrics", iou, gt_off, pr_off, iou_off, slot_off, F, S, slot_row, slot_col, frame_status,
+              float(match_iou), gt_state, pred_state, gt_im, pred_im, gt_cls, pred_cls, gt_id, pred_id, pred_assigned, slot_iou,
+              slot_gid, slot_pid, state_err, bot, top, cell, frame_edge, frame_match, device=dev)
     return slot_iou, slot_gid, slot_pid, state_err, bot, top, cell, frame_edge, frame_match
 
 
@@ -795,18 +742,14 @@ def mot_reduce(offsets, totals, assigned, per_slot, gt_id, pred_id, n_gid, n_pid
     slot_row, slot_col, pred_assigned, frame_status = assigned
     slot_iou, slot_gid, slot_pid, state_err, bot, top, cell, frame_edge, frame_match = per_slot
     _hip.need_gpu(gt_id, pred_id, *per_slot)
-    _mot_typed("mot_reduce", ("gt_id", gt_id, torch.int32), ("pred_id", pred_id, torch.int32))
+    _typed("mot_reduce", ("gt_id", gt_id, torch.int32), ("pred_id", pred_id, torch.int32))
     if n_gid > MOT_MAX_IDS or n_pid > MOT_MAX_IDS:
         raise RuntimeError("mot_reduce takes at most %d distinct ids per side, got %d and %d" % (MOT_MAX_IDS, n_gid, n_pid))
     dev, F, S = gt_id.device, gt_off.numel() - 1, totals[3]
     ws = torch.empty(max(16, lib.rn_mot_workspace_bytes(n_gid, n_pid)), dtype=torch.uint8, device=dev)
     result = torch.empty(MOT_RESULT, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_reduce(F, S, gt_off.data_ptr(), pr_off.data_ptr(), slot_off.data_ptr(), _hip.ptr(frame_status),
-                                     _hip.ptr(frame_edge), _hip.ptr(frame_match), _hip.ptr(slot_row), _hip.ptr(slot_iou),
-                                     _hip.ptr(slot_gid), _hip.ptr(slot_pid), _hip.ptr(state_err), _hip.ptr(bot), _hip.ptr(top),
-                                     _hip.ptr(cell), _hip.ptr(gt_id), _hip.ptr(pred_id), n_gid, n_pid, ws.data_ptr(),
-                                     result.data_ptr(), _hip.stream()), "rn_mot_reduce")
+    _hip.call("rn_mot_reduce", F, S, gt_off, pr_off, slot_off, frame_status, frame_edge, frame_match, slot_row, slot_iou, slot_gid,
+              slot_pid, state_err, bot, top, cell, gt_id, pred_id, n_gid, n_pid, ws, result, device=dev)
     return result
 
 
@@ -830,63 +773,56 @@ def mot_assoc_dims(what, n_gid, n_pid):
 
 
 def _assoc_layout(what, offsets, totals, gt_id, pred_id, iou=None):
-    """The frame layout as the rn_mot_id_* / rn_mot_hota_* entries take it: (pointers, sizes)."""
+    """The frame layout as the rn_mot_id_* / rn_mot_hota_* entries take it: (offset tensors, sizes)."""
     gt_off, pr_off, iou_off, slot_off = offsets
     max_n, _, cells, S = totals
     _hip.need_gpu(gt_id, pred_id, iou, *offsets)
-    _mot_typed(what, ("gt_id", gt_id, torch.int32), ("pred_id", pred_id, torch.int32), ("gt_off", gt_off, torch.int32),
-               ("pr_off", pr_off, torch.int32), ("iou_off", iou_off, torch.int64), ("slot_off", slot_off, torch.int32))
+    _typed(what, ("gt_id", gt_id, torch.int32), ("pred_id", pred_id, torch.int32), ("gt_off", gt_off, torch.int32),
+           ("pr_off", pr_off, torch.int32), ("iou_off", iou_off, torch.int64), ("slot_off", slot_off, torch.int32))
     if max_n > MOT_MAX:
         raise RuntimeError("a frame holds %d objects; the assignment takes at most MOT_MAX = %d per side" % (max_n, MOT_MAX))
     F = gt_off.numel() - 1
     if F < 0 or pr_off.numel() != F + 1 or iou_off.numel() != F + 1 or slot_off.numel() != F + 1:
         raise RuntimeError("%s: the four offset arrays hold F + 1 entries each" % what)
     if iou is not None:
-        _mot_typed(what, ("iou", iou, torch.float64))
+        _typed(what, ("iou", iou, torch.float64))
         if iou.numel() != cells:
             raise RuntimeError("%s: iou holds %d cells, the offsets describe %d" % (what, iou.numel(), cells))
-    return ((gt_off.data_ptr(), pr_off.data_ptr(), iou_off.data_ptr(), slot_off.data_ptr()),
-            (F, max_n, gt_id.numel(), pred_id.numel(), cells, S))
+    return (gt_off, pr_off, iou_off, slot_off), (F, max_n, gt_id.numel(), pred_id.numel(), cells, S)
 
 
 def mot_id_counts(iou, offsets, totals, gt_id, pred_id, n_gid, n_pid, id_iou=0.5):
     """-> (gc int32 [n_gid], pc int32 [n_pid]: frames holding each id; C int32 [n_gid, n_pid]: frames with S_t[g,p] >= id_iou;
     status int32 [2] = (code, first frame): MOT_DUPLICATE_ID where an id occurs twice in a frame on one side)."""
-    lib = _hip.load()
     mot_assoc_dims("mot_id_counts", n_gid, n_pid)
-    ptrs, sizes = _assoc_layout("mot_id_counts", offsets, totals, gt_id, pred_id, iou)
+    offs, sizes = _assoc_layout("mot_id_counts", offsets, totals, gt_id, pred_id, iou)
     dev = gt_id.device
     gc = torch.empty(n_gid, dtype=torch.int32, device=dev)
     pc = torch.empty(n_pid, dtype=torch.int32, device=dev)
     C = torch.empty((n_gid, n_pid), dtype=torch.int32, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_id_counts(_hip.ptr(iou), *ptrs, *sizes, _hip.ptr(gt_id), _hip.ptr(pred_id), n_gid, n_pid, float(id_iou),
-                                        _hip.ptr(gc), _hip.ptr(pc), _hip.ptr(C), status.data_ptr(), _hip.stream()), "rn_mot_id_counts")
+    _hip.call("rn_mot_id_counts", iou, *offs, *sizes, gt_id, pred_id, n_gid, n_pid, float(id_iou), gc, pc, C, status, device=dev)
     return gc, pc, C, status
 
 
-def _assoc_workspace(lib, n_gid, n_pid, dev):
-    return torch.empty(max(16, lib.rn_mot_assoc_workspace_bytes(n_gid, n_pid)), dtype=torch.uint8, device=dev)
+def _assoc_workspace(n_gid, n_pid, dev):
+    return torch.empty(max(16, _hip.load().rn_mot_assoc_workspace_bytes(n_gid, n_pid)), dtype=torch.uint8, device=dev)
 
 
 def mot_id_assign(C):
     """linear_sum_assignment(C, maximize=True) on the id x id counts, one wave -> (match int32 [n_gid]: the prediction id matched
     to each ground-truth id or -1; info int64 [2] = (IDTP, status))."""
-    lib = _hip.load()
     _hip.need_gpu(C)
-    _mot_typed("mot_id_assign", ("C", C, torch.int32))
+    _typed("mot_id_assign", ("C", C, torch.int32))
     if C.dim() != 2:
         raise RuntimeError("mot_id_assign: C is [n_gid, n_pid]")
     n_gid, n_pid = C.shape
     mot_assoc_dims("mot_id_assign", n_gid, n_pid)
     dev = C.device
-    ws = _assoc_workspace(lib, n_gid, n_pid, dev)
+    ws = _assoc_workspace(n_gid, n_pid, dev)
     match = torch.empty(n_gid, dtype=torch.int32, device=dev)
     info = torch.empty(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_id_assign(_hip.ptr(C), n_gid, n_pid, ws.data_ptr(), _hip.ptr(match), info.data_ptr(), _hip.stream()),
-                   "rn_mot_id_assign")
+    _hip.call("rn_mot_id_assign", C, n_gid, n_pid, ws, match, info, device=dev)
     return match, info
 
 
@@ -907,12 +843,11 @@ def mot_id_csr(n_gt, n_pred, gt_id, n_gid):
 def mot_hota_align(iou, offsets, totals, gt_id, pred_id, csr, n_gid, n_pid):
     """The potential-match sums of HOTA's global alignment -> (pot fp64 [n_gid, n_pid], status int32 [2]).  csr = (csr_off,
     csr_frame, csr_row) int32 device tensors (mot_id_csr); row g of pot is summed by one workgroup in ascending frame order."""
-    lib = _hip.load()
     mot_assoc_dims("mot_hota_align", n_gid, n_pid)
-    ptrs, sizes = _assoc_layout("mot_hota_align", offsets, totals, gt_id, pred_id, iou)
+    offs, sizes = _assoc_layout("mot_hota_align", offsets, totals, gt_id, pred_id, iou)
     csr_off, csr_frame, csr_row = csr
     _hip.need_gpu(*csr)
-    _mot_typed("mot_hota_align", ("csr_off", csr_off, torch.int32), ("csr_frame", csr_frame, torch.int32), ("csr_row", csr_row, torch.int32))
+    _typed("mot_hota_align", ("csr_off", csr_off, torch.int32), ("csr_frame", csr_frame, torch.int32), ("csr_row", csr_row, torch.int32))
     if csr_off.numel() != n_gid + 1 or csr_frame.numel() != csr_row.numel():
         raise RuntimeError("mot_hota_align: csr_off [n_gid + 1], csr_frame and csr_row of one length")
     dev = gt_id.device
@@ -920,25 +855,22 @@ def mot_hota_align(iou, offsets, totals, gt_id, pred_id, csr, n_gid, n_pid):
     colsum = torch.empty(pred_id.numel(), dtype=torch.float64, device=dev)
     pot = torch.empty((n_gid, n_pid), dtype=torch.float64, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_hota_align(_hip.ptr(iou), *ptrs, *sizes, _hip.ptr(gt_id), _hip.ptr(pred_id), csr_off.data_ptr(),
-                                         _hip.ptr(csr_frame), _hip.ptr(csr_row), csr_frame.numel(), n_gid, n_pid, _hip.ptr(rowsum),
-                                         _hip.ptr(colsum), _hip.ptr(pot), status.data_ptr(), _hip.stream()), "rn_mot_hota_align")
+    _hip.call("rn_mot_hota_align", iou, *offs, *sizes, gt_id, pred_id, csr_off, csr_frame, csr_row, csr_frame.numel(), n_gid, n_pid,
+              rowsum, colsum, pot, status, device=dev)
     return pot, status
 
 
 def mot_hota_assign(iou, offsets, totals, gt_id, pred_id, gc, pc, pot, alphas):
     """Per scored frame linear_sum_assignment(-(ga * S)), ga = pot / ((gc + pc) - pot) -> (slot_row, slot_col int32 [S], slot_s
     fp64 [S]: the pair's S, slot_n int32 [S]: how many of the ascending alphas pass S >= alpha - 2^-52, frame_status int32 [F])."""
-    lib = _hip.load()
     _hip.need_gpu(gc, pc, pot, alphas)
-    _mot_typed("mot_hota_assign", ("gc", gc, torch.int32), ("pc", pc, torch.int32), ("pot", pot, torch.float64),
-               ("alphas", alphas, torch.float64))
+    _typed("mot_hota_assign", ("gc", gc, torch.int32), ("pc", pc, torch.int32), ("pot", pot, torch.float64),
+           ("alphas", alphas, torch.float64))
     n_gid, n_pid = gc.numel(), pc.numel()
     mot_assoc_dims("mot_hota_assign", n_gid, n_pid)
     if pot.numel() != n_gid * n_pid or alphas.numel() != MOT_ALPHAS:
         raise RuntimeError("mot_hota_assign: pot [n_gid, n_pid], alphas [%d]" % MOT_ALPHAS)
-    ptrs, sizes = _assoc_layout("mot_hota_assign", offsets, totals, gt_id, pred_id, iou)
+    offs, sizes = _assoc_layout("mot_hota_assign", offsets, totals, gt_id, pred_id, iou)
     dev, F, S = gt_id.device, sizes[0], sizes[5]
     score = torch.empty(sizes[4], dtype=torch.float64, device=dev)
     slot_row = torch.empty(S, dtype=torch.int32, device=dev)
@@ -946,37 +878,30 @@ def mot_hota_assign(iou, offsets, totals, gt_id, pred_id, gc, pc, pot, alphas):
     slot_s = torch.empty(S, dtype=torch.float64, device=dev)
     slot_n = torch.empty(S, dtype=torch.int32, device=dev)
     frame_status = torch.zeros(F, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_hota_assign(_hip.ptr(iou), *ptrs, *sizes, _hip.ptr(gt_id), _hip.ptr(pred_id), n_gid, n_pid, _hip.ptr(gc),
-                                          _hip.ptr(pc), _hip.ptr(pot), alphas.data_ptr(), _hip.ptr(score), _hip.ptr(slot_row),
-                                          _hip.ptr(slot_col), _hip.ptr(slot_s), _hip.ptr(slot_n), _hip.ptr(frame_status),
-                                          _hip.stream()), "rn_mot_hota_assign")
+    _hip.call("rn_mot_hota_assign", iou, *offs, *sizes, gt_id, pred_id, n_gid, n_pid, gc, pc, pot, alphas, score, slot_row, slot_col,
+              slot_s, slot_n, frame_status, device=dev)
     return slot_row, slot_col, slot_s, slot_n, frame_status
 
 
 def mot_hota_reduce(offsets, totals, assigned, gt_id, pred_id, gc, pc):
     """assigned = what mot_hota_assign returns -> result fp64 [MOT_ASSOC_RESULT] on the device: per alpha (TP, FN, FP, Loc,
     AssA-sum, AssRe-sum, AssPr-sum), then the status and the first frame with one (layout: include/retinanet_mi355x.h)."""
-    lib = _hip.load()
     slot_row, slot_col, slot_s, slot_n, frame_status = assigned
     _hip.need_gpu(gc, pc, *assigned)
-    _mot_typed("mot_hota_reduce", ("gc", gc, torch.int32), ("pc", pc, torch.int32), ("slot_row", slot_row, torch.int32),
-               ("slot_col", slot_col, torch.int32), ("slot_s", slot_s, torch.float64), ("slot_n", slot_n, torch.int32),
-               ("frame_status", frame_status, torch.int32))
+    _typed("mot_hota_reduce", ("gc", gc, torch.int32), ("pc", pc, torch.int32), ("slot_row", slot_row, torch.int32),
+           ("slot_col", slot_col, torch.int32), ("slot_s", slot_s, torch.float64), ("slot_n", slot_n, torch.int32),
+           ("frame_status", frame_status, torch.int32))
     n_gid, n_pid = gc.numel(), pc.numel()
     mot_assoc_dims("mot_hota_reduce", n_gid, n_pid)
-    ptrs, sizes = _assoc_layout("mot_hota_reduce", offsets, totals, gt_id, pred_id)
+    offs, sizes = _assoc_layout("mot_hota_reduce", offsets, totals, gt_id, pred_id)
     F, S = sizes[0], sizes[5]
     if frame_status.numel() != F or any(t.numel() != S for t in (slot_row, slot_col, slot_s, slot_n)):
         raise RuntimeError("mot_hota_reduce: frame_status [F = %d] and the four slot arrays [S = %d]" % (F, S))
     dev = gt_id.device
-    ws = _assoc_workspace(lib, n_gid, n_pid, dev)
+    ws = _assoc_workspace(n_gid, n_pid, dev)
     result = torch.empty(MOT_ASSOC_RESULT, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_mot_hota_reduce(*ptrs, *sizes, _hip.ptr(frame_status), _hip.ptr(slot_row), _hip.ptr(slot_col),
-                                          _hip.ptr(slot_s), _hip.ptr(slot_n), _hip.ptr(gt_id), _hip.ptr(pred_id), _hip.ptr(gc),
-                                          _hip.ptr(pc), n_gid, n_pid, ws.data_ptr(), result.data_ptr(), _hip.stream()),
-                   "rn_mot_hota_reduce")
+    _hip.call("rn_mot_hota_reduce", *offs, *sizes, frame_status, slot_row, slot_col, slot_s, slot_n, gt_id, pred_id, gc, pc, n_gid,
+              n_pid, ws, result, device=dev)
     return result
 
 
@@ -992,21 +917,12 @@ _REINTERP_BITS = ((REINTERP_BAD_OFFSETS, "frame offsets out of order or outside 
 
 def reinterp_status(device, status=None):
     """The status word the four entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
-    if status is None:
-        return torch.zeros(1, dtype=torch.int32, device=device)
-    _hip.need_gpu(status)
-    _mot_typed("reinterp", ("status", status, torch.int32))
-    if status.numel() != 1:
-        raise RuntimeError("reinterp: status is one int32")
-    return status
+    return _status_word("reinterp", device, status)
 
 
 def reinterp_check(status):
     """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
-    bits = int(status)
-    if bits:
-        raise RuntimeError("the resampling kernels refused their input: " + "; ".join(t for b, t in _REINTERP_BITS if bits & b)
-                           + " (status %d)" % bits)
+    _refused("the resampling kernels refused their input: ", _REINTERP_BITS, status)
 
 
 def _reinterp_frames(what, offsets, R):
@@ -1020,26 +936,22 @@ def _reinterp_frames(what, offsets, R):
 def reinterp_mate(offsets, ids, status=None):
     """datareader.py:416-417 for every row: offsets int64 [F+1], ids int64 [R] -> (mate int32 [R] = the row of the next frame
     with the same id or -1, status)."""
-    lib = _hip.load()
     _hip.need_gpu(offsets, ids)
-    _mot_typed("reinterp_mate", ("offsets", offsets, torch.int64), ("ids", ids, torch.int64))
+    _typed("reinterp_mate", ("offsets", offsets, torch.int64), ("ids", ids, torch.int64))
     if ids.dim() != 1:
         raise RuntimeError("reinterp_mate: ids is int64 [R]")
     R, F, dev = ids.numel(), _reinterp_frames("reinterp_mate", offsets, ids.numel()), ids.device
     status = reinterp_status(dev, status)
     mate = torch.empty(R, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_reinterp_mate(offsets.data_ptr(), _hip.ptr(ids), F, R, _hip.ptr(mate), status.data_ptr(), _hip.stream()),
-                   "rn_reinterp_mate")
+    _hip.call("rn_reinterp_mate", offsets, ids, F, R, mate, status, device=dev)
     return mate, status
 
 
 def reinterp_offsets(offsets, mate, inst_a, status=None):
     """offsets int64 [F+1], mate int32 [R], inst_a int32 [T] -> (count int32 [T] = mated rows of frame inst_a[t], prefix int64
     [T+1] = its exclusive prefix, status)."""
-    lib = _hip.load()
     _hip.need_gpu(offsets, mate, inst_a)
-    _mot_typed("reinterp_offsets", ("offsets", offsets, torch.int64), ("mate", mate, torch.int32), ("inst_a", inst_a, torch.int32))
+    _typed("reinterp_offsets", ("offsets", offsets, torch.int64), ("mate", mate, torch.int32), ("inst_a", inst_a, torch.int32))
     if mate.dim() != 1 or inst_a.dim() != 1:
         raise RuntimeError("reinterp_offsets: mate is int32 [R], inst_a int32 [T]")
     R, T, F, dev = mate.numel(), inst_a.numel(), _reinterp_frames("reinterp_offsets", offsets, mate.numel()), mate.device
@@ -1049,10 +961,7 @@ def reinterp_offsets(offsets, mate, inst_a, status=None):
     frame_count = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
     count = torch.empty(T, dtype=torch.int32, device=dev)
     prefix = torch.empty(T + 1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_reinterp_offsets(offsets.data_ptr(), _hip.ptr(mate), F, R, _hip.ptr(inst_a), T, frame_count.data_ptr(),
-                                           _hip.ptr(count), prefix.data_ptr(), status.data_ptr(), _hip.stream()),
-                   "rn_reinterp_offsets")
+    _hip.call("rn_reinterp_offsets", offsets, mate, F, R, inst_a, T, frame_count, count, prefix, status, device=dev)
     return count, prefix, status
 
 
@@ -1061,11 +970,10 @@ def reinterp_rows(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix, ro
     reinterp_offsets returns it, rows = the size of the output (at least prefix[T]; the host's upper bound, so that nothing
     is read back in between) -> (out_fields fp64 [rows,6], out_src int32 [rows], out_inst int32 [rows], status); only rows
     below prefix[T] are written."""
-    lib = _hip.load()
     _hip.need_gpu(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix)
-    _mot_typed("reinterp_rows", ("offsets", offsets, torch.int64), ("frame_ts", frame_ts, torch.float64),
-               ("fields", fields, torch.float64), ("mate", mate, torch.int32), ("inst_a", inst_a, torch.int32),
-               ("inst_time", inst_time, torch.float64), ("prefix", prefix, torch.int64))
+    _typed("reinterp_rows", ("offsets", offsets, torch.int64), ("frame_ts", frame_ts, torch.float64),
+           ("fields", fields, torch.float64), ("mate", mate, torch.int32), ("inst_a", inst_a, torch.int32),
+           ("inst_time", inst_time, torch.float64), ("prefix", prefix, torch.int64))
     R, T, dev = mate.numel(), inst_a.numel(), fields.device
     F = _reinterp_frames("reinterp_rows", offsets, R)
     rows = int(rows)
@@ -1076,11 +984,8 @@ def reinterp_rows(offsets, frame_ts, fields, mate, inst_a, inst_time, prefix, ro
     out_fields = torch.empty((rows, 6), dtype=torch.float64, device=dev)
     out_src = torch.empty(rows, dtype=torch.int32, device=dev)
     out_inst = torch.empty(rows, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_reinterp_rows(offsets.data_ptr(), _hip.ptr(frame_ts), _hip.ptr(fields), _hip.ptr(mate), _hip.ptr(inst_a),
-                                        _hip.ptr(inst_time), prefix.data_ptr(), F, R, T, rows, _hip.ptr(out_fields),
-                                        _hip.ptr(out_src), _hip.ptr(out_inst), status.data_ptr(), _hip.stream()),
-                   "rn_reinterp_rows")
+    _hip.call("rn_reinterp_rows", offsets, frame_ts, fields, mate, inst_a, inst_time, prefix, F, R, T, rows, out_fields, out_src,
+              out_inst, status, device=dev)
     return out_fields, out_src, out_inst, status
 
 
@@ -1088,13 +993,12 @@ def track_rows(fields, direction, P, P2=None, mat_index=None, status=None):
     """datareader.py:530-550 for N rows: fields fp64 [N,6] (x, y, l, w, h, v), direction fp64 [N], P fp64 [n,3,4] (P2: the
     Homography_Wrapper's second set), mat_index int32 [N] or None (matrix 0) -> (state fp32 [N,7], space fp32 [N,4,2], im fp64
     [N,8,2], box fp64 [N,4], keep uint8 [N], status)."""
-    lib = _hip.load()
     _hip.need_gpu(fields, direction, P, P2, mat_index)
-    _mot_typed("track_rows", ("fields", fields, torch.float64), ("direction", direction, torch.float64), ("P", P, torch.float64))
+    _typed("track_rows", ("fields", fields, torch.float64), ("direction", direction, torch.float64), ("P", P, torch.float64))
     if P2 is not None:
-        _mot_typed("track_rows", ("P2", P2, torch.float64))
+        _typed("track_rows", ("P2", P2, torch.float64))
     if mat_index is not None:
-        _mot_typed("track_rows", ("mat_index", mat_index, torch.int32))
+        _typed("track_rows", ("mat_index", mat_index, torch.int32))
     N, dev = direction.numel(), fields.device
     if P.dim() != 3 or tuple(P.shape[1:]) != (3, 4) or P.shape[0] < 1 or (P2 is not None and P2.shape != P.shape) \
             or fields.numel() != N * 6 or direction.dim() != 1 or (mat_index is not None and tuple(mat_index.shape) != (N,)):
@@ -1105,10 +1009,7 @@ def track_rows(fields, direction, P, P2=None, mat_index=None, status=None):
     im = torch.empty((N, 8, 2), dtype=torch.float64, device=dev)
     box = torch.empty((N, 4), dtype=torch.float64, device=dev)
     keep = torch.empty(N, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_track_rows(_hip.ptr(fields), _hip.ptr(direction), _hip.ptr(mat_index), P.data_ptr(), _hip.ptr(P2),
-                                     P.shape[0], N, _hip.ptr(state), _hip.ptr(space), _hip.ptr(im), _hip.ptr(box), _hip.ptr(keep),
-                                     status.data_ptr(), _hip.stream()), "rn_track_rows")
+    _hip.call("rn_track_rows", fields, direction, mat_index, P, P2, P.shape[0], N, state, space, im, box, keep, status, device=dev)
     return state, space, im, box, keep, status
 
 
@@ -1155,11 +1056,8 @@ def estimate_ts_bias(boxes, camera_idxs, objs, timestamps, ts_bias, phi, alpha, 
         ts = timestamps.double().contiguous()
         cnt = None if count is None else count.to(torch.int32).contiguous()
         ws = torch.empty(lib.rn_ts_bias_workspace_bytes(d, mp), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _hip.check(lib.rn_estimate_ts_bias(boxes.data_ptr(), boxes.shape[1], cams.data_ptr(), d, _hip.ptr(cnt),
-                                               objs.data_ptr(), objs.shape[1], n, ts.data_ptr(), ts_bias.data_ptr(), n_cam,
-                                               float(phi), float(alpha), float(mu_v), ws.data_ptr(), mp, _hip.ptr(pairs),
-                                               _hip.ptr(te), info.data_ptr(), _hip.stream()), "rn_estimate_ts_bias")
+        _hip.call("rn_estimate_ts_bias", boxes, boxes.shape[1], cams, d, cnt, objs, objs.shape[1], n, ts, ts_bias, n_cam, float(phi),
+                  float(alpha), float(mu_v), ws, mp, pairs, te, info, device=dev)
     return (info, pairs, te) if details else info
 
 
@@ -1171,7 +1069,6 @@ def track_crop_prior(X, D, T, F, centers, stamps, bias, pre_loc=None):
     ``view(with_direction=True, dt=1/30.0)``, cam [n] int32 = the nearest camera centre, dt [n] fp64 = the per-object dt
     that rolls each track to its camera's corrected time stamp).  ``pre_loc``: an optional contiguous float32 [n,7] tensor to
     write the view into.  Device tensors, no synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(X, D, T, F, centers, stamps, bias, pre_loc)
     n = X.shape[0]
     for name, t, dtype, shape in (("X", X, torch.float32, (n, 6)), ("D", D, torch.float32, (n,)), ("T", T, torch.float64, (n,)),
@@ -1194,10 +1091,7 @@ def track_crop_prior(X, D, T, F, centers, stamps, bias, pre_loc=None):
     if n:
         X, D, T, F = X.contiguous(), D.contiguous(), T.contiguous(), F.contiguous()
         centers, stamps, bias = centers.contiguous(), stamps.contiguous(), bias.contiguous()
-        with torch.cuda.device(dev):
-            _hip.check(lib.rn_track_crop_prior(X.data_ptr(), D.data_ptr(), T.data_ptr(), F.data_ptr(), centers.data_ptr(),
-                                               stamps.data_ptr(), bias.data_ptr(), c, pre_loc.data_ptr(), cam.data_ptr(),
-                                               dt.data_ptr(), n, _hip.stream()), "rn_track_crop_prior")
+        _hip.call("rn_track_crop_prior", X, D, T, F, centers, stamps, bias, c, pre_loc, cam, dt, n, device=dev)
     return pre_loc, cam, dt
 
 
@@ -1212,7 +1106,6 @@ def fit_nearest(gt, det, offsets):
     frame's detections.  -> (rows int32 [B]: the chosen row of det or -1, resid fp32 [B,5]: det[row,:5] - gt[:, :5] of
     the matched frames compacted in frame order (the caller slices with info[0]; the rest is zero), info int32 [3] =
     (matched, empty frames, frames without a comparable distance)).  Device tensors, no synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(gt, det, offsets)
     if gt.dim() != 2 or gt.shape[1] < 6 or det.dim() != 2 or det.shape[1] < 6:
         raise RuntimeError("fit_nearest: states are [n, >= 6], got %s and %s" % (tuple(gt.shape), tuple(det.shape)))
@@ -1228,9 +1121,7 @@ def fit_nearest(gt, det, offsets):
     resid = torch.zeros((B, 5), dtype=torch.float32, device=dev)
     info = torch.zeros(3, dtype=torch.int32, device=dev)
     if B:
-        with torch.cuda.device(dev):
-            _hip.check(lib.rn_fit_nearest(gt.data_ptr(), det.data_ptr() if D else None, off.data_ptr(), B, D, rows.data_ptr(),
-                                          resid.data_ptr(), info.data_ptr(), _hip.stream()), "rn_fit_nearest")
+        _hip.call("rn_fit_nearest", gt, det, off, B, D, rows, resid, info, device=dev)
     return rows, resid, info
 
 
@@ -1239,7 +1130,6 @@ def residual_moments(E, group=None, groups=None):
     see include/retinanet_mi355x.h.  E [N,k] fp32, k <= 8.  Without ``group``: -> (mean [k], cov [k,k], count int32 [1]).
     With ``group`` [N] integer ids in [0, groups), groups <= 16: -> (mean [G,k], cov [G,k,k], count int32 [G]); a group
     without rows has count 0 and zeros.  fp64 sums in a fixed order, rounded once: two runs give the same bits."""
-    lib = _hip.load()
     _hip.need_gpu(E, group)
     if E.dim() != 2 or not 1 <= E.shape[1] <= MOMENTS_MAX_K:
         raise RuntimeError("residual_moments: E is [N, k] with 1 <= k <= %d, got %s" % (MOMENTS_MAX_K, tuple(E.shape)))
@@ -1259,9 +1149,7 @@ def residual_moments(E, group=None, groups=None):
     mean = torch.empty((G, k), dtype=torch.float32, device=dev)
     cov = torch.empty((G, k, k), dtype=torch.float32, device=dev)
     count = torch.empty(G, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_residual_moments(E.data_ptr() if N else None, N, k, _hip.ptr(group), G, mean.data_ptr(),
-                                           cov.data_ptr(), count.data_ptr(), _hip.stream()), "rn_residual_moments")
+    _hip.call("rn_residual_moments", E, N, k, group, G, mean, cov, count, device=dev)
     if group is None:
         return mean[0], cov[0], count
     return mean, cov, count
@@ -1276,11 +1164,13 @@ EVAL_OK, EVAL_TOO_MANY, EVAL_BAD_LABEL, EVAL_TABLE_FULL = 0, 1, 2, 4       # bit
 EVAL_ROW_WORDS = 8                 # x1 y1 x2 y2 score (fp32 bits) | label image index (int32)
 
 
+_EVAL_BITS = ((EVAL_TOO_MANY, "an image with more than %d detections" % EVAL_MAX_K),
+              (EVAL_BAD_LABEL, "a selected detection whose label is outside [0, num_classes)"),
+              (EVAL_TABLE_FULL, "the detection table is full"))
+
+
 def eval_status_text(status):
-    names = [(EVAL_TOO_MANY, "an image with more than %d detections" % EVAL_MAX_K),
-             (EVAL_BAD_LABEL, "a selected detection whose label is outside [0, num_classes)"),
-             (EVAL_TABLE_FULL, "the detection table is full")]
-    return "; ".join(t for b, t in names if status & b) or "ok"
+    return _bits_text(_EVAL_BITS, status) or "ok"
 
 
 def eval_table(rows, num_images, device):
@@ -1314,7 +1204,6 @@ def eval_select(scores, labels, boxes, table, img_rows, state, image, num_classe
     float32(score_threshold), score descending (ties: lower index first), the first max_detections.  table / img_rows /
     state from eval_table, updated in place; calls for different images are ordered by the stream.  Failures are bits in
     state[1] (EVAL_*), and the image then appends nothing.  No synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(scores, labels, boxes, table, img_rows, state)
     K = scores.shape[0]
     if scores.dim() != 1 or labels.shape != scores.shape or (K and boxes.shape[0] != K):
@@ -1330,12 +1219,10 @@ def eval_select(scores, labels, boxes, table, img_rows, state, image, num_classe
         c0, _ = eval_box_cols(boxes, box_cols)
         scores, boxes = _hip.f32c(scores), _hip.f32c(boxes)
         labels = labels.long().contiguous()
-    with torch.cuda.device(table.device):
-        _hip.check(lib.rn_eval_select(scores.data_ptr() if K else None, labels.data_ptr() if K else None,
-                                      boxes.data_ptr() if K else None, boxes.shape[1] if K else 4, c0, K, float(score_threshold),
-                                      int(max_detections), int(image), img_rows.shape[0], int(num_classes),
-                                      table.data_ptr() if table.shape[0] else None, table.shape[0], state.data_ptr(),
-                                      img_rows.data_ptr(), _hip.stream()), "rn_eval_select")
+    # without detections the boxes may have any shape and any number of rows: the entry point is handed NULL for them
+    _hip.call("rn_eval_select", scores, labels, boxes if K else None, boxes.shape[1] if K else 4, c0, K, float(score_threshold),
+              int(max_detections), int(image), img_rows.shape[0], int(num_classes), table, table.shape[0], state, img_rows,
+              device=table.device)
 
 
 def _eval_check_table(table, state):
@@ -1349,7 +1236,6 @@ def eval_match(table, img_rows, ann_box, ann_offsets, num_classes, iou_threshold
     """The greedy matching of evaluate (csv_eval.py:189-213).  ann_box [M,4] fp64 and ann_offsets int32
     [num_images * num_classes + 1] in (image, class) order.  -> (tp uint8 [rows]: 1 true positive / 0 false positive per
     table row, num_annotations int32 [num_classes] (written into the tensor given, if one is)).  No synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(table, img_rows, ann_box, ann_offsets, num_annotations)
     I, C, M = img_rows.shape[0], int(num_classes), ann_box.shape[0]
     if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous():
@@ -1367,11 +1253,8 @@ def eval_match(table, img_rows, ann_box, ann_offsets, num_classes, iou_threshold
     rows = table.shape[0]
     tp = torch.zeros(rows, dtype=torch.uint8, device=dev)
     taken = torch.empty(M, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_eval_match(table.data_ptr() if rows else None, rows, img_rows.data_ptr() if I else None, I, C,
-                                     ann_box.data_ptr() if M else None, ann_offsets.data_ptr(), M, float(iou_threshold),
-                                     taken.data_ptr() if M else None, tp.data_ptr() if rows else None,
-                                     num_annotations.data_ptr(), _hip.stream()), "rn_eval_match")
+    _hip.call("rn_eval_match", table, rows, img_rows, I, C, ann_box, ann_offsets, M, float(iou_threshold), taken, tp,
+              num_annotations, device=dev)
     return tp, num_annotations
 
 
@@ -1393,10 +1276,8 @@ def eval_ap(table, state, tp, num_annotations, ap=None):
         raise RuntimeError("eval_ap: ap is a contiguous float64 [num_classes] tensor")
     order = torch.full((rows,), -1, dtype=torch.int32, device=dev)
     ws = torch.empty(lib.rn_eval_ap_workspace_bytes(rows), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_eval_ap(table.data_ptr() if rows else None, rows, state.data_ptr(), tp.data_ptr() if rows else None,
-                                  num_annotations.data_ptr(), C, ws.data_ptr() if rows else None, ap.data_ptr(),
-                                  order.data_ptr() if rows else None, _hip.stream()), "rn_eval_ap")
+    # the workspace has a fixed head, so it is not empty for an empty table, where the entry point is handed NULL
+    _hip.call("rn_eval_ap", table, rows, state, tp, num_annotations, C, ws if rows else None, ap, order, device=dev)
     return ap, order
 
 
@@ -1431,7 +1312,6 @@ def eval_corners(boxes, table, img_rows, image, corners):
     """The 16 corner coordinates (columns 0:16 of the directional model's boxes [K, >=16]) of the rows eval_select has just
     appended for `image`, into corners float32 [rows, 16] in place, at the rows' positions.  Same stream as eval_select.
     No synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(boxes, table, img_rows, corners)
     rows, K = table.shape[0], boxes.shape[0]
     if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != EVAL_ROW_WORDS or not table.is_contiguous():
@@ -1443,10 +1323,8 @@ def eval_corners(boxes, table, img_rows, image, corners):
     _eval_cuboid_rows("eval_corners", rows, corners=(corners, torch.float32, (rows, 16)))
     if K:
         boxes = _hip.f32c(boxes)
-    with torch.cuda.device(table.device):
-        _hip.check(lib.rn_eval_corners(boxes.data_ptr() if K else None, boxes.shape[1] if K else 16, K, int(image), img_rows.shape[0],
-                                       img_rows.data_ptr(), table.data_ptr() if rows else None, rows,
-                                       corners.data_ptr() if rows else None, _hip.stream()), "rn_eval_corners")
+    _hip.call("rn_eval_corners", boxes, boxes.shape[1] if K else 16, K, int(image), img_rows.shape[0], img_rows, table, rows, corners,
+              device=table.device)
 
 
 def eval_cuboid_overlap(table, img_rows, corners, ann_corners, ann_offsets, num_classes, overlap="silhouette"):
@@ -1454,7 +1332,6 @@ def eval_cuboid_overlap(table, img_rows, corners, ann_corners, ann_offsets, num_
     the chosen corners (overlap: "silhouette" all 8, "base" 0..3, "top" 4..7; exact clipping in fp64).  ann_corners [M,16]
     fp64, ann_offsets int32 [num_images * num_classes + 1] in (image, class) order.  -> (best_iou float64 [rows], best_ann
     int32 [rows]: the index inside the group, -1 with 0.0 for a group without annotations).  No synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(table, img_rows, corners, ann_corners, ann_offsets)
     if overlap not in EVAL_CUBOID_OVERLAPS:
         raise RuntimeError("eval_cuboid_overlap: overlap is one of %s, got %r" % (sorted(EVAL_CUBOID_OVERLAPS), overlap))
@@ -1463,12 +1340,8 @@ def eval_cuboid_overlap(table, img_rows, corners, ann_corners, ann_offsets, num_
     _eval_cuboid_rows("eval_cuboid_overlap", rows, corners=(corners, torch.float32, (rows, 16)))
     best_iou = torch.zeros(rows, dtype=torch.float64, device=dev)
     best_ann = torch.full((rows,), -1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_eval_cuboid_overlap(table.data_ptr() if rows else None, rows, img_rows.data_ptr() if I else None, I, C,
-                                              corners.data_ptr() if rows else None, ann_corners.data_ptr() if M else None,
-                                              ann_offsets.data_ptr(), M, EVAL_CUBOID_OVERLAPS[overlap],
-                                              best_iou.data_ptr() if rows else None, best_ann.data_ptr() if rows else None,
-                                              _hip.stream()), "rn_eval_cuboid_overlap")
+    _hip.call("rn_eval_cuboid_overlap", table, rows, img_rows, I, C, corners, ann_corners, ann_offsets, M,
+              EVAL_CUBOID_OVERLAPS[overlap], best_iou, best_ann, device=dev)
     return best_iou, best_ann
 
 
@@ -1479,7 +1352,6 @@ def eval_cuboid_assign(table, img_rows, best_iou, best_ann, ann_offsets, num_ann
     device tensor; num_annotated = M, the number of packed annotations.  -> (tp uint8 [T, rows], num_annotations int32
     [num_classes] (written into the tensor given, if one is), matched int32 [rows]: the annotation of the true positives at
     thresholds[0], else -1).  No synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(table, img_rows, best_iou, best_ann, ann_offsets, num_annotations)
     dev, rows, I, C, M = table.device, table.shape[0], img_rows.shape[0], int(num_classes), int(num_annotated)
     if not torch.is_tensor(thresholds):
@@ -1502,13 +1374,8 @@ def eval_cuboid_assign(table, img_rows, best_iou, best_ann, ann_offsets, num_ann
     tp = torch.zeros((T, rows), dtype=torch.uint8, device=dev)
     matched = torch.full((rows,), -1, dtype=torch.int32, device=dev)
     taken = torch.empty(M * T, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_eval_cuboid_assign(table.data_ptr() if rows else None, rows, img_rows.data_ptr() if I else None, I, C,
-                                             ann_offsets.data_ptr(), M, best_iou.data_ptr() if rows else None,
-                                             best_ann.data_ptr() if rows else None, thresholds.data_ptr(), T,
-                                             taken.data_ptr() if M else None, tp.data_ptr() if rows else None,
-                                             num_annotations.data_ptr(), matched.data_ptr() if rows else None, _hip.stream()),
-                   "rn_eval_cuboid_assign")
+    _hip.call("rn_eval_cuboid_assign", table, rows, img_rows, I, C, ann_offsets, M, best_iou, best_ann, thresholds, T, taken, tp,
+              num_annotations, matched, device=dev)
     return tp, num_annotations, matched
 
 
@@ -1516,7 +1383,6 @@ def eval_cuboid_errors(table, state, img_rows, corners, ann_corners, ann_offsets
     """The error figures of the true positives at thresholds[0] (tp: that threshold's flags, uint8 [rows]).  -> (terms
     float64 [rows, 4]: EVAL_CUBOID_TERMS, zeros for every other row; sums float64 [num_classes, 5]: EVAL_CUBOID_SUMS per class,
     added in table order (written into the tensor given, if one is)).  Bit-identical from run to run.  No synchronisation."""
-    lib = _hip.load()
     _hip.need_gpu(table, state, img_rows, corners, ann_corners, ann_offsets, tp, matched, best_iou, sums)
     _eval_check_table(table, state)
     I, C, M = _eval_cuboid_check("eval_cuboid_errors", table, img_rows, ann_corners, ann_offsets, num_classes)
@@ -1528,13 +1394,8 @@ def eval_cuboid_errors(table, state, img_rows, corners, ann_corners, ann_offsets
     elif sums.dtype != torch.float64 or sums.numel() != 5 * C or not sums.is_contiguous():
         raise RuntimeError("eval_cuboid_errors: sums is a contiguous float64 [num_classes, 5] tensor")
     terms = torch.zeros((rows, 4), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_eval_cuboid_errors(table.data_ptr() if rows else None, rows, state.data_ptr(), I, C,
-                                             corners.data_ptr() if rows else None, ann_corners.data_ptr() if M else None,
-                                             ann_offsets.data_ptr(), M, tp.data_ptr() if rows else None,
-                                             matched.data_ptr() if rows else None, best_iou.data_ptr() if rows else None,
-                                             terms.data_ptr() if rows else None, sums.data_ptr(), _hip.stream()),
-                   "rn_eval_cuboid_errors")
+    _hip.call("rn_eval_cuboid_errors", table, rows, state, I, C, corners, ann_corners, ann_offsets, M, tp, matched, best_iou, terms,
+              sums, device=dev)
     return terms, sums
 
 
@@ -1548,7 +1409,6 @@ AUGMENT_TAPS = 7                          # RN_AUG_TAPS
 def frame_ingest(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, nhwc4=False):
     """F.to_tensor + F.normalize of the reference's loaders on device (include/retinanet_mi355x.h, rn_frame_ingest).
     frames_u8: uint8 [B,H,W,3] (or [H,W,3]) -> float32 [B,3,H,W], or [B,H,W,4] with nhwc4=True."""
-    lib = _hip.load()
     _hip.need_gpu(frames_u8)
     if frames_u8.dim() == 3:
         frames_u8 = frames_u8.unsqueeze(0)
@@ -1557,10 +1417,8 @@ def frame_ingest(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD,
     f = frames_u8.contiguous()
     B, H, W, _ = f.shape
     out = torch.empty((B, H, W, 4) if nhwc4 else (B, 3, H, W), dtype=torch.float32, device=f.device)
-    with torch.cuda.device(f.device):
-        _hip.check(lib.rn_frame_ingest(f.data_ptr(), B, H, W, int(bool(swap_rb)), *[float(m) for m in mean],
-                                       *[float(s) for s in std], int(bool(nhwc4)), out.data_ptr(), _hip.stream()),
-                   "rn_frame_ingest")
+    _hip.call("rn_frame_ingest", f, B, H, W, int(bool(swap_rb)), *[float(m) for m in mean], *[float(s) for s in std],
+              int(bool(nhwc4)), out, device=f.device)
     return out
 
 
@@ -1582,7 +1440,6 @@ def frame_ingest_half(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET
     """The loader's 2x reduction + to_tensor + normalize in one pass (include/retinanet_mi355x.h, rn_frame_ingest_half;
     util_track/mp_loader.py:237-243).  frames_u8: uint8 [B,2H,2W,3] (or [2H,2W,3]) -> float32 [B,3,H,W], or [B,H,W,4] with
     nhwc4=True: ``frame_ingest`` of the reduced frame, bit for bit.  keep_u8=True -> (tensor, reduced uint8 [B,H,W,3])."""
-    lib = _hip.load()
     _hip.need_gpu(frames_u8)
     f = _u8_frames(frames_u8, "frame_ingest_half")
     B, H2, W2, _ = f.shape
@@ -1592,10 +1449,8 @@ def frame_ingest_half(frames_u8, swap_rb=False, mean=IMAGENET_MEAN, std=IMAGENET
     H, W = H2 // 2, W2 // 2
     out = torch.empty((B, H, W, 4) if nhwc4 else (B, 3, H, W), dtype=torch.float32, device=f.device)
     u8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=f.device) if keep_u8 else None
-    with torch.cuda.device(f.device):
-        _hip.check(lib.rn_frame_ingest_half(f.data_ptr(), B, H2, W2, int(bool(swap_rb)), *[float(m) for m in mean],
-                                            *[float(s) for s in std], int(bool(nhwc4)), out.data_ptr(), _hip.ptr(u8),
-                                            _hip.stream()), "rn_frame_ingest_half")
+    _hip.call("rn_frame_ingest_half", f, B, H2, W2, int(bool(swap_rb)), *[float(m) for m in mean], *[float(s) for s in std],
+              int(bool(nhwc4)), out, u8, device=f.device)
     return (out, u8) if keep_u8 else out
 
 
@@ -1636,7 +1491,6 @@ def parse_frame_timestamps(frames_u8, sets, prev=None, swap_rb=False, want_mask=
     int32 [G,64,8] device tensor); prev: optional fp64 [B] on the device.
     -> (times fp64 [B], status i32 [B] (TS_READ / TS_FAILED / TS_FELL_BACK), set index i32 [B], digits i8 [B,16],
         first failing cell of the first set i32 [B], the first set's mask uint8 [B,h,n*w] or None)."""
-    lib = _hip.load()
     _hip.need_gpu(frames_u8, prev)
     f = _u8_frames(frames_u8, "parse_frame_timestamps")
     if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray) and torch.is_tensor(sets[1]):
@@ -1664,11 +1518,8 @@ def parse_frame_timestamps(frames_u8, sets, prev=None, swap_rb=False, want_mask=
     digits = torch.empty((B, TS_MAX_CELLS), dtype=torch.int8, device=dev)
     fail_cell = torch.empty(B, dtype=torch.int32, device=dev)
     mask = torch.empty((B, int(geo[0, 3]), int(geo[0, 4]) * int(geo[0, 2])), dtype=torch.uint8, device=dev) if want_mask else None
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_parse_frame_timestamps(f.data_ptr(), B, H, W, f.stride(0) if B > 1 else 0, f.stride(1), int(bool(swap_rb)),
-                                                 geo.ctypes.data, geo.shape[0], tab.data_ptr(), _hip.ptr(prev), times.data_ptr(),
-                                                 status.data_ptr(), set_index.data_ptr(), digits.data_ptr(), fail_cell.data_ptr(),
-                                                 _hip.ptr(mask), _hip.stream()), "rn_parse_frame_timestamps")
+    _hip.call("rn_parse_frame_timestamps", f, B, H, W, f.stride(0) if B > 1 else 0, f.stride(1), int(bool(swap_rb)), geo.ctypes.data,
+              geo.shape[0], tab, prev, times, status, set_index, digits, fail_cell, mask, device=dev)
     return times, status, set_index, digits, fail_cell, mask
 
 
@@ -1716,10 +1567,8 @@ def augment_frames(frames_u8, params, noise=None, seed=0, mean=IMAGENET_MEAN, st
     if B == 0:
         return out
     ws = torch.empty(int(lib.rn_augment_workspace_bytes(B, H, W)) // 8, dtype=torch.int64, device=f.device)
-    with torch.cuda.device(f.device):
-        _hip.check(lib.rn_augment_frames(f.data_ptr(), B, H, W, rec.data_ptr(), tx.data_ptr(), ty.data_ptr(), _hip.ptr(noise),
-                                         int(seed) & 0xFFFFFFFFFFFFFFFF, *[float(m) for m in mean], *[float(s) for s in std],
-                                         ws.data_ptr(), out.data_ptr(), _hip.stream()), "rn_augment_frames")
+    _hip.call("rn_augment_frames", f, B, H, W, rec, tx, ty, noise, int(seed) & 0xFFFFFFFFFFFFFFFF, *[float(m) for m in mean],
+              *[float(s) for s in std], ws, out, device=f.device)
     return out
 
 
@@ -1774,11 +1623,8 @@ def augment_crops(frames_u8, params, K, win_max, crop, noise=None, occlusion=Non
     if B == 0:
         return out
     ws = torch.empty(int(lib.rn_augment_crops_workspace_bytes(B, win_max, crop)) // 8, dtype=torch.int64, device=f.device)
-    with torch.cuda.device(f.device):
-        _hip.check(lib.rn_augment_crops(f.data_ptr(), B, H, W, rec.data_ptr(), tx.data_ptr(), ty.data_ptr(), cx.data_ptr(),
-                                        cy.data_ptr(), K, win_max, crop, _hip.ptr(noise), _hip.ptr(occlusion),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, *[float(m) for m in mean], *[float(s) for s in std],
-                                        ws.data_ptr(), out.data_ptr(), _hip.stream()), "rn_augment_crops")
+    _hip.call("rn_augment_crops", f, B, H, W, rec, tx, ty, cx, cy, K, win_max, crop, noise, occlusion,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, *[float(m) for m in mean], *[float(s) for s in std], ws, out, device=f.device)
     return out
 
 
@@ -1789,7 +1635,6 @@ CROP_MAX_A, CROP_MAX_K = 4096, 256
 def crop_boxes(im_objs, cam_idxs=None, b=1.25):
     """MC_Crop_Tracker.get_crop_boxes (MC3D_crop_tracker.py:920-944): im_objs [n,8,2] -> crop boxes [n,4] float64; with
     cam_idxs also the [n,5] float32 RoI rows (camera, box) that roi_align takes (:1183-1185)."""
-    lib = _hip.load()
     _hip.need_gpu(im_objs, cam_idxs)
     im = im_objs.double().contiguous()
     n = im.shape[0]
@@ -1797,16 +1642,13 @@ def crop_boxes(im_objs, cam_idxs=None, b=1.25):
     rois = None if cam_idxs is None else torch.empty((n, 5), dtype=torch.float32, device=im.device)
     cam = None if cam_idxs is None else cam_idxs.long().contiguous()
     if n:
-        with torch.cuda.device(im.device):
-            _hip.check(lib.rn_crop_boxes(im.data_ptr(), _hip.ptr(cam), n, float(b), boxes.data_ptr(), _hip.ptr(rois),
-                                         _hip.stream()), "rn_crop_boxes")
+        _hip.call("rn_crop_boxes", im, cam, n, float(b), boxes, rois, device=im.device)
     return boxes if rois is None else (boxes, rois)
 
 
 def roi_align(frames, rois, output_size, nhwc4=False):
     """torchvision.ops.roi_align(frames, rois, output_size) with its defaults, on device.  frames [N,C,H,W] float32,
     rois [n,5] (batch index, x1, y1, x2, y2) -> [n,C,h,w], or [n,h,w,4] with nhwc4=True (C <= 4)."""
-    lib = _hip.load()
     _hip.need_gpu(frames, rois)
     f, r = _hip.f32c(frames), _hip.f32c(rois)
     oh, ow = (output_size, output_size) if isinstance(output_size, int) else output_size
@@ -1814,16 +1656,13 @@ def roi_align(frames, rois, output_size, nhwc4=False):
     n = r.shape[0]
     out = torch.empty((n, oh, ow, 4) if nhwc4 else (n, C, oh, ow), dtype=torch.float32, device=f.device)
     if n:
-        with torch.cuda.device(f.device):
-            _hip.check(lib.rn_roi_align(f.data_ptr(), N, C, H, W, r.data_ptr(), n, oh, ow, out.data_ptr(), int(bool(nhwc4)),
-                                        _hip.stream()), "rn_roi_align")
+        _hip.call("rn_roi_align", f, N, C, H, W, r, n, oh, ow, out, int(bool(nhwc4)), device=f.device)
     return out
 
 
 def crop_select(reg_boxes, cls, crop_bx, cam_idxs, pre_loc, H1, H2, P1, P2, cs=112, cd_max=50, W=0.5):
     """Everything after the LOCALIZE detector in the tracker's crop path (MC3D_crop_tracker.py:1192-1226), one
     workgroup per object: -> (state [n,6] f32, class [n] i64, confidence [n] f32)."""
-    lib = _hip.load()
     _hip.need_gpu(reg_boxes, cls, crop_bx, cam_idxs, pre_loc, H1, H2, P1, P2)
     n, A, C = cls.shape
     if A > CROP_MAX_A or cd_max > CROP_MAX_K:
@@ -1839,11 +1678,8 @@ def crop_select(reg_boxes, cls, crop_bx, cam_idxs, pre_loc, H1, H2, P1, P2, cs=1
     oc = torch.empty(n, dtype=torch.int64, device=dev)
     of = torch.empty(n, dtype=torch.float32, device=dev)
     if n:
-        with torch.cuda.device(dev):
-            _hip.check(lib.rn_crop_select(reg_boxes.data_ptr(), cls.data_ptr(), crop_bx.data_ptr(), cam.data_ptr(),
-                                          pre_loc.data_ptr(), H1.data_ptr(), _hip.ptr(H2), P1.data_ptr(), _hip.ptr(P2),
-                                          H1.shape[0], n, A, C, float(cs), int(cd_max), float(W), st.data_ptr(), oc.data_ptr(),
-                                          of.data_ptr(), _hip.stream()), "rn_crop_select")
+        _hip.call("rn_crop_select", reg_boxes, cls, crop_bx, cam, pre_loc, H1, H2, P1, P2, H1.shape[0], n, A, C, float(cs),
+                  int(cd_max), float(W), st, oc, of, device=dev)
     return st, oc, of
 
 
@@ -1865,7 +1701,6 @@ def vanishing_points(lines, offsets):
     """find_vanishing_point (homography.py:96-154) of every line set in one launch, see include/retinanet_mi355x.h.
     lines fp64 [N,4], offsets int64 [S+1] (CSR row ranges; a range outside the N rows sets the VP_BAD_OFFSETS bit) ->
     (out fp64 [S,3] = (px, py, best distance), trace fp64 [S,16,3], status int32 [S]); nothing is synchronised."""
-    lib = _hip.load()
     _hip.need_gpu(lines, offsets)
     if lines.dim() != 2 or lines.shape[1] != 4 or lines.dtype != torch.float64:
         raise RuntimeError("vanishing_points: lines are fp64 [N,4] (x0, y0, x1, y1), got %s %s" % (lines.dtype, tuple(lines.shape)))
@@ -1876,9 +1711,7 @@ def vanishing_points(lines, offsets):
     out = torch.empty((S, 3), dtype=torch.float64, device=dev)
     trace = torch.zeros((S, VP_LEVELS, 3), dtype=torch.float64, device=dev)
     status = torch.empty(S, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_vanishing_points(lines.data_ptr(), lines.shape[0], offsets.data_ptr(), S, out.data_ptr(), trace.data_ptr(),
-                                           status.data_ptr(), _hip.stream()), "rn_vanishing_points")
+    _hip.call("rn_vanishing_points", lines, lines.shape[0], offsets, S, out, trace, status, device=dev)
     return out, trace, status
 
 
@@ -1895,16 +1728,13 @@ def _calib_inputs(boxes, heights, H, P, what):
 def hg_reproj_error(boxes, heights, H, P_orig, C):
     """test_transformation's arithmetic (homography.py:581-587) for every scale C [K] of P_orig's third column ->
     fp64 [K,2] = (top, bottom) mean corner distance in pixels."""
-    lib = _hip.load()
     _hip.need_gpu(boxes, heights, H, P_orig, C)
     boxes, heights, H, P_orig = _calib_inputs(boxes, heights, H, P_orig, "hg_reproj_error")
     if C.dim() != 1 or C.shape[0] == 0 or C.dtype != torch.float64:
         raise RuntimeError("hg_reproj_error: C is fp64 [K] with K >= 1, got %s %s" % (C.dtype, tuple(C.shape)))
     C = C.contiguous()
     out = torch.empty((C.shape[0], 2), dtype=torch.float64, device=boxes.device)
-    with torch.cuda.device(boxes.device):
-        _hip.check(lib.rn_hg_reproj_error(boxes.data_ptr(), heights.data_ptr(), H.data_ptr(), P_orig.data_ptr(), C.data_ptr(),
-                                          boxes.shape[0], C.shape[0], out.data_ptr(), _hip.stream()), "rn_hg_reproj_error")
+    _hip.call("rn_hg_reproj_error", boxes, heights, H, P_orig, C, boxes.shape[0], C.shape[0], out, device=boxes.device)
     return out
 
 
@@ -1912,17 +1742,14 @@ def hg_scale_z(boxes, heights, H, P_orig, granularity=1e-06, max_scale=10.0):
     """The search of scale_Z (homography.py:607-666) in one launch -> (trace fp64 [SZ_MAX_ITERS,10,2] = (C, error), zero
     beyond the iterations run (the search shrinks its step 4.5 x per iteration: 10 iterations at the defaults); out fp64 [3] = (last C evaluated, best C, best error of the last iteration);
     info int32 [2] = (iterations, status bits))."""
-    lib = _hip.load()
     _hip.need_gpu(boxes, heights, H, P_orig)
     boxes, heights, H, P_orig = _calib_inputs(boxes, heights, H, P_orig, "hg_scale_z")
     dev = boxes.device
     trace = torch.zeros((SZ_MAX_ITERS, 10, 2), dtype=torch.float64, device=dev)
     out = torch.empty(3, dtype=torch.float64, device=dev)
     info = torch.empty(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_hg_scale_z(boxes.data_ptr(), heights.data_ptr(), H.data_ptr(), P_orig.data_ptr(), boxes.shape[0],
-                                     float(granularity), float(max_scale), SZ_MAX_ITERS, trace.data_ptr(), out.data_ptr(),
-                                     info.data_ptr(), _hip.stream()), "rn_hg_scale_z")
+    _hip.call("rn_hg_scale_z", boxes, heights, H, P_orig, boxes.shape[0], float(granularity), float(max_scale), SZ_MAX_ITERS, trace,
+              out, info, device=dev)
     return trace, out, info
 
 
@@ -1930,7 +1757,6 @@ def fit_homography(src, dst, offsets, refine=True):
     """Plane homographies dst ~ H [src; 1], one per CSR row range: src, dst fp64 [N,2], offsets int64 [B+1] ->
     (H fp64 [B,3,3] with H[2,2] = 1, NaN where the status is not 0; status int32 [B]).  Stands in for
     cv2.findHomography(src, dst) at its default method; parity with OpenCV is unpinned (include/retinanet_mi355x.h)."""
-    lib = _hip.load()
     _hip.need_gpu(src, dst, offsets)
     if src.dim() != 2 or src.shape[1] != 2 or src.shape != dst.shape or src.dtype != torch.float64 or dst.dtype != torch.float64:
         raise RuntimeError("fit_homography: src and dst are fp64 [N,2], got %s and %s" % (tuple(src.shape), tuple(dst.shape)))
@@ -1939,9 +1765,7 @@ def fit_homography(src, dst, offsets, refine=True):
     B = offsets.shape[0] - 1
     H = torch.empty((B, 3, 3), dtype=torch.float64, device=src.device)
     status = torch.empty(B, dtype=torch.int32, device=src.device)
-    with torch.cuda.device(src.device):
-        _hip.check(lib.rn_fit_homography(src.data_ptr(), dst.data_ptr(), src.shape[0], offsets.data_ptr(), B, int(bool(refine)), H.data_ptr(),
-                                         status.data_ptr(), _hip.stream()), "rn_fit_homography")
+    _hip.call("rn_fit_homography", src, dst, src.shape[0], offsets, B, int(bool(refine)), H, status, device=src.device)
     return H, status
 
 
@@ -1984,18 +1808,15 @@ def _render_boxes(what, name, boxes, dev):
 
 def render_edges(corners, cam, thickness, bit, mask):
     """ORs bit number `bit` into mask along the 14 edges of every box: corners fp64 [n,8,2], cam int32 [n] (rn_render_edges)."""
-    lib = _hip.load()
     _hip.need_gpu(corners, cam, mask)
     n_cam, H, W = _render_plane("render_edges", mask)
     n = _render_boxes("render_edges", "corners", corners, mask.device)
-    _mot_typed("render_edges", ("cam", cam, torch.int32))
+    _typed("render_edges", ("cam", cam, torch.int32))
     if tuple(cam.shape) != (n,) or cam.device != mask.device:
         raise RuntimeError("render_edges: cam is int32 [n] on the mask's device")
     if not (1 <= int(thickness) <= 255 and 0 <= int(bit) <= 15):
         raise RuntimeError("render_edges: 1 <= thickness <= 255 and 0 <= bit <= 15")
-    with torch.cuda.device(mask.device):
-        _hip.check(lib.rn_render_edges(_hip.ptr(corners), _hip.ptr(cam), n, int(thickness), int(bit), mask.data_ptr(), n_cam, H, W,
-                                       _hip.stream()), "rn_render_edges")
+    _hip.call("rn_render_edges", corners, cam, n, int(thickness), int(bit), mask, n_cam, H, W, device=mask.device)
     return mask
 
 
@@ -2010,37 +1831,30 @@ def _render_records(what, name, rec, cols, dev):
 def render_rects(rects, mask, anchors=None):
     """rects int32 [n,8] (RENDER_RECT_COLS): half-open rectangles, filled (mode 0) or outlined (1), absolute or offset from
     (int(min x), int(max y)) of box `anchor` of anchors fp64 [m,8,2] (rn_render_rects)."""
-    lib = _hip.load()
     _hip.need_gpu(mask)
     n_cam, H, W = _render_plane("render_rects", mask)
     n = _render_records("render_rects", "rects", rects, len(RENDER_RECT_COLS), mask.device)
     m = _render_boxes("render_rects", "anchors", anchors, mask.device)
-    with torch.cuda.device(mask.device):
-        _hip.check(lib.rn_render_rects(_hip.ptr(rects), n, _hip.ptr(anchors) if m else None, m, mask.data_ptr(), n_cam, H, W,
-                                       _hip.stream()), "rn_render_rects")
+    _hip.call("rn_render_rects", rects, n, anchors, m, mask, n_cam, H, W, device=mask.device)
     return mask
 
 
 def render_text(runs, text, font, mask, anchors=None):
     """runs int32 [n,9] (RENDER_RUN_COLS) over the bytes of text uint8 [T]; font uint8 [95,8] (rn_render_text)."""
-    lib = _hip.load()
     _hip.need_gpu(text, font, mask)
     n_cam, H, W = _render_plane("render_text", mask)
     n = _render_records("render_text", "runs", runs, len(RENDER_RUN_COLS), mask.device)
     m = _render_boxes("render_text", "anchors", anchors, mask.device)
-    _mot_typed("render_text", ("text", text, torch.uint8), ("font", font, torch.uint8))
+    _typed("render_text", ("text", text, torch.uint8), ("font", font, torch.uint8))
     if text.dim() != 1 or tuple(font.shape) != (95, 8) or text.device != mask.device or font.device != mask.device:
         raise RuntimeError("render_text: text is uint8 [T] and font uint8 [95,8], both on the mask's device")
-    with torch.cuda.device(mask.device):
-        _hip.check(lib.rn_render_text(_hip.ptr(runs), n, _hip.ptr(text), text.numel(), font.data_ptr(), _hip.ptr(anchors) if m else None,
-                                      m, mask.data_ptr(), n_cam, H, W, _hip.stream()), "rn_render_text")
+    _hip.call("rn_render_text", runs, n, text, text.numel(), font, anchors, m, mask, n_cam, H, W, device=mask.device)
     return mask
 
 
 def render_compose(frames, mask, crops_present, cols, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
     """frames fp32 [n_cam,3,H,W] (normalised RGB) + mask uint16 [n_cam,H,W] -> the uint8 mosaic [R*H, cols*W, 3], camera i in
     tile (i // cols, i % cols), unused tiles zero (rn_render_compose)."""
-    lib = _hip.load()
     _hip.need_gpu(frames, mask, out)
     n_cam, H, W = _render_plane("render_compose", mask)
     if frames.dtype != torch.float32 or tuple(frames.shape) != (n_cam, 3, H, W) or not frames.is_contiguous() \
@@ -2055,9 +1869,8 @@ def render_compose(frames, mask, crops_present, cols, mean=IMAGENET_MEAN, std=IM
         out = torch.empty((rows * H, cols * W, 3), dtype=torch.uint8, device=mask.device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (rows * H, cols * W, 3) or not out.is_contiguous() or out.device != mask.device:
         raise RuntimeError("render_compose: out is a contiguous uint8 [%d,%d,3] tensor on the mask's device" % (rows * H, cols * W))
-    with torch.cuda.device(mask.device):
-        _hip.check(lib.rn_render_compose(frames.data_ptr(), *[float(m) for m in mean], *[float(s) for s in std], mask.data_ptr(),
-                                         int(bool(crops_present)), out.data_ptr(), n_cam, H, W, cols, _hip.stream()), "rn_render_compose")
+    _hip.call("rn_render_compose", frames, *[float(m) for m in mean], *[float(s) for s in std], mask, int(bool(crops_present)), out,
+              n_cam, H, W, cols, device=mask.device)
     return out
 
 
@@ -2078,9 +1891,8 @@ def replay_boxes(state7, dt, P1, P2=None, offset=0, count=None):
     """Rows [offset, offset + count) of state7 fp32 [R,7] = (x, y, l, w, h, direction, v), the objects of one label instant,
     in every camera: dt fp64 [C], P1 / P2 fp64 [C,3,4] -> (views fp32 [C*n,7], image corners fp64 [C*n,8,2], side int32 [C*n],
     camera int32 [C*n]); row c*n + i is object i in camera c (rn_replay_boxes)."""
-    lib = _hip.load()
     _hip.need_gpu(state7, dt, P1, P2)
-    _mot_typed("replay_boxes", ("state7", state7, torch.float32), ("dt", dt, torch.float64), ("P1", P1, torch.float64))
+    _typed("replay_boxes", ("state7", state7, torch.float32), ("dt", dt, torch.float64), ("P1", P1, torch.float64))
     if state7.dim() != 2 or state7.shape[1] != 7 or dt.dim() != 1 or dt.shape[0] < 1:
         raise RuntimeError("replay_boxes: state7 is fp32 [R,7] and dt fp64 [C], C >= 1, got %s and %s" % (tuple(state7.shape), tuple(dt.shape)))
     C, dev = dt.shape[0], state7.device
@@ -2101,17 +1913,13 @@ def replay_boxes(state7, dt, P1, P2=None, offset=0, count=None):
     side = torch.empty(C * n, dtype=torch.int32, device=dev)
     cam = torch.empty(C * n, dtype=torch.int32, device=dev)
     if n:
-        with torch.cuda.device(dev):
-            _hip.check(lib.rn_replay_boxes(state7.data_ptr() + 28 * offset, n, dt.data_ptr(), P1.data_ptr(), _hip.ptr(P2), C,
-                                           views.data_ptr(), im.data_ptr(), side.data_ptr(), cam.data_ptr(), _hip.stream()),
-                       "rn_replay_boxes")
+        _hip.call("rn_replay_boxes", state7.data_ptr() + 28 * offset, n, dt, P1, P2, C, views, im, side, cam, device=dev)
     return views, im, side, cam
 
 
 def replay_compose(frames_u8, mask, size=None, swap_rb=False, out=None):
     """frames uint8 [n_cam,H,W,3] + mask uint16 [n_cam,H,W] (bits REPLAY_BITS) -> the uint8 RGB mosaic [OH,OW,3], tiles as
     ``replay_layout``; size = (OW, OH) or None for the canvas itself (rn_replay_compose)."""
-    lib = _hip.load()
     _hip.need_gpu(frames_u8, mask, out)
     n_cam, H, W = _render_plane("replay_compose", mask)
     if frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != (n_cam, H, W, 3) or not frames_u8.is_contiguous() \
@@ -2128,9 +1936,7 @@ def replay_compose(frames_u8, mask, size=None, swap_rb=False, out=None):
         out = torch.empty((OH, OW, 3), dtype=torch.uint8, device=mask.device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (OH, OW, 3) or not out.is_contiguous() or out.device != mask.device:
         raise RuntimeError("replay_compose: out is a contiguous uint8 [%d,%d,3] tensor on the mask's device" % (OH, OW))
-    with torch.cuda.device(mask.device):
-        _hip.check(lib.rn_replay_compose(frames_u8.data_ptr(), int(bool(swap_rb)), mask.data_ptr(), out.data_ptr(), n_cam, H, W, rows,
-                                         OW, OH, _hip.stream()), "rn_replay_compose")
+    _hip.call("rn_replay_compose", frames_u8, int(bool(swap_rb)), mask, out, n_cam, H, W, rows, OW, OH, device=mask.device)
     return out
 
 
@@ -2144,7 +1950,6 @@ def _u8_frame(what, name, f):
 def frame_absdiff(a, b, y0=100, y1=500, x0=100, x1=500):
     """sum |a - b| over a[y0:y1, x0:x1, :] of two uint8 [H,W,3] frames, the window clipped to the frame -> int64 [1] on the
     device, an exact integer (rn_frame_absdiff; datareader.py:617 divides it by the window's size)."""
-    lib = _hip.load()
     _hip.need_gpu(a, b)
     _u8_frame("frame_absdiff", "a", a)
     _u8_frame("frame_absdiff", "b", b)
@@ -2155,9 +1960,7 @@ def frame_absdiff(a, b, y0=100, y1=500, x0=100, x1=500):
         raise RuntimeError("frame_absdiff: window bounds are non-negative int32")
     partial = torch.empty(REPLAY_ABSDIFF_BLOCKS, dtype=torch.int64, device=a.device)
     out = torch.empty(1, dtype=torch.int64, device=a.device)
-    with torch.cuda.device(a.device):
-        _hip.check(lib.rn_frame_absdiff(a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], y0, y1, x0, x1, partial.data_ptr(),
-                                        out.data_ptr(), _hip.stream()), "rn_frame_absdiff")
+    _hip.call("rn_frame_absdiff", a, b, a.shape[0], a.shape[1], y0, y1, x0, x1, partial, out, device=a.device)
     return out
 
 
@@ -2169,15 +1972,12 @@ def absdiff_window(H, W, y0=100, y1=500, x0=100, x1=500):
 def running_frame(running, frame, first=False):
     """running fp64 [H,W,3] <- frame's values (first) or 0.95 * running + 0.05 * frame, one rounding per operation, in place
     (rn_running_frame; datareader.py:74-77).  -> running."""
-    lib = _hip.load()
     _hip.need_gpu(running, frame)
     _u8_frame("running_frame", "frame", frame)
     if running.dtype != torch.float64 or running.shape != frame.shape or not running.is_contiguous() or running.device != frame.device:
         raise RuntimeError("running_frame: running is a contiguous fp64 %s tensor on the frame's device, got %s %s"
                            % (tuple(frame.shape), running.dtype, tuple(running.shape)))
-    with torch.cuda.device(frame.device):
-        _hip.check(lib.rn_running_frame(running.data_ptr(), frame.data_ptr(), frame.numel(), int(bool(first)), _hip.stream()),
-                   "rn_running_frame")
+    _hip.call("rn_running_frame", running, frame, frame.numel(), int(bool(first)), device=frame.device)
     return running
 
 
@@ -2200,21 +2000,12 @@ _LABEL_BITS = ((LABEL_BAD_OFFSETS, "tracklet offsets out of order or outside the
 
 def label_status(device, status=None):
     """The status word the three entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
-    if status is None:
-        return torch.zeros(1, dtype=torch.int32, device=device)
-    _hip.need_gpu(status)
-    _mot_typed("label", ("status", status, torch.int32))
-    if status.numel() != 1:
-        raise RuntimeError("label: status is one int32")
-    return status
+    return _status_word("label", device, status)
 
 
 def label_check(status):
     """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
-    bits = int(status)
-    if bits:
-        raise RuntimeError("the label kernels refused their input: " + "; ".join(t for b, t in _LABEL_BITS if bits & b)
-                           + " (status %d)" % bits)
+    _refused("the label kernels refused their input: ", _LABEL_BITS, status)
 
 
 def label_pair_index(cam, prev):
@@ -2223,12 +2014,12 @@ def label_pair_index(cam, prev):
 
 
 def _label_table(what, offsets, cols, frame=None):
-    _mot_typed(what, ("offsets", offsets, torch.int64), ("cols", cols, torch.float64))
+    _typed(what, ("offsets", offsets, torch.int64), ("cols", cols, torch.float64))
     if offsets.dim() != 1 or offsets.numel() < 1 or cols.dim() != 2 or cols.shape[1] != 3:
         raise RuntimeError("%s: offsets is int64 [T+1], cols fp64 [R,3]" % what)
     T, R = offsets.numel() - 1, cols.shape[0]
     if frame is not None:
-        _mot_typed(what, ("frame", frame, torch.int32))
+        _typed(what, ("frame", frame, torch.int32))
         if tuple(frame.shape) != (R,):
             raise RuntimeError("%s: frame is int32 [R]" % what)
     if T >= 2 ** 31 or R >= 2 ** 31:
@@ -2241,7 +2032,6 @@ def label_pair_samples(offsets, cols, n_cam, key_col, val0, val1=-1, status=None
     n_cam + camera), cols fp64 [R,3] (x, y, timestamp); key_col / val0 / val1 pick the columns (val1 -1: none) -> (flags uint8
     [P, n_ids, 5], values fp64 [P, n_ids, 5, 4] = (cam's val0, prev's val0, cam's val1, prev's val1), status); pair
     ``label_pair_index(cam, prev)``, P = n_cam (n_cam - 1) / 2."""
-    lib = _hip.load()
     _hip.need_gpu(offsets, cols)
     T, R = _label_table("label_pair_samples", offsets, cols)
     n_cam, key_col, val0, val1 = int(n_cam), int(key_col), int(val0), int(val1)
@@ -2252,17 +2042,13 @@ def label_pair_samples(offsets, cols, n_cam, key_col, val0, val1=-1, status=None
     status = label_status(dev, status)
     flags = torch.empty((P, n_ids, LABEL_POINTS), dtype=torch.uint8, device=dev)
     values = torch.empty((P, n_ids, LABEL_POINTS, 4), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_pair_samples(offsets.data_ptr(), _hip.ptr(cols), R, n_cam, n_ids, key_col, val0, val1,
-                                             _hip.ptr(flags), _hip.ptr(values), status.data_ptr(), _hip.stream()),
-                   "rn_label_pair_samples")
+    _hip.call("rn_label_pair_samples", offsets, cols, R, n_cam, n_ids, key_col, val0, val1, flags, values, status, device=dev)
     return flags, values, status
 
 
 def label_outliers(offsets, cols, frame, n_frames, n_visit, status=None):
     """seems_to_be_working.py:2195-2231 along every tracklet: frame int32 [R] (ascending inside a tracklet), n_frames =
     len(data), n_visit = the frames the walk reaches before its break -> (delete uint8 [R], status)."""
-    lib = _hip.load()
     _hip.need_gpu(offsets, cols, frame)
     T, R = _label_table("label_outliers", offsets, cols, frame)
     F, n_visit, dev = int(n_frames), int(n_visit), cols.device
@@ -2270,9 +2056,7 @@ def label_outliers(offsets, cols, frame, n_frames, n_visit, status=None):
         raise RuntimeError("label_outliers: 0 <= n_frames < 2^31, n_visit >= 0")
     status = label_status(dev, status)
     delete = torch.empty(R, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_outliers(offsets.data_ptr(), _hip.ptr(cols), _hip.ptr(frame), T, R, F, n_visit, _hip.ptr(delete),
-                                         status.data_ptr(), _hip.stream()), "rn_label_outliers")
+    _hip.call("rn_label_outliers", offsets, cols, frame, T, R, F, n_visit, delete, status, device=dev)
     return delete, status
 
 
@@ -2284,7 +2068,7 @@ def label_interpolate(offsets, cols, frame, all_ts, rows, status=None):
     lib = _hip.load()
     _hip.need_gpu(offsets, cols, frame, all_ts)
     T, R = _label_table("label_interpolate", offsets, cols, frame)
-    _mot_typed("label_interpolate", ("all_ts", all_ts, torch.float64))
+    _typed("label_interpolate", ("all_ts", all_ts, torch.float64))
     rows, dev = int(rows), cols.device
     if all_ts.dim() != 2 or not 1 <= all_ts.shape[1] <= LABEL_MAX_CAMS or T % all_ts.shape[1] or all_ts.shape[0] >= 2 ** 31 \
             or rows < 0:
@@ -2296,10 +2080,8 @@ def label_interpolate(offsets, cols, frame, all_ts, rows, status=None):
     out_src = torch.empty(rows, dtype=torch.int32, device=dev)
     out_frame = torch.empty(rows, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_interpolate(offsets.data_ptr(), _hip.ptr(cols), _hip.ptr(frame), _hip.ptr(all_ts), T, R, F, n_cam,
-                                            rows, ws.data_ptr(), _hip.ptr(out), _hip.ptr(out_src), _hip.ptr(out_frame),
-                                            total.data_ptr(), status.data_ptr(), _hip.stream()), "rn_label_interpolate")
+    _hip.call("rn_label_interpolate", offsets, cols, frame, all_ts, T, R, F, n_cam, rows, ws, out, out_src, out_frame, total, status,
+              device=dev)
     return out, out_src, out_frame, total, status
 
 
@@ -2322,12 +2104,11 @@ def label_rebase(state6, cam, P1_old, P2_old, P1_new, P2_new, radii, grid=11, st
     [n], P1_* fp64 [n_cam,3,4] (or [n_cam,12]), P2_* alike or None (no wrapper switch), radii fp64 [rounds] on the device,
     2 <= grid <= 16 -> (centre fp64 [n,2], err fp64 [n], idx int32 [n, rounds], status).  A box the kernel leaves out (its
     status bit is set) keeps NaN / -1."""
-    lib = _hip.load()
     _hip.need_gpu(state6, cam, P1_old, P2_old, P1_new, P2_new, radii)
     specs = [("state6", state6, torch.float64), ("cam", cam, torch.int32), ("P1_old", P1_old, torch.float64),
              ("P1_new", P1_new, torch.float64), ("radii", radii, torch.float64)]
     specs += [(k, v, torch.float64) for k, v in (("P2_old", P2_old), ("P2_new", P2_new)) if v is not None]
-    _mot_typed("label_rebase", *specs)
+    _typed("label_rebase", *specs)
     n, n_cam, rounds, grid = state6.shape[0], P1_old.shape[0], radii.numel(), int(grid)
     if state6.dim() != 2 or state6.shape[1] != 6 or tuple(cam.shape) != (n,) or radii.dim() != 1 or n >= 2 ** 31:
         raise RuntimeError("label_rebase: state6 is fp64 [n,6], cam int32 [n], radii fp64 [rounds]")
@@ -2342,35 +2123,30 @@ def label_rebase(state6, cam, P1_old, P2_old, P1_new, P2_new, radii, grid=11, st
     centre = torch.empty((n, 2), dtype=torch.float64, device=dev)
     err = torch.empty(n, dtype=torch.float64, device=dev)
     idx = torch.empty((n, rounds), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_rebase(_hip.ptr(state6), _hip.ptr(cam), n, _hip.ptr(P1_old), _hip.ptr(P2_old), _hip.ptr(P1_new),
-                                       _hip.ptr(P2_new), n_cam, radii.data_ptr(), rounds, grid, _hip.ptr(centre), _hip.ptr(err),
-                                       _hip.ptr(idx), status.data_ptr(), _hip.stream()), "rn_label_rebase")
+    _hip.call("rn_label_rebase", state6, cam, n, P1_old, P2_old, P1_new, P2_new, n_cam, radii, rounds, grid, centre, err, idx, status,
+              device=dev)
     return centre, err, idx, status
 
 
 def label_offset_y(xy, coef, y_straight, direction, reverse=False):
     """seems_to_be_working.py:1792-1802 for every box: xy fp64 [n,2], coef fp64 [n,3] = (p2, p1, p0), y_straight fp64 [n]
     (subtracted from the offset where direction is -1), direction int32 [n] -> y fp64 [n], y - offset or, reverse, y + offset."""
-    lib = _hip.load()
     _hip.need_gpu(xy, coef, y_straight, direction)
-    _mot_typed("label_offset_y", ("xy", xy, torch.float64), ("coef", coef, torch.float64), ("y_straight", y_straight, torch.float64),
-               ("direction", direction, torch.int32))
+    _typed("label_offset_y", ("xy", xy, torch.float64), ("coef", coef, torch.float64), ("y_straight", y_straight, torch.float64),
+           ("direction", direction, torch.int32))
     n = xy.shape[0]
     if xy.dim() != 2 or xy.shape[1] != 2 or tuple(coef.shape) != (n, 3) or tuple(y_straight.shape) != (n,) or \
             tuple(direction.shape) != (n,):
         raise RuntimeError("label_offset_y: xy is fp64 [n,2], coef fp64 [n,3], y_straight fp64 [n], direction int32 [n]")
     out = torch.empty(n, dtype=torch.float64, device=xy.device)
-    with torch.cuda.device(xy.device):
-        _hip.check(lib.rn_label_offset_y(_hip.ptr(xy), _hip.ptr(coef), _hip.ptr(y_straight), _hip.ptr(direction), n,
-                                         int(bool(reverse)), _hip.ptr(out), _hip.stream()), "rn_label_offset_y")
+    _hip.call("rn_label_offset_y", xy, coef, y_straight, direction, n, int(bool(reverse)), out, device=xy.device)
     return out
 
 
 # ------------------------------------------------------------------------------------------------ detector-assisted labelling
 def _label_cameras(what, n, cam, P1, P2):
     specs = [("cam", cam, torch.int32), ("P1", P1, torch.float64)] + ([] if P2 is None else [("P2", P2, torch.float64)])
-    _mot_typed(what, *specs)
+    _typed(what, *specs)
     n_cam = P1.shape[0] if P1.dim() else -1
     if tuple(cam.shape) != (n,) or n >= 2 ** 31:
         raise RuntimeError("%s: cam is int32 [n] for the n = %d boxes" % (what, n))
@@ -2387,9 +2163,8 @@ def label_crop_windows(state6, cam, P1, P2, ber=1.2, width=1920, height=1080, st
     direction), cam int32 [n], P1 fp64 [n_cam,3,4] (or [n_cam,12]), P2 alike or None (no wrapper switch) -> (crop_box fp32 [n,4],
     rois fp32 [n,5] = (camera, window), win fp32 [n,3] = (minx, miny, scale), skipped uint8 [n], status).  A box whose crop box
     leaves the frame is flagged in ``skipped`` and keeps NaN in rois and win, as the reference returns silently."""
-    lib = _hip.load()
     _hip.need_gpu(state6, cam, P1, P2)
-    _mot_typed("label_crop_windows", ("state6", state6, torch.float32))
+    _typed("label_crop_windows", ("state6", state6, torch.float32))
     if state6.dim() != 2 or state6.shape[1] != 6:
         raise RuntimeError("label_crop_windows: state6 is fp32 [n,6]")
     n = state6.shape[0]
@@ -2400,10 +2175,8 @@ def label_crop_windows(state6, cam, P1, P2, ber=1.2, width=1920, height=1080, st
     rois = torch.empty((n, 5), dtype=torch.float32, device=dev)
     win = torch.empty((n, 3), dtype=torch.float32, device=dev)
     skipped = torch.empty(n, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_crop_windows(_hip.ptr(state6), _hip.ptr(cam), n, _hip.ptr(P1), _hip.ptr(P2), n_cam, float(ber),
-                                             float(width), float(height), _hip.ptr(crop_box), _hip.ptr(rois), _hip.ptr(win),
-                                             _hip.ptr(skipped), status.data_ptr(), _hip.stream()), "rn_label_crop_windows")
+    _hip.call("rn_label_crop_windows", state6, cam, n, P1, P2, n_cam, float(ber), float(width), float(height), crop_box, rois, win,
+              skipped, status, device=dev)
     return crop_box, rois, win, skipped, status
 
 
@@ -2412,9 +2185,8 @@ def label_best_anchor(cls, reg, win, cs=112):
     localiser's LOCALIZE outputs), win fp32 [n,3] = (minx, miny, scale) -> (box fp32 [n,4] in frame coordinates, anchor int32
     [n], confidence fp32 [n], class int32 [n]).  torch.max / torch.argmax: a NaN counts as largest, equal values go to the
     lower index."""
-    lib = _hip.load()
     _hip.need_gpu(cls, reg, win)
-    _mot_typed("label_best_anchor", ("cls", cls, torch.float32), ("reg", reg, torch.float32), ("win", win, torch.float32))
+    _typed("label_best_anchor", ("cls", cls, torch.float32), ("reg", reg, torch.float32), ("win", win, torch.float32))
     if cls.dim() != 3 or cls.shape[1] < 1 or cls.shape[2] < 1 or tuple(reg.shape) != (cls.shape[0], cls.shape[1], 4) or \
             tuple(win.shape) != (cls.shape[0], 3) or cls.shape[0] >= 2 ** 31 or cls.shape[1] * cls.shape[2] >= 2 ** 31:
         raise RuntimeError("label_best_anchor: cls is fp32 [n,A,C] with A, C >= 1, reg fp32 [n,A,4], win fp32 [n,3]")
@@ -2424,10 +2196,7 @@ def label_best_anchor(cls, reg, win, cs=112):
     anchor = torch.empty(n, dtype=torch.int32, device=dev)
     conf = torch.empty(n, dtype=torch.float32, device=dev)
     klass = torch.empty(n, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_best_anchor(_hip.ptr(cls), _hip.ptr(reg), _hip.ptr(win), n, A, C, float(cs), _hip.ptr(box),
-                                            _hip.ptr(anchor), _hip.ptr(conf), _hip.ptr(klass), _hip.stream()),
-                   "rn_label_best_anchor")
+    _hip.call("rn_label_best_anchor", cls, reg, win, n, A, C, float(cs), box, anchor, conf, klass, device=dev)
     return box, anchor, conf, klass
 
 
@@ -2438,15 +2207,14 @@ def label_fit_box2d(tmpl, cam, centre, target, P1, P2, radii, grid=11, skip=None
     fp32 [n,2], err fp32 [n], idx int32 [n, rounds], status).  A box the kernel leaves out (its status bit is set) keeps
     NaN / -1, and so does, without a status bit, a box whose byte of ``skip`` (uint8 [n], ``label_crop_windows``' skipped) is
     set."""
-    lib = _hip.load()
     _hip.need_gpu(tmpl, cam, centre, target, P1, P2, radii, skip)
-    _mot_typed("label_fit_box2d", ("tmpl", tmpl, torch.float32), ("centre", centre, torch.float32),
-               ("target", target, torch.float32), ("radii", radii, torch.float64))
+    _typed("label_fit_box2d", ("tmpl", tmpl, torch.float32), ("centre", centre, torch.float32),
+           ("target", target, torch.float32), ("radii", radii, torch.float64))
     n, rounds, grid = tmpl.shape[0] if tmpl.dim() else -1, radii.numel(), int(grid)
     if tuple(tmpl.shape) != (n, 4) or tuple(centre.shape) != (n, 2) or tuple(target.shape) != (n, 4) or radii.dim() != 1:
         raise RuntimeError("label_fit_box2d: tmpl is fp32 [n,4], centre fp32 [n,2], target fp32 [n,4], radii fp64 [rounds]")
     if skip is not None:
-        _mot_typed("label_fit_box2d", ("skip", skip, torch.uint8))
+        _typed("label_fit_box2d", ("skip", skip, torch.uint8))
         if tuple(skip.shape) != (n,):
             raise RuntimeError("label_fit_box2d: skip is uint8 [n]")
     n_cam = _label_cameras("label_fit_box2d", n, cam, P1, P2)
@@ -2457,10 +2225,8 @@ def label_fit_box2d(tmpl, cam, centre, target, P1, P2, radii, grid=11, skip=None
     out = torch.empty((n, 2), dtype=torch.float32, device=dev)
     err = torch.empty(n, dtype=torch.float32, device=dev)
     idx = torch.empty((n, rounds), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_fit_box2d(_hip.ptr(tmpl), _hip.ptr(cam), _hip.ptr(centre), _hip.ptr(target), _hip.ptr(skip), n, _hip.ptr(P1),
-                                          _hip.ptr(P2), n_cam, radii.data_ptr(), rounds, grid, _hip.ptr(out), _hip.ptr(err),
-                                          _hip.ptr(idx), status.data_ptr(), _hip.stream()), "rn_label_fit_box2d")
+    _hip.call("rn_label_fit_box2d", tmpl, cam, centre, target, skip, n, P1, P2, n_cam, radii, rounds, grid, out, err, idx, status,
+              device=dev)
     return out, err, idx, status
 
 
@@ -2491,10 +2257,9 @@ def spline_waves(grp):
 def label_box_weights(state6, cam, P1, P2=None, status=None):
     """seems_to_be_working.py:1186-1196 for every box: state6 fp64 [n,6] = (x, y, l, w, h, direction), cam int32 [n], P1 / P2 fp64
     [n_cam,12] (P2 None: no wrapper switch) -> (out fp64 [n,4] = (x_weight, y_weight, x_diff, y_diff), status)."""
-    lib = _hip.load()
     _hip.need_gpu(state6, cam, P1, P2)
     specs = [("state6", state6, torch.float64), ("cam", cam, torch.int32), ("P1", P1, torch.float64)]
-    _mot_typed("label_box_weights", *(specs + ([("P2", P2, torch.float64)] if P2 is not None else [])))
+    _typed("label_box_weights", *(specs + ([("P2", P2, torch.float64)] if P2 is not None else [])))
     n, n_cam = state6.shape[0], P1.shape[0]
     if state6.dim() != 2 or state6.shape[1] != 6 or tuple(cam.shape) != (n,) or P1.numel() != n_cam * 12 or n >= 2 ** 31 or \
             not 1 <= n_cam <= LABEL_MAX_CAMS or (P2 is not None and tuple(P2.shape) != tuple(P1.shape)):
@@ -2502,14 +2267,12 @@ def label_box_weights(state6, cam, P1, P2=None, status=None):
     dev = state6.device
     status = label_status(dev, status)
     out = torch.empty((n, 4), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_box_weights(_hip.ptr(state6), _hip.ptr(cam), n, _hip.ptr(P1), _hip.ptr(P2), n_cam, _hip.ptr(out),
-                                            status.data_ptr(), _hip.stream()), "rn_label_box_weights")
+    _hip.call("rn_label_box_weights", state6, cam, n, P1, P2, n_cam, out, status, device=dev)
     return out, status
 
 
 def _spline_rows(what, grp, tx, *cols):
-    _mot_typed(what, ("grp", grp, torch.int32), ("tx", tx, torch.float64), *[("column", c, torch.float64) for c in cols])
+    _typed(what, ("grp", grp, torch.int32), ("tx", tx, torch.float64), *[("column", c, torch.float64) for c in cols])
     if grp.dim() != 2 or grp.shape[1] != SPLINE_GRP or tx.dim() != 1 or any(tuple(c.shape) != tuple(tx.shape) for c in cols) or \
             grp.shape[0] >= 2 ** 31 or tx.numel() >= 2 ** 31:
         raise RuntimeError("%s: grp is int32 [G,%d], tx and the other columns fp64 [R]" % (what, SPLINE_GRP))
@@ -2532,10 +2295,9 @@ def spline_fit(grp, waves, tx, val, wt, s, ncap, workspace=None, status=None):
     ``spline_waves``, tx / val / wt fp64 [R], s fp64 [NC], ncap = the largest knot count any lane may reach -> (workspace fp64
     [19 * ncap, NW * 64] (row 0.. the knots t, row ncap.. the coefficients c of every lane), n int32 [NW * 64], ier int32,
     fp fp64, iterations int32, status).  ``workspace``: a tensor of a former call to reuse (at least as large)."""
-    lib = _hip.load()
     _hip.need_gpu(grp, waves, tx, val, wt, s, workspace)
     G, R = _spline_rows("spline_fit", grp, tx, val, wt)
-    _mot_typed("spline_fit", ("waves", waves, torch.int32), ("s", s, torch.float64))
+    _typed("spline_fit", ("waves", waves, torch.int32), ("s", s, torch.float64))
     ncap = _spline_ncap("spline_fit", ncap)
     if waves.dim() != 2 or waves.shape[1] != 2 or s.dim() != 1 or waves.shape[0] >= 2 ** 25 or s.numel() >= 2 ** 31:
         raise RuntimeError("spline_fit: waves is int32 [NW,2], s fp64 [NC]")
@@ -2551,10 +2313,7 @@ def spline_fit(grp, waves, tx, val, wt, s, ncap, workspace=None, status=None):
     ier = torch.empty(NL, dtype=torch.int32, device=dev)
     fp = torch.empty(NL, dtype=torch.float64, device=dev)
     iters = torch.empty(NL, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_spline_fit(_hip.ptr(grp), G, _hip.ptr(waves), NW, _hip.ptr(tx), _hip.ptr(val), _hip.ptr(wt), R, _hip.ptr(s),
-                                     s.numel(), ncap, workspace.data_ptr(), _hip.ptr(n), _hip.ptr(ier), _hip.ptr(fp), _hip.ptr(iters),
-                                     status.data_ptr(), _hip.stream()), "rn_spline_fit")
+    _hip.call("rn_spline_fit", grp, G, waves, NW, tx, val, wt, R, s, s.numel(), ncap, workspace, n, ier, fp, iters, status, device=dev)
     return workspace.reshape(-1)[:need].view(SPLINE_WS_COLS * ncap, NL), n, ier, fp, iters, status
 
 
@@ -2562,11 +2321,10 @@ def spline_select(grp, tx, val, wt, wscore, n_cand, ncap, workspace, n, ier, fp,
     """seems_to_be_working.py:1238-1294 for every group, one workgroup each, on the output of ``spline_fit`` -> (scores fp64 [NC]
     (NaN: skipped), win int32 [G,3] = (candidate or -1, n, ier), figures fp64 [G,5] = (fp, score, sqrt(mean r^2), sqrt(mean (w
     r)^2), sqrt(max (w r)^2)), t fp64 [G, ncap], c fp64 [G, ncap], status)."""
-    lib = _hip.load()
     _hip.need_gpu(grp, tx, val, wt, wscore, workspace, n, ier, fp)
     G, R = _spline_rows("spline_select", grp, tx, val, wt, wscore)
-    _mot_typed("spline_select", ("workspace", workspace, torch.float64), ("n", n, torch.int32), ("ier", ier, torch.int32),
-               ("fp", fp, torch.float64))
+    _typed("spline_select", ("workspace", workspace, torch.float64), ("n", n, torch.int32), ("ier", ier, torch.int32),
+           ("fp", fp, torch.float64))
     ncap, NC, NL = _spline_ncap("spline_select", ncap), int(n_cand), n.numel()
     if NL % 64 or tuple(ier.shape) != (NL,) or tuple(fp.shape) != (NL,) or workspace.numel() < SPLINE_WS_COLS * ncap * NL or \
             not 0 <= NC < 2 ** 31:
@@ -2578,16 +2336,13 @@ def spline_select(grp, tx, val, wt, wscore, n_cand, ncap, workspace, n, ier, fp,
     fig = torch.empty((G, SPLINE_FIGS), dtype=torch.float64, device=dev)
     t = torch.empty((G, ncap), dtype=torch.float64, device=dev)
     c = torch.empty((G, ncap), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_spline_select(_hip.ptr(grp), G, _hip.ptr(tx), _hip.ptr(val), _hip.ptr(wt), _hip.ptr(wscore), R, NC, NL // 64,
-                                        ncap, workspace.data_ptr(), _hip.ptr(n), _hip.ptr(ier), _hip.ptr(fp), spline_metric(metric),
-                                        _hip.ptr(scores), _hip.ptr(win), _hip.ptr(fig), _hip.ptr(t), _hip.ptr(c), status.data_ptr(),
-                                        _hip.stream()), "rn_spline_select")
+    _hip.call("rn_spline_select", grp, G, tx, val, wt, wscore, R, NC, NL // 64, ncap, workspace, n, ier, fp, spline_metric(metric),
+              scores, win, fig, t, c, status, device=dev)
     return scores, win, fig, t, c, status
 
 
 def _spline_pack(what, st, sc, snk):
-    _mot_typed(what, ("st", st, torch.float64), ("sc", sc, torch.float64), ("snk", snk, torch.int32))
+    _typed(what, ("st", st, torch.float64), ("sc", sc, torch.float64), ("snk", snk, torch.int32))
     if st.dim() != 2 or tuple(sc.shape) != tuple(st.shape) or tuple(snk.shape) != (st.shape[0], 2) or st.shape[0] >= 2 ** 31:
         raise RuntimeError("%s: st and sc are fp64 [S, ncap], snk int32 [S,2] = (n, k)" % what)
     return st.shape[0], _spline_ncap(what, st.shape[1])
@@ -2596,16 +2351,13 @@ def _spline_pack(what, st, sc, snk):
 def spline_eval(st, sc, snk, qs, qt):
     """FITPACK splev with extrapolation, one thread per query: st / sc fp64 [S, ncap] the knots and coefficients, snk int32 [S,2] =
     (n, k) (n = 0: no spline), qs int32 [Q] the spline of every query, qt fp64 [Q] -> fp64 [Q] (NaN without a spline)."""
-    lib = _hip.load()
     _hip.need_gpu(st, sc, snk, qs, qt)
     S, ncap = _spline_pack("spline_eval", st, sc, snk)
-    _mot_typed("spline_eval", ("qs", qs, torch.int32), ("qt", qt, torch.float64))
+    _typed("spline_eval", ("qs", qs, torch.int32), ("qt", qt, torch.float64))
     if qs.dim() != 1 or tuple(qt.shape) != tuple(qs.shape):
         raise RuntimeError("spline_eval: qs is int32 [Q], qt fp64 [Q]")
     out = torch.empty(qs.numel(), dtype=torch.float64, device=st.device)
-    with torch.cuda.device(st.device):
-        _hip.check(lib.rn_spline_eval(_hip.ptr(st), _hip.ptr(sc), _hip.ptr(snk), S, ncap, _hip.ptr(qs), _hip.ptr(qt), qs.numel(),
-                                      _hip.ptr(out), _hip.stream()), "rn_spline_eval")
+    _hip.call("rn_spline_eval", st, sc, snk, S, ncap, qs, qt, qs.numel(), out, device=st.device)
     return out
 
 
@@ -2614,11 +2366,10 @@ def label_ts_shift(st, sc, snk, off, rs, rx, base, run, shifts, use_run=True, me
     int64 [E+1] the rows of every entry, rs int32 [Rr] / rx fp64 [Rr] the spline and the label x of its kept objects, base / run
     fp64 [E] the camera's time stamp and running error, shifts fp64 [trials < 64] -> (best_t fp64 [E], errs fp64 [E,2] = (best,
     initial), best_i int32 [E], status)."""
-    lib = _hip.load()
     _hip.need_gpu(st, sc, snk, off, rs, rx, base, run, shifts)
     S, ncap = _spline_pack("label_ts_shift", st, sc, snk)
-    _mot_typed("label_ts_shift", ("off", off, torch.int64), ("rs", rs, torch.int32), ("rx", rx, torch.float64),
-               ("base", base, torch.float64), ("run", run, torch.float64), ("shifts", shifts, torch.float64))
+    _typed("label_ts_shift", ("off", off, torch.int64), ("rs", rs, torch.int32), ("rx", rx, torch.float64),
+           ("base", base, torch.float64), ("run", run, torch.float64), ("shifts", shifts, torch.float64))
     E, Rr, trials = off.numel() - 1, rs.numel(), shifts.numel()
     if off.dim() != 1 or E < 0 or rs.dim() != 1 or tuple(rx.shape) != (Rr,) or tuple(base.shape) != (E,) or tuple(run.shape) != (E,) \
             or shifts.dim() != 1 or not 1 <= trials < 64 or E >= 2 ** 31 or Rr >= 2 ** 31:
@@ -2628,11 +2379,8 @@ def label_ts_shift(st, sc, snk, off, rs, rx, base, run, shifts, use_run=True, me
     best_t = torch.empty(E, dtype=torch.float64, device=dev)
     errs = torch.empty((E, 2), dtype=torch.float64, device=dev)
     best_i = torch.empty(E, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_ts_shift(_hip.ptr(st), _hip.ptr(sc), _hip.ptr(snk), S, ncap, _hip.ptr(off), _hip.ptr(rs), _hip.ptr(rx), E,
-                                         Rr, _hip.ptr(base), _hip.ptr(run), _hip.ptr(shifts), trials, int(bool(use_run)),
-                                         spline_metric(metric), _hip.ptr(best_t), _hip.ptr(errs), _hip.ptr(best_i), status.data_ptr(),
-                                         _hip.stream()), "rn_label_ts_shift")
+    _hip.call("rn_label_ts_shift", st, sc, snk, S, ncap, off, rs, rx, E, Rr, base, run, shifts, trials, int(bool(use_run)),
+              spline_metric(metric), best_t, errs, best_i, status, device=dev)
     return best_t, errs, best_i, status
 
 
@@ -2664,10 +2412,8 @@ def label_series(offsets, cols, n_cam, lane=None, lds_rows=None, status=None):
     series = torch.empty((LABEL_SERIES_PLANES, R), dtype=torch.float64, device=dev)
     counts = torch.empty((n_ids, 3), dtype=torch.int32, device=dev)
     figs = torch.empty((n_ids, 2), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_series(offsets.data_ptr(), _hip.ptr(cols), R, n_cam, n_ids, int(lane is not None), lo, hi, lds_rows,
-                                       ws.data_ptr(), _hip.ptr(order), _hip.ptr(keep), _hip.ptr(series), _hip.ptr(counts),
-                                       _hip.ptr(figs), status.data_ptr(), _hip.stream()), "rn_label_series")
+    _hip.call("rn_label_series", offsets, cols, R, n_cam, n_ids, int(lane is not None), lo, hi, lds_rows, ws, order, keep, series,
+              counts, figs, status, device=dev)
     return order, keep, series, counts, figs, status
 
 
@@ -2675,9 +2421,8 @@ def label_group_rmse(im, group, n_groups, status=None):
     """manual_annotator_state_v3.py:3997-4000 for every group, one workgroup each: im fp64 [n,8,2] (``hg_to_im``), group int32
     [n], ascending ids in [0, n_groups) -> (rmse fp64 [n_groups], mean fp64 [n_groups,2], count int32 [n_groups], status); an
     empty group gives NaN, NaN, 0."""
-    lib = _hip.load()
     _hip.need_gpu(im, group)
-    _mot_typed("label_group_rmse", ("im", im, torch.float64), ("group", group, torch.int32))
+    _typed("label_group_rmse", ("im", im, torch.float64), ("group", group, torch.int32))
     n, G = group.numel(), int(n_groups)
     if group.dim() != 1 or tuple(im.shape) != (n, 8, 2) or n >= 2 ** 31 or not 0 <= G < 2 ** 31:
         raise RuntimeError("label_group_rmse: im is fp64 [n,8,2], group int32 [n], 0 <= n_groups < 2^31")
@@ -2686,7 +2431,5 @@ def label_group_rmse(im, group, n_groups, status=None):
     rmse = torch.empty(G, dtype=torch.float64, device=dev)
     mean = torch.empty((G, 2), dtype=torch.float64, device=dev)
     count = torch.empty(G, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.rn_label_group_rmse(_hip.ptr(im), _hip.ptr(group), n, G, _hip.ptr(rmse), _hip.ptr(mean), _hip.ptr(count),
-                                           status.data_ptr(), _hip.stream()), "rn_label_group_rmse")
+    _hip.call("rn_label_group_rmse", im, group, n, G, rmse, mean, count, status, device=dev)
     return rmse, mean, count, status

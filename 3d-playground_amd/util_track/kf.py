@@ -15,10 +15,6 @@ import torch
 from retinanet_mi355x import _hip
 
 
-def _p(t):
-    return t.data_ptr()
-
-
 class Torch_KF(object):
     def __init__(self, device, state_err=10000, meas_err=1, mod_err=1, INIT=None, ADD_MEAN_Q=False, ADD_MEAN_R=False):
         device = torch.device(device)
@@ -156,9 +152,7 @@ class Torch_KF(object):
               or out.device != self.F.device):
             raise RuntimeError("view: out has to be a contiguous float32 [%d, %d] tensor on %s" % (n, cols, self.F.device))
         dtt, flag = (None, 0) if dt is None else self._dt(dt)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.load().rn_kf_view(_p(self.X), _p(self.D), _p(self.F), _hip.ptr(dtt), flag, int(bool(with_direction)),
-                                              _p(out), n, _hip.stream()), "rn_kf_view")
+        _hip.call("rn_kf_view", self.X, self.D, self.F, dtt, flag, int(bool(with_direction)), out, n, device=self.device)
         inverted = dict([(self.obj_idxs[key], key) for key in self.obj_idxs.keys()])
         return [inverted[i] for i in range(n)], out
 
@@ -168,9 +162,8 @@ class Torch_KF(object):
         dtt, flag = self._dt(self.dt_default if dt is None else dt)
         self.X, self.P = self.X.float().contiguous(), self.P.float().contiguous()
         self.D, self.T = self.D.float().contiguous(), self.T.double().contiguous()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.load().rn_kf_predict(_p(self.X), _p(self.P), _p(self.D), _p(self.T), _p(self.F), _p(self.Q), _p(dtt),
-                                                 flag, float(self.dt_default), len(self.X), _hip.stream()), "rn_kf_predict")
+        _hip.call("rn_kf_predict", self.X, self.P, self.D, self.T, self.F, self.Q, dtt, flag, float(self.dt_default), len(self.X),
+                  device=self.device)
 
     def update(self, detections, obj_ids, measurement_idx=1):              # kf.py:335-403
         if measurement_idx == 1:
@@ -203,9 +196,8 @@ class Torch_KF(object):
             return
         r = torch.as_tensor(rows, dtype=torch.int32, device=self.device)
         self.X, self.P = self.X.float().contiguous(), self.P.float().contiguous()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.load().rn_kf_update(_p(self.X), _p(self.P), _p(r), _p(z), _p(H.contiguous()), _p(R.contiguous()),
-                                                _p(mu_R.contiguous()), len(rows), _hip.stream()), "rn_kf_update")
+        _hip.call("rn_kf_update", self.X, self.P, r, z, H.contiguous(), R.contiguous(), mu_R.contiguous(), len(rows),
+                  device=self.device)
 
     def objs(self, with_direction=False, with_time=False):                 # kf.py:420-428
         return self.view(dt=None, with_direction=with_direction)
