@@ -14,6 +14,9 @@ per operation, i.e. Python's; the reference's weights are kept as written, which
 The rows of the file come from ``results_csv.results_rows``, the formatter of the tracker's own result file.  There is no CPU
 path.
 
+Beyond the reference: ``stitch(params, fill, save)`` joins the fragments a vehicle leaves behind when the tracker loses it and
+fills the gaps (track_stitch.py, csrc/stitch.hip).
+
 Differences a caller can see: ``reinterpolate`` writes to ``save`` (the reference ignores the argument and
 always writes its default name, :450-451; the default value is that name, so a call without arguments behaves the same);
 ``frequency <= 0`` raises ValueError (the reference loops forever); the per-instant progress print of ``write_to_file`` is
@@ -479,6 +482,18 @@ class Data_Reader():
         self.d_idx = 0
         if save is not None:
             self.write_to_file(save_file=save)
+
+    def stitch(self, params=None, fill=True, save=None):
+        """Beyond the reference: joins the fragments of one vehicle under one id (track_stitch.stitch_tracks; ``params`` overrides
+        track_stitch.DEFAULTS) and, with ``fill``, fills the gap of every link.  Replaces ``data``, resets ``d_idx``, writes
+        ``save`` unless it is None -> the report.  On an error nothing is replaced."""
+        import track_stitch
+        new_data, report = track_stitch.stitch_tracks(self.data, params, fill, self._device())
+        self.data = new_data
+        self.d_idx = 0
+        if save is not None:
+            self.write_to_file(save_file=save)
+        return report
 
     def file_rows(self):
         """The rows ``write_to_file`` writes, from ``data`` as it is now: one ops.track_rows launch, then results_rows."""

@@ -139,6 +139,15 @@ SIGNATURES = {
     "rn_label_series_workspace_bytes": (c_i64, [c_i64]),
     "rn_label_series": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, c_f64, c_f64, c_i32] + [c_vp] * 8),
     "rn_label_group_rmse": (c_i32, [c_vp, c_vp, c_i64, c_i64] + [c_vp] * 5),
+    "rn_stitch_endpoints": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "rn_stitch_costs": (c_i32, [c_vp, c_i64] + [c_f64] * 7 + [c_vp, c_vp]),
+    "rn_stitch_candidates": (c_i32, [c_vp, c_i64] + [c_f64] * 7 + [c_vp] * 4),
+    "rn_stitch_compact": (c_i32, [c_vp, c_i64] + [c_f64] * 7 + [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "rn_stitch_assign_workspace_bytes": (c_i64, [c_i64]),
+    "rn_stitch_assign": (c_i32, [c_vp, c_i64] + [c_f64] * 7 + [c_vp, c_vp, c_vp, c_i64] + [c_vp] * 6),
+    "rn_stitch_chains": (c_i32, [c_vp, c_vp, c_i64] + [c_vp] * 6),
+    "rn_stitch_fill_count": (c_i32, [c_vp, c_vp, c_i64, c_f64] + [c_vp] * 4),
+    "rn_stitch_fill_rows": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_f64] + [c_vp] * 6),
 }
 
 class ConvDesc(ctypes.Structure):

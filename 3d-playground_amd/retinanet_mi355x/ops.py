@@ -1013,6 +1013,205 @@ def track_rows(fields, direction, P, P2=None, mat_index=None, status=None):
     return state, space, im, box, keep, status
 
 
+# ------------------------------------------------------------------------------------------------ track stitching
+STITCH_EP = 16                     # RN_STITCH_EP: doubles of one end point
+STITCH_MAX_TRACKLETS = 32768
+STITCH_MAX_FIT = 64
+STITCH_MAX_FILL = 1048576
+STITCH_DENSE_MAX = 8192            # stitch_costs only: the dense matrix stays below 512 MiB
+(STITCH_NONFINITE, STITCH_BAD_OFFSETS, STITCH_TOO_MANY, STITCH_SOLVER, STITCH_BAD_CANDIDATES, STITCH_BAD_LINK, STITCH_BAD_PREFIX,
+ STITCH_FILL_OVERFLOW) = 1, 2, 4, 8, 16, 32, 64, 128
+_STITCH_BITS = ((STITCH_NONFINITE, "a NaN or an infinity among the packed fields"),
+                (STITCH_BAD_OFFSETS, "tracklet offsets out of order, an empty tracklet or rows outside the packed ones"),
+                (STITCH_TOO_MANY, "more than %d tails and heads with a candidate in one direction" % LSAP_MAX_MIN),
+                (STITCH_SOLVER, "the assignment found no complete matching"),
+                (STITCH_BAD_CANDIDATES, "candidate counts or entries outside the tracklets"),
+                (STITCH_BAD_LINK, "a link outside the tracklets"),
+                (STITCH_BAD_PREFIX, "a new row outside its prefix slot"),
+                (STITCH_FILL_OVERFLOW, "a link with %d new rows or more" % STITCH_MAX_FILL))
+STITCH_SCALES = ("max_gap", "back_tol", "sigma_x0", "sigma_x1", "sigma_y", "sigma_size", "max_cost")
+
+
+def stitch_status(device, status=None):
+    """The status word the stitching entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
+    return _status_word("stitch", device, status)
+
+
+def stitch_check(status):
+    """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
+    _refused("the stitching kernels refused their input: ", _STITCH_BITS, status)
+
+
+def stitch_scales(scales):
+    """The seven scales of a link cost in STITCH_SCALES order, as floats; ValueError unless back_tol >= 0 and the others > 0."""
+    s = tuple(float(v) for v in scales)
+    if len(s) != len(STITCH_SCALES):
+        raise ValueError("a link cost takes the seven scales %s" % (STITCH_SCALES,))
+    for name, v in zip(STITCH_SCALES, s):
+        if not (v >= 0 if name == "back_tol" else v > 0) or v == float("inf"):
+            raise ValueError("stitching scale %s must be a positive finite number, got %r" % (name, v))
+    return s
+
+
+def _stitch_ep(what, ep):
+    _hip.need_gpu(ep)
+    _typed(what, ("ep", ep, torch.float64))
+    if ep.dim() != 3 or tuple(ep.shape[1:]) != (2, STITCH_EP):
+        raise RuntimeError("%s: ep is fp64 [N,2,%d], got %s" % (what, STITCH_EP, tuple(ep.shape)))
+    if ep.shape[0] > STITCH_MAX_TRACKLETS:
+        raise RuntimeError("%s: at most %d tracklets, got %d" % (what, STITCH_MAX_TRACKLETS, ep.shape[0]))
+    return ep.shape[0], ep.device
+
+
+def _stitch_int(what, N, *specs):
+    for name, t in specs:
+        _hip.need_gpu(t)
+        _typed(what, (name, t, torch.int32))
+        if tuple(t.shape) != (N,):
+            raise RuntimeError("%s: %s is int32 [N = %d], got %s" % (what, name, N, tuple(t.shape)))
+
+
+def stitch_endpoints(offsets, cols, direction, fit_n, status=None):
+    """offsets int64 [N+1], cols fp64 [R,7] = (t, x, y, l, w, h, v), direction int32 [R] -> (ep fp64 [N,2,STITCH_EP] = the head
+    and the tail of every tracklet (layout: include/retinanet_mi355x.h), status)."""
+    _hip.need_gpu(offsets, cols, direction)
+    _typed("stitch_endpoints", ("offsets", offsets, torch.int64), ("cols", cols, torch.float64), ("direction", direction, torch.int32))
+    fit_n = int(fit_n)
+    if not 1 <= fit_n <= STITCH_MAX_FIT:
+        raise ValueError("fit_n is 1 .. %d, got %d" % (STITCH_MAX_FIT, fit_n))
+    R = direction.numel()
+    if offsets.dim() != 1 or offsets.numel() < 1 or cols.dim() != 2 or tuple(cols.shape) != (R, 7) or direction.dim() != 1 or R >= 2 ** 31:
+        raise RuntimeError("stitch_endpoints: offsets int64 [N+1], cols fp64 [R,7], direction int32 [R], fewer than 2^31 rows")
+    N, dev = offsets.numel() - 1, cols.device
+    if N > STITCH_MAX_TRACKLETS:
+        raise RuntimeError("stitch_endpoints: at most %d tracklets, got %d" % (STITCH_MAX_TRACKLETS, N))
+    status = stitch_status(dev, status)
+    ep = torch.empty((N, 2, STITCH_EP), dtype=torch.float64, device=dev)
+    _hip.call("rn_stitch_endpoints", offsets, cols, direction, N, R, fit_n, ep, status, device=dev)
+    return ep, status
+
+
+def stitch_costs(ep, scales):
+    """The dense matrix of every ordered pair (a's tail -> b's head): W fp64 [N,N], cost - max_cost for a linkable pair and 0
+    otherwise.  For tests and small inputs (N <= STITCH_DENSE_MAX); the product path never materialises it."""
+    N, dev = _stitch_ep("stitch_costs", ep)
+    scales = stitch_scales(scales)
+    if N > STITCH_DENSE_MAX:
+        raise RuntimeError("stitch_costs: the dense matrix is for at most %d tracklets, got %d" % (STITCH_DENSE_MAX, N))
+    W = torch.empty((N, N), dtype=torch.float64, device=dev)
+    _hip.call("rn_stitch_costs", ep, N, *scales, W, device=dev)
+    return W
+
+
+def stitch_candidates(ep, scales):
+    """-> (cand int32 [2,2,N]: per direction (sgn = +1 first) the tails and the heads with a candidate, ascending, -1 behind;
+    ncand int32 [4] = (nr'+, nc'+, nr'-, nc'-))."""
+    N, dev = _stitch_ep("stitch_candidates", ep)
+    scales = stitch_scales(scales)
+    has = torch.empty((2, N), dtype=torch.uint8, device=dev)
+    cand = torch.empty((2, 2, N), dtype=torch.int32, device=dev)
+    ncand = torch.empty(4, dtype=torch.int32, device=dev)
+    _hip.call("rn_stitch_candidates", ep, N, *scales, has, cand, ncand, device=dev)
+    return cand, ncand
+
+
+def _stitch_cand(what, N, cand, ncand):
+    _hip.need_gpu(cand, ncand)
+    _typed(what, ("cand", cand, torch.int32), ("ncand", ncand, torch.int32))
+    if tuple(cand.shape) != (2, 2, N) or tuple(ncand.shape) != (4,):
+        raise RuntimeError("%s: cand int32 [2,2,N = %d], ncand int32 [4]" % (what, N))
+
+
+def stitch_compact(ep, scales, cand, ncand, cap, status=None):
+    """The compressed matrices: Wc fp64 [cap], direction + as [nr'+, nc'+] from 0 and direction - as [nr'-, nc'-] behind it; cap
+    = the host's upper bound of the cells (n+ ^2 + n- ^2 of the tracklets per direction), so that nothing is read back in
+    between.  -> (Wc, status)."""
+    N, dev = _stitch_ep("stitch_compact", ep)
+    scales = stitch_scales(scales)
+    _stitch_cand("stitch_compact", N, cand, ncand)
+    cap = int(cap)
+    if cap < 0:
+        raise RuntimeError("stitch_compact: cap >= 0")
+    status = stitch_status(dev, status)
+    Wc = torch.empty(cap, dtype=torch.float64, device=dev)
+    _hip.call("rn_stitch_compact", ep, N, *scales, cand, ncand, cap, Wc, status, device=dev)
+    return Wc, status
+
+
+def stitch_assign(ep, scales, cand, ncand, Wc, status=None):
+    """scipy.optimize.linear_sum_assignment on each direction's Wc; the links are the assigned cells with W < 0 -> (next int32
+    [N], prev int32 [N] (-1: none), link_cost fp64 [N] at the tail's index, status)."""
+    N, dev = _stitch_ep("stitch_assign", ep)
+    scales = stitch_scales(scales)
+    _stitch_cand("stitch_assign", N, cand, ncand)
+    _hip.need_gpu(Wc)
+    _typed("stitch_assign", ("Wc", Wc, torch.float64))
+    status = stitch_status(dev, status)
+    ws = torch.empty(max(int(_hip.load().rn_stitch_assign_workspace_bytes(N)), 16), dtype=torch.uint8, device=dev)
+    nxt = torch.empty(N, dtype=torch.int32, device=dev)
+    prev = torch.empty(N, dtype=torch.int32, device=dev)
+    link_cost = torch.empty(N, dtype=torch.float64, device=dev)
+    _hip.call("rn_stitch_assign", ep, N, *scales, cand, ncand, Wc, Wc.numel(), ws, nxt, prev, link_cost, status, device=dev)
+    return nxt, prev, link_cost, status
+
+
+def stitch_chains(prev, ids, status=None):
+    """prev int32 [N], ids int64 [N] -> (root int32 [N] = the chain's earliest fragment, rank int32 [N] = the position in the
+    chain, new_id int64 [N] = ids[root], status)."""
+    N, dev = prev.numel(), prev.device
+    _stitch_int("stitch_chains", N, ("prev", prev))
+    _hip.need_gpu(ids)
+    _typed("stitch_chains", ("ids", ids, torch.int64))
+    if tuple(ids.shape) != (N,) or N > STITCH_MAX_TRACKLETS:
+        raise RuntimeError("stitch_chains: ids is int64 [N], N <= %d" % STITCH_MAX_TRACKLETS)
+    status = stitch_status(dev, status)
+    ws = torch.empty(4 * max(N, 1), dtype=torch.int32, device=dev)
+    root = torch.empty(N, dtype=torch.int32, device=dev)
+    rank = torch.empty(N, dtype=torch.int32, device=dev)
+    new_id = torch.empty(N, dtype=torch.int64, device=dev)
+    _hip.call("rn_stitch_chains", prev, ids, N, ws, root, rank, new_id, status, device=dev)
+    return root, rank, new_id, status
+
+
+def _fill_rate(fill_rate):
+    fill_rate = float(fill_rate)
+    if not 0 < fill_rate < float("inf"):
+        raise ValueError("fill_rate must be a positive finite number, got %r" % fill_rate)
+    return fill_rate
+
+
+def stitch_fill_count(ep, nxt, fill_rate, status=None):
+    """-> (count int32 [N] = the new rows of the link that starts at tracklet a's tail, prefix int64 [N+1], status)."""
+    N, dev = _stitch_ep("stitch_fill_count", ep)
+    _stitch_int("stitch_fill_count", N, ("next", nxt))
+    fill_rate = _fill_rate(fill_rate)
+    status = stitch_status(dev, status)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    prefix = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    _hip.call("rn_stitch_fill_count", ep, nxt, N, fill_rate, count, prefix, status, device=dev)
+    return count, prefix, status
+
+
+def stitch_fill_rows(ep, nxt, prefix, fill_rate, rows, status=None):
+    """rows = the size of the output (at least prefix[N]; the host's upper bound) -> (fields fp64 [rows,6] in datareader.FIELDS
+    order, time fp64 [rows], link int32 [rows] = the tail's tracklet, side uint8 [rows], status); only rows below prefix[N] are
+    written."""
+    N, dev = _stitch_ep("stitch_fill_rows", ep)
+    _stitch_int("stitch_fill_rows", N, ("next", nxt))
+    _hip.need_gpu(prefix)
+    _typed("stitch_fill_rows", ("prefix", prefix, torch.int64))
+    fill_rate, rows = _fill_rate(fill_rate), int(rows)
+    if tuple(prefix.shape) != (N + 1,) or rows < 0:
+        raise RuntimeError("stitch_fill_rows: prefix int64 [N+1], rows >= 0")
+    status = stitch_status(dev, status)
+    fields = torch.empty((rows, 6), dtype=torch.float64, device=dev)
+    time = torch.empty(rows, dtype=torch.float64, device=dev)
+    link = torch.empty(rows, dtype=torch.int32, device=dev)
+    side = torch.empty(rows, dtype=torch.uint8, device=dev)
+    _hip.call("rn_stitch_fill_rows", ep, nxt, prefix, N, rows, fill_rate, fields, time, link, side, status, device=dev)
+    return fields, time, link, side, status
+
+
 # ------------------------------------------------------------------------------------------------ time stamp bias
 TS_MAX_CAMS = 1024                # RN_TS_MAX_CAMS
 TS_OK, TS_OVERFLOW, TS_BAD_CAMERA = 0, 1, 2

@@ -62,6 +62,10 @@ Operator                                         reference code it stands for
   spline_fit / spline_select / spline_eval       ... its UnivariateSpline fits (FITPACK     seems_to_be_working.py:1233-1294
                                                  curfit), scores and winner; splev
   label_ts_shift(splines, entries, shifts, ..)   Annotator.adjust_ts_with_trajectories seems_to_be_working.py:1416-1442
+  stitch_endpoints / stitch_costs /              joining the fragments of one vehicle  beyond the reference (csrc/stitch.hip,
+  stitch_candidates / stitch_compact /           (link costs, assignment, chains, gap  track_stitch.py)
+  stitch_assign / stitch_chains /                fill)
+  stitch_fill_count / stitch_fill_rows
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -903,3 +907,96 @@ def label_ts_shift(st: torch.Tensor, sc: torch.Tensor, snk: torch.Tensor, off: t
 def _(st, sc, snk, off, rs, rx, base, run, shifts, use_run, metric):
     E, e = base.shape[0], base.new_empty
     return (e((E,), dtype=torch.float64), e((E, 2), dtype=torch.float64), e((E,), dtype=torch.int32), e((1,), dtype=torch.int32))
+
+
+# ---- track stitching (csrc/stitch.hip, beyond the reference: track_stitch.py): the status word comes last where an op has one;
+# scales = the seven floats of ops.STITCH_SCALES
+OPERATORS += ("stitch_endpoints", "stitch_costs", "stitch_candidates", "stitch_compact", "stitch_assign", "stitch_chains",
+              "stitch_fill_count", "stitch_fill_rows")
+
+
+@_lib.custom_op(NS + "::stitch_endpoints", mutates_args=(), device_types="cuda")
+def stitch_endpoints(offsets: torch.Tensor, cols: torch.Tensor, direction: torch.Tensor, fit_n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.stitch_endpoints(offsets, cols, direction, fit_n)
+
+
+@stitch_endpoints.register_fake
+def _(offsets, cols, direction, fit_n):
+    return cols.new_empty((offsets.shape[0] - 1, 2, ops.STITCH_EP), dtype=torch.float64), cols.new_empty((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::stitch_costs", mutates_args=(), device_types="cuda")
+def stitch_costs(ep: torch.Tensor, scales: List[float]) -> torch.Tensor:
+    return ops.stitch_costs(ep, scales)
+
+
+@stitch_costs.register_fake
+def _(ep, scales):
+    return ep.new_empty((ep.shape[0], ep.shape[0]), dtype=torch.float64)
+
+
+@_lib.custom_op(NS + "::stitch_candidates", mutates_args=(), device_types="cuda")
+def stitch_candidates(ep: torch.Tensor, scales: List[float]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.stitch_candidates(ep, scales)
+
+
+@stitch_candidates.register_fake
+def _(ep, scales):
+    return ep.new_empty((2, 2, ep.shape[0]), dtype=torch.int32), ep.new_empty((4,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::stitch_compact", mutates_args=(), device_types="cuda")
+def stitch_compact(ep: torch.Tensor, scales: List[float], cand: torch.Tensor, ncand: torch.Tensor, cap: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.stitch_compact(ep, scales, cand, ncand, cap)
+
+
+@stitch_compact.register_fake
+def _(ep, scales, cand, ncand, cap):
+    return ep.new_empty((cap,), dtype=torch.float64), ep.new_empty((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::stitch_assign", mutates_args=(), device_types="cuda")
+def stitch_assign(ep: torch.Tensor, scales: List[float], cand: torch.Tensor, ncand: torch.Tensor,
+                  Wc: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.stitch_assign(ep, scales, cand, ncand, Wc)
+
+
+@stitch_assign.register_fake
+def _(ep, scales, cand, ncand, Wc):
+    N, e = ep.shape[0], ep.new_empty
+    return e((N,), dtype=torch.int32), e((N,), dtype=torch.int32), e((N,), dtype=torch.float64), e((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::stitch_chains", mutates_args=(), device_types="cuda")
+def stitch_chains(prev: torch.Tensor, ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.stitch_chains(prev, ids)
+
+
+@stitch_chains.register_fake
+def _(prev, ids):
+    N, e = prev.shape[0], prev.new_empty
+    return e((N,), dtype=torch.int32), e((N,), dtype=torch.int32), e((N,), dtype=torch.int64), e((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::stitch_fill_count", mutates_args=(), device_types="cuda")
+def stitch_fill_count(ep: torch.Tensor, nxt: torch.Tensor, fill_rate: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.stitch_fill_count(ep, nxt, fill_rate)
+
+
+@stitch_fill_count.register_fake
+def _(ep, nxt, fill_rate):
+    N, e = ep.shape[0], ep.new_empty
+    return e((N,), dtype=torch.int32), e((N + 1,), dtype=torch.int64), e((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::stitch_fill_rows", mutates_args=(), device_types="cuda")
+def stitch_fill_rows(ep: torch.Tensor, nxt: torch.Tensor, prefix: torch.Tensor, fill_rate: float,
+                     rows: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.stitch_fill_rows(ep, nxt, prefix, fill_rate, rows)
+
+
+@stitch_fill_rows.register_fake
+def _(ep, nxt, prefix, fill_rate, rows):
+    e = ep.new_empty
+    return (e((rows, 6), dtype=torch.float64), e((rows,), dtype=torch.float64), e((rows,), dtype=torch.int32), e((rows,), dtype=torch.uint8),
+            e((1,), dtype=torch.int32))

@@ -1534,6 +1534,71 @@ int rn_label_series(const int64_t *offsets, const double *cols, int64_t R, int n
 int rn_label_group_rmse(const double *im, const int32_t *group, int64_t n, int64_t n_groups, double *rmse, double *mean,
                         int32_t *count, int32_t *status, void *stream);
 
+/* ---- track stitching (csrc/stitch.hip): joining the fragments of one vehicle (track_stitch.py) -----------------------------------
+ * Beyond the reference.  A tracklet is all rows of one id in time order; the host packs offsets int64 [N+1], cols fp64 [R,7] = (t, x,
+ * y, l, w, h, v), direction int32 [R], N <= RN_STITCH_MAX_TRACKLETS.  fp64 with one rounding per operation, every expression in
+ * the order tests/stitch_cases.py writes it.  All entry points that take one share a status word (int32, zeroed by the caller, bits
+ * OR-ed in): a bad index is never used, its item is left out.  The seven scales of a cost follow N in this order: max_gap (s),
+ * back_tol, sigma_x0, sigma_x1 (per second of gap), sigma_y, sigma_size (feet), max_cost.
+ *   rn_stitch_endpoints    ep fp64 [N,2,RN_STITCH_EP]: end 0 = the head (first rows), end 1 = the tail.  Over the k = min(n, fit_n)
+ *                          rows nearest the end, sums sequential in ascending row order: mt, mx, Stt = sum (t - mt)^2, Stx = sum
+ *                          (t - mt)(x - mx); vx = Stx / Stt, or sgn * v of the end row when k < 2 or Stt <= 0; sgn = +1 when the
+ *                          sum of the tracklet's directions is >= 0, else -1.  Fields: 0 t of the end row, 1 x^ = mx + vx (t - mt),
+ *                          2 vx, 3..6 the means of y, l, w, h, 7..11 the end row's x, y, l, w, h, 12 sgn, 13 k, 14..15 zero.
+ *                          1 <= fit_n <= RN_STITCH_MAX_FIT.  A NaN or infinity anywhere in cols: RN_STITCH_NONFINITE.
+ *   rn_stitch_costs        W fp64 [N,N], W[a,b] for a's tail -> b's head with gap = t_s[b] - t_e[a]: linkable when a != b, sgn
+ *                          equal, 0 < gap <= max_gap, sgn (x^_s[b] - x^_e[a]) >= -back_tol and cost < max_cost, where cost =
+ *                          ((|x^_e + vx_e gap - x^_s| + |x^_s - vx_s gap - x^_e|) / 2) / (sigma_x0 + sigma_x1 gap) + |y_e - y_s| /
+ *                          sigma_y + (|dl| + |dw| + |dh|) / sigma_size.  W = cost - max_cost when linkable, else 0.
+ *   rn_stitch_candidates   the same pairs without the matrix: has uint8 [2,N] (workspace: row_has, col_has), then cand int32
+ *                          [2,2,N] = per direction (sgn = +1 first) the tails and the heads that have a candidate, ascending, -1
+ *                          behind; ncand int32 [4] = (nr'+, nc'+, nr'-, nc'-).
+ *   rn_stitch_compact      Wc fp64: direction + at 0 as [nr'+, nc'+], direction - behind it as [nr'-, nc'-]; cap = the doubles Wc
+ *                          holds.  The cells are those of W, bit for bit.
+ *   rn_stitch_assign       scipy.optimize.linear_sum_assignment(Wc) per direction on one wave64 (lsap_dev.h; it transposes when
+ *                          nr' > nc'); a link is an assigned cell with W < 0.  next / prev int32 [N] (-1: none), link_cost fp64 [N]
+ *                          at the tail's index.  min(nr', nc') > RN_LSAP_MAX_MIN: RN_STITCH_TOO_MANY, no links for that direction.
+ *   rn_stitch_chains       root int32 [N] = the chain's earliest fragment, rank int32 [N] = the position in the chain, new_id int64
+ *                          [N] = ids[root]; pointer jumping in one launch, workspace int32 [4 N].
+ *   rn_stitch_fill_count   count int32 [N] at the tail's index = how many k >= 1 have t_e + k (1.0 / fill_rate) < t_s (at most
+ *                          RN_STITCH_MAX_FILL, else RN_STITCH_FILL_OVERFLOW and 0); prefix int64 [N+1] its exclusive prefix.
+ *   rn_stitch_fill_rows    one thread per new row of the U the arrays hold (prefix[N] <= U): t_k, u = (t_k - t_e) / g, g = t_s -
+ *                          t_e; fields fp64 [U,6] = (x, y, l, w, h, v): x the cubic Hermite through the end rows' x with the fitted
+ *                          slopes, v = |dx/dt|, the others (1 - u) A + u B of the end rows; time fp64 [U]; link int32 [U] = the tail's
+ *                          tracklet; side uint8 [U] = 0 when u <= 0.5, else 1. */
+#define RN_STITCH_EP 16
+#define RN_STITCH_MAX_TRACKLETS 32768
+#define RN_STITCH_MAX_FIT 64
+#define RN_STITCH_MAX_FILL 1048576
+#define RN_STITCH_NONFINITE 1         /* a NaN or an infinity in cols */
+#define RN_STITCH_BAD_OFFSETS 2       /* tracklet offsets not monotone, an empty tracklet, or rows outside R */
+#define RN_STITCH_TOO_MANY 4          /* min(nr', nc') of a direction above RN_LSAP_MAX_MIN */
+#define RN_STITCH_SOLVER 8            /* the solver found no complete assignment (not reachable with finite cells) */
+#define RN_STITCH_BAD_CANDIDATES 16   /* candidate counts or entries outside the tracklets or outside cap */
+#define RN_STITCH_BAD_LINK 32         /* a next / prev entry outside the tracklets, or pointing at itself */
+#define RN_STITCH_BAD_PREFIX 64       /* a new row outside its prefix slot or outside the U rows */
+#define RN_STITCH_FILL_OVERFLOW 128   /* a link with RN_STITCH_MAX_FILL new rows or more */
+int rn_stitch_endpoints(const int64_t *offsets, const double *cols, const int32_t *direction, int64_t N, int64_t R, int fit_n,
+                        double *ep, int32_t *status, void *stream);
+int rn_stitch_costs(const double *ep, int64_t N, double max_gap, double back_tol, double sigma_x0, double sigma_x1, double sigma_y,
+                    double sigma_size, double max_cost, double *W, void *stream);
+int rn_stitch_candidates(const double *ep, int64_t N, double max_gap, double back_tol, double sigma_x0, double sigma_x1,
+                         double sigma_y, double sigma_size, double max_cost, uint8_t *has, int32_t *cand, int32_t *ncand,
+                         void *stream);
+int rn_stitch_compact(const double *ep, int64_t N, double max_gap, double back_tol, double sigma_x0, double sigma_x1, double sigma_y,
+                      double sigma_size, double max_cost, const int32_t *cand, const int32_t *ncand, int64_t cap, double *Wc,
+                      int32_t *status, void *stream);
+int64_t rn_stitch_assign_workspace_bytes(int64_t N);
+int rn_stitch_assign(const double *ep, int64_t N, double max_gap, double back_tol, double sigma_x0, double sigma_x1, double sigma_y,
+                     double sigma_size, double max_cost, const int32_t *cand, const int32_t *ncand, const double *Wc, int64_t cap,
+                     void *workspace, int32_t *next, int32_t *prev, double *link_cost, int32_t *status, void *stream);
+int rn_stitch_chains(const int32_t *prev, const int64_t *ids, int64_t N, int32_t *workspace, int32_t *root, int32_t *rank,
+                     int64_t *new_id, int32_t *status, void *stream);
+int rn_stitch_fill_count(const double *ep, const int32_t *next, int64_t N, double fill_rate, int32_t *count, int64_t *prefix,
+                         int32_t *status, void *stream);
+int rn_stitch_fill_rows(const double *ep, const int32_t *next, const int64_t *prefix, int64_t N, int64_t U, double fill_rate,
+                        double *fields, double *time, int32_t *link, uint8_t *side, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -516,6 +516,15 @@ def gen_label_assist():
                           stdout=subprocess.DEVNULL)
 
 
+def gen_track_stitch():
+    """tests/golden/track_stitch.npz: the reference's shipped 3D_tracking_results.csv packed by tracklet, and the restatement of
+    tests/stitch_cases.py on it.  Its own script (tools/make_golden_track_stitch.py), in a child process: it imports this
+    repository's datareader under the name the reference's module takes above."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.join(REPO, "tools", "make_golden_track_stitch.py"), "--out", OUT],
+                          stdout=subprocess.DEVNULL)
+
+
 def gen_replay():
     """tests/golden/replay.npz: the reference's own Data_Reader.plot_in over scripted cameras behind a recording cv2 stand-in.
     Its own script (tools/make_golden_replay.py), in a child process, for the reason gen_datareader gives."""
@@ -1699,7 +1708,7 @@ def main():
     m_dir, l_dir, u_dir, a_dir = import_variant("dir")
     dir_mods = (m_dir, l_dir, u_dir, a_dir)
     m_2d, l_2d, u_2d, a_2d = import_variant("2d")
-    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit", "label_rewrite", "label_trajectory", "label_quality", "label_assist"}
+    which = set(argv) or {"anchors", "losses", "boxes", "model", "model_deep", "homography", "csv", "csv_rows", "tracker_post", "crop_refine", "kf", "tracker_assoc", "ts_bias", "fit_filter", "csv_eval", "augment", "augment_crop", "mot_eval", "calibration", "frames4k", "datareader", "replay", "tracker_run", "label_audit", "label_rewrite", "label_trajectory", "label_quality", "label_assist", "track_stitch"}
     if "anchors" in which:
         gen_anchors(a_dir)
     if "losses" in which:
@@ -1758,6 +1767,8 @@ def main():
         gen_label_quality()
     if "label_assist" in which:
         gen_label_assist()
+    if "track_stitch" in which:
+        gen_track_stitch()
     for fn in sorted(os.listdir(OUT)):
         print("%-20s %8.1f KiB" % (fn, os.path.getsize(os.path.join(OUT, fn)) / 1024))
     del dir_mods
