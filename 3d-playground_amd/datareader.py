@@ -15,7 +15,8 @@ The rows of the file come from ``results_csv.results_rows``, the formatter of th
 path.
 
 Beyond the reference: ``stitch(params, fill, save)`` joins the fragments a vehicle leaves behind when the tracker loses it and
-fills the gaps (track_stitch.py, csrc/stitch.hip).
+fills the gaps (track_stitch.py, csrc/stitch.hip); ``smooth(kf_params, params, save)`` replaces every row's fields by the means of
+a fixed-interval smoother over its track (track_smooth.py, csrc/smooth.hip).
 
 Differences a caller can see: ``reinterpolate`` writes to ``save`` (the reference ignores the argument and
 always writes its default name, :450-451; the default value is that name, so a call without arguments behaves the same);
@@ -489,6 +490,18 @@ class Data_Reader():
         ``save`` unless it is None -> the report.  On an error nothing is replaced."""
         import track_stitch
         new_data, report = track_stitch.stitch_tracks(self.data, params, fill, self._device())
+        self.data = new_data
+        self.d_idx = 0
+        if save is not None:
+            self.write_to_file(save_file=save)
+        return report
+
+    def smooth(self, kf_params, params=None, save=None):
+        """Beyond the reference: replaces x, y, l, w, h, v of every row by the means of a fixed-interval smoother over its track
+        (track_smooth.smooth_tracks; ``kf_params`` as fit_filter.fit returns it, ``params`` overrides track_smooth.DEFAULTS).
+        Replaces ``data``, resets ``d_idx``, writes ``save`` unless it is None -> the report.  On an error nothing is replaced."""
+        import track_smooth
+        new_data, report = track_smooth.smooth_tracks(self.data, kf_params, params, self._device())
         self.data = new_data
         self.d_idx = 0
         if save is not None:

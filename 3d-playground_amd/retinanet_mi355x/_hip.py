@@ -148,6 +148,8 @@ SIGNATURES = {
     "rn_stitch_chains": (c_i32, [c_vp, c_vp, c_i64] + [c_vp] * 6),
     "rn_stitch_fill_count": (c_i32, [c_vp, c_vp, c_i64, c_f64] + [c_vp] * 4),
     "rn_stitch_fill_rows": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_f64] + [c_vp] * 6),
+    "rn_smooth_filter": (c_i32, [c_vp] * 5 + [c_f64, c_f64, c_i64, c_i64] + [c_vp] * 5),
+    "rn_smooth_rts": (c_i32, [c_vp] * 5 + [c_f64, c_i64, c_i64] + [c_vp] * 4),
 }
 
 class ConvDesc(ctypes.Structure):

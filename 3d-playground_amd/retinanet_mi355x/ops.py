@@ -1212,6 +1212,105 @@ def stitch_fill_rows(ep, nxt, prefix, fill_rate, rows, status=None):
     return fields, time, link, side, status
 
 
+# ------------------------------------------------------------------------------------------------ fixed-interval smoothing
+SMOOTH_MODEL = 97                  # RN_SMOOTH_MODEL: q_scale Q [6,6], r_scale R [5,5], P0 [6,6]
+SMOOTH_FILT = 27                   # 6 filtered means + the 21 covariance entries a <= b
+SMOOTH_OUT = 12                    # 6 smoothed means + 6 smoothed variances
+SMOOTH_MAX_TRACKLETS = 1048576
+SMOOTH_NONFINITE, SMOOTH_BAD_OFFSETS, SMOOTH_BAD_DT, SMOOTH_PIVOT, SMOOTH_BAD_ORDER = 1, 2, 4, 8, 16
+_SMOOTH_BITS = ((SMOOTH_NONFINITE, "a NaN or an infinity among the packed fields"),
+                (SMOOTH_BAD_OFFSETS, "tracklet offsets out of order, an empty tracklet or rows outside the packed ones"),
+                (SMOOTH_BAD_DT, "a repeated or decreasing time stamp inside a tracklet"),
+                (SMOOTH_PIVOT, "a covariance that is not positive definite (a pivot <= 0)"),
+                (SMOOTH_BAD_ORDER, "an order entry outside the tracklets"))
+
+
+def smooth_status(device, status=None):
+    """The status word the smoothing entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
+    return _status_word("smooth", device, status)
+
+
+def smooth_check(status):
+    """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
+    _refused("the smoothing kernels refused their input: ", _SMOOTH_BITS, status)
+
+
+def smooth_model(kf_params, q_scale=1.0, r_scale=1.0):
+    """The packed model block of the smoother, a host fp64 array [SMOOTH_MODEL] = q_scale Q [6,6], r_scale R [5,5], P0 = P [6,6],
+    row-major.  ``kf_params`` is what ``Torch_KF(INIT=...)`` takes (fit_filter.fit): its float32 ``Q``, ``R`` and ``P`` are widened
+    exactly; ``H`` is not read (the measurement is the row's x, y, l, w, h: H = [I5 | 0]), nor are ``mu_Q`` / ``mu_R``.  ValueError
+    on a wrong shape, a non-finite entry, a non-positive scale or an asymmetric matrix."""
+    scales = []
+    for name, v in (("q_scale", q_scale), ("r_scale", r_scale)):
+        v = float(v)
+        if not 0 < v < float("inf"):
+            raise ValueError("%s must be a positive finite number, got %r" % (name, v))
+        scales.append(v)
+    mats = []
+    for name, n in (("Q", 6), ("R", 5), ("P", 6)):
+        if name not in kf_params:
+            raise ValueError("kf_params holds no %r" % name)
+        m = kf_params[name]
+        m = m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+        if m.shape != (n, n):
+            raise ValueError("kf_params[%r] is [%d,%d], got %s" % (name, n, n, tuple(m.shape)))
+        m = m.astype(np.float64)
+        if not np.isfinite(m).all():
+            raise ValueError("kf_params[%r] holds a NaN or an infinity" % name)
+        if not np.array_equal(m, m.T):
+            raise ValueError("kf_params[%r] is not symmetric" % name)
+        mats.append(m)
+    return np.concatenate(((scales[0] * mats[0]).reshape(-1), (scales[1] * mats[1]).reshape(-1), mats[2].reshape(-1)))
+
+
+def _smooth_inputs(what, offsets, order, cols, direction, model, dt_default):
+    _hip.need_gpu(offsets, order, cols, direction, model)
+    _typed(what, ("offsets", offsets, torch.int64), ("order", order, torch.int32), ("cols", cols, torch.float64),
+           ("direction", direction, torch.int32), ("model", model, torch.float64))
+    R = direction.numel()
+    if offsets.dim() != 1 or offsets.numel() < 1 or cols.dim() != 2 or tuple(cols.shape) != (R, 7) or direction.dim() != 1 \
+            or R >= 2 ** 31 or tuple(order.shape) != (offsets.numel() - 1,) or tuple(model.shape) != (SMOOTH_MODEL,):
+        raise RuntimeError("%s: offsets int64 [N+1], order int32 [N], cols fp64 [R,7], direction int32 [R], model fp64 [%d], fewer "
+                           "than 2^31 rows" % (what, SMOOTH_MODEL))
+    N = offsets.numel() - 1
+    if N > SMOOTH_MAX_TRACKLETS:
+        raise RuntimeError("%s: at most %d tracklets, got %d" % (what, SMOOTH_MAX_TRACKLETS, N))
+    dt_default = float(dt_default)
+    if not 0 < dt_default < float("inf"):
+        raise ValueError("dt_default must be a positive finite number, got %r" % dt_default)
+    return N, R, cols.device, dt_default
+
+
+def smooth_filter(offsets, order, cols, direction, model, gate, dt_default, status=None):
+    """The forward pass.  offsets int64 [N+1], order int32 [N] (lane i works on tracklet order[i]; track_smooth.lane_order gives the
+    stable argsort of descending length, any permutation gives the same bytes), cols fp64 [R,7]
+    = (t, x, y, l, w, h, v), direction int32 [R], model fp64 [SMOOTH_MODEL] (``smooth_model``, uploaded), gate >= 0 (0: no gating)
+    -> (filt fp64 [R,SMOOTH_FILT], nis fp64 [R], flag uint8 [R], status)."""
+    N, R, dev, dt_default = _smooth_inputs("smooth_filter", offsets, order, cols, direction, model, dt_default)
+    gate = float(gate)
+    if not 0 <= gate < float("inf"):
+        raise ValueError("gate is 0 (off) or a positive finite number, got %r" % gate)
+    status = smooth_status(dev, status)
+    filt = torch.zeros((R, SMOOTH_FILT), dtype=torch.float64, device=dev)
+    nis = torch.zeros(R, dtype=torch.float64, device=dev)
+    flag = torch.zeros(R, dtype=torch.uint8, device=dev)
+    _hip.call("rn_smooth_filter", offsets, order, cols, direction, model, gate, dt_default, N, R, filt, nis, flag, status, device=dev)
+    return filt, nis, flag, status
+
+
+def smooth_rts(offsets, order, cols, direction, model, dt_default, filt, status=None):
+    """The backward pass over ``smooth_filter``'s filt -> (out fp64 [R,SMOOTH_OUT] = the 6 smoothed means and variances, status)."""
+    N, R, dev, dt_default = _smooth_inputs("smooth_rts", offsets, order, cols, direction, model, dt_default)
+    _hip.need_gpu(filt)
+    _typed("smooth_rts", ("filt", filt, torch.float64))
+    if tuple(filt.shape) != (R, SMOOTH_FILT):
+        raise RuntimeError("smooth_rts: filt is fp64 [R = %d, %d], got %s" % (R, SMOOTH_FILT, tuple(filt.shape)))
+    status = smooth_status(dev, status)
+    out = torch.zeros((R, SMOOTH_OUT), dtype=torch.float64, device=dev)
+    _hip.call("rn_smooth_rts", offsets, order, cols, direction, model, dt_default, N, R, filt, out, status, device=dev)
+    return out, status
+
+
 # ------------------------------------------------------------------------------------------------ time stamp bias
 TS_MAX_CAMS = 1024                # RN_TS_MAX_CAMS
 TS_OK, TS_OVERFLOW, TS_BAD_CAMERA = 0, 1, 2

@@ -66,6 +66,8 @@ Operator                                         reference code it stands for
   stitch_candidates / stitch_compact /           (link costs, assignment, chains, gap  track_stitch.py)
   stitch_assign / stitch_chains /                fill)
   stitch_fill_count / stitch_fill_rows
+  smooth_filter / smooth_rts                     fixed-interval (RTS) smoothing of     beyond the reference (csrc/smooth.hip,
+                                                 every tracklet                        track_smooth.py)
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -1000,3 +1002,31 @@ def _(ep, nxt, prefix, fill_rate, rows):
     e = ep.new_empty
     return (e((rows, 6), dtype=torch.float64), e((rows,), dtype=torch.float64), e((rows,), dtype=torch.int32), e((rows,), dtype=torch.uint8),
             e((1,), dtype=torch.int32))
+
+
+# ---- fixed-interval smoothing (csrc/smooth.hip, beyond the reference: track_smooth.py): the status word comes last
+OPERATORS += ("smooth_filter", "smooth_rts")
+
+
+@_lib.custom_op(NS + "::smooth_filter", mutates_args=(), device_types="cuda")
+def smooth_filter(offsets: torch.Tensor, order: torch.Tensor, cols: torch.Tensor, direction: torch.Tensor, model: torch.Tensor,
+                  gate: float, dt_default: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.smooth_filter(offsets, order, cols, direction, model, gate, dt_default)
+
+
+@smooth_filter.register_fake
+def _(offsets, order, cols, direction, model, gate, dt_default):
+    R, e = cols.shape[0], cols.new_empty
+    return (e((R, ops.SMOOTH_FILT), dtype=torch.float64), e((R,), dtype=torch.float64), e((R,), dtype=torch.uint8),
+            e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::smooth_rts", mutates_args=(), device_types="cuda")
+def smooth_rts(offsets: torch.Tensor, order: torch.Tensor, cols: torch.Tensor, direction: torch.Tensor, model: torch.Tensor,
+               dt_default: float, filt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.smooth_rts(offsets, order, cols, direction, model, dt_default, filt)
+
+
+@smooth_rts.register_fake
+def _(offsets, order, cols, direction, model, dt_default, filt):
+    return cols.new_empty((cols.shape[0], ops.SMOOTH_OUT), dtype=torch.float64), cols.new_empty((1,), dtype=torch.int32)

@@ -1599,6 +1599,39 @@ int rn_stitch_fill_count(const double *ep, const int32_t *next, int64_t N, doubl
 int rn_stitch_fill_rows(const double *ep, const int32_t *next, const int64_t *prefix, int64_t N, int64_t U, double fill_rate,
                         double *fields, double *time, int32_t *link, uint8_t *side, int32_t *status, void *stream);
 
+/* ---- fixed-interval smoothing (csrc/smooth.hip): a Rauch-Tung-Striebel pass over every tracklet (track_smooth.py) ---------------
+ * Beyond the reference.  Tracklets as for stitching: offsets int64 [N+1], cols fp64 [R,7] = (t, x, y, l, w, h, v), direction int32
+ * [R], N <= RN_SMOOTH_MAX_TRACKLETS, R < 2^31.  order int32 [N]: lane i of the grid works on tracklet order[i] (the host passes the
+ * stable argsort of descending length; any permutation gives the same bytes).  model fp64 [RN_SMOOTH_MODEL] = q_scale Q [6,6],
+ * r_scale R [5,5], P0 [6,6], row-major, each symmetric.  State (x, y, l, w, h, v), measurement (x, y, l, w, h) of the row: H = [I5 | 0]
+ * is fixed.  d = +1 when the sum of the tracklet's directions is >= 0, else -1; F = I with F[0][5] = f = d dt, dt = t_k - t_(k-1); Qk =
+ * ((q_scale Q[a][b]) dt) / dt_default.  fp64 with one rounding per operation, every expression in the order tests/smooth_cases.py
+ * writes it; a covariance is its 21 entries a <= b, row-major.
+ *   rn_smooth_filter   row 0: s = the row's (x, y, l, w, h, v), P = P0.  Row k >= 1: s[0] += f s[5]; P- = F P F^T + Qk in the sparse
+ *                      form (row 0 of F P, then column 0); y = z - s-[:5], S = P-[:5,:5] + R = L D L^T (Cholesky-Crout, no square
+ *                      roots); nis = y^T S^-1 y; gate > 0 and nis > gate: flag = 1 and s = s-, P = P- (the row counts as missing);
+ *                      else K = P-[:,:5] S^-1, s = s- + K y, P = (I - K H) P- (I - K H)^T + K R K^T.  filt fp64 [R,RN_SMOOTH_FILT] = 6
+ *                      means + the 21 entries, nis fp64 [R] (0 at a first row), flag uint8 [R].  gate = 0: no gating.
+ *   rn_smooth_rts      k = n-2 .. 0 from filt: P-(k+1) recomputed as above, C = P_k F^T (P-(k+1))^-1 by a 6x6 L D L^T, s^s_k = s_k + C
+ *                      (s^s_(k+1) - F s_k), P^s_k = P_k + C (P^s_(k+1) - P-(k+1)) C^T; row n-1 keeps its filtered values.  out fp64
+ *                      [R,RN_SMOOTH_OUT] = the 6 smoothed means and the 6 smoothed variances.
+ * Both OR bits into the status word (int32, zeroed by the caller); the lane of a refused tracklet ends there and what its rows
+ * hold is unspecified. */
+#define RN_SMOOTH_MODEL 97
+#define RN_SMOOTH_FILT 27
+#define RN_SMOOTH_OUT 12
+#define RN_SMOOTH_MAX_TRACKLETS 1048576
+#define RN_SMOOTH_NONFINITE 1         /* a NaN or an infinity in a row's fields */
+#define RN_SMOOTH_BAD_OFFSETS 2       /* tracklet offsets out of order, an empty tracklet, or rows outside R */
+#define RN_SMOOTH_BAD_DT 4            /* a time step <= 0 inside a tracklet */
+#define RN_SMOOTH_PIVOT 8             /* a pivot of S or of P- that is not a positive finite number */
+#define RN_SMOOTH_BAD_ORDER 16        /* an order entry outside the tracklets */
+int rn_smooth_filter(const int64_t *offsets, const int32_t *order, const double *cols, const int32_t *direction, const double *model,
+                     double gate, double dt_default, int64_t N, int64_t R, double *filt, double *nis, uint8_t *flag, int32_t *status,
+                     void *stream);
+int rn_smooth_rts(const int64_t *offsets, const int32_t *order, const double *cols, const int32_t *direction, const double *model,
+                  double dt_default, int64_t N, int64_t R, const double *filt, double *out, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
