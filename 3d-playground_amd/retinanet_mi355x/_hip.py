@@ -239,6 +239,7 @@ SIGNATURES.update({
     "rn_conv_wgrad_batched_flags": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32] + [c_i32] * 12 + [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "rn_conv_wgrad_det_workspace_bytes": (c_i64, [c_i32, c_i32, c_i64] + [c_i32] * 9),
     "rn_conv_wgrad_plan": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_i32] + [c_i32] * 12 + [c_i32, c_i32, c_i32, c_vp]),
+    "rn_conv_bwd_1x1": (c_i32, [c_vp] * 8 + [c_i32] + [c_vp] * 5 + [c_i32] * 6 + [c_vp]),
     "rn_f32_to_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "rn_bf16_to_f32": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "rn_conv_igemm_bf16": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -855,6 +855,54 @@ def wgrad(dy, x, dw, cout, k, stride, pad, kw_pad=None, in_relu=False, flops=0.0
     return dw
 
 
+# ---- data and weight gradient of a 1x1 stride-1 layer in one pass over dy (csrc/conv_bwd_1x1.hip; split3 mode)
+BWD_FUSED_1X1 = os.environ.get("RN_BWD_FUSED_1X1", "1") != "0"   # 0: the engine keeps the pair of launches (A/B)
+# (Cin, Cout) the kernel is built for AND profiles/bwd_fused_1x1.txt shows faster than the data-gradient / weight-gradient pair
+BWD_FUSED_SHAPES = frozenset({(64, 256)})
+BWD_FUSED_LAUNCHES = 0                           # launches so far (tests count the layers that took the path)
+
+
+def bwd_1x1_fused(dy, x, w_dgrad, dw, colsum, mask=None, mask_mode=None, flops=0.0, sign=False):
+    """-> dx = mask * dgrad(dy, w_dgrad) [N,H,W,Cin], and dw [Cout][Cin] += wgrad(dy, x), colsum [Cout] += column sums of dy, by ONE
+    launch of rn_conv_bwd_1x1.  dy [N,H,W,Cout], x [N,H,W,Cin] dense fp32; w_dgrad: the layer's packed data-gradient weights with
+    their fp16 twin (pack_weights(..., 1) in split3 mode).  mask: a tensor of dx's shape whose positive elements pass; mask_mode 1
+    reads it as fp32, 2 reads its sign bits (mask._rn_sign), None: the bits if it carries them.  sign: also write dx's sign bits.
+    flops: of ONE of the two products (the layer's count); timed as conv_bwd_fused with the FLOPs of both, every operand once."""
+    global BWD_FUSED_LAUNCHES
+    lib = _hip.load()
+    N, H, W, cout = dy.shape
+    cin = x.shape[3]
+    tw = getattr(w_dgrad, "_rn_split16", None)
+    if tw is None:
+        raise RuntimeError("bwd_1x1_fused needs the fp16 twin of the data-gradient weights (split3 mode)")
+    if not (dy.is_contiguous() and x.is_contiguous() and dy.dtype == x.dtype == torch.float32 and x.shape[:3] == dy.shape[:3]):
+        raise RuntimeError("bwd_1x1_fused: dy and x must be dense fp32 tensors over the same pixels")
+    mptr, mmode = None, 0
+    if mask is not None:
+        bits = getattr(mask, "_rn_sign", None)
+        if mask_mode is None:
+            mask_mode = 2 if (bits is not None and BITMASKS) else 1
+        if mask_mode == 2 and bits is None:
+            raise RuntimeError("bwd_1x1_fused: mask_mode 2 needs a mask that carries its sign bits")
+        mptr, mmode = (bits if mask_mode == 2 else mask).data_ptr(), mask_mode
+    dy_am, x_am = amax_words(dy), amax_words(x)
+    dx = torch.empty((N, H, W, cin), dtype=torch.float32, device=dy.device)
+    sbits = _sign_words(dx, sign)
+    dx_am = amax_slot(dy.device, N)
+    kind = "conv_bwd_fused" + (" %dx%dx%d %d->%d" % (N, H, W, cin, cout) if prof.BY_SHAPE else "")
+    nb = 0.0
+    if prof.ACTIVE is not None:                      # algorithmic bytes: every operand once
+        nb = 4.0 * (dy.numel() + x.numel() + dx.numel() * (1 + {0: 0.0, 1: 1.0, 2: 1.0 / 32}[mmode] + (1.0 / 32 if sbits is not None else 0.0))
+                    + w_dgrad.numel() + dw.numel() + cout)
+    rc = prof.timed(kind, 2.0 * flops, lambda: lib.rn_conv_bwd_1x1(
+        dy.data_ptr(), x.data_ptr(), tw[0].data_ptr(), tw[1].data_ptr(), dx.data_ptr(), dw.data_ptr(), _hip.ptr(colsum), mptr, mmode,
+        None, _hip.ptr(sbits), dy_am.data_ptr(), x_am.data_ptr(), dx_am.data_ptr(), N, H, W, cin, cout, 1, _hip.stream()), nb)
+    _hip.check(rc, "rn_conv_bwd_1x1")
+    BWD_FUSED_LAUNCHES += 1
+    amax_attach(dx, dx_am)
+    return dx
+
+
 def unpack_wgrad(dw, w_packed, weight_shape, kw_pad=None, c_pad=None, scale=None, mean=None, rstd=None, colsum=None,
                  want_bn=False, out=None):
     """-> (dweight OIHW, dgamma or None, dbeta or None); out = the same triple as destination tensors (contiguous fp32

@@ -438,6 +438,24 @@ class Layer:
             return cv.dgrad_s2_classes(g, self.dgrad_weights(), in_hw, s.cin, s.k, s.pad, **kw)
         return cv.dgrad(g, self.dgrad_weights(), in_hw, s.cin, s.k, s.stride, s.pad, add2=add2, **kw)
 
+    def bwd_fused_ok(self, g, x):
+        """May bwd_fused take this layer's gradients of g and x?  A 1x1 stride-1 fp32 layer of a shape cv.BWD_FUSED_SHAPES lists, split3
+        products with amax words, dense operands, atomic (not fixed-order) accumulation, pre-split data-gradient weights at hand."""
+        s = self.spec
+        return (not self.bf16 and not self.fp8 and s.k == 1 and s.stride == 1 and s.pad == 0 and (s.cin, s.cout) in cv.BWD_FUSED_SHAPES
+                and g.dtype == torch.float32 and x.dtype == torch.float32 and g.is_contiguous() and x.is_contiguous()
+                and g.shape[3] == s.cout and x.shape[3] == s.cin and x.shape[:3] == g.shape[:3]
+                and cv.get_fp32_mfma() == "split3" and cv.want_amax() and not cv.get_option(cv.OPT_DETERMINISTIC)
+                and getattr(self.dgrad_weights(), "_rn_split16", None) is not None)
+
+    def bwd_fused(self, g, x, mask=None):
+        """bwd_params(g, x) and bwd_data(g, mask=mask) by one launch that reads g once (cv.bwd_1x1_fused) -> the data gradient."""
+        s = self.spec
+        if self.dw is None:
+            self.dw = torch.zeros_like(self.wf)
+            self.cs = torch.zeros(s.cout, dtype=torch.float32, device=g.device)
+        return cv.bwd_1x1_fused(g, x, self.dgrad_weights(), self.dw, self.cs, mask=mask, flops=self.flops(g.shape[0], g.shape[1], g.shape[2]))
+
     def bwd_data_compact(self, g):
         """1x1 stride-2 shortcut: gradient on the OUTPUT grid only ([N,Ho,Wo,Cin]); it belongs at the even input
         positions and is added there by the consumer's epilogue (add2), the odd positions get nothing."""
@@ -1186,6 +1204,11 @@ class Engine:
             else:
                 aside(lambda: L.bwd_params_group(gs, xs), tuple(gs) + tuple(xs))
 
+        def fused(L, g, x):
+            """Data and weight gradient of L in one launch that reads g once (Layer.bwd_fused), on the main stream: the data gradient is
+            needed next.  Only where no per-layer hook watches the pair's order; RN_BWD_FUSED_1X1=0 keeps the pair everywhere."""
+            return cv.BWD_FUSED_1X1 and not self.bwd16 and not self.fp8 and self.grad_hook is None and L.bwd_fused_ok(g, x)
+
         def done(layer):
             nonlocal next_bucket
             if batched:
@@ -1321,8 +1344,11 @@ class Engine:
             in_hw = hw(xin)
             last = roles["conv2"] if self.kind == "basic" else roles["conv3"]
             tin = t1 if self.kind == "basic" else t2
-            wg(last, g, tin)
-            gt = last.bwd_data(g, hw(tin), mask=tin)
+            if fused(last, g, tin):
+                gt = last.bwd_fused(g, tin, mask=tin)
+            else:
+                wg(last, g, tin)
+                gt = last.bwd_data(g, hw(tin), mask=tin)
             done(last)
             if self.kind != "basic":
                 wg(roles["conv2"], gt, t1)
@@ -1337,11 +1363,14 @@ class Engine:
                 extra = lateral.get(prev_layer)
             dcompact = None
             if "down" in roles:
-                wg(roles["down"], g, xin)
-                if roles["down"].spec.stride == 2 and roles["conv1"].spec.stride == 1 and not self.bwd16:
+                if extra is None and fused(roles["down"], g, xin):
+                    dres = roles["down"].bwd_fused(g, xin)
+                elif roles["down"].spec.stride == 2 and roles["conv1"].spec.stride == 1 and not self.bwd16:
+                    wg(roles["down"], g, xin)
                     dcompact = roles["down"].bwd_data_compact(g)       # bottleneck: conv1 is 1x1 s1, takes add2
                     dres = extra
                 else:
+                    wg(roles["down"], g, xin)
                     dres = roles["down"].bwd_data(g, in_hw, add=extra)
                 done(roles["down"])
             else:

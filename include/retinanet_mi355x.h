@@ -771,6 +771,20 @@ int rn_conv_wgrad_batched_flags(const float *dy, int ldy, const float *x, float 
 int rn_conv_wgrad_plan(int ldy, int nbatch, int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
                        int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int in_relu, int have_amax,
                        int have_flags, int det, int32_t *out);
+/* Data AND weight gradient of a 1x1 stride-1 pad-0 convolution in one pass over dy (csrc/conv_bwd_1x1.hip; RN_FP32_SPLIT3 only).  Built
+ * for Cin = 64, Cout = 256: dy [N,H,W,256], x [N,H,W,64] and dx [N,H,W,64] dense fp32, 16-byte aligned.
+ *   dx = mask * (dy . w)   with w_split / w_unscale the layer's pre-split data-gradient weights (rn_split_weights_f16 of the packed
+ *        [64][256] tensor: rn_conv_desc.w_format 3); stored once.  mask_mode 0: none (mask NULL); 1: mask = fp32 [N,H,W,64], elements
+ *        > 0 pass (rn_conv_igemm's mask of a ReLU output); 2: mask = the sign bits of such a tensor (RN_MASK_BITS layout).  sign_out,
+ *        if not NULL, receives dx's sign bits; dx_amax, if not NULL, its amax tables (one per image).
+ *   dw [256][64] += dy^T x,  colsum [256] += column sums of dy (NULL: not wanted): fp32 atomics into zeroed accumulators, as
+ *        rn_conv_wgrad_batched -- same layout, so rn_unpack_batched reads them unchanged.
+ * dy_amax / x_amax: the operands' amax tables (one per image, both required).  Both products split the operands with the scale of the
+ * pixel's IMAGE (rn_conv_igemm's rule), so an image's dx does not depend on the rest of the batch.  RN_EINVAL for what is not built:
+ * other channel counts, stride != 1, an addend (add != NULL), another product mode, RN_OPT_DETERMINISTIC (no fixed-order form). */
+int rn_conv_bwd_1x1(const float *dy, const float *x, const void *w_split, const float *w_unscale, float *dx, float *dw, float *colsum,
+                    const void *mask, int mask_mode, const float *add, void *sign_out, const void *dy_amax, const void *x_amax,
+                    void *dx_amax, int N, int H, int W, int Cin, int Cout, int stride, void *stream);
 
 /* ---------------------------------------------------------------- bf16 convolution engine -----------------
  * The reduced-precision form of rn_conv_igemm / rn_conv_wgrad for BASELINE configs[2] (bf16 MFMA,
