@@ -16,7 +16,9 @@ path.
 
 Beyond the reference: ``stitch(params, fill, save)`` joins the fragments a vehicle leaves behind when the tracker loses it and
 fills the gaps (track_stitch.py, csrc/stitch.hip); ``smooth(kf_params, params, save)`` replaces every row's fields by the means of
-a fixed-interval smoother over its track (track_smooth.py, csrc/smooth.hip).
+a fixed-interval smoother over its track (track_smooth.py, csrc/smooth.hip); ``traffic_state(params)`` turns the rows into flow,
+density and speed per lane over a space-time grid and into every row's leader, gap, headway and time to collision
+(traffic_state.py, csrc/traffic.hip).
 
 Differences a caller can see: ``reinterpolate`` writes to ``save`` (the reference ignores the argument and
 always writes its default name, :450-451; the default value is that name, so a call without arguments behaves the same);
@@ -507,6 +509,15 @@ class Data_Reader():
         if save is not None:
             self.write_to_file(save_file=save)
         return report
+
+    def traffic_state(self, params=None):
+        """Beyond the reference: the traffic measures of ``data`` as it is now (traffic_state.py; ``params`` overrides
+        traffic_state.DEFAULTS) -> {"fields": traffic_fields' dict (flow, density and speed per direction and lane over a space-time
+        grid), "following": car_following's dict (leader, gap, headway and time to collision of every row)}.  ``data`` and ``d_idx``
+        are left alone."""
+        import traffic_state
+        return {"fields": traffic_state.traffic_fields(self.data, params, self._device()),
+                "following": traffic_state.car_following(self.data, params, self._device())}
 
     def file_rows(self):
         """The rows ``write_to_file`` writes, from ``data`` as it is now: one ops.track_rows launch, then results_rows."""

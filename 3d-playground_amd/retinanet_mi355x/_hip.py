@@ -150,6 +150,9 @@ SIGNATURES = {
     "rn_stitch_fill_rows": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_f64] + [c_vp] * 6),
     "rn_smooth_filter": (c_i32, [c_vp] * 5 + [c_f64, c_f64, c_i64, c_i64] + [c_vp] * 5),
     "rn_smooth_rts": (c_i32, [c_vp] * 5 + [c_f64, c_i64, c_i64] + [c_vp] * 4),
+    "rn_traffic_lanes": (c_i32, [c_vp] * 4 + [c_i32, c_vp, c_i32, c_i64, c_i64] + [c_vp] * 4),
+    "rn_traffic_cells": (c_i32, [c_vp] * 4 + [c_i32, c_vp, c_i32, c_i64, c_i64, c_f64, c_f64, c_i64, c_f64, c_f64, c_i64, c_f64] + [c_vp] * 6),
+    "rn_traffic_leaders": (c_i32, [c_vp] * 6 + [c_i64] * 4 + [c_vp] * 8),
 }
 
 class ConvDesc(ctypes.Structure):

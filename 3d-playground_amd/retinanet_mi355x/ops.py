@@ -1311,6 +1311,116 @@ def smooth_rts(offsets, order, cols, direction, model, dt_default, filt, status=
     return out, status
 
 
+# ------------------------------------------------------------------------------------------------ traffic state
+TRAFFIC_Q = 1 << 20                # RN_TRAFFIC_Q: the fixed-point unit of T and D is 2^-20 s or ft
+TRAFFIC_COUNTERS = 8
+TRAFFIC_MAX_EDGES = 64
+TRAFFIC_MAX_CUTS = 4096
+TRAFFIC_CELL_COUNTERS = ("segments", "used", "skipped_gap", "skipped_lane", "pieces", "outside")
+TRAFFIC_LEADER_COUNTERS = ("with_leader", "overlaps")
+TRAFFIC_NONFINITE, TRAFFIC_BAD_OFFSETS, TRAFFIC_BAD_FRAME, TRAFFIC_TOO_MANY_CUTS, TRAFFIC_RANGE, TRAFFIC_BAD_DIR = 1, 2, 4, 8, 16, 32
+_TRAFFIC_BITS = ((TRAFFIC_NONFINITE, "a NaN or an infinity among the packed fields"),
+                 (TRAFFIC_BAD_OFFSETS, "tracklet offsets out of order or not covering the packed rows"),
+                 (TRAFFIC_BAD_FRAME, "frame offsets out of order or a frame row outside the packed rows"),
+                 (TRAFFIC_TOO_MANY_CUTS, "a segment that crosses more than %d grid lines" % TRAFFIC_MAX_CUTS),
+                 (TRAFFIC_RANGE, "a segment of 2^20 s or ft or more"),
+                 (TRAFFIC_BAD_DIR, "a tracklet direction that is neither +1 nor -1"))
+
+
+def traffic_status(device, status=None):
+    """The status word the traffic entry points OR their bits into: a zeroed int32 [1] unless one is handed on."""
+    return _status_word("traffic", device, status)
+
+
+def traffic_check(status):
+    """Raises on a non-zero status word (an int, or the int32 [1] tensor: one element is read back)."""
+    _refused("the traffic kernels refused their input: ", _TRAFFIC_BITS, status)
+
+
+def _traffic_inputs(what, offsets, cols, edges_pos, edges_neg):
+    _hip.need_gpu(offsets, cols, edges_pos, edges_neg)
+    _typed(what, ("offsets", offsets, torch.int64), ("cols", cols, torch.float64), ("edges_pos", edges_pos, torch.float64),
+           ("edges_neg", edges_neg, torch.float64))
+    if offsets.dim() != 1 or offsets.numel() < 1 or cols.dim() != 2 or cols.shape[1] != 7 or cols.shape[0] >= 2 ** 31 \
+            or edges_pos.dim() != 1 or edges_neg.dim() != 1 or max(edges_pos.numel(), edges_neg.numel()) > TRAFFIC_MAX_EDGES:
+        raise RuntimeError("%s: offsets int64 [N+1], cols fp64 [R,7], fewer than 2^31 rows, edges_pos and edges_neg fp64 with at most %d "
+                           "entries each" % (what, TRAFFIC_MAX_EDGES))
+    return offsets.numel() - 1, cols.shape[0], cols.device, max(edges_pos.numel(), edges_neg.numel(), 1) - 1
+
+
+def _traffic_dir(what, N, dir):
+    _hip.need_gpu(dir)
+    _typed(what, ("dir", dir, torch.int32))
+    if tuple(dir.shape) != (N,):
+        raise RuntimeError("%s: dir is int32 [N = %d], got %s" % (what, N, tuple(dir.shape)))
+
+
+def traffic_lanes(offsets, cols, direction, edges_pos, edges_neg, status=None):
+    """offsets int64 [N+1], cols fp64 [R,7] = (t, x, y, l, w, h, v), direction int32 [R], the ascending lane edges of direction +1
+    and -1 -> (dir int32 [N] = +1 when the tracklet's directions sum to >= 0 else -1, lane int32 [R] = the k with edges[k] <= y <
+    edges[k+1] of the row's own y under its tracklet's dir, else -1; status)."""
+    N, R, dev, _ = _traffic_inputs("traffic_lanes", offsets, cols, edges_pos, edges_neg)
+    _hip.need_gpu(direction)
+    _typed("traffic_lanes", ("direction", direction, torch.int32))
+    if tuple(direction.shape) != (R,):
+        raise RuntimeError("traffic_lanes: direction is int32 [R = %d], got %s" % (R, tuple(direction.shape)))
+    status = traffic_status(dev, status)
+    dir = torch.ones(N, dtype=torch.int32, device=dev)
+    lane = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    _hip.call("rn_traffic_lanes", offsets, cols, direction, edges_pos, edges_pos.numel(), edges_neg, edges_neg.numel(), N, R, dir, lane,
+              status, device=dev)
+    return dir, lane, status
+
+
+def traffic_cells(offsets, cols, dir, edges_pos, edges_neg, t0, dt, nt, x0, dx, nx, max_gap, status=None):
+    """Edie's sums over the grid t0 + it dt (it < nt), x0 + ix dx (ix < nx): every segment (two consecutive rows of a tracklet, at
+    most max_gap apart, with a lane) is cut at the grid lines it crosses and each piece adds its time and its distance in units of
+    1 / TRAFFIC_Q to one cell -> (T int64 [2,L,nt,nx], D int64 [2,L,nt,nx], n int32 [2,L,nt,nx] = the pieces, counters int64
+    [TRAFFIC_COUNTERS] in TRAFFIC_CELL_COUNTERS order, status); index 0 of the first axis is direction +1, L = the lanes of the longer
+    edge array.  The rule: include/retinanet_mi355x.h, restated in tests/traffic_cases.py."""
+    N, R, dev, L = _traffic_inputs("traffic_cells", offsets, cols, edges_pos, edges_neg)
+    _traffic_dir("traffic_cells", N, dir)
+    t0, dt, x0, dx, max_gap, nt, nx = float(t0), float(dt), float(x0), float(dx), float(max_gap), int(nt), int(nx)
+    inf = float("inf")
+    if not (abs(t0) < inf and abs(x0) < inf and 0 < dt < inf and 0 < dx < inf and max_gap > 0):
+        raise ValueError("traffic_cells: t0 and x0 finite, dt and dx positive and finite, max_gap positive")
+    if nt < 0 or nx < 0 or 2 * L * nt * nx >= 2 ** 31:
+        raise RuntimeError("traffic_cells: a grid of 2 x %d x %d x %d cells; fewer than 2^31 are supported" % (L, nt, nx))
+    status = traffic_status(dev, status)
+    T = torch.zeros((2, L, nt, nx), dtype=torch.int64, device=dev)
+    D = torch.zeros((2, L, nt, nx), dtype=torch.int64, device=dev)
+    n = torch.zeros((2, L, nt, nx), dtype=torch.int32, device=dev)
+    counters = torch.zeros(TRAFFIC_COUNTERS, dtype=torch.int64, device=dev)
+    _hip.call("rn_traffic_cells", offsets, cols, dir, edges_pos, edges_pos.numel(), edges_neg, edges_neg.numel(), N, R, t0, dt, nt, x0, dx,
+              nx, max_gap, T, D, n, counters, status, device=dev)
+    return T, D, n, counters, status
+
+
+def traffic_leaders(offsets, cols, dir, lane, frame_off, frame_rows, status=None):
+    """Every frame taken as one instant: frame_off int64 [F+1] into frame_rows int32 [Rf], the packed rows of each frame (every row
+    at most once).  For a row the leader is the nearest row ahead of it (dir (x_j - x) > 0) in the same frame, direction and lane
+    >= 0, ties to the smaller tracklet -> (leader int32 [R] = the packed row or -1, spacing, gap = spacing - l, headway = spacing / v
+    (inf unless v > 0), ttc = gap / (v - v_leader) (inf unless closing with gap > 0): fp64 [R], inf without a leader; counters int64
+    [TRAFFIC_COUNTERS] in TRAFFIC_LEADER_COUNTERS order, status)."""
+    _hip.need_gpu(offsets, cols, lane, frame_off, frame_rows)
+    _typed("traffic_leaders", ("offsets", offsets, torch.int64), ("cols", cols, torch.float64), ("lane", lane, torch.int32),
+           ("frame_off", frame_off, torch.int64), ("frame_rows", frame_rows, torch.int32))
+    if offsets.dim() != 1 or offsets.numel() < 1 or cols.dim() != 2 or cols.shape[1] != 7 or cols.shape[0] >= 2 ** 31 \
+            or tuple(lane.shape) != (cols.shape[0],) or frame_off.dim() != 1 or frame_off.numel() < 1 or frame_off.numel() > 2 ** 31 \
+            or frame_rows.dim() != 1 or frame_rows.numel() >= 2 ** 31:
+        raise RuntimeError("traffic_leaders: offsets int64 [N+1], cols fp64 [R,7], lane int32 [R], frame_off int64 [F+1], frame_rows int32 "
+                           "[Rf], fewer than 2^31 rows and frames")
+    N, R, dev = offsets.numel() - 1, cols.shape[0], cols.device
+    _traffic_dir("traffic_leaders", N, dir)
+    status = traffic_status(dev, status)
+    leader = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    spacing, gap, headway, ttc = (torch.full((R,), float("inf"), dtype=torch.float64, device=dev) for _ in range(4))
+    counters = torch.zeros(TRAFFIC_COUNTERS, dtype=torch.int64, device=dev)
+    _hip.call("rn_traffic_leaders", offsets, cols, dir, lane, frame_off, frame_rows, N, R, frame_off.numel() - 1, frame_rows.numel(), leader,
+              spacing, gap, headway, ttc, counters, status, device=dev)
+    return leader, spacing, gap, headway, ttc, counters, status
+
+
 # ------------------------------------------------------------------------------------------------ time stamp bias
 TS_MAX_CAMS = 1024                # RN_TS_MAX_CAMS
 TS_OK, TS_OVERFLOW, TS_BAD_CAMERA = 0, 1, 2

@@ -68,6 +68,8 @@ Operator                                         reference code it stands for
   stitch_fill_count / stitch_fill_rows
   smooth_filter / smooth_rts                     fixed-interval (RTS) smoothing of     beyond the reference (csrc/smooth.hip,
                                                  every tracklet                        track_smooth.py)
+  traffic_lanes / traffic_cells /                flow, density and speed per lane      beyond the reference (csrc/traffic.hip,
+  traffic_leaders                                over a grid; leader, gap, headway     traffic_state.py)
 
 The whole-network training call stays one ``torch.autograd.Function`` (modules._NetFn): its inputs are the module's ~200
 parameters and its saved state is a Python structure of activations, which is a scheduler, not an operator.
@@ -1030,3 +1032,47 @@ def smooth_rts(offsets: torch.Tensor, order: torch.Tensor, cols: torch.Tensor, d
 @smooth_rts.register_fake
 def _(offsets, order, cols, direction, model, dt_default, filt):
     return cols.new_empty((cols.shape[0], ops.SMOOTH_OUT), dtype=torch.float64), cols.new_empty((1,), dtype=torch.int32)
+
+
+# ---- traffic state (csrc/traffic.hip, beyond the reference: traffic_state.py): the status word comes last
+OPERATORS += ("traffic_lanes", "traffic_cells", "traffic_leaders")
+
+
+@_lib.custom_op(NS + "::traffic_lanes", mutates_args=(), device_types="cuda")
+def traffic_lanes(offsets: torch.Tensor, cols: torch.Tensor, direction: torch.Tensor, edges_pos: torch.Tensor,
+                  edges_neg: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.traffic_lanes(offsets, cols, direction, edges_pos, edges_neg)
+
+
+@traffic_lanes.register_fake
+def _(offsets, cols, direction, edges_pos, edges_neg):
+    e = cols.new_empty
+    return e((offsets.shape[0] - 1,), dtype=torch.int32), e((cols.shape[0],), dtype=torch.int32), e((1,), dtype=torch.int32)
+
+
+@_lib.custom_op(NS + "::traffic_cells", mutates_args=(), device_types="cuda")
+def traffic_cells(offsets: torch.Tensor, cols: torch.Tensor, dir: torch.Tensor, edges_pos: torch.Tensor, edges_neg: torch.Tensor,
+                  t0: float, dt: float, nt: int, x0: float, dx: float, nx: int,
+                  max_gap: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.traffic_cells(offsets, cols, dir, edges_pos, edges_neg, t0, dt, nt, x0, dx, nx, max_gap)
+
+
+@traffic_cells.register_fake
+def _(offsets, cols, dir, edges_pos, edges_neg, t0, dt, nt, x0, dx, nx, max_gap):
+    e, shape = cols.new_empty, (2, max(edges_pos.shape[0], edges_neg.shape[0], 1) - 1, nt, nx)
+    return (e(shape, dtype=torch.int64), e(shape, dtype=torch.int64), e(shape, dtype=torch.int32),
+            e((ops.TRAFFIC_COUNTERS,), dtype=torch.int64), e((1,), dtype=torch.int32))
+
+
+@_lib.custom_op(NS + "::traffic_leaders", mutates_args=(), device_types="cuda")
+def traffic_leaders(offsets: torch.Tensor, cols: torch.Tensor, dir: torch.Tensor, lane: torch.Tensor, frame_off: torch.Tensor,
+                    frame_rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                       torch.Tensor, torch.Tensor]:
+    return ops.traffic_leaders(offsets, cols, dir, lane, frame_off, frame_rows)
+
+
+@traffic_leaders.register_fake
+def _(offsets, cols, dir, lane, frame_off, frame_rows):
+    R, e = cols.shape[0], cols.new_empty
+    return ((e((R,), dtype=torch.int32),) + tuple(e((R,), dtype=torch.float64) for _ in range(4))
+            + (e((ops.TRAFFIC_COUNTERS,), dtype=torch.int64), e((1,), dtype=torch.int32)))

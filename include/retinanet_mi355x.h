@@ -1646,6 +1646,53 @@ int rn_smooth_filter(const int64_t *offsets, const int32_t *order, const double 
 int rn_smooth_rts(const int64_t *offsets, const int32_t *order, const double *cols, const int32_t *direction, const double *model,
                   double dt_default, int64_t N, int64_t R, const double *filt, double *out, int32_t *status, void *stream);
 
+/* ---- traffic state from tracking output (csrc/traffic.hip): Edie's fields per lane, leaders and gaps (traffic_state.py) -----------
+ * Beyond the reference.  Tracklets as for stitching: offsets int64 [N+1] (offsets[0] = 0, offsets[N] = R, ascending), cols fp64
+ * [R,7] = (t, x, y, l, w, h, v), direction int32 [R], R < 2^31.  Lane edges: two fp64 arrays, edges_pos [n_pos] for direction +1 and
+ * edges_neg [n_neg] for -1, each ascending, at most RN_TRAFFIC_MAX_EDGES entries; the lane of y is the first k with edges[k] <= y <
+ * edges[k+1], else -1; L = max(n_pos, n_neg) - 1 (0 when that is negative).  fp64 with one rounding per operation, every expression
+ * in the order tests/traffic_cases.py writes it.
+ *   rn_traffic_lanes    dir int32 [N] = +1 when the sum of the tracklet's directions is >= 0, else -1; lane int32 [R] = the lane of
+ *                       the row's own y under its tracklet's dir.  Every field of every row is checked for a NaN or an infinity.
+ *   rn_traffic_cells    one thread per segment (rows a, b = a + 1 of one tracklet) over the grid t0 + it dt, x0 + ix dx, it < nt, ix <
+ *                       nx.  Tt = t_b - t_a, X = x_b - x_a; not 0 < Tt <= max_gap: skipped_gap; the lane of ym = (y_a + y_b) 0.5 under
+ *                       dir is -1: skipped_lane.  Cuts s in (0, 1): ((t0 + k dt) - t_a) / Tt for k = ka + 1 .. kb, ka = floor((t_a - t0)
+ *                       / dt), kb likewise of t_b, and ((x0 + m dx) - x_a) / X for m = ma + 1 .. mb of lo = min(x_a, x_b) and hi =
+ *                       max(x_a, x_b); k and m are formed as ka + (double)i.  Pieces [u, v] between consecutive values of {0, cuts, 1}
+ *                       in ascending order, those with v <= u dropped; with sm = (u + v) 0.5 a piece belongs to it = floor(((t_a + sm
+ *                       Tt) - t0) / dt), ix = floor(((x_a + sm X) - x0) / dx); outside the grid: `outside`; else T += rint(((v - u) Tt)
+ *                       Q), D += rint(((v - u) |X|) Q), n += 1 at [dir index (0 for +1, 1 for -1), lane, it, ix], Q = RN_TRAFFIC_Q.
+ *                       T, D int64 and n int32 [2,L,nt,nx] and counters int64 [RN_TRAFFIC_COUNTERS] = (segments, used, skipped_gap,
+ *                       skipped_lane, pieces, outside, 0, 0) are ADDED to: the caller zeroes them.  2 L nt nx < 2^31.  The sums are
+ *                       integers, so they do not depend on the order the atomics land in.
+ *   rn_traffic_leaders  one workgroup per frame f, whose rows are frame_rows[frame_off[f] .. frame_off[f+1]) (int64 [F+1] into int32
+ *                       [Rf] packed row indices, every packed row at most once).  For row i the candidates are the frame's rows j !=
+ *                       i with dir_j == dir_i, lane_j == lane_i >= 0 and s = dir_i (x_j - x_i) > 0; the leader is the one with the
+ *                       smallest s, then the smaller tracklet index, then the smaller row.  leader int32 [R] (packed row, -1: none),
+ *                       spacing = s, gap = s - l_i, headway = s / v_i when v_i > 0 else +inf, ttc = gap / (v_i - v_j) when v_i > v_j
+ *                       and gap > 0 else +inf: fp64 [R] each.  Rows outside every frame are not written: the caller fills -1 and
+ *                       +inf.  counters int64 [RN_TRAFFIC_COUNTERS] = (rows with a leader, rows with gap < 0, 0 ...), added to.
+ * All OR bits into the status word (int32, zeroed by the caller); a refused row or segment is left out. */
+#define RN_TRAFFIC_Q 1048576
+#define RN_TRAFFIC_COUNTERS 8
+#define RN_TRAFFIC_MAX_EDGES 64
+#define RN_TRAFFIC_MAX_CUTS 4096
+#define RN_TRAFFIC_NONFINITE 1        /* a NaN or an infinity in a row's fields */
+#define RN_TRAFFIC_BAD_OFFSETS 2      /* tracklet offsets out of order or not covering the R rows */
+#define RN_TRAFFIC_BAD_FRAME 4        /* frame offsets out of order, or a frame row outside the packed rows */
+#define RN_TRAFFIC_TOO_MANY_CUTS 8    /* a segment crosses more than RN_TRAFFIC_MAX_CUTS grid lines */
+#define RN_TRAFFIC_RANGE 16           /* a segment of 2^20 s or ft or more: its fixed-point share is not trusted */
+#define RN_TRAFFIC_BAD_DIR 32         /* a dir entry that is neither +1 nor -1 */
+int rn_traffic_lanes(const int64_t *offsets, const double *cols, const int32_t *direction, const double *edges_pos, int n_pos,
+                     const double *edges_neg, int n_neg, int64_t N, int64_t R, int32_t *dir, int32_t *lane, int32_t *status,
+                     void *stream);
+int rn_traffic_cells(const int64_t *offsets, const double *cols, const int32_t *dir, const double *edges_pos, int n_pos,
+                     const double *edges_neg, int n_neg, int64_t N, int64_t R, double t0, double dt, int64_t nt, double x0, double dx,
+                     int64_t nx, double max_gap, int64_t *T, int64_t *D, int32_t *n, int64_t *counters, int32_t *status, void *stream);
+int rn_traffic_leaders(const int64_t *offsets, const double *cols, const int32_t *dir, const int32_t *lane, const int64_t *frame_off,
+                       const int32_t *frame_rows, int64_t N, int64_t R, int64_t F, int64_t Rf, int32_t *leader, double *spacing,
+                       double *gap, double *headway, double *ttc, int64_t *counters, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
