@@ -163,20 +163,103 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const WinoTable g, float *
     }
 }
 
+// LIST instance of wino_in_kernel for the FORWARD of a layer whose output is needed on a known set of tiles only (the regression tower's
+// need sets): thread id -> entry of the list of 16-row units that hold a needed tile -> tile, as in
+// wino_in_both_kernel<true, true>.  A needed tile (flags[row] != 0) gets its transform and its row word; the other tiles of a listed unit
+// get ZERO rows -- the weight gradient's K-steps read whole units of the kept V, and 0 x garbage is NaN.  Nothing else is visited or
+// stored.  The arithmetic is wino_in_kernel's, line by line (the results are bit-identical on the needed tiles).
+__global__ __launch_bounds__(256) void wino_in_list_kernel(const WinoTable g, float *__restrict__ V, int C, int64_t t0, int64_t Tpad,
+                                                           unsigned *__restrict__ row_amax, unsigned *__restrict__ tensor_amax,
+                                                           const unsigned char *__restrict__ flags, const int *__restrict__ units,
+                                                           const int *__restrict__ n_units) {
+    wino_tensor_word(g, tensor_amax, WINO_GAIN_BT);
+    const int cq = C >> 2;
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (the plain id: the list's entries fill the first workgroups only)
+    const int64_t t_last = g.tile_end[g.n - 1];
+    const int64_t it = id / cq;
+    const int c4 = (int)(id - it * cq) * 4;
+    const int nu_raw = *n_units, nu_max = (int)(Tpad >> 4);
+    const int64_t rows = 16 * (int64_t)(nu_raw < 0 ? 0 : (nu_raw < nu_max ? nu_raw : nu_max));
+    if ((id - threadIdx.x) >= rows * cq) return;              // (the whole workgroup)
+    int64_t gt_raw = it < rows ? (int64_t)units[it >> 4] * 16 + (it & 15) - t0 : t_last;
+    if (gt_raw < 0) gt_raw = t_last;
+    const int64_t gt = gt_raw < t_last ? gt_raw : t_last - 1;   // (threads past the end still help with the table read below)
+    int64_t tile;
+    const int q = wino_locate(g, gt, tile);
+    const float *x = g.src[0];
+    const unsigned *xw = g.amax[0];
+    WINO_SELECT(q, g, pr, x = g.src[i_]; xw = g.amax[i_];)
+    const int H = pr.H, W = pr.W, TW = pr.TW;
+    const int n = (int)(tile / (pr.TH * TW));
+    const int r = (int)(tile - (int64_t)n * pr.TH * TW);
+    const int th = r / TW, tw = r - th * TW;
+    const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
+    const float *xb = x + (int64_t)n * H * W * C + c4;
+    const bool needed = gt_raw < t_last && flags[t0 + gt] != 0;
+    if (row_amax != nullptr) {                                // wave-cooperative: every lane the largest exponent of ITS image's table
+        const int e_img = rn_amax_exp_lanes(xw != nullptr ? reinterpret_cast<const unsigned char *>(xw) + (int64_t)n * RN_AMAX_BYTES : nullptr);
+        if (needed && c4 == 0) row_amax[t0 + gt] = rn_amax_word_of_exp(e_img, WINO_GAIN_BT);
+    }
+    if (gt_raw >= t_last) return;
+    float *vb = V + (t0 + gt) * C + c4;
+    if (!needed) {
+#pragma unroll
+        for (int p = 0; p < 36; ++p) st_stream(vb + (int64_t)p * Tpad * C, f4(0.f));
+        return;
+    }
+    float4 t[6][6];                                           // t[i][j] = (B^T d)[i][j]: columns first
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        float4 d[6], o[6];
+        const int w = w0 + j;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int h = h0 + i;
+            const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+            d[i] = ok ? *reinterpret_cast<const float4 *>(xb + ((int64_t)h * W + w) * C) : f4(0.f);
+        }
+        bt6(d, o);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) t[i][j] = o[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {                              // rows: V[i][.] = t[i][.] B
+        float4 o[6];
+        bt6(t[i], o);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) st_stream(vb + (int64_t)(i * 6 + j) * Tpad * C, o[j]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- output transform
 // mask_mode / add / act as in rn_conv_desc (mask and add have the geometry of y, dense [N,H,W,Cout]).
 // FLAGS (tile activity flags): a tile whose flag in `fin` is 0 has M = 0 exactly -- it reads no M and runs the epilogue on
 // zeros; `fout` receives the flags of the STORED tensor for the next layer's transforms: a non-zero pixel sets its own tile and the
 // neighbours whose 6x6 patch contains it (plain byte stores of 1).  Either pointer may be NULL.
-template <bool PBITS, bool PADD, bool FLAGS = false>
+// LIST (the forward of a layer whose output is needed on a known set of tiles): thread id -> entry of the list of needed
+// tile rows (rn_tile_lists: tiles / n_tiles on the device) -> tile.  A listed tile runs the whole epilogue -- bias, ReLU, sign bits, the
+// result's amax table, dense or strided destination -- exactly as the dense instance does; every other tile loads nothing and stores
+// nothing.  The launch keeps the dense grid (the list's length is known on the device only).
+template <bool PBITS, bool PADD, bool FLAGS = false, bool LIST = false>
 __global__ __launch_bounds__(256, 2) void wino_out_kernel(const WinoTable g, const float *__restrict__ M, int Cout, int64_t t0,
                                                        int64_t Tpad, const float *__restrict__ scale,
                                                        const float *__restrict__ shift, int mask_mode, int act, int64_t y_bs,
                                                        const unsigned char *__restrict__ fin = nullptr,
-                                                       unsigned char *__restrict__ fout = nullptr) {
+                                                       unsigned char *__restrict__ fout = nullptr,
+                                                       const int *__restrict__ tiles = nullptr,
+                                                       const int *__restrict__ n_tiles = nullptr) {
     const int cq = Cout >> 2;
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t gt = id / cq;
+    const int64_t it = id / cq;
+    int64_t gt_sel = it;
+    if constexpr (LIST) {
+        const int nt_raw = *n_tiles;
+        const int64_t nt = nt_raw < 0 ? 0 : (nt_raw < Tpad ? nt_raw : Tpad);
+        if ((id - threadIdx.x) / cq >= nt) return;            // (the whole workgroup: nothing of it is listed)
+        gt_sel = it < nt ? (int64_t)tiles[it] - t0 : g.tile_end[g.n - 1];
+        if (gt_sel < 0) gt_sel = g.tile_end[g.n - 1];
+    }
+    const int64_t gt = gt_sel;
     // (the body sits in a one-trip loop so that threads past the last tile leave it by `break` and reach the amax commit at the end)
     float am = 0.f;                                           // largest |y| this thread stores (the result's amax word of image n)
     unsigned *yam = nullptr;
@@ -185,7 +268,7 @@ __global__ __launch_bounds__(256, 2) void wino_out_kernel(const WinoTable g, con
     do {
     if (gt >= g.tile_end[g.n - 1]) break;
     live = true;
-    const int c4 = (int)(id - gt * cq) * 4;
+    const int c4 = (int)(id - it * cq) * 4;
     int64_t tile;
     const int q = wino_locate(g, gt, tile);
     float *y = g.dst[0];
@@ -677,6 +760,26 @@ extern "C" int rn_wino_input_both_group_lists(const rn_wino_group *g, float *V, 
     return RN_OK;
 }
 
+// rn_wino_input_group (B^T d B form) over the work list of `flags`: the forward of a layer whose output is needed on the flagged tiles only.
+extern "C" int rn_wino_input_group_list(const rn_wino_group *g, float *V, int C, int64_t tile_offset, int64_t Tpad, void *row_amax,
+                                        void *tensor_amax, const void *flags, const void *units, const void *n_units, void *stream) {
+    WinoTable t;
+    const int rc = wino_table(g, t);
+    if (rc) return rc;
+    if (!V || C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
+    if (!flags || !units || !n_units || ((uintptr_t)units & 3) || ((uintptr_t)n_units & 3) || (Tpad & 15)) return RN_EINVAL;
+    for (int i = 0; i < t.n; ++i)
+        if (!t.src[i]) return RN_EINVAL;
+    // (the list may hold any unit of the Tpad rows -- those of another launch's problems included, which this one skips)
+    const dim3 gl(rn_blocks(Tpad * (C >> 2), 256));
+    hipLaunchKernelGGL(wino_in_list_kernel, gl, dim3(256), 0, (hipStream_t)stream, t, V, C, tile_offset, Tpad,
+                       reinterpret_cast<unsigned *>(row_amax), reinterpret_cast<unsigned *>(tensor_amax),
+                       reinterpret_cast<const unsigned char *>(flags), reinterpret_cast<const int *>(units),
+                       reinterpret_cast<const int *>(n_units));
+    RN_LAUNCH_CHECK();
+    return RN_OK;
+}
+
 extern "C" int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
                                         void *v_row_amax, void *z_tensor_amax, void *stream) {
     return rn_wino_input_both_group_flags(g, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, nullptr, stream);
@@ -722,6 +825,38 @@ extern "C" int rn_wino_output_group(const rn_wino_group *g, const float *M, int 
                                     const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
                                     void *stream) {
     return rn_wino_output_group_flags(g, M, Cout, tile_offset, Tpad, scale, shift, mask_mode, act, y_batch_stride, nullptr, nullptr, stream);
+}
+// rn_wino_output_group over a work list of needed tile rows (rn_tile_lists: tiles / n_tiles on the device): the listed tiles get what the
+// dense call stores, nothing else is read or written.
+extern "C" int rn_wino_output_group_list(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
+                                         const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
+                                         const void *tiles, const void *n_tiles, void *stream) {
+    WinoTable t;
+    const int rc = wino_table(g, t);
+    if (rc) return rc;
+    if (Cout <= 0 || (Cout & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
+    if (!tiles || !n_tiles || ((uintptr_t)tiles & 3) || ((uintptr_t)n_tiles & 3)) return RN_EINVAL;
+    if (mask_mode < 0 || (mask_mode & ~(3 | RN_MASK_BITS)) || (mask_mode & 3) == 3 || mask_mode == RN_MASK_BITS) return RN_EINVAL;
+    if (act < 0 || act > 2 || y_batch_stride < 0 || (y_batch_stride & 3)) return RN_EINVAL;
+    for (int i = 0; i < t.n; ++i) {
+        if (!t.dst[i] || (mask_mode != 0) != (t.mask[i] != nullptr)) return RN_EINVAL;
+        if (((mask_mode & RN_MASK_BITS) || t.sign[i]) && (Cout & 31)) return RN_EINVAL;     // whole words per pixel
+        if (y_batch_stride && y_batch_stride < (int64_t)t.p[i].H * t.p[i].W * Cout) return RN_EINVAL;
+    }
+    const bool pbits = (mask_mode & RN_MASK_BITS) != 0;
+    bool padd = true;
+    for (int i = 0; i < t.n; ++i) padd = padd && t.add[i] != nullptr;
+    const dim3 grid(rn_blocks(Tpad * (Cout >> 2), 256));      // (the list may hold any of the Tpad rows)
+#define RN_WINO_OUT_L(B, A) hipLaunchKernelGGL((wino_out_kernel<B, A, false, true>), grid, dim3(256), 0, (hipStream_t)stream, t, M, Cout, tile_offset, \
+                                               Tpad, scale, shift, mask_mode, act, y_batch_stride, (const unsigned char *)nullptr,                   \
+                                               (unsigned char *)nullptr, reinterpret_cast<const int *>(tiles), reinterpret_cast<const int *>(n_tiles))
+    if (pbits && padd) RN_WINO_OUT_L(true, true);
+    else if (pbits) RN_WINO_OUT_L(true, false);
+    else if (padd) RN_WINO_OUT_L(false, true);
+    else RN_WINO_OUT_L(false, false);
+#undef RN_WINO_OUT_L
+    RN_LAUNCH_CHECK();
+    return RN_OK;
 }
 
 // Single-problem forms.

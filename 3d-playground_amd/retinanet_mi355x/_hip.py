@@ -41,6 +41,7 @@ SIGNATURES = {
     "rn_focal_loss_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "rn_focal_loss_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rn_assign": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "rn_reg_need_tiles": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
     "rn_decode_dir": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp]),
     "rn_decode_dir_select": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "rn_decode_2d": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_f32, c_vp]),
@@ -172,6 +173,7 @@ class ConvDesc(ctypes.Structure):
 
 
 RN_MAX_GROUP = 5
+RN_REG_NEED_ARRAYS = 6                                 # flag arrays rn_reg_need_tiles fills
 
 
 class ConvGroup(ctypes.Structure):
@@ -210,6 +212,8 @@ SIGNATURES.update({
     "rn_wino_input_both_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "rn_wino_input_both_group_flags": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "rn_tile_lists": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rn_wino_input_group_list": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rn_wino_output_group_list": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rn_wino_input_both_group_lists": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rn_wino_output_group_flags": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "rn_wino_output_group": (c_i32, [ctypes.POINTER(WinoGroup), c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),

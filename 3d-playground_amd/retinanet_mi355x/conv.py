@@ -472,6 +472,71 @@ def _wino_transform_in(xs, V, C, Tpad, dy_form, want_rows=False, want_tensor=Fal
     return rows, tword
 
 
+# A forward that computes a layer on its NEED SET only leaves the rest of what it allocates unwritten.  NEED_POISON (tests;
+# off by default) fills every such tensor with NaN (all-ones words for sign bits) first: nothing unwritten may reach a result.
+NEED_POISON = False
+DENSE = "dense"
+
+
+def _need_fill(t, fill):
+    """fill None: leave t as allocated; "zero": what a DENSE backward may read of it must be zero; NEED_POISON overrides both."""
+    if NEED_POISON:
+        t.fill_(float("nan")) if t.is_floating_point() else t.fill_(-1)
+    elif fill == "zero":
+        t.zero_()
+    return t
+
+
+def _wino_transform_in_list(xs, V, C, Tpad, lists, want_tensor=False):
+    """_wino_transform_in (B^T d B form) over the work list of a need set (a TileLists of the flags of the tiles whose transform anybody
+    reads): rn_wino_input_group_list.  One launch: at most RN_MAX_GROUP problems.  -> (row words [Tpad] or None, tensor word or None)."""
+    lib = _hip.load()
+    assert len(xs) <= _hip.RN_MAX_GROUP and lists.flags.numel() >= Tpad
+    am = want_amax()
+    rows = torch.zeros(Tpad, dtype=torch.int32, device=V.device) if am else None
+    tword = amax_single(V.device) if am and want_tensor else None
+    t = sum(x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4) for x in xs)
+    g = _wino_group(xs, srcs=xs, amaxs=[amax_words(x) for x in xs] if am else None)
+    nb = 4.0 * (sum(x.numel() for x in xs) + 36 * t * C)           # (nominal: the dense call's bytes)
+    _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_group_list(
+        ctypes.byref(g), V.data_ptr(), C, 0, Tpad, _hip.ptr(rows), _hip.ptr(tword), lists.flags.data_ptr(), lists.units.data_ptr(),
+        lists.counts.data_ptr() + 4, _hip.stream())), "rn_wino_input_group_list")
+    return rows, tword
+
+
+class RegNeed:
+    """The need sets of one step's regression tower (reg_need_tiles): flags / lists[k], k as in rn_reg_need_tiles -- 0: P0 (the output
+    layer's result), 1..4: D^2 .. D^5 (conv4 .. conv1's results), 5: D(P0) (the output layer's input transform, which its weight gradient
+    reads on the backward's depth-0 tiles); hws: the pyramid levels they were made for; B, Tpad."""
+    __slots__ = ("flags", "lists", "hws", "B", "Tpad")
+
+
+def reg_need_tiles(anchors, ann, directional, B, hws, per_pixel, flag_buf=None, list_bufs=None):
+    """The need sets of the regression tower's forward from the labels (rn_reg_need_tiles) and their work lists (rn_tile_lists), all on the
+    device and on the current stream, without a host read.  anchors [1, A, 4] / [A, 4], ann [B, N, 27 | 5]; hws: (H, W) of the
+    pyramid levels.  flag_buf (uint8, RN_REG_NEED_ARRAYS * wino_tpad(T)) / list_bufs: the caller's buffers, kept across steps."""
+    lib = _hip.load()
+    dev = anchors.device
+    _hip.need_gpu(anchors, ann)
+    n = _hip.RN_REG_NEED_ARRAYS
+    T = sum(B * ((h + 3) // 4) * ((w + 3) // 4) for h, w in hws)
+    Tpad = wino_tpad(T)
+    A = anchors.numel() // 4
+    if flag_buf is None:
+        flag_buf = torch.empty(n * Tpad, dtype=torch.uint8, device=dev)
+    assert flag_buf.dtype == torch.uint8 and flag_buf.numel() == n * Tpad and anchors.is_contiguous() and ann.is_contiguous()
+    assert ann.dtype == torch.float32 and anchors.dtype == torch.float32 and ann.shape[0] == B
+    Hs = (ctypes.c_int * len(hws))(*[h for h, _ in hws])
+    Ws = (ctypes.c_int * len(hws))(*[w for _, w in hws])
+    _hip.check(lib.rn_reg_need_tiles(anchors.data_ptr(), _hip.ptr(ann) if ann.numel() else None, B, A, ann.shape[1], int(directional),
+                                     len(hws), Hs, Ws, per_pixel, flag_buf.data_ptr(), Tpad, _hip.stream()), "rn_reg_need_tiles")
+    r = RegNeed()
+    r.flags = [flag_buf[k * Tpad:(k + 1) * Tpad] for k in range(n)]
+    r.lists = [tile_lists(f, Tpad, buf=None if list_bufs is None else list_bufs[k]) for k, f in enumerate(r.flags)]
+    r.hws, r.B, r.Tpad = [tuple(x) for x in hws], B, Tpad
+    return r
+
+
 def _wino_workspace(device, floats_v, floats_m):
     """V and M of the Winograd path: two scratch tensors per device AND stream (layers launched on different streams run
     concurrently), grown on demand and reused by every layer of that stream."""
@@ -536,17 +601,26 @@ def wino_flags_ok(T, C, cout):
 
 
 def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds=None, masks=None, mask_mode=2,
-                    flops=0.0, keep_v=False, y_batch_stride=0, V_in=None, V_ready=None, sign=False, flags_out=None):
+                    flops=0.0, keep_v=False, y_batch_stride=0, V_in=None, V_ready=None, sign=False, flags_out=None,
+                    need=None, need_in=None, need_fill=None):
     """3x3 / stride 1 / padding 1 convolution of several inputs [N,H,W,C] with the same (transformed) weights U
     [36, Cout, Kpad]: one grouped input transform into V, ONE batched GEMM launch, one grouped output transform with
     the epilogue (outs: dense tensors, or slices with y_batch_stride).  Returns the outputs (and, with keep_v, the
     (V, shapes) pair wino_wgrad_group accepts).  flops is informational (the GEMM is priced by its executed FLOPs).
     A V_ready that carries tile flags (wino_wgrad_group(flags=...)) makes the GEMM and the output transform skip the inactive tiles;
-    flags_out: a zeroed tile_flags array that receives the flags of the results (the next layer's gradient)."""
+    flags_out: a zeroed tile_flags array that receives the flags of the results (the next layer's gradient).
+    need (a forward whose result is read on a known set of tiles only): the TileLists of that set -- the GEMM walks its
+    blocks, the output transform its tiles, and nothing else of the outputs (values, sign bits, amax tables) is written.  need_in: the
+    TileLists the input transform walks (default: need; it must hold every tile whose V anybody reads later -- the weight gradient), or
+    DENSE for the dense transform (a V somebody else shares).  need_fill "zero": what is skipped is zero instead of unwritten (kept V,
+    fresh outputs, sign bits) -- for a backward that runs dense."""
     lib = _hip.load()
     dev = xs[0].device
     C = xs[0].shape[3]
     cout = U.shape[1]                                # rows of the transformed weights = output channels
+    if need is not None:
+        assert V_ready is None and flags_out is None and len(xs) <= _hip.RN_MAX_GROUP
+        need_in = need if need_in is None else need_in
     tiles = [x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4) for x in xs]
     T = sum(tiles)
     Tpad = wino_tpad(T)
@@ -562,17 +636,29 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
         V = V_in[0]
     elif keep_v:                                     # the caller keeps B^T d B of the inputs for the weight gradient
         V = torch.empty(36 * Tpad * C, dtype=torch.float32, device=dev)
+        if need is not None and need_in is not DENSE:
+            _need_fill(V, need_fill)
+    if need is not None and NEED_POISON:
+        M[:36 * Tpad * cout].fill_(float("nan"))
+        if not keep_v and not reuse:
+            V[:36 * Tpad * C].fill_(float("nan"))
     assert all(x.is_contiguous() for x in xs)
     v_am = (None, None)                              # split3: V's amax words (one per tile row for this GEMM, one for the weight gradient)
     if reuse:                                        # a kept / handed-over V comes with them
         src = V_ready if ready else V_in
         v_am = src[2] if len(src) > 2 and src[2] is not None else (None, None)
+    elif need is not None and need_in is not DENSE:
+        assert need_in.flags.numel() >= Tpad
+        v_am = _wino_transform_in_list(xs, V, C, Tpad, need_in, want_tensor=keep_v)
     else:
         v_am = _wino_transform_in(xs, V, C, Tpad, 0, want_rows=True, want_tensor=keep_v)
     flags = V_ready[3] if ready and len(V_ready) > 3 else None      # V holds the ACTIVE tiles only: every later stage must skip the others
     lists = V_ready[4] if ready and len(V_ready) > 4 else None      # ... and the GEMM walks their work list instead of the dense grid
     if flags_out is not None:
         assert flags_out.dtype == torch.uint8 and flags_out.numel() >= Tpad and len(xs) <= _hip.RN_MAX_GROUP
+    if need is not None:
+        assert need.flags.numel() >= Tpad
+        lists = need
     # rows past T hold whatever the scratch tensor held: they produce rows of M nobody reads
     Vv = V[:36 * Tpad * C].view(36, 1, Tpad, C)
     Mv = M[:36 * Tpad * cout].view(36, 1, Tpad, cout)
@@ -583,6 +669,9 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
                x_amax=v_am[0], x_amax_rows=True, row_active=flags, row_list=lists)    # executed FLOPs: same kernel, same family (nominal with flags)
     if outs is None:
         outs = [torch.empty((x.shape[0], x.shape[1], x.shape[2], cout), dtype=torch.float32, device=dev) for x in xs]
+        if need is not None:
+            for o in outs:
+                _need_fill(o, need_fill)
     off = 0
     for k in range(0, len(xs), _hip.RN_MAX_GROUP):
         sl = slice(k, k + _hip.RN_MAX_GROUP)
@@ -600,7 +689,14 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
         nops = 1 + (pa is not None and pa[0] is not None) + (1.0 / 32 if mbits else 1.0) * has_mask + (1.0 / 32 if signs[0] is not None else 0.0)
         nb = 4.0 * (36 * t * cout + nops * sum(x.shape[0] * x.shape[1] * x.shape[2] for x in part) * cout)
         mm = (mask_mode | (MASK_BITS if mbits else 0)) if has_mask else 0
-        if flags is not None or flags_out is not None:
+        if need is not None:
+            for w_ in signs:
+                if w_ is not None:
+                    _need_fill(w_, need_fill)
+            _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group_list(
+                ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
+                act, y_batch_stride, need.tiles.data_ptr(), need.counts.data_ptr(), _hip.stream())), "rn_wino_output_group_list")
+        elif flags is not None or flags_out is not None:
             _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group_flags(
                 ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
                 act, y_batch_stride, _hip.ptr(flags), _hip.ptr(flags_out), _hip.stream())), "rn_wino_output_group_flags")

@@ -33,6 +33,10 @@ SPARSE_REG = os.environ.get("RN_SPARSE_REG", "1") != "0"
 # ... and its flagged stages walk device-side work lists (cv.tile_lists) instead of launching dense grids whose workgroups test their
 # flags and leave.  RN_SPARSE_REG_LISTS=0: the early-exit instances (A/B); inert when RN_SPARSE_REG=0.
 SPARSE_REG_LISTS = os.environ.get("RN_SPARSE_REG_LISTS", "1") != "0"
+# The loss reads the regression output at the positive anchors only, and the labels say before the forward where those are: the tower's
+# FORWARD computes each layer on its need set (the label tiles, dilated once per 3x3 layer below) instead of on every tile.
+# Independent of SPARSE_REG, which keeps switching the backward only.  RN_SPARSE_REG_FWD=0: the dense forward (A/B).
+SPARSE_REG_FWD = os.environ.get("RN_SPARSE_REG_FWD", "1") != "0"
 # bf16 engine: the weight gradient of a head layer over its five pyramid levels as ONE launch (rn_conv_wgrad_bf16_grouped); 0: one per level (A/B)
 GROUPED_WGRAD_BF16 = os.environ.get("RN_GROUPED_WGRAD_BF16", "1") != "0"
 # bf16 engine: the data gradient of a 1x1 stride-2 shortcut computed on its output grid and stored at the even input positions; 0: the generic form (A/B)
@@ -253,10 +257,12 @@ class Layer:
                                  add=add, add_mode=add_mode, add_hw=add_hw, act=act, y_batch_stride=y_batch_stride,
                                  out_scale=self.out_scale, flops=self.flops(x.shape[0], Ho, Wo))
 
-    def fwd_group(self, xs, act=cv.ACT_NONE, outs=None, y_batch_stride=None, wino=False, shared_v=None):
+    def fwd_group(self, xs, act=cv.ACT_NONE, outs=None, y_batch_stride=None, wino=False, shared_v=None, need=None, need_in=None,
+                  need_fill=None):
         """Same convolution on several inputs (pyramid levels) in one launch.  outs: destination tensors/views
         (with y_batch_stride) or None for fresh dense outputs.  wino: Winograd path (dense outputs only).  shared_v: the kept
-        input transform of ANOTHER layer that read the same xs (both towers' conv1 read the pyramid): reused, not recomputed."""
+        input transform of ANOTHER layer that read the same xs (both towers' conv1 read the pyramid): reused, not recomputed.
+        need / need_in / need_fill: the Winograd form on a need set only (cv.wino_conv_group); the other forms have no such thing."""
         s = self.spec
         mode = self.mode()
         if self.fp8:
@@ -296,9 +302,10 @@ class Layer:
             fl = sum(self.flops(x.shape[0], x.shape[1], x.shape[2]) for x in xs)
             r = cv.wino_conv_group(xs, self.wino_weights(0), outs=outs, scale=self.scale, shift=self.shift, act=act, flops=fl,
                                    keep_v=self.keep_v, y_batch_stride=y_batch_stride or 0, V_in=shared_v if self.keep_v else None,
-                                   sign=self.sign and act == cv.ACT_RELU)
+                                   sign=self.sign and act == cv.ACT_RELU, need=need, need_in=need_in, need_fill=need_fill)
             ys, self.saved_v = r if self.keep_v else (r, None)
             return ys
+        assert need is None, "%s does not take the Winograd form: no need sets" % s.name
         probs, ys, fl = [], [], 0.0
         for i, x in enumerate(xs):
             N, Hi, Wi, _ = x.shape
@@ -982,9 +989,42 @@ class Engine:
         return on
 
     # ------------------------------------------------------------------------------------------- forward
-    def forward(self, P, img, save, x4=None):
+    def reg_need(self, anchors, ann, directional, B, H, W):
+        """The need sets of the regression tower's forward for a training step on B images of H x W with labels ann (cv.reg_need_tiles;
+        DESIGN.md 4.4), or None where the sparse forward does not apply: RN_SPARSE_REG_FWD=0, anything but fp32 in a split product mode
+        with the Winograd path on, or a tower whose backward could not honour tile flags (cv.wino_flags_ok).  Flags and lists live in
+        buffers of their own, kept across steps; _reg_flags / _reg_lists are the backward's and keep their meaning.
+        Eager steps only: a step that is being captured into a graph keeps the dense forward, and so does every later step of an engine
+        that has been captured once -- its replays and its eager steps then compute the same bits (the sparse forward may choose finer
+        split3 scales than the dense one).  The benchmark's step replayed from a captured graph with the sparse forward in it ended in a
+        segmentation fault of the host process whose cause is not known; until it is, captured steps run the launch sequence they
+        always ran."""
+        if not (SPARSE_REG_FWD and self.use_wino and not self.bwd16 and not self.bf16 and not self.fp8 and ann.is_cuda):
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            self._captured_once = True
+        if getattr(self, "_captured_once", False):
+            return None
+        Lout, L4 = self.layers["regressionModel.output"], self.layers["regressionModel.conv4"]
+        hws = arch.pyramid_shapes(H, W)
+        T = sum(B * ((h + 3) // 4) * ((w + 3) // 4) for h, w in hws)
+        if not (Lout.wino_layer and L4.wino_layer and cv.wino_flags_ok(T, L4.spec.cin, L4.spec.cout)
+                and cv.wino_flags_ok(T, Lout.spec.cin, Lout.spec.cout) and len(hws) <= _hip.RN_MAX_GROUP):
+            return None
+        Tpad, n = cv.wino_tpad(T), _hip.RN_REG_NEED_ARRAYS
+        fb = getattr(self, "_reg_need_flag_buf", None)
+        if fb is None or fb.numel() != n * Tpad or fb.device != ann.device:
+            fb = self._reg_need_flag_buf = torch.empty(n * Tpad, dtype=torch.uint8, device=ann.device)
+            self._reg_need_list_bufs = [torch.empty(cv.tile_lists_numel(Tpad), dtype=torch.int32, device=ann.device) for _ in range(n)]
+        need = cv.reg_need_tiles(anchors, ann, directional, B, hws, arch.NUM_ANCHORS, flag_buf=fb, list_bufs=self._reg_need_list_bufs)
+        self._reg_need_flags, self._reg_need_lists = need.flags, need.lists
+        return need
+
+    def forward(self, P, img, save, x4=None, reg_need=None):
         """img [B,3,H,W] on device -> (reg [B,A,n_reg], cls [B,A,C], saved activations or None).  x4: the input already
-        in the stem's layout ([B,H,W,4] fp32, e.g. from ops.frame_ingest(nhwc4=True)); img is then ignored."""
+        in the stem's layout ([B,H,W,4] fp32, e.g. from ops.frame_ingest(nhwc4=True)); img is then ignored.
+        reg_need (training; self.reg_need(...) of this batch's labels): the regression tower computes each layer on its need set only, and
+        reg holds values at the anchors of the label tiles -- the ones the loss reads -- and is unwritten elsewhere.  None: dense."""
         Ls = self.layers
         if save and os.environ.get("RN_BATCHED_PREP", "1") != "0":
             self._prepare_training(P)
@@ -1091,6 +1131,13 @@ class Engine:
         side = self.tower_streams(x4.device)
         main = torch.cuda.current_stream(x4.device)
         v_ready = None
+        # the regression tower on its need sets: only for the batch and pyramid they were made for, and only where a backward follows
+        need = reg_need if (save and reg_need is not None and reg_need.B == B and self.use_wino and not self.bf16 and not self.fp8
+                            and reg_need.hws == [(f.shape[1], f.shape[2]) for f in pyramid]) else None
+        # a backward that will run dense (A/B: RN_SPARSE_REG=0, RN_WINO_FUSE_DY=0) reads every tile of what this forward keeps: zeros there
+        need_fill = None if (SPARSE_REG and FUSE_DY) else "zero"
+        if need is not None and cv.NEED_POISON:
+            reg.fill_(float("nan"))
         if side is not None:
             fork = main.record_event()
         for ti, (prefix, out, width, act) in enumerate((("regressionModel", reg, self.n_reg, cv.ACT_NONE),
@@ -1105,8 +1152,12 @@ class Engine:
                 for i in range(1, 5):                                     # one launch per tower conv, all 5 levels
                     first = Ls["regressionModel.conv1"]                   # both towers' conv1 transform the same pyramid: once
                     shared = first.saved_v if (i == 1 and prefix == "classificationModel") else None
+                    # need sets (regression tower): conv i's result is read on D^(6-i)(P0); conv1's input transform is the one the
+                    # classification tower shares, so it stays dense
+                    nd = need.lists[5 - i] if (need is not None and ti == 0) else None
                     ts = Ls["%s.conv%d" % (prefix, i)].fwd_group(ts, act=cv.ACT_RELU, wino=save and self.use_wino and not self.bf16 and not self.fp8,
-                                                                 shared_v=shared)
+                                                                 shared_v=shared, need=nd, need_in=cv.DENSE if (nd is not None and i == 1) else None,
+                                                                 need_fill=need_fill if nd is not None else None)
                     acts.append(ts)
                     if side is not None and ti == 0 and i == 1:
                         v_ready = side[0].record_event()
@@ -1114,7 +1165,11 @@ class Engine:
                 for cnt in counts:
                     views.append(out.view(B, -1)[:, off * width:])
                     off += cnt
-                Ls[prefix + ".output"].fwd_group(ts, act=act, outs=views, y_batch_stride=A * width)
+                # the output layer's result is read on P0; its input transform is kept for the weight gradient, which reads it on the
+                # backward's depth-0 tiles -- inside D(P0)
+                nd = need.lists[0] if (need is not None and ti == 0) else None
+                Ls[prefix + ".output"].fwd_group(ts, act=act, outs=views, y_batch_stride=A * width, need=nd,
+                                                 need_in=need.lists[5] if nd is not None else None, need_fill=need_fill if nd is not None else None)
             if save:
                 S["towers"][prefix] = [[acts[i][li] for i in range(4)] for li in range(5)]
         if side is not None:

@@ -155,10 +155,12 @@ class _NetFn(torch.autograd.Function):
     def forward(ctx, net, img, ann, *params):
         eng = net._engine
         P = net._tensor_dict()
-        reg, cls, S = eng.forward(P, img, save=True)
         anc = eng.anchors(img.shape[2], img.shape[3], img.device)
         lib = _hip.load()
         ann_c = _hip.f32c(ann)
+        # the loss below reads the regression output at the positive anchors only: the tower computes what they need (Engine.reg_need)
+        need = eng.reg_need(anc, ann_c, net.directional, img.shape[0], img.shape[2], img.shape[3])
+        reg, cls, S = eng.forward(P, img, save=True, reg_need=need)
         B, A, C = cls.shape
         ws = ops.focal_workspace(B, A, img.device)
         losses = torch.empty(3, dtype=torch.float32, device=img.device)

@@ -74,6 +74,17 @@ int rn_focal_loss_bwd(const float *cls, const float *reg, const float *anchors, 
 int rn_assign(const float *anchors, const float *ann, int B, int64_t A, int N, int directional,
               float *iou_max, int32_t *argmax, int32_t *state, void *stream);
 
+/* NEED SETS of the regression tower's forward.  The loss reads the regression output at the positive anchors only (rn_assign's rule: best
+ * IoU >= 0.5 against the image's valid labels), so the labels decide before the forward which 4x4 output tiles of which pyramid level
+ * are ever read: P0 = the tiles that hold a pixel with a positive anchor; the 3x3 layers below need its dilations D^k on the tile grid of
+ * one image of one level.  anchors [A,4] in level order, per_pixel anchors per pixel, pixels row-major; H / W: n_levels (<= RN_MAX_GROUP)
+ * HOST ints, sum H*W*per_pixel == A.  flags: RN_REG_NEED_ARRAYS arrays of Tpad bytes each (Tpad a multiple of 16 that holds every tile;
+ * 16-byte aligned), in the tile order of rn_wino_group (levels concatenated; image, tile row, tile column), zeroed and filled here on
+ * the device, no host read: [0] P0, [1] D^2(P0), [2] D^3(P0), [3] D^4(P0), [4] D^5(P0), [5] D(P0).  rn_tile_lists makes their work lists. */
+#define RN_REG_NEED_ARRAYS 6
+int rn_reg_need_tiles(const float *anchors, const float *ann, int B, int64_t A, int N, int directional, int n_levels,
+                      const int *H, const int *W, int per_pixel, void *flags, int64_t Tpad, void *stream);
+
 /* ---------------------------------------------------------------- decode / clip ---------------------------
  * rn_decode_dir replaces BBoxTransform.forward (D/utils.py:102-149): reg [B,A,12] -> boxes [B,A,20].
  * rn_decode_2d  replaces BBoxTransform.forward (R/utils.py:102-126) with std (.1,.1,.2,.2) and, when
@@ -928,6 +939,17 @@ int rn_tile_lists(const void *flags, int64_t Tpad, void *counts, void *tiles, vo
 int rn_wino_input_both_group_lists(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
                                    void *v_row_amax, void *z_tensor_amax, const void *flags, const void *units, const void *n_units,
                                    void *stream);
+/* The FORWARD of a layer whose output is needed on a known set of tiles only (rn_reg_need_tiles), over the work lists of that set's flags:
+ *   rn_wino_input_group_list: thread -> entry of `units` -> tile.  A flagged tile gets what rn_wino_input_group stores (bit for bit) and its
+ *       row word; the other tiles of a listed 16-row unit get ZERO rows (the weight gradient reads whole units of a kept V); nothing else
+ *       is visited.  The caller zeroes the row words.  tensor_amax as rn_wino_input_group.
+ *   rn_wino_output_group_list: thread -> entry of `tiles` (n_tiles = counts) -> tile.  A listed tile gets what rn_wino_output_group stores
+ *       (result, sign bits, amax table); every other tile is neither read nor written. */
+int rn_wino_input_group_list(const rn_wino_group *g, float *V, int C, int64_t tile_offset, int64_t Tpad, void *row_amax,
+                             void *tensor_amax, const void *flags, const void *units, const void *n_units, void *stream);
+int rn_wino_output_group_list(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
+                              const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
+                              const void *tiles, const void *n_tiles, void *stream);
 int rn_wino_input(const float *x, float *V, int N, int H, int W, int C, int64_t tile_offset, int64_t Tpad, void *stream);
 int rn_wino_output(const float *M, float *y, int N, int H, int W, int Cout, int64_t tile_offset, int64_t Tpad,
                    const float *scale, const float *shift, const float *add, const float *mask, int mask_mode, int act,
