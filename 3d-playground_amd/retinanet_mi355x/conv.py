@@ -90,18 +90,8 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
     row instead -- the Winograd stage); a dense result gets words of its own (y._rn_amax), `amax` = the words several launches that fill
     ONE tensor share (the parity classes of a stride-2 data gradient)."""
     lib = _hip.load()
-    N, Hi, Wi, Cin = x.shape
-    Ho, Wo, Cout, kh, kw, a, b, p, ds = geom
-    p_h, p_w = p if isinstance(p, tuple) else (p, p)
-    os_, oo_h, oo_w, Hy, Wy = (1, 0, 0, Ho, Wo) if out_map is None else out_map
-    ybs = Hy * Wy * Cout if y_batch_stride is None else y_batch_stride
-    if add_batch_stride is None:
-        add_batch_stride = ybs if add_mode == 1 else add_hw[0] * add_hw[1] * Cout
-    a2 = (0, 0, 0, 0) if add2 is None else (3, add2.shape[1], add2.shape[2], add2.shape[1] * add2.shape[2] * Cout)
     mask_ptr, mask_mode = _mask_operand(mask, mask_mode)
-    d = ConvDesc(N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, a, b, p_h, p_w, ds, act, add_mode, add_hw[0], add_hw[1],
-                 mask_mode, int(in_relu), os_, oo_h, oo_w, Hy, Wy,
-                 a2[0], a2[1], a2[2], a2[3], Hi * Wi * Cin, ybs, add_batch_stride, w_batch_stride)
+    d = _make_desc(x, geom, act, add_mode, add_hw, mask_mode, in_relu, out_map, y_batch_stride, add_batch_stride, add2, w_batch_stride)
     amax_drop(y)                                         # a reused destination: the words of what it held before are stale
     if row_active is not None:                           # tile flags of the Winograd stage (rn_conv_desc.row_active)
         d.row_active = row_active.data_ptr()
@@ -111,12 +101,9 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
     d.sign_out = None if bits is None else bits.data_ptr()
     yam = None
     if want_amax() and not w_batch_stride and y_batch_stride is None and (out_map is None or amax is not None):
-        yam = amax if amax is not None else amax_slot(y.device, N)
+        yam = amax if amax is not None else amax_slot(y.device, d.N)
         d.y_amax = yam.data_ptr()
-    if kind is None:
-        kind = "conv_igemm_4x1" if Cout <= 64 else "conv_igemm_2x2"
-    if prof.BY_SHAPE:                                    # profiling aid (tools/profile_layers.py): one row per layer shape
-        kind += " %dx%dx%d %d->%d k%d a%d b%d ds%d%s" % (N, Ho, Wo, Cin, Cout, kh, a, b, ds, " x36" if w_batch_stride else "")
+    kind = _kind(kind or ("conv_igemm_4x1" if d.Cout <= 64 else "conv_igemm_2x2"), d)
     ws_bytes = 0 if w_batch_stride else lib.rn_conv_splitk_workspace_bytes(ctypes.byref(d))   # > 0: few output tiles, long K -> split-K
     if ws_bytes > 0:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
@@ -138,7 +125,7 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
         wptr, d.w_format = ws.data_ptr(), 2
     nb = 0.0
     if prof.ACTIVE is not None:            # algorithmic bytes: every operand once (the split kernels read weights as 6-byte terms)
-        out_el = N * Ho * Wo * Cout
+        out_el = d.N * d.Ho * d.Wo * d.Cout
         mask_el = 0.0 if mask is None else (1.0 / 32 if mask_mode & MASK_BITS else 1.0)
         nb = 4.0 * (x.numel() + out_el * (1 + (add is not None) + mask_el + (1.0 / 32 if bits is not None else 0.0))) \
             + {0: 4.0, 1: 6.0, 2: 6.0, 3: 4.0}[d.w_format] * w_packed.numel() + (4.0 * add2.numel() if add2 is not None else 0.0)
@@ -151,7 +138,9 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
     return y
 
 
-def _make_desc(x, geom, act, add_mode, add_hw, mask_mode, in_relu, out_map, y_batch_stride, add_batch_stride, add2):
+def _make_desc(x, geom, act, add_mode, add_hw, mask_mode, in_relu, out_map, y_batch_stride, add_batch_stride, add2, w_batch_stride=0):
+    """The rn_conv_desc of one problem (x: anything with the input's shape; geom, out_map, add2 as conv_igemm takes them) -- the one place
+    a descriptor is filled from Python.  The pointer fields and w_format are the caller's to set."""
     N, Hi, Wi, Cin = x.shape
     Ho, Wo, Cout, kh, kw, a, b, p, ds = geom
     p_h, p_w = p if isinstance(p, tuple) else (p, p)
@@ -162,7 +151,48 @@ def _make_desc(x, geom, act, add_mode, add_hw, mask_mode, in_relu, out_map, y_ba
     a2 = (0, 0, 0, 0) if add2 is None else (3, add2.shape[1], add2.shape[2], add2.shape[1] * add2.shape[2] * Cout)
     return ConvDesc(N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, a, b, p_h, p_w, ds, act, add_mode, add_hw[0], add_hw[1],
                     mask_mode, int(in_relu), os_, oo_h, oo_w, Hy, Wy, a2[0], a2[1], a2[2], a2[3],
-                    Hi * Wi * Cin, ybs, add_batch_stride)
+                    Hi * Wi * Cin, ybs, add_batch_stride, w_batch_stride)
+
+
+def _kind(family, d, grouped=False, geometry=True):
+    """What a launch is timed under: its kernel family and, with prof.BY_SHAPE (a profiling aid, tools/profile_layers.py: one row per
+    layer shape), the shape of the problem d -- of a group's first problem, which shares its channels and taps with the others."""
+    if not prof.BY_SHAPE:
+        return family
+    if grouped:
+        return family + " grouped %d->%d k%d" % (d.Cin, d.Cout, d.kh)
+    shape = " %dx%dx%d %d->%d k%d" % (d.N, d.Ho, d.Wo, d.Cin, d.Cout, d.kh)
+    return family + shape + (" a%d b%d ds%d%s" % (d.a, d.b, d.div_shift, " x36" if d.w_batch_stride else "") if geometry else "")
+
+
+def _conv_group(problems, act, x_dtype=None, operands=True, sign=True):
+    """The rn_conv_group of up to RN_MAX_GROUP problems (dicts with x, y, geom and optional add, mask, mask_mode, y_batch_stride, sign)
+    with everything but tile_end (_tile_ends).  The engine's policy: x_dtype, what every x must be (the results then all fp32 or none
+    of them); operands, whether it takes an addend and a mask; sign, whether a dense result may get sign words when its problem asks."""
+    g = _hip.ConvGroup()
+    g.n = len(problems)
+    yf32 = problems[0]["y"].dtype == torch.float32
+    for i, pr in enumerate(problems):
+        x, y, ybs = pr["x"], pr["y"], pr.get("y_batch_stride")
+        assert x_dtype is None or (x.dtype == x_dtype and (y.dtype == torch.float32) == yf32)
+        add, mask = (pr.get("add"), pr.get("mask")) if operands else (None, None)
+        mask_ptr, mmode = _mask_operand(mask, pr.get("mask_mode", 2))
+        d = _make_desc(x, pr["geom"], act, 1 if add is not None else 0, (0, 0), mmode, False, None, ybs, None, None)
+        amax_drop(y)
+        bits = _sign_words(y, sign and pr.get("sign", False) and ybs is None)
+        d.sign_out = None if bits is None else bits.data_ptr()
+        g.d[i] = d
+        g.x[i], g.y[i], g.add[i], g.mask[i] = x.data_ptr(), y.data_ptr(), _hip.ptr(add), mask_ptr
+    return g
+
+
+def _tile_ends(g, rows, cols):
+    """Fill g.tile_end, the running count of output tiles over the group's problems, for a kernel whose tile is rows x cols."""
+    total = 0
+    for i in range(g.n):
+        d = g.d[i]
+        total += ((d.N * d.Ho * d.Wo + rows - 1) // rows) * ((d.Cout + cols - 1) // cols)
+        g.tile_end[i] = total
 
 
 # ---------------------------------------------------------------------------------------------- Winograd F(4x4,3x3)
@@ -835,35 +865,19 @@ def conv_igemm_grouped(problems, w_packed, scale=None, shift=None, act=ACT_NONE,
     """One launch for up to 5 problems sharing weights / epilogue scalars (the pyramid levels of a head tower).
     problems: list of dicts with x, y, geom and optional add, mask, mask_mode, y_batch_stride, sign (write y's sign bits)."""
     lib = _hip.load()
-    g = _hip.ConvGroup()
-    g.n = len(problems)
-    total = 0
-    wptr, wfmt, wus = None, None, None
+    g = _conv_group(problems, act)
+    wptr, wfmt, wus = _w_operand(w_packed, g.d[0])       # the problems share Cin / Cout / taps: one kernel family, one weight form for all
     yams = []
-    for i, pr in enumerate(problems):
-        x, geom = pr["x"], pr["geom"]
-        add, mask = pr.get("add"), pr.get("mask")
-        mask_ptr, mmode = _mask_operand(mask, pr.get("mask_mode", 2))
-        d = _make_desc(x, geom, act, 1 if add is not None else 0, (0, 0), mmode, False, None, pr.get("y_batch_stride"), None, None)
-        if wfmt is None:                       # the problems share Cin / Cout / taps: one kernel family, one weight form for all
-            wptr, wfmt, wus = _w_operand(w_packed, d)
+    for i, pr in enumerate(problems):                    # what only this engine has: the weight form and the split3 amax words
+        d, x = g.d[i], pr["x"]
         d.w_format, d.w_unscale = wfmt, wus
         if wfmt == 3:
             d.x_amax, d.x_amax_img_stride, d.x_amax_row_stride = amax_words(x).data_ptr(), 1, 0
-        amax_drop(pr["y"])
-        bits = _sign_words(pr["y"], pr.get("sign", False) and pr.get("y_batch_stride") is None)
-        d.sign_out = None if bits is None else bits.data_ptr()
-        yam = amax_slot(x.device, x.shape[0]) if want_amax() and pr.get("y_batch_stride") is None else None
-        yams.append(yam)
-        d.y_amax = None if yam is None else yam.data_ptr()
-        g.d[i] = d
-        M = d.N * d.Ho * d.Wo
-        total += (M + 255) // 256 if d.Cout <= 64 else ((M + 127) // 128) * ((d.Cout + 127) // 128)
-        g.tile_end[i] = total
-        g.x[i], g.y[i], g.add[i], g.mask[i] = x.data_ptr(), pr["y"].data_ptr(), _hip.ptr(add), mask_ptr
-    kind = "conv_igemm_4x1" if problems[0]["geom"][2] <= 64 else "conv_igemm_2x2"
-    if prof.BY_SHAPE:
-        kind += " grouped %d->%d k%d" % (g.d[0].Cin, g.d[0].Cout, g.d[0].kh)
+        yams.append(amax_slot(x.device, x.shape[0]) if want_amax() and pr.get("y_batch_stride") is None else None)
+        d.y_amax = _hip.ptr(yams[i])
+    narrow = g.d[0].Cout <= 64                           # at most 64 output channels: 256-row strips, else 128 x 128 tiles
+    _tile_ends(g, *((256, 64) if narrow else (128, 128)))
+    kind = _kind("conv_igemm_4x1" if narrow else "conv_igemm_2x2", g.d[0], grouped=True)
     nb = 0.0
     if prof.ACTIVE is not None:
         nb = {0: 4.0, 1: 6.0, 3: 4.0}[wfmt] * w_packed.numel()
@@ -879,21 +893,30 @@ def conv_igemm_grouped(problems, w_packed, scale=None, shift=None, act=ACT_NONE,
             amax_attach(pr["y"], yam)
 
 
-def fprop(x, w_packed, cout, k, stride, pad, kw_pad=None, **kw):
-    """Forward convolution, NHWC in -> new NHWC out."""
+def _fprop(conv, dtype, x, w_packed, cout, k, stride, pad, kw_pad, kw):
+    """A fresh [N,Ho,Wo,cout] result of `dtype` and engine `conv`'s forward launch into it."""
     N, Hi, Wi, _ = x.shape
     Ho, Wo = out_size(Hi, k, stride, pad), out_size(Wi, k, stride, pad)
-    y = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=x.device)
-    return conv_igemm(x, w_packed, y, (Ho, Wo, cout, k, k if kw_pad is None else kw_pad, stride, 1, -pad, 0), **kw)
+    y = torch.empty((N, Ho, Wo, cout), dtype=dtype, device=x.device)
+    return conv(x, w_packed, y, (Ho, Wo, cout, k, k if kw_pad is None else kw_pad, stride, 1, -pad, 0), **kw)
+
+
+def _dgrad(conv, dtype, dy, w_packed_dgrad, in_hw, cin, k, stride, pad, kw):
+    """A fresh [N,Hi,Wi,cin] result of `dtype` and engine `conv`'s generic data-gradient launch into it."""
+    Hi, Wi = in_hw
+    dx = torch.empty((dy.shape[0], Hi, Wi, cin), dtype=dtype, device=dy.device)
+    return conv(dy, w_packed_dgrad, dx, (Hi, Wi, cin, k, k, 1, -1, pad, stride.bit_length() - 1), **kw)
+
+
+def fprop(x, w_packed, cout, k, stride, pad, kw_pad=None, **kw):
+    """Forward convolution, NHWC in -> new NHWC out."""
+    return _fprop(conv_igemm, torch.float32, x, w_packed, cout, k, stride, pad, kw_pad, kw)
 
 
 def dgrad(dy, w_packed_dgrad, in_hw, cin, k, stride, pad, **kw):
     """Data gradient, generic form: dy [N,Ho,Wo,Cout(_pad)] -> dx [N,Hi,Wi,Cin].  For stride 2 every tap is tried
     at every input pixel and 3 of 4 fail the divisibility test (wasted MFMAs): prefer dgrad_s2_classes."""
-    N = dy.shape[0]
-    Hi, Wi = in_hw
-    dx = torch.empty((N, Hi, Wi, cin), dtype=torch.float32, device=dy.device)
-    return conv_igemm(dy, w_packed_dgrad, dx, (Hi, Wi, cin, k, k, 1, -1, pad, stride.bit_length() - 1), **kw)
+    return _dgrad(conv_igemm, torch.float32, dy, w_packed_dgrad, in_hw, cin, k, stride, pad, kw)
 
 
 def s2_classes(k, pad):
@@ -911,28 +934,34 @@ def s2_classes(k, pad):
     return out
 
 
-def dgrad_s2_classes(dy, class_weights, in_hw, cin, k, pad, flops=0.0, **kw):
-    """Stride-2 data gradient without wasted taps: one launch per output-parity class, each a stride-1 convolution
-    of dy with that class's tap subset (class_weights[i] from pack_weights(..., taps=...)), stored at the class's
-    strided positions.  add / mask (same geometry as dx) apply per class."""
-    N, Ho, Wo, _ = dy.shape
+def _dgrad_s2_classes(conv, dtype, share_amax, dy, class_weights, in_hw, cin, k, pad, flops, kw):
+    """dgrad_s2_classes for engine `conv` and a result of `dtype`.  share_amax (fp32, split3): the classes fill ONE tensor, so all of
+    them leave their exponents in one set of amax words, attached to the result."""
+    N = dy.shape[0]
     Hi, Wi = in_hw
-    dx = torch.empty((N, Hi, Wi, cin), dtype=torch.float32, device=dy.device)
+    dx = torch.empty((N, Hi, Wi, cin), dtype=dtype, device=dy.device)
     classes = s2_classes(k, pad)
     if len(classes) < 4:
         dx.zero_()                                  # classes without taps (k = 1) receive no gradient
     total_taps = sum(c[2][1] * c[2][3] for c in classes)
-    slot = amax_slot(dy.device, N) if want_amax() else None   # split3: the classes fill ONE tensor: one set of amax words for all of them
+    if share_amax:
+        kw = dict(kw, amax=amax_slot(dy.device, N))
     for (ph, pw, (r0, nr, s0, ns), (dh0, dw0)), wc in zip(classes, class_weights):
         gh, gw = (Hi - ph + 1) // 2, (Wi - pw + 1) // 2
         if gh <= 0 or gw <= 0:
             continue
         # input row = a + dh0 - i, input column = b + dw0 - j  (a = 1, b = -1, p = dh0, p_w = dw0)
-        conv_igemm(dy, wc, dx, (gh, gw, cin, nr, ns, 1, -1, (dh0, dw0), 0), out_map=(2, ph, pw, Hi, Wi),
-                   flops=flops * nr * ns / total_taps, amax=slot, **kw)
-    if slot is not None:
-        amax_attach(dx, slot)
+        conv(dy, wc, dx, (gh, gw, cin, nr, ns, 1, -1, (dh0, dw0), 0), out_map=(2, ph, pw, Hi, Wi), flops=flops * nr * ns / total_taps, **kw)
+    if share_amax:
+        amax_attach(dx, kw["amax"])
     return dx
+
+
+def dgrad_s2_classes(dy, class_weights, in_hw, cin, k, pad, flops=0.0, **kw):
+    """Stride-2 data gradient without wasted taps: one launch per output-parity class, each a stride-1 convolution
+    of dy with that class's tap subset (class_weights[i] from pack_weights(..., taps=...)), stored at the class's
+    strided positions.  add / mask (same geometry as dx) apply per class."""
+    return _dgrad_s2_classes(conv_igemm, torch.float32, want_amax(), dy, class_weights, in_hw, cin, k, pad, flops, kw)
 
 
 def wgrad(dy, x, dw, cout, k, stride, pad, kw_pad=None, in_relu=False, flops=0.0, colsum=None):
@@ -1181,6 +1210,8 @@ def pack_weights_bf16(weight, mode=0, scale=None, c_pad=None, taps=None):
 
 def _p8_suffix(fn_name, d, yf32):
     """"_p8" when a single launch takes the eight-wave 256 x 256 kernel for this problem (profiling only: the kernel families are timed apart)."""
+    if prof.ACTIVE is None:
+        return ""
     t = getattr(_hip.load(), fn_name)(ctypes.byref(d), int(yf32))
     return "_p8" if t == 256256 and fn_name.endswith("fp8_tile") or t >= 1000000 else ""
 
@@ -1196,11 +1227,7 @@ def conv_igemm_bf16(x, w_packed, y, geom, scale=None, shift=None, add=None, add_
     amax_drop(y)
     bits = _sign_words(y, sign and y_batch_stride is None and out_map is None and y.dtype == torch.bfloat16)
     d.sign_out = None if bits is None else bits.data_ptr()
-    kind = "conv_igemm_bf16"
-    if prof.ACTIVE is not None:
-        kind += _p8_suffix("rn_conv_igemm_bf16_tile", d, y.dtype == torch.float32)
-    if prof.BY_SHAPE:                                    # profiling aid (tools/profile_layers.py): one row per layer shape
-        kind += " %dx%dx%d %d->%d k%d a%d b%d ds%d" % (d.N, d.Ho, d.Wo, d.Cin, d.Cout, d.kh, d.a, d.b, d.div_shift)
+    kind = _kind("conv_igemm_bf16" + _p8_suffix("rn_conv_igemm_bf16_tile", d, y.dtype == torch.float32), d)
     rc = prof.timed(kind, flops, lambda: lib.rn_conv_igemm_bf16(
         ctypes.byref(d), x.data_ptr(), w_packed.data_ptr(), y.data_ptr(), int(y.dtype == torch.float32), _hip.ptr(scale),
         _hip.ptr(shift), _hip.ptr(add), mask_ptr, _hip.stream()))
@@ -1209,18 +1236,12 @@ def conv_igemm_bf16(x, w_packed, y, geom, scale=None, shift=None, add=None, add_
 
 
 def fprop_bf16(x, w_packed, cout, k, stride, pad, out_dtype=torch.bfloat16, **kw):
-    N, Hi, Wi, _ = x.shape
-    Ho, Wo = out_size(Hi, k, stride, pad), out_size(Wi, k, stride, pad)
-    y = torch.empty((N, Ho, Wo, cout), dtype=out_dtype, device=x.device)
-    return conv_igemm_bf16(x, w_packed, y, (Ho, Wo, cout, k, k, stride, 1, -pad, 0), **kw)
+    return _fprop(conv_igemm_bf16, out_dtype, x, w_packed, cout, k, stride, pad, None, kw)
 
 
 def dgrad_bf16(dy, w_packed_dgrad, in_hw, cin, k, pad, **kw):
     """Stride-1 data gradient in bf16 (dy [N,Ho,Wo,Cout(_pad)] bf16 -> dx [N,Hi,Wi,Cin] bf16)."""
-    N = dy.shape[0]
-    Hi, Wi = in_hw
-    dx = torch.empty((N, Hi, Wi, cin), dtype=torch.bfloat16, device=dy.device)
-    return conv_igemm_bf16(dy, w_packed_dgrad, dx, (Hi, Wi, cin, k, k, 1, -1, pad, 0), **kw)
+    return _dgrad(conv_igemm_bf16, torch.bfloat16, dy, w_packed_dgrad, in_hw, cin, k, 1, pad, kw)
 
 
 def wgrad_bf16(dy, x, dw, cout, k, stride, pad, flops=0.0, colsum=None):
@@ -1263,28 +1284,12 @@ def wgrad_bf16_grouped(dys, xs, dw, cout, k, stride, pad, flops=0.0, colsum=None
 def dgrad_any_bf16(dy, w_packed_dgrad, in_hw, cin, k, stride, pad, **kw):
     """Data gradient, generic form (every tap tried at every input pixel; for stride 2 three of four fail the divisibility
     test): used for the 1x1 stride-2 shortcuts, whose single tap makes the waste irrelevant."""
-    N = dy.shape[0]
-    Hi, Wi = in_hw
-    dx = torch.empty((N, Hi, Wi, cin), dtype=torch.bfloat16, device=dy.device)
-    return conv_igemm_bf16(dy, w_packed_dgrad, dx, (Hi, Wi, cin, k, k, 1, -1, pad, stride.bit_length() - 1), **kw)
+    return _dgrad(conv_igemm_bf16, torch.bfloat16, dy, w_packed_dgrad, in_hw, cin, k, stride, pad, kw)
 
 
 def dgrad_s2_classes_bf16(dy, class_weights, in_hw, cin, k, pad, flops=0.0, **kw):
     """dgrad_s2_classes with bf16 operands: one launch per output-parity class, stored at the class's strided positions."""
-    N, Ho, Wo, _ = dy.shape
-    Hi, Wi = in_hw
-    dx = torch.empty((N, Hi, Wi, cin), dtype=torch.bfloat16, device=dy.device)
-    classes = s2_classes(k, pad)
-    if len(classes) < 4:
-        dx.zero_()
-    total_taps = sum(c[2][1] * c[2][3] for c in classes)
-    for (ph, pw, (r0, nr, s0, ns), (dh0, dw0)), wc in zip(classes, class_weights):
-        gh, gw = (Hi - ph + 1) // 2, (Wi - pw + 1) // 2
-        if gh <= 0 or gw <= 0:
-            continue
-        conv_igemm_bf16(dy, wc, dx, (gh, gw, cin, nr, ns, 1, -1, (dh0, dw0), 0), out_map=(2, ph, pw, Hi, Wi),
-                        flops=flops * nr * ns / total_taps, **kw)
-    return dx
+    return _dgrad_s2_classes(conv_igemm_bf16, torch.bfloat16, False, dy, class_weights, in_hw, cin, k, pad, flops, kw)
 
 
 def maxpool_fwd_bf16(x, want_argmax=False):
@@ -1321,29 +1326,11 @@ def conv_igemm_bf16_grouped(problems, w_packed, scale=None, shift=None, act=ACT_
     """conv_igemm_grouped with bf16 operands: one launch for up to 5 problems sharing weights / epilogue scalars (the
     pyramid levels of a head layer).  All results bf16, or all fp32 (the dtype of the first y decides)."""
     lib = _hip.load()
-    g = _hip.ConvGroup()
-    g.n = len(problems)
-    total = 0
     yf32 = problems[0]["y"].dtype == torch.float32
-    for i, pr in enumerate(problems):
-        x, geom = pr["x"], pr["geom"]
-        add, mask = pr.get("add"), pr.get("mask")
-        assert x.dtype == torch.bfloat16 and (pr["y"].dtype == torch.float32) == yf32
-        mask_ptr, mmode = _mask_operand(mask, pr.get("mask_mode", 2))
-        d = _make_desc(x, geom, act, 1 if add is not None else 0, (0, 0), mmode, False, None, pr.get("y_batch_stride"), None, None)
-        amax_drop(pr["y"])
-        bits = _sign_words(pr["y"], pr.get("sign", False) and pr.get("y_batch_stride") is None and not yf32)
-        d.sign_out = None if bits is None else bits.data_ptr()
-        g.d[i] = d
-        g.x[i], g.y[i], g.add[i], g.mask[i] = x.data_ptr(), pr["y"].data_ptr(), _hip.ptr(add), mask_ptr
-    trm, trn = divmod(lib.rn_conv_igemm_bf16_tile_rows(ctypes.byref(g), int(yf32)), 1000)   # the launcher's tile for this group
-    for i in range(g.n):
-        d = g.d[i]
-        M = d.N * d.Ho * d.Wo
-        total += ((M + trm - 1) // trm) * ((d.Cout + trn - 1) // trn)
-        g.tile_end[i] = total
-    kind = "conv_igemm_bf16" + ("_p8" if (trm, trn) == (256, 256) else "") \
-        + (" grouped %d->%d k%d" % (g.d[0].Cin, g.d[0].Cout, g.d[0].kh) if prof.BY_SHAPE else "")
+    g = _conv_group(problems, act, x_dtype=torch.bfloat16, sign=not yf32)
+    tile = divmod(lib.rn_conv_igemm_bf16_tile_rows(ctypes.byref(g), int(yf32)), 1000)       # the launcher's tile for this group
+    _tile_ends(g, *tile)
+    kind = _kind("conv_igemm_bf16" + ("_p8" if tile == (256, 256) else ""), g.d[0], grouped=True)
     rc = prof.timed(kind, flops, lambda: lib.rn_conv_igemm_bf16_grouped(
         ctypes.byref(g), w_packed.data_ptr(), int(yf32), _hip.ptr(scale), _hip.ptr(shift), _hip.stream()))
     _hip.check(rc, "rn_conv_igemm_bf16_grouped")
@@ -1428,11 +1415,7 @@ def conv_igemm_fp8(xq, wq, y, geom, scale, shift=None, add=None, add_mode=0, add
     assert xq.dtype == torch.uint8 and wq.dtype == torch.uint8 and y.dtype in (torch.uint8, torch.float32)
     d = _make_desc(xq, geom, act, add_mode, add_hw, 0, False, None, y_batch_stride, None, None)
     amax_drop(y)
-    kind = "conv_igemm_fp8"
-    if prof.ACTIVE is not None:
-        kind += _p8_suffix("rn_conv_igemm_fp8_tile", d, y.dtype == torch.float32)
-    if prof.BY_SHAPE:
-        kind += " %dx%dx%d %d->%d k%d" % (d.N, d.Ho, d.Wo, d.Cin, d.Cout, d.kh)
+    kind = _kind("conv_igemm_fp8" + _p8_suffix("rn_conv_igemm_fp8_tile", d, y.dtype == torch.float32), d, geometry=False)
     rc = prof.timed(kind, flops, lambda: lib.rn_conv_igemm_fp8(
         ctypes.byref(d), xq.data_ptr(), wq.data_ptr(), y.data_ptr(), int(y.dtype == torch.float32), _hip.ptr(scale), _hip.ptr(shift),
         _hip.ptr(add), float(add._rn_scale) if add is not None else 1.0, 1.0 / float(out_scale), _hip.stream()))
@@ -1446,22 +1429,11 @@ def conv_igemm_fp8_grouped(problems, wq, scale, shift=None, act=ACT_NONE, out_sc
     """rn_conv_igemm_fp8_grouped: up to RN_MAX_GROUP problems (dicts with x, y, geom, optional y_batch_stride) that share the
     e4m3 weights, the folded scale vector (so: ONE input scale for all of them) and the activation; results all e4m3 or all fp32."""
     lib = _hip.load()
-    g = _hip.ConvGroup()
-    g.n = len(problems)
     yf32 = problems[0]["y"].dtype == torch.float32
-    total = 0
-    for i, pr in enumerate(problems):
-        x = pr["x"]
-        assert x.dtype == torch.uint8 and (pr["y"].dtype == torch.float32) == yf32
-        g.d[i] = _make_desc(x, pr["geom"], act, 0, (0, 0), 0, False, None, pr.get("y_batch_stride"), None, None)
-        amax_drop(pr["y"])
-        g.x[i], g.y[i], g.add[i], g.mask[i] = x.data_ptr(), pr["y"].data_ptr(), None, None
-    trm, trn = divmod(lib.rn_conv_igemm_fp8_tile_rows(ctypes.byref(g), int(yf32)), 1000)    # the launcher's tile for this group
-    for i in range(g.n):
-        d = g.d[i]
-        total += ((d.N * d.Ho * d.Wo + trm - 1) // trm) * ((d.Cout + trn - 1) // trn)
-        g.tile_end[i] = total
-    kind = "conv_igemm_fp8" + ("_p8" if (trm, trn) == (256, 256) else "") + (" grouped %d->%d k%d" % (g.d[0].Cin, g.d[0].Cout, g.d[0].kh) if prof.BY_SHAPE else "")
+    g = _conv_group(problems, act, x_dtype=torch.uint8, operands=False, sign=False)
+    tile = divmod(lib.rn_conv_igemm_fp8_tile_rows(ctypes.byref(g), int(yf32)), 1000)        # the launcher's tile for this group
+    _tile_ends(g, *tile)
+    kind = _kind("conv_igemm_fp8" + ("_p8" if tile == (256, 256) else ""), g.d[0], grouped=True)
     rc = prof.timed(kind, flops, lambda: lib.rn_conv_igemm_fp8_grouped(
         ctypes.byref(g), wq.data_ptr(), int(yf32), _hip.ptr(scale), _hip.ptr(shift), 1.0, 1.0 / float(out_scale), _hip.stream()))
     _hip.check(rc, "rn_conv_igemm_fp8_grouped")

@@ -247,15 +247,41 @@ class Layer:
         is e4m3 with this layer's calibrated scale, or fp32 when `out` is an fp32 destination (the head outputs)."""
         s = self.spec
         Ho, Wo = out_hw
-        sx = float(x._rn_scale)
-        scale = self._fp8_scales.get(sx)
-        if scale is None:                              # x_scale * weight row scale * folded batch-norm scale, per input scale seen
-            scale = self._fp8_scales[sx] = (self.wscale * sx).contiguous()
         if out is None:
             out = torch.empty((x.shape[0], Ho, Wo, s.cout), dtype=torch.uint8, device=x.device)
-        return cv.conv_igemm_fp8(x, self.wq, out, (Ho, Wo, s.cout, s.k, self.kw_pad, s.stride, 1, -s.pad, 0), scale, shift=self.shift,
-                                 add=add, add_mode=add_mode, add_hw=add_hw, act=act, y_batch_stride=y_batch_stride,
+        return cv.conv_igemm_fp8(x, self.wq, out, (Ho, Wo, s.cout, s.k, self.kw_pad, s.stride, 1, -s.pad, 0), self._fp8_scale(float(x._rn_scale)),
+                                 shift=self.shift, add=add, add_mode=add_mode, add_hw=add_hw, act=act, y_batch_stride=y_batch_stride,
                                  out_scale=self.out_scale, flops=self.flops(x.shape[0], Ho, Wo))
+
+    def _fp8_scale(self, sx):
+        """The scale vector of an e4m3 launch whose input has scale sx: x_scale * weight row scale * folded batch-norm scale, made once
+        per input scale seen."""
+        scale = self._fp8_scales.get(sx)
+        if scale is None:
+            scale = self._fp8_scales[sx] = (self.wscale * sx).contiguous()
+        return scale
+
+    def _problems(self, xs, dtype, outs=None, y_batch_stride=None, sign=False, in_hws=None, adds=None, masks=None):
+        """The problems of ONE grouped launch over xs (the dicts of cv.conv_igemm*_grouped) -> (problems, results, FLOPs).  Forward: the
+        results are outs, or fresh [N,Ho,Wo,cout] tensors of dtype.  With in_hws, the stride-1 data gradient of the output gradients xs:
+        fresh [N,Hi,Wi,cin] results, adds / masks per problem."""
+        s = self.spec
+        probs, ys, fl = [], [], 0.0
+        for i, x in enumerate(xs):
+            N, H, W, _ = x.shape
+            if in_hws is None:
+                Ho, Wo = cv.out_size(H, s.k, s.stride, s.pad), cv.out_size(W, s.k, s.stride, s.pad)
+                shape, geom = (N, Ho, Wo, s.cout), (Ho, Wo, s.cout, s.k, self.kw_pad, s.stride, 1, -s.pad, 0)
+                fl += self.flops(N, Ho, Wo)
+            else:
+                Hi, Wi = in_hws[i]
+                shape, geom = (N, Hi, Wi, s.cin), (Hi, Wi, s.cin, s.k, s.k, 1, -1, s.pad, 0)
+                fl += self.flops(N, H, W)
+            y = outs[i] if outs is not None else torch.empty(shape, dtype=dtype, device=x.device)
+            ys.append(y)
+            probs.append({"x": x, "y": y, "geom": geom, "y_batch_stride": y_batch_stride, "sign": sign,
+                          "add": None if adds is None else adds[i], "mask": None if masks is None else masks[i]})
+        return probs, ys, fl
 
     def fwd_group(self, xs, act=cv.ACT_NONE, outs=None, y_batch_stride=None, wino=False, shared_v=None, need=None, need_in=None,
                   need_fill=None):
@@ -272,28 +298,13 @@ class Layer:
             if len(scales) > 1 or len(xs) > _hip.RN_MAX_GROUP:      # different input scales cannot share one folded scale vector
                 return [self._fwd_fp8(x, (x.shape[1], x.shape[2]), act, None, 0, (0, 0), None if outs is None else outs[i], y_batch_stride)
                         for i, x in enumerate(xs)]
-            sx = scales.pop()
-            scale = self._fp8_scales.get(sx)
-            if scale is None:
-                scale = self._fp8_scales[sx] = (self.wscale * sx).contiguous()
-            probs, ys, fl = [], [], 0.0
-            for i, x in enumerate(xs):
-                N, Hi, Wi, _ = x.shape
-                y = outs[i] if outs is not None else torch.empty((N, Hi, Wi, s.cout), dtype=torch.uint8, device=x.device)
-                ys.append(y)
-                fl += self.flops(N, Hi, Wi)
-                probs.append({"x": x, "y": y, "geom": (Hi, Wi, s.cout, s.k, self.kw_pad, 1, 1, -s.pad, 0), "y_batch_stride": y_batch_stride})
-            cv.conv_igemm_fp8_grouped(probs, self.wq, scale, shift=self.shift, act=act, out_scale=self.out_scale, flops=fl)
+            probs, ys, fl = self._problems(xs, torch.uint8, outs, y_batch_stride)
+            cv.conv_igemm_fp8_grouped(probs, self.wq, self._fp8_scale(scales.pop()), shift=self.shift, act=act, out_scale=self.out_scale,
+                                      flops=fl)
             return ys
+        sign = self.sign and act == cv.ACT_RELU
         if mode == "bf16":                             # the levels of a head layer as one grouped bf16 launch
-            probs, ys, fl = [], [], 0.0
-            for i, x in enumerate(xs):
-                N, Hi, Wi, _ = x.shape
-                y = outs[i] if outs is not None else torch.empty((N, Hi, Wi, s.cout), dtype=torch.bfloat16, device=x.device)
-                ys.append(y)
-                fl += self.flops(N, Hi, Wi)
-                probs.append({"x": x, "y": y, "geom": (Hi, Wi, s.cout, s.k, self.kw_pad, 1, 1, -s.pad, 0),
-                              "y_batch_stride": y_batch_stride, "sign": self.sign and act == cv.ACT_RELU})
+            probs, ys, fl = self._problems(xs, torch.bfloat16, outs, y_batch_stride, sign)
             cv.conv_igemm_bf16_grouped(probs, self.wf16, scale=self.scale, shift=self.shift, act=act, flops=fl)
             for y in ys:
                 y._rn_qscale = self.out_scale
@@ -302,19 +313,11 @@ class Layer:
             fl = sum(self.flops(x.shape[0], x.shape[1], x.shape[2]) for x in xs)
             r = cv.wino_conv_group(xs, self.wino_weights(0), outs=outs, scale=self.scale, shift=self.shift, act=act, flops=fl,
                                    keep_v=self.keep_v, y_batch_stride=y_batch_stride or 0, V_in=shared_v if self.keep_v else None,
-                                   sign=self.sign and act == cv.ACT_RELU, need=need, need_in=need_in, need_fill=need_fill)
+                                   sign=sign, need=need, need_in=need_in, need_fill=need_fill)
             ys, self.saved_v = r if self.keep_v else (r, None)
             return ys
         assert need is None, "%s does not take the Winograd form: no need sets" % s.name
-        probs, ys, fl = [], [], 0.0
-        for i, x in enumerate(xs):
-            N, Hi, Wi, _ = x.shape
-            Ho, Wo = cv.out_size(Hi, s.k, s.stride, s.pad), cv.out_size(Wi, s.k, s.stride, s.pad)
-            y = outs[i] if outs is not None else torch.empty((N, Ho, Wo, s.cout), dtype=torch.float32, device=x.device)
-            ys.append(y)
-            fl += self.flops(N, Ho, Wo)
-            probs.append({"x": x, "y": y, "geom": (Ho, Wo, s.cout, s.k, self.kw_pad, s.stride, 1, -s.pad, 0),
-                          "y_batch_stride": y_batch_stride, "sign": self.sign and act == cv.ACT_RELU})
+        probs, ys, fl = self._problems(xs, torch.float32, outs, y_batch_stride, sign)
         cv.conv_igemm_grouped(probs, self.wf, scale=self.scale, shift=self.shift, act=act, flops=fl)
         if outs is None:
             for y in ys:
@@ -330,14 +333,7 @@ class Layer:
         assert s.stride == 1
         self.flags_out_done = False
         if self.bf16:
-            probs, outs, fl = [], [], 0.0
-            for i, g in enumerate(gs):
-                Hi, Wi = in_hws[i]
-                dx = torch.empty((g.shape[0], Hi, Wi, s.cin), dtype=torch.bfloat16, device=g.device)
-                outs.append(dx)
-                fl += self.flops(g.shape[0], g.shape[1], g.shape[2])
-                probs.append({"x": g, "y": dx, "geom": (Hi, Wi, s.cin, s.k, s.k, 1, -1, s.pad, 0),
-                              "add": None if adds is None else adds[i], "mask": None if masks is None else masks[i]})
+            probs, outs, fl = self._problems(gs, torch.bfloat16, in_hws=in_hws, adds=adds, masks=masks)
             cv.conv_igemm_bf16_grouped(probs, self.dgrad_weights16(), flops=fl)
             return outs
         if (wino or self.wino_active) and self.wino_ok and all(g.shape[3] == s.cout for g in gs):
@@ -346,15 +342,7 @@ class Layer:
             self.flags_out_done = flags_out is not None
             return cv.wino_conv_group(gs, self.wino_weights(1), adds=adds, masks=masks, mask_mode=2, flops=fl, V_ready=ready,
                                       flags_out=flags_out)
-        probs, outs, fl = [], [], 0.0
-        for i, g in enumerate(gs):
-            N = g.shape[0]
-            Hi, Wi = in_hws[i]
-            dx = torch.empty((N, Hi, Wi, s.cin), dtype=torch.float32, device=g.device)
-            outs.append(dx)
-            fl += self.flops(N, g.shape[1], g.shape[2])
-            probs.append({"x": g, "y": dx, "geom": (Hi, Wi, s.cin, s.k, s.k, 1, -1, s.pad, 0),
-                          "add": None if adds is None else adds[i], "mask": None if masks is None else masks[i]})
+        probs, outs, fl = self._problems(gs, torch.float32, in_hws=in_hws, adds=adds, masks=masks)
         cv.conv_igemm_grouped(probs, self.dgrad_weights(), flops=fl)
         return outs
 
@@ -364,13 +352,18 @@ class Layer:
         return 2.0 * N * Ho * Wo * s.cout * s.cin * s.k * s.k
 
     # ---- backward
+    def _grad_acc(self, device):
+        """The step's zeroed accumulators, made by the first contribution: dw (the weight gradient, packed like wf) and cs (the column
+        sums of the output gradient)."""
+        if self.dw is None:
+            self.dw = torch.zeros_like(self.wf)
+            self.cs = torch.zeros(self.spec.cout, dtype=torch.float32, device=device)
+
     def bwd_params(self, g, x, in_relu=False, side=None):
         """Accumulate wgrad(g, x) and colsum(g).  g: [N,Ho,Wo,ld] with ld >= cout.  side: a stream for the reductions of the Winograd form
         (cv.wino_wgrad_group); the other forms run where they are called."""
         s = self.spec
-        if self.dw is None:
-            self.dw = torch.zeros_like(self.wf)
-            self.cs = torch.zeros(s.cout, dtype=torch.float32, device=g.device)
+        self._grad_acc(g.device)
         if self.bf16:
             assert not in_relu
             cv.wgrad_bf16(g, x, self.dw, s.cout, s.k, s.stride, s.pad, flops=self.flops(g.shape[0], g.shape[1], g.shape[2]),
@@ -390,10 +383,8 @@ class Layer:
         flags: the tile activity flags of gs, for the Winograd form (cv.wino_wgrad_group); the other forms are dense.
         lists: the buffer their work lists are built in (cv.wino_wgrad_group), or None: the flagged stages visit every tile."""
         s = self.spec
+        self._grad_acc(gs[0].device)
         if (wino or self.wino_active) and self.wino_ok and all(g.shape[3] == s.cout and g.is_contiguous() for g in gs):
-            if self.dw is None:
-                self.dw = torch.zeros_like(self.wf)
-                self.cs = torch.zeros(s.cout, dtype=torch.float32, device=gs[0].device)
             fl = sum(self.flops(g.shape[0], g.shape[1], g.shape[2]) for g in gs)
             du, self.du = getattr(self, "du", None), None
             self.dy_v = cv.wino_wgrad_group(gs, xs, self.dw, self.cs, flops=fl, V=self.saved_v, dU=du, fuse_dgrad_input=FUSE_DY, side=side,
@@ -402,9 +393,6 @@ class Layer:
             return
         if self.bf16 and GROUPED_WGRAD_BF16 and 1 < len(gs) <= 5 and all(g.is_contiguous() and x.is_contiguous() for g, x in zip(gs, xs)) \
                 and len({g.shape[3] for g in gs}) == 1:
-            if self.dw is None:
-                self.dw = torch.zeros_like(self.wf)
-                self.cs = torch.zeros(s.cout, dtype=torch.float32, device=gs[0].device)
             fl = sum(self.flops(g.shape[0], g.shape[1], g.shape[2]) for g in gs)
             cv.wgrad_bf16_grouped(gs, xs, self.dw, s.cout, s.k, s.stride, s.pad, flops=fl, colsum=self.cs)
             return
@@ -413,10 +401,10 @@ class Layer:
 
     def bwd_data(self, g, in_hw, add=None, mask=None, mask_mode=2, add2=None):
         s = self.spec
+        kw = dict(add=add, add_mode=1 if add is not None else 0, mask=mask, mask_mode=mask_mode,
+                  flops=self.flops(g.shape[0], g.shape[1], g.shape[2]))
         if self.bf16:
             assert add2 is None
-            kw = dict(add=add, add_mode=1 if add is not None else 0, mask=mask, mask_mode=mask_mode,
-                      flops=self.flops(g.shape[0], g.shape[1], g.shape[2]))
             if s.stride == 2 and s.k > 1:
                 return cv.dgrad_s2_classes_bf16(g, self.dgrad_weights16(), in_hw, s.cin, s.k, s.pad, **kw)
             if s.stride == 2 and s.k == 1 and s.pad == 0 and mask is None and S2_SHORTCUT_COMPACT:
@@ -438,8 +426,6 @@ class Layer:
             ready, self.dy_v = getattr(self, "dy_v", None), None
             return cv.wino_conv_group([g], self.wino_weights(1), adds=None if add is None else [add],
                                       masks=None if mask is None else [mask], mask_mode=mask_mode, V_ready=ready)[0]
-        kw = dict(add=add, add_mode=1 if add is not None else 0, mask=mask, mask_mode=mask_mode,
-                  flops=self.flops(g.shape[0], g.shape[1], g.shape[2]))
         if s.stride == 2 and s.k > 1:
             assert add2 is None
             return cv.dgrad_s2_classes(g, self.dgrad_weights(), in_hw, s.cin, s.k, s.pad, **kw)
@@ -457,10 +443,7 @@ class Layer:
 
     def bwd_fused(self, g, x, mask=None):
         """bwd_params(g, x) and bwd_data(g, mask=mask) by one launch that reads g once (cv.bwd_1x1_fused) -> the data gradient."""
-        s = self.spec
-        if self.dw is None:
-            self.dw = torch.zeros_like(self.wf)
-            self.cs = torch.zeros(s.cout, dtype=torch.float32, device=g.device)
+        self._grad_acc(g.device)
         return cv.bwd_1x1_fused(g, x, self.dgrad_weights(), self.dw, self.cs, mask=mask, flops=self.flops(g.shape[0], g.shape[1], g.shape[2]))
 
     def bwd_data_compact(self, g):
