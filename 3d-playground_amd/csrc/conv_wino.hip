@@ -100,23 +100,56 @@ __device__ __forceinline__ int wino_locate(const WinoTable &g, int64_t gt, int64
     return q;
 }
 
-// ---------------------------------------------------------------------------------------------- input transform
+// ---------------------------------------------------------------------------------------------- input-side transforms
+// Two tensors come from one pass over a 6x6 input patch: V = B^T d B of the patch (the input transform of the forward and of the data
+// gradient) and, for the weight gradient, Z = A dy A^T of its inner 4x4 --
+//     dL/dg = G^T [ sum over tiles of (A dy A^T) .* (B^T d B) ] G:
+// dU[p] = Z_p^T V_p is the weight-gradient GEMM kernel run as 36 batched 1x1 problems (rn_conv_wgrad_batched); wino_dw_kernel folds
+// G^T dU G into the layer's packed gradient.  Z at position (1,1) is the plain sum of the tile's dy, so the bias gradient is the column
+// sum of that one batch entry.  wino_in_kernel below is every input-side kernel; these are the pieces it is made of.
 #define WINO_SELECT(q, g, pr, EXTRA)                          \
     WinoProblem pr = g.p[0];                                   \
     _Pragma("unroll") for (int i_ = 1; i_ < RN_MAX_GROUP; ++i_) \
         if (q == i_) { pr = g.p[i_]; EXTRA }
 
-__global__ __launch_bounds__(256) void wino_in_kernel(const WinoTable g, float *__restrict__ V, int C, int64_t t0, int64_t Tpad,
-                                                      unsigned *__restrict__ row_amax, unsigned *__restrict__ tensor_amax) {
-    wino_tensor_word(g, tensor_amax, WINO_GAIN_BT);
-    const int cq = C >> 2;
-    // 6x6 patches of neighbouring tiles overlap by two pixels: every input pixel is read by 2.25 tiles.  With the plain id the
-    // tiles of one image row are spread over all eight XCDs and each L2 fetched its own copy of the shared pixels (PMC: 2.06x
-    // the input from HBM); one contiguous band of tiles per XCD keeps the re-reads in that L2.
-    const int64_t id = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
-    const int64_t gt_raw = id / cq, t_last = g.tile_end[g.n - 1];
-    const int64_t gt = gt_raw < t_last ? gt_raw : t_last - 1;   // (threads past the end still help with the table read below)
-    const int c4 = (int)(id - gt_raw * cq) * 4;
+// o = A v for one 4-vector (A = transpose of the A^T of at6)
+__device__ __forceinline__ void a6(const float4 v[4], float4 o[6]) {
+    const float4 s02 = v[0] + v[2], s13 = v[1] + v[3];
+    o[0] = v[0];
+    o[1] = s02 + s13;
+    o[2] = s02 - s13;
+    const float4 e = v[0] + 4.f * v[2], f = 2.f * v[1] + 8.f * v[3];
+    o[3] = e + f;
+    o[4] = e - f;
+    o[5] = v[3];
+}
+
+// Thread -> tile row of the launch (gt_raw; t_last and above: none) and the thread's four channels (c4).  Dense: thread id / (C / 4).
+// LIST (rn_tile_lists): thread id -> entry of the list of aligned 16-row units -> tile; entries of another launch's problems (below t0)
+// count as none.  The launch cannot know the list's length (it is on the device only): false = the whole workgroup lies past its end.
+template <bool LIST>
+__device__ __forceinline__ bool wino_thread_tile(int64_t id, int cq, int64_t t0, int64_t Tpad, int64_t t_last, const int *units,
+                                                 const int *n_units, int64_t &gt_raw, int &c4) {
+    gt_raw = id / cq;
+    c4 = (int)(id - gt_raw * cq) * 4;
+    if constexpr (LIST) {
+        const int nu_raw = *n_units, nu_max = (int)(Tpad >> 4);
+        const int64_t rows = 16 * (int64_t)(nu_raw < 0 ? 0 : (nu_raw < nu_max ? nu_raw : nu_max));
+        if ((id - threadIdx.x) >= rows * cq) return false;
+        const int64_t it = gt_raw;
+        gt_raw = it < rows ? (int64_t)units[it >> 4] * 16 + (it & 15) - t0 : t_last;
+        if (gt_raw < 0) gt_raw = t_last;
+    }
+    return true;
+}
+
+// Tile row -> its place: the problem's extent, the patch's corner, the thread's channels of its image, the image's amax table.
+struct WinoPlace {
+    int H, W, h0, w0, n;
+    const float *xb;
+    const unsigned *xw;                                       // (the amax tables of the problem's images, or NULL)
+};
+__device__ __forceinline__ WinoPlace wino_place(const WinoTable &g, int64_t gt, int C, int c4) {
     int64_t tile;
     const int q = wino_locate(g, gt, tile);
     const float *x = g.src[0];
@@ -126,109 +159,120 @@ __global__ __launch_bounds__(256) void wino_in_kernel(const WinoTable g, float *
     const int n = (int)(tile / (pr.TH * TW));
     const int r = (int)(tile - (int64_t)n * pr.TH * TW);
     const int th = r / TW, tw = r - th * TW;
-    const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
-    const float *xb = x + (int64_t)n * H * W * C + c4;
-    if (row_amax != nullptr) {                                // wave-cooperative: every lane the largest exponent of ITS image's table
-        const int e_img = rn_amax_exp_lanes(xw != nullptr ? reinterpret_cast<const unsigned char *>(xw) + (int64_t)n * RN_AMAX_BYTES : nullptr);
-        if (gt_raw < t_last && c4 == 0) row_amax[t0 + gt] = rn_amax_word_of_exp(e_img, WINO_GAIN_BT);
-    }
-    if (gt_raw >= t_last) return;
-    float4 t[6][6];                                           // t[i][j] = (B^T d)[i][j]: columns first
+    return {H, W, 4 * th - 1, 4 * tw - 1, n, x + (int64_t)n * H * W * C + c4, xw};
+}
+// The row word of V (above).  Wave-cooperative -- every lane the largest exponent of ITS image's table -- so every thread of the workgroup
+// comes here, those past the last tile on the last tile's place; `store` says whose word is written.
+__device__ __forceinline__ void wino_row_word(unsigned *row_amax, const WinoPlace &p, bool store, int64_t row) {
+    if (row_amax == nullptr) return;
+    const int e_img = rn_amax_exp_lanes(p.xw != nullptr ? reinterpret_cast<const unsigned char *>(p.xw) + (int64_t)p.n * RN_AMAX_BYTES : nullptr);
+    if (store) row_amax[row] = rn_amax_word_of_exp(e_img, WINO_GAIN_BT);
+}
+
+// The second 1-D transform, row by row, and the tile's 36 stores, one per plane of Tpad rows: V[i][.] = t[i][.] B / Z[a][.] = tz[a][.] A^T
+__device__ __forceinline__ void wino_store_v(const float4 (&t)[6][6], float *vb, int64_t Tpad, int C) {
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float4 d[6], o[6];
-        const int w = w0 + j;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int h = h0 + i;
-#ifdef RN_WINO_ABL       // knock-out (timing only, wrong results): no halo loads.  Measured on the head-tower group: 0.249 -> 0.227 ms,
-                         // i.e. the 2.25x re-reads through L2 cost 9 %; the rest is the HBM stream itself (1.17 GB at 5.1 TB/s)
-            const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W && i >= 1 && i <= 4 && j >= 1 && j <= 4;
-#else
-            const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-#endif
-            d[i] = ok ? *reinterpret_cast<const float4 *>(xb + ((int64_t)h * W + w) * C) : f4(0.f);
-        }
-        bt6(d, o);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) t[i][j] = o[i];
-    }
-    float *vb = V + (t0 + gt) * C + c4;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {                              // rows: V[i][.] = t[i][.] B
+    for (int i = 0; i < 6; ++i) {
         float4 o[6];
         bt6(t[i], o);
 #pragma unroll
         for (int j = 0; j < 6; ++j) st_stream(vb + (int64_t)(i * 6 + j) * Tpad * C, o[j]);
     }
 }
-
-// LIST instance of wino_in_kernel for the FORWARD of a layer whose output is needed on a known set of tiles only (the regression tower's
-// need sets): thread id -> entry of the list of 16-row units that hold a needed tile -> tile, as in
-// wino_in_both_kernel<true, true>.  A needed tile (flags[row] != 0) gets its transform and its row word; the other tiles of a listed unit
-// get ZERO rows -- the weight gradient's K-steps read whole units of the kept V, and 0 x garbage is NaN.  Nothing else is visited or
-// stored.  The arithmetic is wino_in_kernel's, line by line (the results are bit-identical on the needed tiles).
-__global__ __launch_bounds__(256) void wino_in_list_kernel(const WinoTable g, float *__restrict__ V, int C, int64_t t0, int64_t Tpad,
-                                                           unsigned *__restrict__ row_amax, unsigned *__restrict__ tensor_amax,
-                                                           const unsigned char *__restrict__ flags, const int *__restrict__ units,
-                                                           const int *__restrict__ n_units) {
-    wino_tensor_word(g, tensor_amax, WINO_GAIN_BT);
-    const int cq = C >> 2;
-    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (the plain id: the list's entries fill the first workgroups only)
-    const int64_t t_last = g.tile_end[g.n - 1];
-    const int64_t it = id / cq;
-    const int c4 = (int)(id - it * cq) * 4;
-    const int nu_raw = *n_units, nu_max = (int)(Tpad >> 4);
-    const int64_t rows = 16 * (int64_t)(nu_raw < 0 ? 0 : (nu_raw < nu_max ? nu_raw : nu_max));
-    if ((id - threadIdx.x) >= rows * cq) return;              // (the whole workgroup)
-    int64_t gt_raw = it < rows ? (int64_t)units[it >> 4] * 16 + (it & 15) - t0 : t_last;
-    if (gt_raw < 0) gt_raw = t_last;
-    const int64_t gt = gt_raw < t_last ? gt_raw : t_last - 1;   // (threads past the end still help with the table read below)
-    int64_t tile;
-    const int q = wino_locate(g, gt, tile);
-    const float *x = g.src[0];
-    const unsigned *xw = g.amax[0];
-    WINO_SELECT(q, g, pr, x = g.src[i_]; xw = g.amax[i_];)
-    const int H = pr.H, W = pr.W, TW = pr.TW;
-    const int n = (int)(tile / (pr.TH * TW));
-    const int r = (int)(tile - (int64_t)n * pr.TH * TW);
-    const int th = r / TW, tw = r - th * TW;
-    const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
-    const float *xb = x + (int64_t)n * H * W * C + c4;
-    const bool needed = gt_raw < t_last && flags[t0 + gt] != 0;
-    if (row_amax != nullptr) {                                // wave-cooperative: every lane the largest exponent of ITS image's table
-        const int e_img = rn_amax_exp_lanes(xw != nullptr ? reinterpret_cast<const unsigned char *>(xw) + (int64_t)n * RN_AMAX_BYTES : nullptr);
-        if (needed && c4 == 0) row_amax[t0 + gt] = rn_amax_word_of_exp(e_img, WINO_GAIN_BT);
-    }
-    if (gt_raw >= t_last) return;
-    float *vb = V + (t0 + gt) * C + c4;
-    if (!needed) {
+__device__ __forceinline__ void wino_store_z(const float4 (&tz)[6][4], float *zb, int64_t Tpad, int C) {
 #pragma unroll
-        for (int p = 0; p < 36; ++p) st_stream(vb + (int64_t)p * Tpad * C, f4(0.f));
+    for (int a = 0; a < 6; ++a) {
+        float4 o[6];
+        a6(tz[a], o);
+#pragma unroll
+        for (int b = 0; b < 6; ++b) st_stream(zb + (int64_t)(a * 6 + b) * Tpad * C, o[b]);
+    }
+}
+__device__ __forceinline__ void wino_store_zero(float *b, int64_t Tpad, int C) {
+#pragma unroll
+    for (int p = 0; p < 36; ++p) st_stream(b + (int64_t)p * Tpad * C, f4(0.f));
+}
+
+// OUT: what a launch produces.  WINO_V: B^T d B with its row words; WINO_Z: A dy A^T; WINO_VZ: both transforms of an output gradient in
+// ONE pass over it -- the backward of a Winograd layer needs both and read dy twice; the patch a thread has loaded for V holds the
+// pixels of Z.
+// FLAGS (tile activity flags; one byte per row of V / Z): a tile with flag 0 is not transformed.
+//   WINO_VZ (flags 16-byte aligned): such a tile has an all-zero patch, so V = Z = 0 exactly: it writes no V (the GEMM's rows of such a
+//     tile are never read).  Its rows of Z are written -- as zeros -- only where the reduction may read them: it skips whole aligned units
+//     of 16 rows, so a unit with any active tile is complete.  Every tile gets its row word.
+//   WINO_V (the FORWARD of a layer whose output is needed on a known set of tiles only: the regression tower's need sets): a needed tile
+//     gets its transform and its row word; the other tiles get ZERO rows -- the weight gradient's K-steps read whole units of the kept V,
+//     and 0 x garbage is NaN.
+// LIST (with FLAGS; rn_tile_lists): the threads walk the list of 16-row units that hold a flagged tile instead of every tile: the listed
+//   units' tiles are treated exactly as above, the others are never visited, stored or given a row word (the caller zeroes the row
+//   words: rows of the GEMM nobody reads).  A workgroup past the end of the list leaves after one scalar load.
+// The instances: <V>, <V, FLAGS, LIST>, <Z>, <VZ>, <VZ, FLAGS>, <VZ, FLAGS, LIST>.
+enum { WINO_V = 1, WINO_Z = 2, WINO_VZ = 3 };
+template <int OUT, bool FLAGS = false, bool LIST = false>
+__global__ __launch_bounds__(256) void wino_in_kernel(const WinoTable g, float *__restrict__ V, float *__restrict__ Z, int C, int64_t t0,
+                                                      int64_t Tpad, unsigned *__restrict__ row_amax, unsigned *__restrict__ tensor_amax,
+                                                      const unsigned char *__restrict__ flags, const int *__restrict__ units,
+                                                      const int *__restrict__ n_units) {
+    constexpr bool WANT_V = (OUT & WINO_V) != 0, WANT_Z = (OUT & WINO_Z) != 0;
+    wino_tensor_word(g, tensor_amax, WANT_Z ? WINO_GAIN_A : WINO_GAIN_BT);
+    // 6x6 patches of neighbouring tiles overlap by two pixels: every input pixel is read by 2.25 tiles.  With the plain id the
+    // tiles of one image row are spread over all eight XCDs and each L2 fetched its own copy of the shared pixels (PMC: 2.06x
+    // the input from HBM); one contiguous band of tiles per XCD keeps the re-reads in that L2.  Not for Z alone (no halo), and not with
+    // LIST: the list's entries fill the first workgroups only, which the XCD bands would put on one XCD.
+    const int cq = C >> 2;
+    const int64_t id = (int64_t)(WANT_V && !LIST ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x) * 256 + threadIdx.x;
+    const int64_t t_last = g.tile_end[g.n - 1];
+    int64_t gt_raw;
+    int c4;
+    if (!wino_thread_tile<LIST>(id, cq, t0, Tpad, t_last, units, n_units, gt_raw, c4)) return;
+    const bool live = gt_raw < t_last;
+    if (!WANT_V && !live) return;                             // (no row word to help with)
+    const int64_t gt = live ? gt_raw : t_last - 1;            // (threads past the end still help with the table read of the row word)
+    const WinoPlace p = wino_place(g, gt, C, c4);
+    const int64_t row = t0 + gt;
+    bool flagged = true;
+    if constexpr (FLAGS && !WANT_Z) flagged = live && flags[row] != 0;      // (V alone: only a needed tile gets its row word)
+    if constexpr (WANT_V) wino_row_word(row_amax, p, live && flagged && c4 == 0, row);
+    if (!live) return;
+    if constexpr (FLAGS && WANT_Z) flagged = flags[row] != 0;
+    if (!flagged) {
+        if constexpr (!WANT_Z) wino_store_zero(V + row * C + c4, Tpad, C);
+        else {
+            const uint4 u = *reinterpret_cast<const uint4 *>(flags + (row & ~(int64_t)15));
+            if ((u.x | u.y | u.z | u.w) != 0u) wino_store_zero(Z + row * C + c4, Tpad, C);
+        }
         return;
     }
-    float4 t[6][6];                                           // t[i][j] = (B^T d)[i][j]: columns first
+    // The patch, column by column, through the first 1-D transform: t[i][j] = (B^T d)[i][j] (WANT_V) and tz[a][j] = (A dy)[a][j], dy = the
+    // patch's rows / columns 1..4 (WANT_Z; alone it loads only those).  Pixels outside the image are zero.  No halo loads at all (a timing
+    // knock-out) took the head-tower group's V from 0.249 to 0.227 ms: the 2.25x re-reads through L2 cost 9 %, the rest is the HBM stream
+    // itself (1.17 GB at 5.1 TB/s).  (In place, not behind a helper like the stores: with the arrays handed to an inlined function the
+    // compiler contracted the flagged <WINO_VZ> instances' transforms into other fma's -- other bits -- and took 6 more registers.)
+    float4 t[6][6], tz[6][4];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
+    for (int j = WANT_V ? 0 : 1; j < (WANT_V ? 6 : 5); ++j) {
         float4 d[6], o[6];
-        const int w = w0 + j;
+        const int w = p.w0 + j;
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int h = h0 + i;
-            const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-            d[i] = ok ? *reinterpret_cast<const float4 *>(xb + ((int64_t)h * W + w) * C) : f4(0.f);
+        for (int i = WANT_V ? 0 : 1; i < (WANT_V ? 6 : 5); ++i) {
+            const int h = p.h0 + i;
+            const bool ok = (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
+            d[i] = ok ? *reinterpret_cast<const float4 *>(p.xb + ((int64_t)h * p.W + w) * C) : f4(0.f);
         }
-        bt6(d, o);
+        if constexpr (WANT_V) {
+            bt6(d, o);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) t[i][j] = o[i];
+            for (int i = 0; i < 6; ++i) t[i][j] = o[i];
+        }
+        if (WANT_Z && j >= 1 && j <= 4) {
+            float4 oz[6];
+            a6(d + 1, oz);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) tz[a][j - 1] = oz[a];
+        }
     }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {                              // rows: V[i][.] = t[i][.] B
-        float4 o[6];
-        bt6(t[i], o);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) st_stream(vb + (int64_t)(i * 6 + j) * Tpad * C, o[j]);
-    }
+    if constexpr (WANT_Z) wino_store_z(tz, Z + row * C + c4, Tpad, C);
+    if constexpr (WANT_V) wino_store_v(t, V + row * C + c4, Tpad, C);
 }
 
 // ---------------------------------------------------------------------------------------------- output transform
@@ -428,165 +472,6 @@ __global__ void wino_weight_kernel(const float *__restrict__ w, float *__restric
     }
 }
 
-// ---------------------------------------------------------------------------------------------- weight gradient
-// dL/dg = G^T [ sum over tiles of (A dy A^T) .* (B^T d B) ] G.  Z = A dy A^T (4x4 output-gradient tile -> 6x6) is this
-// kernel; V = B^T d B is wino_in_kernel; dU[p] = Z_p^T V_p is the weight-gradient GEMM kernel run as 36 batched 1x1
-// problems (rn_conv_wgrad_batched); wino_dw_kernel folds G^T dU G into the layer's packed gradient.  Z at position
-// (1,1) is the plain sum of the tile's dy, so the bias gradient is the column sum of that one batch entry.
-// o = A v for one 4-vector (A = transpose of the A^T of at6)
-__device__ __forceinline__ void a6(const float4 v[4], float4 o[6]) {
-    const float4 s02 = v[0] + v[2], s13 = v[1] + v[3];
-    o[0] = v[0];
-    o[1] = s02 + s13;
-    o[2] = s02 - s13;
-    const float4 e = v[0] + 4.f * v[2], f = 2.f * v[1] + 8.f * v[3];
-    o[3] = e + f;
-    o[4] = e - f;
-    o[5] = v[3];
-}
-
-__global__ __launch_bounds__(256) void wino_dy_kernel(const WinoTable g, float *__restrict__ Z, int C, int64_t t0, int64_t Tpad,
-                                                      unsigned *__restrict__ tensor_amax) {
-    wino_tensor_word(g, tensor_amax, WINO_GAIN_A);
-    const int cq = C >> 2;
-    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t gt = id / cq;
-    if (gt >= g.tile_end[g.n - 1]) return;
-    const int c4 = (int)(id - gt * cq) * 4;
-    int64_t tile;
-    const int q = wino_locate(g, gt, tile);
-    const float *dy = g.src[0];
-    WINO_SELECT(q, g, pr, dy = g.src[i_];)
-    const int H = pr.H, W = pr.W, TW = pr.TW;
-    const int n = (int)(tile / (pr.TH * TW));
-    const int r = (int)(tile - (int64_t)n * pr.TH * TW);
-    const int th = r / TW, tw = r - th * TW;
-    const float *yb = dy + (int64_t)n * H * W * C + c4;
-    float4 t[6][4];                                           // t[a][j] = (A dy)[a][j]
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float4 v[4], o[6];
-        const int w = 4 * tw + j;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int h = 4 * th + i;
-            v[i] = (h < H && w < W) ? *reinterpret_cast<const float4 *>(yb + ((int64_t)h * W + w) * C) : f4(0.f);
-        }
-        a6(v, o);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) t[a][j] = o[a];
-    }
-    float *zb = Z + (t0 + gt) * C + c4;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-        float4 o[6];
-        a6(t[a], o);
-#pragma unroll
-        for (int b = 0; b < 6; ++b) st_stream(zb + (int64_t)(a * 6 + b) * Tpad * C, o[b]);
-    }
-}
-
-// Both transforms of an output gradient in ONE pass over it: V = B^T dy B (the data gradient's input transform: 6x6 patches with
-// their halo) and Z = A dy A^T (the weight gradient's: the patch's inner 4x4).  The backward of a Winograd layer needs both and
-// read dy twice; the patch a thread has loaded for V holds the pixels of Z.
-// FLAGS (tile activity flags; one byte per row of V / Z, 16-byte aligned): a tile with flag 0 has an all-zero patch, so
-// V = Z = 0 exactly: it loads nothing and writes no V (the GEMM's rows of such a tile are never read).  Its rows of Z are written -- as
-// zeros -- only where the reduction may read them: it skips whole aligned units of 16 rows, so a unit with any active tile is complete.
-// LIST (with FLAGS; rn_tile_lists): thread id -> entry of the list of 16-row units that hold an active tile -> tile, instead of thread id ->
-// tile: the listed units' tiles are treated exactly as above, the others are never visited.  The launch keeps the dense grid (the list's
-// length is known on the device only); a workgroup past the end of the list leaves after one scalar load.  Row words of V are written for
-// the listed units only (the caller zeroes the others: rows of the GEMM nobody reads).
-template <bool FLAGS = false, bool LIST = false>
-__global__ __launch_bounds__(256) void wino_in_both_kernel(const WinoTable g, float *__restrict__ V, float *__restrict__ Z, int C,
-                                                           int64_t t0, int64_t Tpad, unsigned *__restrict__ v_row_amax,
-                                                           unsigned *__restrict__ z_tensor_amax,
-                                                           const unsigned char *__restrict__ flags = nullptr,
-                                                           const int *__restrict__ units = nullptr,
-                                                           const int *__restrict__ n_units = nullptr) {
-    wino_tensor_word(g, z_tensor_amax, WINO_GAIN_A);
-    const int cq = C >> 2;
-    // (LIST: the plain id -- the list's entries fill the first workgroups only, which the XCD bands would put on one XCD)
-    const int64_t id = (int64_t)(LIST ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x)) * 256 + threadIdx.x;
-    const int64_t t_last = g.tile_end[g.n - 1];
-    int64_t gt_raw = id / cq;
-    const int c4 = (int)(id - gt_raw * cq) * 4;
-    if constexpr (LIST) {
-        const int nu_raw = *n_units, nu_max = (int)(Tpad >> 4);
-        const int64_t rows = 16 * (int64_t)(nu_raw < 0 ? 0 : (nu_raw < nu_max ? nu_raw : nu_max));
-        if ((id - threadIdx.x) >= rows * cq) return;          // (the whole workgroup)
-        const int64_t it = gt_raw;
-        gt_raw = it < rows ? (int64_t)units[it >> 4] * 16 + (it & 15) - t0 : t_last;
-        if (gt_raw < 0) gt_raw = t_last;
-    }
-    const int64_t gt = gt_raw < t_last ? gt_raw : t_last - 1;   // (threads past the end still help with the table read below)
-    int64_t tile;
-    const int q = wino_locate(g, gt, tile);
-    const float *x = g.src[0];
-    const unsigned *xw = g.amax[0];
-    WINO_SELECT(q, g, pr, x = g.src[i_]; xw = g.amax[i_];)
-    const int H = pr.H, W = pr.W, TW = pr.TW;
-    const int n = (int)(tile / (pr.TH * TW));
-    const int r = (int)(tile - (int64_t)n * pr.TH * TW);
-    const int th = r / TW, tw = r - th * TW;
-    const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
-    const float *xb = x + (int64_t)n * H * W * C + c4;
-    if (v_row_amax != nullptr) {
-        const int e_img = rn_amax_exp_lanes(xw != nullptr ? reinterpret_cast<const unsigned char *>(xw) + (int64_t)n * RN_AMAX_BYTES : nullptr);
-        if (gt_raw < t_last && c4 == 0) v_row_amax[t0 + gt] = rn_amax_word_of_exp(e_img, WINO_GAIN_BT);
-    }
-    if (gt_raw >= t_last) return;
-    if constexpr (FLAGS) {
-        const int64_t row = t0 + gt;
-        if (flags[row] == 0) {
-            const uint4 u = *reinterpret_cast<const uint4 *>(flags + (row & ~(int64_t)15));
-            if ((u.x | u.y | u.z | u.w) != 0u) {
-                float *zb0 = Z + row * C + c4;
-#pragma unroll
-                for (int p = 0; p < 36; ++p) st_stream(zb0 + (int64_t)p * Tpad * C, f4(0.f));
-            }
-            return;
-        }
-    }
-    float4 t[6][6];                                           // t[i][j] = (B^T d)[i][j]
-    float4 tz[6][4];                                          // tz[a][j] = (A dy)[a][j], dy = the patch's rows / columns 1..4
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        float4 d[6], o[6];
-        const int w = w0 + j;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int h = h0 + i;
-            const bool ok = (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-            d[i] = ok ? *reinterpret_cast<const float4 *>(xb + ((int64_t)h * W + w) * C) : f4(0.f);
-        }
-        bt6(d, o);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) t[i][j] = o[i];
-        if (j >= 1 && j <= 4) {
-            float4 oz[6];
-            a6(d + 1, oz);
-#pragma unroll
-            for (int a = 0; a < 6; ++a) tz[a][j - 1] = oz[a];
-        }
-    }
-    float *zb = Z + (t0 + gt) * C + c4;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-        float4 o[6];
-        a6(tz[a], o);
-#pragma unroll
-        for (int b = 0; b < 6; ++b) st_stream(zb + (int64_t)(a * 6 + b) * Tpad * C, o[b]);
-    }
-    float *vb = V + (t0 + gt) * C + c4;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        float4 o[6];
-        bt6(t[i], o);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) st_stream(vb + (int64_t)(i * 6 + j) * Tpad * C, o[j]);
-    }
-}
-
 // The work lists of one flag array, by ONE workgroup: the active tile rows, the aligned 16-row units and the 128-row blocks
 // that hold an active row, each ascending, and the three counts (counts[0..2] = tiles, units, blocks).  Thread t owns 128-row block t (at
 // most 256 of them: the launcher's check) as eight 16-bit masks of its non-zero flag bytes; one exclusive prefix sum over the threads'
@@ -691,45 +576,64 @@ static int wino_table(const rn_wino_group *g, WinoTable &t) {
     return RN_OK;
 }
 
-extern "C" int rn_wino_input_group(const rn_wino_group *g, float *V, int C, int64_t tile_offset, int64_t Tpad, int dy_form,
-                                   void *row_amax, void *tensor_amax, void *stream) {
+// The input side's one checker and launcher.  out: WINO_V / WINO_Z / WINO_VZ; flags / list: the forms of wino_in_kernel.
+static int wino_input_launch(const rn_wino_group *g, int out, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad, void *row_amax,
+                             void *tensor_amax, const void *flags, bool list, const void *units, const void *n_units, void *stream) {
     WinoTable t;
     const int rc = wino_table(g, t);
     if (rc) return rc;
-    if (C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
+    const int64_t T = t.tile_end[t.n - 1];
+    if (C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + T > Tpad) return RN_EINVAL;
+    if (((out & WINO_V) && !V) || ((out & WINO_Z) && !Z)) return RN_EINVAL;
+    if (out == WINO_Z && row_amax != nullptr) return RN_EINVAL;       // A dy A^T feeds the weight gradient only: the tensor word
+    if (list && (!flags || !units || !n_units || (((uintptr_t)units | (uintptr_t)n_units) & 3))) return RN_EINVAL;
+    if (flags != nullptr && (Tpad & 15)) return RN_EINVAL;            // whole 16-row units
+    if (flags != nullptr && out == WINO_VZ && ((uintptr_t)flags & 15)) return RN_EINVAL;      // ... which WINO_VZ reads 16 bytes at a time
     for (int i = 0; i < t.n; ++i)
         if (!t.src[i]) return RN_EINVAL;
-    const dim3 grid(rn_blocks(t.tile_end[t.n - 1] * (C >> 2), 256));
-    if (dy_form && row_amax != nullptr) return RN_EINVAL;    // A dy A^T feeds the weight gradient only: the tensor word
-    if (dy_form) hipLaunchKernelGGL(wino_dy_kernel, grid, dim3(256), 0, (hipStream_t)stream, t, V, C, tile_offset, Tpad,
-                                    reinterpret_cast<unsigned *>(tensor_amax));
-    else hipLaunchKernelGGL(wino_in_kernel, grid, dim3(256), 0, (hipStream_t)stream, t, V, C, tile_offset, Tpad,
-                            reinterpret_cast<unsigned *>(row_amax), reinterpret_cast<unsigned *>(tensor_amax));
+    // The list of a forward's need set may hold any unit of the Tpad rows -- those of another launch's problems included, which this one
+    // skips; a backward's holds units of the group's own tiles only.
+    const dim3 grid(rn_blocks((list && out == WINO_V ? Tpad : T) * (C >> 2), 256));
+#define RN_WINO_IN(...) hipLaunchKernelGGL((wino_in_kernel<__VA_ARGS__>), grid, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad, \
+                                           reinterpret_cast<unsigned *>(row_amax), reinterpret_cast<unsigned *>(tensor_amax),                  \
+                                           reinterpret_cast<const unsigned char *>(flags), reinterpret_cast<const int *>(units),               \
+                                           reinterpret_cast<const int *>(n_units))
+    if (out == WINO_Z) RN_WINO_IN(WINO_Z);
+    else if (out == WINO_V && !list) RN_WINO_IN(WINO_V);
+    else if (out == WINO_V) RN_WINO_IN(WINO_V, true, true);
+    else if (flags == nullptr) RN_WINO_IN(WINO_VZ);
+    else if (!list) RN_WINO_IN(WINO_VZ, true);
+    else RN_WINO_IN(WINO_VZ, true, true);
+#undef RN_WINO_IN
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
 
+extern "C" int rn_wino_input_group(const rn_wino_group *g, float *V, int C, int64_t tile_offset, int64_t Tpad, int dy_form,
+                                   void *row_amax, void *tensor_amax, void *stream) {
+    return wino_input_launch(g, dy_form ? WINO_Z : WINO_V, dy_form ? nullptr : V, dy_form ? V : nullptr, C, tile_offset, Tpad, row_amax,
+                             tensor_amax, nullptr, false, nullptr, nullptr, stream);
+}
+// rn_wino_input_group (B^T d B form) over the work list of `flags`: the forward of a layer whose output is needed on the flagged tiles only.
+extern "C" int rn_wino_input_group_list(const rn_wino_group *g, float *V, int C, int64_t tile_offset, int64_t Tpad, void *row_amax,
+                                        void *tensor_amax, const void *flags, const void *units, const void *n_units, void *stream) {
+    return wino_input_launch(g, WINO_V, V, nullptr, C, tile_offset, Tpad, row_amax, tensor_amax, flags, true, units, n_units, stream);
+}
 extern "C" int rn_wino_input_both_group_flags(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
                                               void *v_row_amax, void *z_tensor_amax, const void *flags, void *stream) {
-    WinoTable t;
-    const int rc = wino_table(g, t);
-    if (rc) return rc;
-    if (!V || !Z || C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
-    if (flags != nullptr && (((uintptr_t)flags & 15) || (Tpad & 15))) return RN_EINVAL;      // whole 16-byte units of flags
-    for (int i = 0; i < t.n; ++i)
-        if (!t.src[i]) return RN_EINVAL;
-    const dim3 grid(rn_blocks(t.tile_end[t.n - 1] * (C >> 2), 256));
-    if (flags != nullptr)
-        hipLaunchKernelGGL(wino_in_both_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad,
-                           reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax),
-                           reinterpret_cast<const unsigned char *>(flags));
-    else
-        hipLaunchKernelGGL(wino_in_both_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad,
-                           reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax),
-                           (const unsigned char *)nullptr);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
+    return wino_input_launch(g, WINO_VZ, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, flags, false, nullptr, nullptr, stream);
 }
+extern "C" int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                        void *v_row_amax, void *z_tensor_amax, void *stream) {
+    return wino_input_launch(g, WINO_VZ, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, nullptr, false, nullptr, nullptr, stream);
+}
+// rn_wino_input_both_group_flags over the work list of `flags` (rn_tile_lists: units / n_units on the device).
+extern "C" int rn_wino_input_both_group_lists(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
+                                              void *v_row_amax, void *z_tensor_amax, const void *flags, const void *units,
+                                              const void *n_units, void *stream) {
+    return wino_input_launch(g, WINO_VZ, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, flags, true, units, n_units, stream);
+}
+
 extern "C" int rn_tile_lists(const void *flags, int64_t Tpad, void *counts, void *tiles, void *units, void *blocks, void *stream) {
     if (!flags || !counts || !tiles || !units || !blocks || Tpad <= 0 || (Tpad & 255) || Tpad > 256 * 128) return RN_EINVAL;      // one thread per block
     if (((uintptr_t)flags & 15) || (((uintptr_t)counts | (uintptr_t)tiles | (uintptr_t)units | (uintptr_t)blocks) & 3)) return RN_EINVAL;
@@ -740,123 +644,61 @@ extern "C" int rn_tile_lists(const void *flags, int64_t Tpad, void *counts, void
     return RN_OK;
 }
 
-// rn_wino_input_both_group_flags over the work list of `flags` (rn_tile_lists: units / n_units on the device).
-extern "C" int rn_wino_input_both_group_lists(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
-                                              void *v_row_amax, void *z_tensor_amax, const void *flags, const void *units,
-                                              const void *n_units, void *stream) {
+// The output side's one checker and launcher.  form: which of wino_out_kernel's <FLAGS, LIST> the call is.
+enum { WINO_OUT_DENSE, WINO_OUT_FLAGS, WINO_OUT_LIST };
+static int wino_output_launch(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad, const float *scale,
+                              const float *shift, int mask_mode, int act, int64_t y_batch_stride, int form, const void *flags_in,
+                              void *flags_out, const void *tiles, const void *n_tiles, void *stream) {
     WinoTable t;
     const int rc = wino_table(g, t);
     if (rc) return rc;
-    if (!V || !Z || C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
-    if (!flags || !units || !n_units || ((uintptr_t)flags & 15) || ((uintptr_t)units & 3) || (Tpad & 15)) return RN_EINVAL;
-    for (int i = 0; i < t.n; ++i)
-        if (!t.src[i]) return RN_EINVAL;
-    const dim3 gl(rn_blocks(t.tile_end[t.n - 1] * (C >> 2), 256));
-    hipLaunchKernelGGL((wino_in_both_kernel<true, true>), gl, dim3(256), 0, (hipStream_t)stream, t, V, Z, C, tile_offset, Tpad,
-                       reinterpret_cast<unsigned *>(v_row_amax), reinterpret_cast<unsigned *>(z_tensor_amax),
-                       reinterpret_cast<const unsigned char *>(flags), reinterpret_cast<const int *>(units),
-                       reinterpret_cast<const int *>(n_units));
+    const int64_t T = t.tile_end[t.n - 1];
+    if (Cout <= 0 || (Cout & 3) || tile_offset < 0 || tile_offset + T > Tpad) return RN_EINVAL;
+    if (form == WINO_OUT_LIST && (!tiles || !n_tiles || (((uintptr_t)tiles | (uintptr_t)n_tiles) & 3))) return RN_EINVAL;
+    if (mask_mode < 0 || (mask_mode & ~(3 | RN_MASK_BITS)) || (mask_mode & 3) == 3 || mask_mode == RN_MASK_BITS) return RN_EINVAL;
+    if (act < 0 || act > 2 || y_batch_stride < 0 || (y_batch_stride & 3)) return RN_EINVAL;
+    // the instance that requests a launch's mask bits / addends in one batch (wino_out_kernel): addends only when every problem has one
+    const bool pbits = (mask_mode & RN_MASK_BITS) != 0;
+    bool padd = true;
+    for (int i = 0; i < t.n; ++i) {
+        if (!t.dst[i] || (mask_mode != 0) != (t.mask[i] != nullptr)) return RN_EINVAL;
+        if ((pbits || t.sign[i]) && (Cout & 31)) return RN_EINVAL;    // whole words per pixel
+        if (y_batch_stride && y_batch_stride < (int64_t)t.p[i].H * t.p[i].W * Cout) return RN_EINVAL;
+        padd = padd && t.add[i] != nullptr;
+    }
+    // (a list may hold any of the Tpad rows, and its length is known on the device only)
+    const dim3 grid(rn_blocks((form == WINO_OUT_LIST ? Tpad : T) * (Cout >> 2), 256));
+#define RN_WINO_OUT(F, L) {wino_out_kernel<false, false, F, L>, wino_out_kernel<false, true, F, L>, wino_out_kernel<true, false, F, L>, \
+                           wino_out_kernel<true, true, F, L>}
+    static constexpr decltype(&wino_out_kernel<false, false>) instance[3][4] = {RN_WINO_OUT(false, false), RN_WINO_OUT(true, false),
+                                                                                 RN_WINO_OUT(false, true)};      // [form][2 pbits + padd]
+#undef RN_WINO_OUT
+    hipLaunchKernelGGL(instance[form][2 * pbits + padd], grid, dim3(256), 0, (hipStream_t)stream, t, M, Cout, tile_offset, Tpad, scale, shift,
+                       mask_mode, act, y_batch_stride, reinterpret_cast<const unsigned char *>(flags_in),
+                       reinterpret_cast<unsigned char *>(flags_out), reinterpret_cast<const int *>(tiles), reinterpret_cast<const int *>(n_tiles));
     RN_LAUNCH_CHECK();
     return RN_OK;
-}
-
-// rn_wino_input_group (B^T d B form) over the work list of `flags`: the forward of a layer whose output is needed on the flagged tiles only.
-extern "C" int rn_wino_input_group_list(const rn_wino_group *g, float *V, int C, int64_t tile_offset, int64_t Tpad, void *row_amax,
-                                        void *tensor_amax, const void *flags, const void *units, const void *n_units, void *stream) {
-    WinoTable t;
-    const int rc = wino_table(g, t);
-    if (rc) return rc;
-    if (!V || C <= 0 || (C & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
-    if (!flags || !units || !n_units || ((uintptr_t)units & 3) || ((uintptr_t)n_units & 3) || (Tpad & 15)) return RN_EINVAL;
-    for (int i = 0; i < t.n; ++i)
-        if (!t.src[i]) return RN_EINVAL;
-    // (the list may hold any unit of the Tpad rows -- those of another launch's problems included, which this one skips)
-    const dim3 gl(rn_blocks(Tpad * (C >> 2), 256));
-    hipLaunchKernelGGL(wino_in_list_kernel, gl, dim3(256), 0, (hipStream_t)stream, t, V, C, tile_offset, Tpad,
-                       reinterpret_cast<unsigned *>(row_amax), reinterpret_cast<unsigned *>(tensor_amax),
-                       reinterpret_cast<const unsigned char *>(flags), reinterpret_cast<const int *>(units),
-                       reinterpret_cast<const int *>(n_units));
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-}
-
-extern "C" int rn_wino_input_both_group(const rn_wino_group *g, float *V, float *Z, int C, int64_t tile_offset, int64_t Tpad,
-                                        void *v_row_amax, void *z_tensor_amax, void *stream) {
-    return rn_wino_input_both_group_flags(g, V, Z, C, tile_offset, Tpad, v_row_amax, z_tensor_amax, nullptr, stream);
 }
 
 extern "C" int rn_wino_output_group_flags(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
                                           const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
                                           const void *flags_in, void *flags_out, void *stream) {
-    WinoTable t;
-    const int rc = wino_table(g, t);
-    if (rc) return rc;
-    if (Cout <= 0 || (Cout & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
-    if (mask_mode < 0 || (mask_mode & ~(3 | RN_MASK_BITS)) || (mask_mode & 3) == 3 || mask_mode == RN_MASK_BITS) return RN_EINVAL;
-    if (act < 0 || act > 2 || y_batch_stride < 0 || (y_batch_stride & 3)) return RN_EINVAL;
-    for (int i = 0; i < t.n; ++i) {
-        if (!t.dst[i] || (mask_mode != 0) != (t.mask[i] != nullptr)) return RN_EINVAL;
-        if (((mask_mode & RN_MASK_BITS) || t.sign[i]) && (Cout & 31)) return RN_EINVAL;     // whole words per pixel
-        if (y_batch_stride && y_batch_stride < (int64_t)t.p[i].H * t.p[i].W * Cout) return RN_EINVAL;
-    }
-    // the instance that requests a launch's mask bits / addends in one batch (wino_out_kernel): addends only when every problem has one
-    const bool pbits = (mask_mode & RN_MASK_BITS) != 0;
-    bool padd = true;
-    for (int i = 0; i < t.n; ++i) padd = padd && t.add[i] != nullptr;
-    const dim3 grid(rn_blocks(t.tile_end[t.n - 1] * (Cout >> 2), 256));
-    const unsigned char *fin = reinterpret_cast<const unsigned char *>(flags_in);
-    unsigned char *fout = reinterpret_cast<unsigned char *>(flags_out);
-#define RN_WINO_OUT(B, A, F) hipLaunchKernelGGL((wino_out_kernel<B, A, F>), grid, dim3(256), 0, (hipStream_t)stream, t, M, Cout, tile_offset, Tpad, \
-                                                scale, shift, mask_mode, act, y_batch_stride, fin, fout)
-    if (fin != nullptr || fout != nullptr) {
-        if (pbits && padd) RN_WINO_OUT(true, true, true);
-        else if (pbits) RN_WINO_OUT(true, false, true);
-        else if (padd) RN_WINO_OUT(false, true, true);
-        else RN_WINO_OUT(false, false, true);
-    } else if (pbits && padd) RN_WINO_OUT(true, true, false);
-    else if (pbits) RN_WINO_OUT(true, false, false);
-    else if (padd) RN_WINO_OUT(false, true, false);
-    else RN_WINO_OUT(false, false, false);
-#undef RN_WINO_OUT
-    RN_LAUNCH_CHECK();
-    return RN_OK;
+    return wino_output_launch(g, M, Cout, tile_offset, Tpad, scale, shift, mask_mode, act, y_batch_stride,
+                              flags_in || flags_out ? WINO_OUT_FLAGS : WINO_OUT_DENSE, flags_in, flags_out, nullptr, nullptr, stream);
 }
 extern "C" int rn_wino_output_group(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
                                     const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
                                     void *stream) {
-    return rn_wino_output_group_flags(g, M, Cout, tile_offset, Tpad, scale, shift, mask_mode, act, y_batch_stride, nullptr, nullptr, stream);
+    return wino_output_launch(g, M, Cout, tile_offset, Tpad, scale, shift, mask_mode, act, y_batch_stride, WINO_OUT_DENSE, nullptr, nullptr,
+                              nullptr, nullptr, stream);
 }
 // rn_wino_output_group over a work list of needed tile rows (rn_tile_lists: tiles / n_tiles on the device): the listed tiles get what the
 // dense call stores, nothing else is read or written.
 extern "C" int rn_wino_output_group_list(const rn_wino_group *g, const float *M, int Cout, int64_t tile_offset, int64_t Tpad,
                                          const float *scale, const float *shift, int mask_mode, int act, int64_t y_batch_stride,
                                          const void *tiles, const void *n_tiles, void *stream) {
-    WinoTable t;
-    const int rc = wino_table(g, t);
-    if (rc) return rc;
-    if (Cout <= 0 || (Cout & 3) || tile_offset < 0 || tile_offset + t.tile_end[t.n - 1] > Tpad) return RN_EINVAL;
-    if (!tiles || !n_tiles || ((uintptr_t)tiles & 3) || ((uintptr_t)n_tiles & 3)) return RN_EINVAL;
-    if (mask_mode < 0 || (mask_mode & ~(3 | RN_MASK_BITS)) || (mask_mode & 3) == 3 || mask_mode == RN_MASK_BITS) return RN_EINVAL;
-    if (act < 0 || act > 2 || y_batch_stride < 0 || (y_batch_stride & 3)) return RN_EINVAL;
-    for (int i = 0; i < t.n; ++i) {
-        if (!t.dst[i] || (mask_mode != 0) != (t.mask[i] != nullptr)) return RN_EINVAL;
-        if (((mask_mode & RN_MASK_BITS) || t.sign[i]) && (Cout & 31)) return RN_EINVAL;     // whole words per pixel
-        if (y_batch_stride && y_batch_stride < (int64_t)t.p[i].H * t.p[i].W * Cout) return RN_EINVAL;
-    }
-    const bool pbits = (mask_mode & RN_MASK_BITS) != 0;
-    bool padd = true;
-    for (int i = 0; i < t.n; ++i) padd = padd && t.add[i] != nullptr;
-    const dim3 grid(rn_blocks(Tpad * (Cout >> 2), 256));      // (the list may hold any of the Tpad rows)
-#define RN_WINO_OUT_L(B, A) hipLaunchKernelGGL((wino_out_kernel<B, A, false, true>), grid, dim3(256), 0, (hipStream_t)stream, t, M, Cout, tile_offset, \
-                                               Tpad, scale, shift, mask_mode, act, y_batch_stride, (const unsigned char *)nullptr,                   \
-                                               (unsigned char *)nullptr, reinterpret_cast<const int *>(tiles), reinterpret_cast<const int *>(n_tiles))
-    if (pbits && padd) RN_WINO_OUT_L(true, true);
-    else if (pbits) RN_WINO_OUT_L(true, false);
-    else if (padd) RN_WINO_OUT_L(false, true);
-    else RN_WINO_OUT_L(false, false);
-#undef RN_WINO_OUT_L
-    RN_LAUNCH_CHECK();
-    return RN_OK;
+    return wino_output_launch(g, M, Cout, tile_offset, Tpad, scale, shift, mask_mode, act, y_batch_stride, WINO_OUT_LIST, nullptr, nullptr, tiles,
+                              n_tiles, stream);
 }
 
 // Single-problem forms.

@@ -483,21 +483,35 @@ def _wino_group(xs, srcs=None, dsts=None, adds=None, masks=None, mask_bits=False
     return g
 
 
-def _wino_transform_in(xs, V, C, Tpad, dy_form, want_rows=False, want_tensor=False):
+def _wino_tiles(x):
+    """4x4 output tiles of one problem [N,H,W,.]: its rows in each of the 36 planes of V / M / Z."""
+    return x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4)
+
+
+def _wino_launch(kind, nb, name, *args):
+    """One launch of a Winograd transform on the current stream, timed as `kind` over nb bytes."""
+    prof.timed(kind, nb, lambda: _hip.call(name, *args))
+
+
+def _wino_transform_in(xs, V, C, Tpad, dy_form, want_rows=False, want_tensor=False, lists=None):
     """Input-side transform of every problem of xs into V, RN_MAX_GROUP problems per launch.  split3 (want_rows / want_tensor): also the
-    transformed tensor's amax words, derived from the sources' per-image words -- returns (row words [Tpad] or None, tensor word or None)."""
-    lib = _hip.load()
+    transformed tensor's amax words, derived from the sources' per-image words -- returns (row words [Tpad] or None, tensor word or None).
+    lists (B^T d B form, one launch): over the work list of a need set (a TileLists of the flags of the tiles whose transform anybody reads)."""
+    assert lists is None or (not dy_form and len(xs) <= _hip.RN_MAX_GROUP and lists.flags.numel() >= Tpad)
     off = 0
     am = want_amax() and (want_rows or want_tensor)
     rows = torch.zeros(Tpad, dtype=torch.int32, device=V.device) if am and want_rows else None
     tword = amax_single(V.device) if am and want_tensor else None
     for k in range(0, len(xs), _hip.RN_MAX_GROUP):
         part = xs[k:k + _hip.RN_MAX_GROUP]
-        t = sum(x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4) for x in part)
+        t = sum(_wino_tiles(x) for x in part)
         g = _wino_group(part, srcs=part, amaxs=[amax_words(x) for x in part] if am else None)
-        nb = 4.0 * (sum(x.numel() for x in part) + 36 * t * C)
-        _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_group(
-            ctypes.byref(g), V.data_ptr(), C, off, Tpad, dy_form, _hip.ptr(rows), _hip.ptr(tword), _hip.stream())), "rn_wino_input_group")
+        nb = 4.0 * (sum(x.numel() for x in part) + 36 * t * C)           # (with lists nominal: the dense call's bytes)
+        if lists is None:
+            _wino_launch("wino_input", nb, "rn_wino_input_group", ctypes.byref(g), V, C, off, Tpad, dy_form, rows, tword)
+        else:
+            _wino_launch("wino_input", nb, "rn_wino_input_group_list", ctypes.byref(g), V, C, off, Tpad, rows, tword, lists.flags, lists.units,
+                         lists.counts.data_ptr() + 4)
         off += t
     return rows, tword
 
@@ -517,21 +531,25 @@ def _need_fill(t, fill):
     return t
 
 
-def _wino_transform_in_list(xs, V, C, Tpad, lists, want_tensor=False):
-    """_wino_transform_in (B^T d B form) over the work list of a need set (a TileLists of the flags of the tiles whose transform anybody
-    reads): rn_wino_input_group_list.  One launch: at most RN_MAX_GROUP problems.  -> (row words [Tpad] or None, tensor word or None)."""
-    lib = _hip.load()
-    assert len(xs) <= _hip.RN_MAX_GROUP and lists.flags.numel() >= Tpad
-    am = want_amax()
-    rows = torch.zeros(Tpad, dtype=torch.int32, device=V.device) if am else None
-    tword = amax_single(V.device) if am and want_tensor else None
-    t = sum(x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4) for x in xs)
-    g = _wino_group(xs, srcs=xs, amaxs=[amax_words(x) for x in xs] if am else None)
-    nb = 4.0 * (sum(x.numel() for x in xs) + 36 * t * C)           # (nominal: the dense call's bytes)
-    _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_group_list(
-        ctypes.byref(g), V.data_ptr(), C, 0, Tpad, _hip.ptr(rows), _hip.ptr(tword), lists.flags.data_ptr(), lists.units.data_ptr(),
-        lists.counts.data_ptr() + 4, _hip.stream())), "rn_wino_input_group_list")
-    return rows, tword
+def _wino_transform_both(g, V, Z, C, Tpad, rows, tword, nb, flags=None, lists=None):
+    """B^T dy B (into V, with its row words) and A dy A^T (into Z, with its tensor word) of group g in one pass, one launch.
+    flags: skip the inactive tiles; lists (of these flags): walk the unit list instead of every tile."""
+    if lists is None:
+        return _wino_launch("wino_input", nb, "rn_wino_input_both_group_flags", ctypes.byref(g), V, Z, C, 0, Tpad, rows, tword, flags)
+    assert lists.flags.data_ptr() == flags.data_ptr()
+    _wino_launch("wino_input", nb, "rn_wino_input_both_group_lists", ctypes.byref(g), V, Z, C, 0, Tpad, rows, tword, flags, lists.units,
+                 lists.counts.data_ptr() + 4)
+
+
+def _wino_transform_out(g, M, cout, off, Tpad, nb, *epilogue, need=None, flags=None, flags_out=None):
+    """Output transform of group g from M at tile row `off`, one launch; epilogue = (scale, shift, mask_mode, act, y_batch_stride).
+    need (a TileLists): its listed tiles only; flags / flags_out: M is zero where flags are / the results' flags are wanted."""
+    if need is not None:
+        _wino_launch("wino_output", nb, "rn_wino_output_group_list", ctypes.byref(g), M, cout, off, Tpad, *epilogue, need.tiles, need.counts)
+    elif flags is not None or flags_out is not None:
+        _wino_launch("wino_output", nb, "rn_wino_output_group_flags", ctypes.byref(g), M, cout, off, Tpad, *epilogue, flags, flags_out)
+    else:
+        _wino_launch("wino_output", nb, "rn_wino_output_group", ctypes.byref(g), M, cout, off, Tpad, *epilogue)
 
 
 class RegNeed:
@@ -644,14 +662,13 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
     TileLists the input transform walks (default: need; it must hold every tile whose V anybody reads later -- the weight gradient), or
     DENSE for the dense transform (a V somebody else shares).  need_fill "zero": what is skipped is zero instead of unwritten (kept V,
     fresh outputs, sign bits) -- for a backward that runs dense."""
-    lib = _hip.load()
     dev = xs[0].device
     C = xs[0].shape[3]
     cout = U.shape[1]                                # rows of the transformed weights = output channels
     if need is not None:
         assert V_ready is None and flags_out is None and len(xs) <= _hip.RN_MAX_GROUP
         need_in = need if need_in is None else need_in
-    tiles = [x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4) for x in xs]
+    tiles = [_wino_tiles(x) for x in xs]
     T = sum(tiles)
     Tpad = wino_tpad(T)
     V, M = _wino_workspace(dev, 0 if keep_v else 36 * Tpad * C, 36 * Tpad * cout)
@@ -677,11 +694,8 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
     if reuse:                                        # a kept / handed-over V comes with them
         src = V_ready if ready else V_in
         v_am = src[2] if len(src) > 2 and src[2] is not None else (None, None)
-    elif need is not None and need_in is not DENSE:
-        assert need_in.flags.numel() >= Tpad
-        v_am = _wino_transform_in_list(xs, V, C, Tpad, need_in, want_tensor=keep_v)
     else:
-        v_am = _wino_transform_in(xs, V, C, Tpad, 0, want_rows=True, want_tensor=keep_v)
+        v_am = _wino_transform_in(xs, V, C, Tpad, 0, want_rows=True, want_tensor=keep_v, lists=need_in if need is not None and need_in is not DENSE else None)
     flags = V_ready[3] if ready and len(V_ready) > 3 else None      # V holds the ACTIVE tiles only: every later stage must skip the others
     lists = V_ready[4] if ready and len(V_ready) > 4 else None      # ... and the GEMM walks their work list instead of the dense grid
     if flags_out is not None:
@@ -723,22 +737,12 @@ def wino_conv_group(xs, U, outs=None, scale=None, shift=None, act=ACT_NONE, adds
             for w_ in signs:
                 if w_ is not None:
                     _need_fill(w_, need_fill)
-            _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group_list(
-                ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
-                act, y_batch_stride, need.tiles.data_ptr(), need.counts.data_ptr(), _hip.stream())), "rn_wino_output_group_list")
-        elif flags is not None or flags_out is not None:
-            _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group_flags(
-                ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
-                act, y_batch_stride, _hip.ptr(flags), _hip.ptr(flags_out), _hip.stream())), "rn_wino_output_group_flags")
-        else:
-            _hip.check(prof.timed("wino_output", nb, lambda: lib.rn_wino_output_group(
-                ctypes.byref(g), M.data_ptr(), cout, off, Tpad, _hip.ptr(scale), _hip.ptr(shift), mm,
-                act, y_batch_stride, _hip.stream())), "rn_wino_output_group")
+        _wino_transform_out(g, M, cout, off, Tpad, nb, scale, shift, mm, act, y_batch_stride, need=need, flags=flags, flags_out=flags_out)
         if yams is not None:
             for o, w_ in zip(outs[sl], yams):
                 amax_attach(o, w_)
         off += t
-    return (outs, (V, tuple(tuple(x.shape) for x in xs), v_am)) if keep_v else outs   # V + the shapes it belongs to (+ its amax word)
+    return (outs, (V, shapes, v_am)) if keep_v else outs   # V + the shapes it belongs to (+ its amax word)
 
 
 _WINO_Z = {}
@@ -785,7 +789,7 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
     dev = xs[0].device
     C, cout = xs[0].shape[3], gs[0].shape[3]
     zst = None
-    tiles = [x.shape[0] * ((x.shape[1] + 3) // 4) * ((x.shape[2] + 3) // 4) for x in xs]
+    tiles = [_wino_tiles(x) for x in xs]
     T = sum(tiles)
     Tpad = wino_tpad(T)
     # V: (B^T d B of the forward's inputs, their shapes) kept by wino_conv_group(keep_v=True); used only for the same grouping
@@ -820,15 +824,7 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
             lists = None
         elif not isinstance(lists, TileLists):
             lists = tile_lists(flags, Tpad, buf=None if lists is True else lists)
-        if lists is not None:
-            assert lists.flags.data_ptr() == flags.data_ptr()
-            _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group_lists(
-                ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), flags.data_ptr(),
-                lists.units.data_ptr(), lists.counts.data_ptr() + 4, _hip.stream())), "rn_wino_input_both_group_lists")
-        else:
-            _hip.check(prof.timed("wino_input", nb, lambda: lib.rn_wino_input_both_group_flags(
-                ctypes.byref(g), Vd.data_ptr(), Z.data_ptr(), cout, 0, Tpad, _hip.ptr(vd_rows), _hip.ptr(z_tw), _hip.ptr(flags),
-                _hip.stream())), "rn_wino_input_both_group_flags")
+        _wino_transform_both(g, Vd, Z, cout, Tpad, vd_rows, z_tw, nb, flags=flags, lists=lists)
         v_dy = (Vd, tuple(tuple(t.shape) for t in gs), (vd_rows, None)) + ((flags,) if flags is not None else ()) \
             + ((lists,) if lists is not None else ())
     else:

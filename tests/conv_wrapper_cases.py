@@ -18,7 +18,9 @@ ENTRY_POINTS = {"rn_conv_igemm", "rn_conv_igemm_splitk", "rn_conv_igemm_grouped"
                 "rn_conv_igemm_fp8", "rn_conv_igemm_fp8_grouped", "rn_amax", "rn_split_weights", "rn_conv_wgrad_batched",
                 "rn_conv_wgrad_batched_det", "rn_conv_wgrad_det_workspace_bytes", "rn_conv_wgrad_bf16", "rn_conv_wgrad_bf16_grouped",
                 "rn_conv_bwd_1x1",
-                "rn_wino_input_group", "rn_wino_input_both_group_flags", "rn_wino_output_group", "rn_wino_dw"}      # (by way of Layer only)
+                "rn_wino_input_group", "rn_wino_input_group_list", "rn_wino_input_both_group_flags", "rn_wino_input_both_group_lists",
+                "rn_wino_output_group", "rn_wino_output_group_flags", "rn_wino_output_group_list", "rn_tile_lists", "rn_wino_dw",
+                "rn_conv_wgrad_batched_flags"}
 KIND_PREFIXES = {"conv_igemm_4x1", "conv_igemm_2x2", "stem", "conv_igemm_bf16", "conv_igemm_bf16_p8", "conv_igemm_fp8", "conv_igemm_fp8_p8",
                  "conv_wgrad", "conv_wgrad_bf16", "conv_bwd_fused", "wino_input", "wino_output"}
 GROUPED = ("rn_conv_igemm_grouped", "rn_conv_igemm_bf16_grouped", "rn_conv_igemm_fp8_grouped")
@@ -826,6 +828,115 @@ def _(env):
     return ys + L.bwd_data_group(gs, LEVELS[:2], wino=True)
 
 
+# ------------------------------------------------------------------------------------------------------------------ wino_conv_group / wino_wgrad_group
+# ... called directly: every Winograd entry point, its list and flag forms, and a group of more than RN_MAX_GROUP problems (two launches,
+# the second at a tile offset).  Records made on the wrappers before their transform helpers were folded.
+WINO_LEVELS = LEVELS + [(5, 3)]
+OPT_WGRAD_ONCE = 4
+WINO_SPLIT3 = dict(mfma=SPLIT3, wants_f16=1, options={OPT_WGRAD_ONCE: 1})
+
+
+def wino_xs(env, n, c, prefix="x"):
+    return [env.t("%s%d" % (prefix, i), (2, h, w, c)) for i, (h, w) in enumerate(WINO_LEVELS[:n])]
+
+
+def wino_shapes(ts):
+    return tuple(tuple(t.shape) for t in ts)
+
+
+def wino_lists(env, name, tpad=256):
+    """The TileLists of a named flag array, built in a named buffer (the rn_tile_lists call is part of the record)."""
+    i32 = env.torch.int32
+    return env.cv.tile_lists(env.t(name, (tpad,), env.torch.uint8), tpad, buf=env.t(name + "_lists", (env.cv.tile_lists_numel(tpad),), i32))
+
+
+@variants("wino/conv_six_problems", native={}, split3=WINO_SPLIT3, by_shape=dict(by_shape=True))
+def _(env):
+    xs = wino_xs(env, 6, 32)
+    return env.cv.wino_conv_group(xs, env.t("U", (36, 64, 32)), scale=env.t("scale", (64,)), shift=env.t("shift", (64,)), act=env.cv.ACT_RELU, sign=True)
+
+
+@variants("wino/conv_six_problems_ybs_add_mask", native={}, split3=WINO_SPLIT3)
+def _(env):
+    xs = wino_xs(env, 6, 32)
+    rows = sum(h * w for h, w in WINO_LEVELS)
+    buf, outs, r0 = env.t("ybuf", (2, rows, 64)), [], 0
+    for h, w in WINO_LEVELS:
+        outs.append(buf[:, r0:r0 + h * w])
+        r0 += h * w
+    adds = [env.t("add%d" % i, (2, h, w, 64)) for i, (h, w) in enumerate(WINO_LEVELS)]
+    masks = [with_sign(env, "mask%d" % i, (2, h, w, 64)) for i, (h, w) in enumerate(WINO_LEVELS[:5])] + [env.t("mask5", (2, 5, 3, 64))]
+    return env.cv.wino_conv_group(xs, env.t("U", (36, 64, 32)), outs=outs, adds=adds, masks=masks, mask_mode=1, y_batch_stride=rows * 64, sign=True)
+
+
+@variants("wino/wgrad_six_problems", native={}, split3=WINO_SPLIT3, deterministic=dict(options={OPT_DETERMINISTIC: 1}))
+def _(env):
+    xs, gs = wino_xs(env, 6, 32), wino_xs(env, 6, 64, "g")
+    return env.cv.wino_wgrad_group(gs, xs, env.t("dw", (64, kpad(3, 32))), env.t("colsum", (64,)))
+
+
+def wino_need(need_in):
+    def fn(env):
+        xs = wino_xs(env, 2, 32)
+        need = wino_lists(env, "need")
+        nin = {"same": None, "dense": env.cv.DENSE}[need_in] if need_in != "own" else wino_lists(env, "need_in")
+        outs, kept = env.cv.wino_conv_group(xs, env.t("U", (36, 64, 32)), shift=env.t("shift", (64,)), act=env.cv.ACT_RELU, keep_v=True, sign=True,
+                                            need=need, need_in=nin, need_fill="zero")
+        return outs + [kept[0]] + [w for w in kept[2] if w is not None]
+    return fn
+
+
+variants("wino/conv_need", native={}, split3=WINO_SPLIT3)(wino_need("same"))
+case("wino/conv_need_in_own", **WINO_SPLIT3)(wino_need("own"))
+variants("wino/conv_need_in_dense", native={}, split3=WINO_SPLIT3)(wino_need("dense"))
+
+
+@case("wino/conv_need_workspace_v")
+def _(env):
+    """Without keep_v: V in the shared workspace, nothing filled."""
+    return env.cv.wino_conv_group(wino_xs(env, 2, 32), env.t("U", (36, 64, 32)), need=wino_lists(env, "need"))
+
+
+@variants("wino/conv_flags_out", native={}, split3=WINO_SPLIT3)
+def _(env):
+    xs = wino_xs(env, 2, 32)
+    adds = [env.t("add%d" % i, (2, h, w, 64)) for i, (h, w) in enumerate(WINO_LEVELS[:2])]
+    masks = [with_sign(env, "mask%d" % i, (2, h, w, 64)) for i, (h, w) in enumerate(WINO_LEVELS[:2])]
+    return env.cv.wino_conv_group(xs, env.t("U", (36, 64, 32)), adds=adds, masks=masks, flags_out=env.t("flags_out", (256,), env.torch.uint8))
+
+
+def wino_v_ready(with_lists):
+    def fn(env):
+        gs = wino_xs(env, 2, 128, "g")
+        lists = wino_lists(env, "flags")
+        ready = (env.t("Vd", (36 * 256 * 128,)), wino_shapes(gs), (env.t("rows", (256,), env.torch.int32), None), lists.flags) + ((lists,) if with_lists else ())
+        masks = [env.t("mask%d" % i, (2, h, w, 96)) for i, (h, w) in enumerate(WINO_LEVELS[:2])]
+        return env.cv.wino_conv_group(gs, env.t("U", (36, 96, 128)), masks=masks, V_ready=ready, flags_out=env.t("flags_out", (256,), env.torch.uint8))
+    return fn
+
+
+case("wino/conv_v_ready_flags", **WINO_SPLIT3)(wino_v_ready(False))
+case("wino/conv_v_ready_lists", **WINO_SPLIT3)(wino_v_ready(True))
+
+
+def wino_wgrad_fused(lists):
+    def fn(env):
+        i32 = env.torch.int32
+        xs, gs = wino_xs(env, 2, 96), wino_xs(env, 2, 128, "g")
+        kept = (env.t("V", (36 * 256 * 96,)), wino_shapes(xs), (None, env.t("v_word", (1,), i32)))
+        flags = env.t("flags", (256,), env.torch.uint8)
+        how = {"none": None, "here": True, "buffer": env.t("list_buf", (env.cv.tile_lists_numel(256),), i32) if lists == "buffer" else None}[lists]
+        v_dy = env.cv.wino_wgrad_group(gs, xs, env.t("dw", (128, kpad(3, 96))), env.t("colsum", (128,)), V=kept, fuse_dgrad_input=True, flags=flags, lists=how)
+        return [v_dy[0]] + [w for w in v_dy[2] if w is not None] + [t if isinstance(t, env.torch.Tensor) else t.buf for t in v_dy[3:]]
+    return fn
+
+
+variants("wino/wgrad_fused_flags", split3=WINO_SPLIT3, native_runs_dense=dict(options={OPT_WGRAD_ONCE: 1}), no_once_runs_dense=dict(mfma=SPLIT3, wants_f16=1))(
+    wino_wgrad_fused("none"))
+variants("wino/wgrad_fused_lists", built_here=WINO_SPLIT3, native_runs_dense=dict(options={OPT_WGRAD_ONCE: 1}))(wino_wgrad_fused("here"))
+case("wino/wgrad_fused_lists_buffer", **WINO_SPLIT3)(wino_wgrad_fused("buffer"))
+
+
 EXPECTED = {
     'igemm/plain/native': {'calls': [('rn_conv_igemm', [('D', 2, 8, 8, 32, 8, 8, 64, 3, 3, 1, 1, -1, -1, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 8, 8, 0, 0, 0, 0, 2048, 4096), 'x', 'w', 'y', 'scale',
         'shift', None, None, None, 'stream'], ('conv_igemm_4x1', 1000000.0, 122880.0))], 'returned': ('torch.float32', (2, 8, 8, 64), 'y'), 'carried': {}},
@@ -1315,4 +1426,195 @@ EXPECTED = {
         ('rn_wino_output_group', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'dst': ['ret[2]', 'ret[3]']}, 'other', 64, 0, 256, None, None, 0, 0, 0, 'stream'], ('wino_output',
         346112.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 128), 'ret[0]'), ('torch.float32', (2, 4, 4, 128), 'ret[1]'), ('torch.float32', (2, 16, 12, 64), 'ret[2]'),
         ('torch.float32', (2, 4, 4, 64), 'ret[3]')], 'carried': {'ret[0]': {'_rn_sign': 1536}, 'ret[1]': {'_rn_sign': 128}}},
+    'wino/conv_six_problems/native': {'calls': [('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3', 'x4']},
+        'other', 32, 0, 256, 0, None, None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5']}, 'other', 32, 34, 256,
+        0, None, None, 'stream'], ('wino_input', 22272.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0,
+        8192, 16384, 0, 2048), 'other', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 5603328.0, 3833856.0)), ('rn_wino_output_group', [{'n': 5, 'N': [2, 2, 2, 2,
+        2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'dst': ['ret[0]', 'ret[1]', 'ret[2]', 'ret[3]', 'ret[4]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign', 'ret[2]._rn_sign',
+        'ret[3]._rn_sign', 'ret[4]._rn_sign']}, 'other', 64, 0, 256, 'scale', 'shift', 0, 1, 0, 'stream'], ('wino_output', 433728.0, 0.0)), ('rn_wino_output_group', [{'n': 1, 'N': [2],
+        'H': [5], 'W': [3], 'dst': ['ret[5]'], 'sign': ['ret[5]._rn_sign']}, 'other', 64, 34, 256, 'scale', 'shift', 0, 1, 0, 'stream'], ('wino_output', 44784.0, 0.0))],
+        'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]'), ('torch.float32', (2, 2, 2, 64), 'ret[2]'), ('torch.float32', (2, 1, 1, 64),
+        'ret[3]'), ('torch.float32', (2, 3, 5, 64), 'ret[4]'), ('torch.float32', (2, 5, 3, 64), 'ret[5]')], 'carried': {'ret[0]': {'_rn_sign': 768}, 'ret[1]': {'_rn_sign': 64},
+        'ret[2]': {'_rn_sign': 16}, 'ret[3]': {'_rn_sign': 4}, 'ret[4]': {'_rn_sign': 60}, 'ret[5]': {'_rn_sign': 60}}},
+    'wino/conv_six_problems/split3': {'calls': [('rn_amax', ['x0', 6144, 2, 'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2, 'x1._rn_amax', 'stream'], None), ('rn_amax', ['x2',
+        128, 2, 'x2._rn_amax', 'stream'], None), ('rn_amax', ['x3', 32, 2, 'x3._rn_amax', 'stream'], None), ('rn_amax', ['x4', 480, 2, 'x4._rn_amax', 'stream'], None),
+        ('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3', 'x4'], 'amax': ['x0._rn_amax', 'x1._rn_amax',
+        'x2._rn_amax', 'x3._rn_amax', 'x4._rn_amax']}, 'other', 32, 0, 256, 0, 'other', None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_amax', ['x5', 480, 2, 'x5._rn_amax', 'stream'],
+        None), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5'], 'amax': ['x5._rn_amax']}, 'other', 32, 34, 256, 0, 'other', None, 'stream'], ('wino_input',
+        22272.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048), 'other', 'U', 'other',
+        None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 5603328.0, 3833856.0)), ('rn_wino_output_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1,
+        5], 'dst': ['ret[0]', 'ret[1]', 'ret[2]', 'ret[3]', 'ret[4]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign', 'ret[2]._rn_sign', 'ret[3]._rn_sign', 'ret[4]._rn_sign'],
+        'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax', 'ret[2]._rn_amax', 'ret[3]._rn_amax', 'ret[4]._rn_amax']}, 'other', 64, 0, 256, 'scale', 'shift', 0, 1, 0, 'stream'], ('wino_output',
+        433728.0, 0.0)), ('rn_wino_output_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'dst': ['ret[5]'], 'sign': ['ret[5]._rn_sign'], 'amax': ['ret[5]._rn_amax']}, 'other', 64, 34, 256,
+        'scale', 'shift', 0, 1, 0, 'stream'], ('wino_output', 44784.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]'),
+        ('torch.float32', (2, 2, 2, 64), 'ret[2]'), ('torch.float32', (2, 1, 1, 64), 'ret[3]'), ('torch.float32', (2, 3, 5, 64), 'ret[4]'), ('torch.float32', (2, 5, 3, 64), 'ret[5]')],
+        'carried': {'x0': {'_rn_amax': 128}, 'x1': {'_rn_amax': 128}, 'x2': {'_rn_amax': 128}, 'x3': {'_rn_amax': 128}, 'x4': {'_rn_amax': 128}, 'x5': {'_rn_amax': 128},
+        'ret[0]': {'_rn_sign': 768, '_rn_amax': 128}, 'ret[1]': {'_rn_sign': 64, '_rn_amax': 128}, 'ret[2]': {'_rn_sign': 16, '_rn_amax': 128}, 'ret[3]': {'_rn_sign': 4, '_rn_amax': 128},
+        'ret[4]': {'_rn_sign': 60, '_rn_amax': 128}, 'ret[5]': {'_rn_sign': 60, '_rn_amax': 128}}},
+    'wino/conv_six_problems/by_shape': {'calls': [('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3',
+        'x4']}, 'other', 32, 0, 256, 0, None, None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5']}, 'other', 32,
+        34, 256, 0, None, None, 'stream'], ('wino_input', 22272.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0,
+        0, 0, 8192, 16384, 0, 2048), 'other', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1 36x1x256 32->64 k1 a1 b1 ds0 x36', 5603328.0, 3833856.0)),
+        ('rn_wino_output_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'dst': ['ret[0]', 'ret[1]', 'ret[2]', 'ret[3]', 'ret[4]'],
+        'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign', 'ret[2]._rn_sign', 'ret[3]._rn_sign', 'ret[4]._rn_sign']}, 'other', 64, 0, 256, 'scale', 'shift', 0, 1, 0, 'stream'], ('wino_output',
+        433728.0, 0.0)), ('rn_wino_output_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'dst': ['ret[5]'], 'sign': ['ret[5]._rn_sign']}, 'other', 64, 34, 256, 'scale', 'shift', 0, 1, 0,
+        'stream'], ('wino_output', 44784.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]'), ('torch.float32', (2, 2, 2, 64),
+        'ret[2]'), ('torch.float32', (2, 1, 1, 64), 'ret[3]'), ('torch.float32', (2, 3, 5, 64), 'ret[4]'), ('torch.float32', (2, 5, 3, 64), 'ret[5]')],
+        'carried': {'ret[0]': {'_rn_sign': 768}, 'ret[1]': {'_rn_sign': 64}, 'ret[2]': {'_rn_sign': 16}, 'ret[3]': {'_rn_sign': 4}, 'ret[4]': {'_rn_sign': 60}, 'ret[5]': {'_rn_sign': 60}}},
+    'wino/conv_six_problems_ybs_add_mask/native': {'calls': [('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2',
+        'x3', 'x4']}, 'other', 32, 0, 256, 0, None, None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5']}, 'other',
+        32, 34, 256, 0, None, None, 'stream'], ('wino_input', 22272.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0,
+        0, 0, 0, 8192, 16384, 0, 2048), 'other', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 5603328.0, 3833856.0)), ('rn_wino_output_group', [{'n': 5, 'N': [2,
+        2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'dst': ['ybuf', 'ybuf+49152', 'ybuf+53248', 'ybuf+54272', 'ybuf+54528'], 'add': ['add0', 'add1', 'add2', 'add3', 'add4'],
+        'mask': ['mask0._rn_sign', 'mask1._rn_sign', 'mask2._rn_sign', 'mask3._rn_sign', 'mask4._rn_sign']}, 'other', 64, 0, 256, None, None, 5, 0, 15552, 'stream'], ('wino_output',
+        550464.0, 0.0)), ('rn_wino_output_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'dst': ['ybuf+58368'], 'add': ['add5'], 'mask': ['mask5']}, 'other', 64, 34, 256, None, None, 1, 0,
+        15552, 'stream'], ('wino_output', 59904.0, 0.0))], 'returned': [('torch.float32', (2, 192, 64), 'ret[0]'), ('torch.float32', (2, 16, 64), 'ret[1]'), ('torch.float32', (2, 4, 64),
+        'ret[2]'), ('torch.float32', (2, 1, 64), 'ret[3]'), ('torch.float32', (2, 15, 64), 'ret[4]'), ('torch.float32', (2, 15, 64), 'ret[5]')], 'carried': {'mask0': {'_rn_sign': 768},
+        'mask1': {'_rn_sign': 64}, 'mask2': {'_rn_sign': 16}, 'mask3': {'_rn_sign': 4}, 'mask4': {'_rn_sign': 60}}},
+    'wino/conv_six_problems_ybs_add_mask/split3': {'calls': [('rn_amax', ['x0', 6144, 2, 'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2, 'x1._rn_amax', 'stream'], None),
+        ('rn_amax', ['x2', 128, 2, 'x2._rn_amax', 'stream'], None), ('rn_amax', ['x3', 32, 2, 'x3._rn_amax', 'stream'], None), ('rn_amax', ['x4', 480, 2, 'x4._rn_amax', 'stream'], None),
+        ('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3', 'x4'], 'amax': ['x0._rn_amax', 'x1._rn_amax',
+        'x2._rn_amax', 'x3._rn_amax', 'x4._rn_amax']}, 'other', 32, 0, 256, 0, 'other', None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_amax', ['x5', 480, 2, 'x5._rn_amax', 'stream'],
+        None), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5'], 'amax': ['x5._rn_amax']}, 'other', 32, 34, 256, 0, 'other', None, 'stream'], ('wino_input',
+        22272.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048), 'other', 'U', 'other',
+        None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 5603328.0, 3833856.0)), ('rn_wino_output_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1,
+        5], 'dst': ['ybuf', 'ybuf+49152', 'ybuf+53248', 'ybuf+54272', 'ybuf+54528'], 'add': ['add0', 'add1', 'add2', 'add3', 'add4'], 'mask': ['mask0._rn_sign', 'mask1._rn_sign',
+        'mask2._rn_sign', 'mask3._rn_sign', 'mask4._rn_sign']}, 'other', 64, 0, 256, None, None, 5, 0, 15552, 'stream'], ('wino_output', 550464.0, 0.0)), ('rn_wino_output_group', [{'n': 1,
+        'N': [2], 'H': [5], 'W': [3], 'dst': ['ybuf+58368'], 'add': ['add5'], 'mask': ['mask5']}, 'other', 64, 34, 256, None, None, 1, 0, 15552, 'stream'], ('wino_output', 59904.0, 0.0))],
+        'returned': [('torch.float32', (2, 192, 64), 'ret[0]'), ('torch.float32', (2, 16, 64), 'ret[1]'), ('torch.float32', (2, 4, 64), 'ret[2]'), ('torch.float32', (2, 1, 64), 'ret[3]'),
+        ('torch.float32', (2, 15, 64), 'ret[4]'), ('torch.float32', (2, 15, 64), 'ret[5]')], 'carried': {'x0': {'_rn_amax': 128}, 'x1': {'_rn_amax': 128}, 'x2': {'_rn_amax': 128},
+        'x3': {'_rn_amax': 128}, 'x4': {'_rn_amax': 128}, 'x5': {'_rn_amax': 128}, 'mask0': {'_rn_sign': 768}, 'mask1': {'_rn_sign': 64}, 'mask2': {'_rn_sign': 16}, 'mask3': {'_rn_sign': 4},
+        'mask4': {'_rn_sign': 60}}},
+    'wino/wgrad_six_problems/native': {'calls': [('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3', 'x4']},
+        'other', 32, 0, 256, 0, None, None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5']}, 'other', 32, 34, 256,
+        0, None, None, 'stream'], ('wino_input', 22272.0, 0.0)), ('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['g0', 'g1',
+        'g2', 'g3', 'g4']}, 'other', 64, 0, 256, 1, None, None, 'stream'], ('wino_input', 430080.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['g5']},
+        'other', 64, 34, 256, 1, None, None, 'stream'], ('wino_input', 44544.0, 0.0)), ('rn_conv_wgrad_batched', ['other', 64, 'other', 'other', 'colsum', 36, 16384, 8192, 2048, 7, 1, 1, 38,
+        32, 1, 38, 64, 1, 1, 1, 0, 0, None, 0, None, 0, 'stream'], ('conv_wgrad', 5603328.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 64, 32, 'stream'], None)], 'returned': None,
+        'carried': {}},
+    'wino/wgrad_six_problems/split3': {'calls': [('rn_amax', ['x0', 6144, 2, 'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2, 'x1._rn_amax', 'stream'], None), ('rn_amax', ['x2',
+        128, 2, 'x2._rn_amax', 'stream'], None), ('rn_amax', ['x3', 32, 2, 'x3._rn_amax', 'stream'], None), ('rn_amax', ['x4', 480, 2, 'x4._rn_amax', 'stream'], None),
+        ('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3', 'x4'], 'amax': ['x0._rn_amax', 'x1._rn_amax',
+        'x2._rn_amax', 'x3._rn_amax', 'x4._rn_amax']}, 'other', 32, 0, 256, 0, None, 'other', 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_amax', ['x5', 480, 2, 'x5._rn_amax', 'stream'],
+        None), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5'], 'amax': ['x5._rn_amax']}, 'other', 32, 34, 256, 0, None, 'other', 'stream'], ('wino_input',
+        22272.0, 0.0)), ('rn_amax', ['g0', 12288, 2, 'g0._rn_amax', 'stream'], None), ('rn_amax', ['g1', 1024, 2, 'g1._rn_amax', 'stream'], None), ('rn_amax', ['g2', 256, 2, 'g2._rn_amax',
+        'stream'], None), ('rn_amax', ['g3', 64, 2, 'g3._rn_amax', 'stream'], None), ('rn_amax', ['g4', 960, 2, 'g4._rn_amax', 'stream'], None), ('rn_wino_input_group', [{'n': 5, 'N': [2, 2,
+        2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['g0', 'g1', 'g2', 'g3', 'g4'], 'amax': ['g0._rn_amax', 'g1._rn_amax', 'g2._rn_amax', 'g3._rn_amax', 'g4._rn_amax']},
+        'other', 64, 0, 256, 1, None, 'other', 'stream'], ('wino_input', 430080.0, 0.0)), ('rn_amax', ['g5', 960, 2, 'g5._rn_amax', 'stream'], None), ('rn_wino_input_group', [{'n': 1,
+        'N': [2], 'H': [5], 'W': [3], 'src': ['g5'], 'amax': ['g5._rn_amax']}, 'other', 64, 34, 256, 1, None, 'other', 'stream'], ('wino_input', 44544.0, 0.0)), ('rn_conv_wgrad_batched',
+        ['other', 64, 'other', 'other', 'colsum', 36, 16384, 8192, 2048, 7, 1, 1, 38, 32, 1, 38, 64, 1, 1, 1, 0, 0, 'other', -1, 'other', -1, 'stream'], ('conv_wgrad', 5603328.0, 0.0)),
+        ('rn_wino_dw', ['other', 'dw', 64, 32, 'stream'], None)], 'returned': None, 'carried': {'x0': {'_rn_amax': 128}, 'x1': {'_rn_amax': 128}, 'x2': {'_rn_amax': 128},
+        'x3': {'_rn_amax': 128}, 'x4': {'_rn_amax': 128}, 'x5': {'_rn_amax': 128}, 'g0': {'_rn_amax': 128}, 'g1': {'_rn_amax': 128}, 'g2': {'_rn_amax': 128}, 'g3': {'_rn_amax': 128},
+        'g4': {'_rn_amax': 128}, 'g5': {'_rn_amax': 128}}},
+    'wino/wgrad_six_problems/deterministic': {'calls': [('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['x0', 'x1', 'x2', 'x3',
+        'x4']}, 'other', 32, 0, 256, 0, None, None, 'stream'], ('wino_input', 215040.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3], 'src': ['x5']}, 'other', 32,
+        34, 256, 0, None, None, 'stream'], ('wino_input', 22272.0, 0.0)), ('rn_wino_input_group', [{'n': 5, 'N': [2, 2, 2, 2, 2], 'H': [16, 4, 2, 1, 3], 'W': [12, 4, 2, 1, 5], 'src': ['g0',
+        'g1', 'g2', 'g3', 'g4']}, 'other', 64, 0, 256, 1, None, None, 'stream'], ('wino_input', 430080.0, 0.0)), ('rn_wino_input_group', [{'n': 1, 'N': [2], 'H': [5], 'W': [3],
+        'src': ['g5']}, 'other', 64, 34, 256, 1, None, None, 'stream'], ('wino_input', 44544.0, 0.0)), ('rn_conv_wgrad_det_workspace_bytes', [64, 36, 2048, 1, 1, 38, 32, 1, 38, 64, 1, 1],
+        ('conv_wgrad', 5603328.0, 0.0)), ('rn_conv_wgrad_batched_det', ['other', 64, 'other', 'other', 'colsum', 36, 16384, 8192, 2048, 7, 1, 1, 38, 32, 1, 38, 64, 1, 1, 1, 0, 0, None, 0,
+        None, 0, None, 0, 'stream'], ('conv_wgrad', 5603328.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 64, 32, 'stream'], None)], 'returned': None, 'carried': {}},
+    'wino/conv_need/native': {'calls': [('rn_tile_lists', ['need', 256, 'need_lists', 'need_lists+88', 'need_lists+24', 'need_lists+16', 'stream'], None), ('rn_wino_input_group_list',
+        [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['x0', 'x1']}, 'ret[2]', 32, 0, 256, None, None, 'need', 'need_lists+24', 'need_lists+4', 'stream'], ('wino_input',
+        173056.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048, 0, None, None, None,
+        None, 0, 0, None, 'need_lists+16', 'need_lists+8'), 'ret[2]', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)),
+        ('rn_wino_output_group_list', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'dst': ['ret[0]', 'ret[1]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign']}, 'other', 64, 0, 256,
+        None, 'shift', 0, 1, 0, 'need_lists+88', 'need_lists', 'stream'], ('wino_output', 349440.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2,
+        4, 4, 64), 'ret[1]'), ('torch.float32', (294912,), 'ret[2]')], 'carried': {'ret[0]': {'_rn_sign': 768}, 'ret[1]': {'_rn_sign': 64}}},
+    'wino/conv_need/split3': {'calls': [('rn_tile_lists', ['need', 256, 'need_lists', 'need_lists+88', 'need_lists+24', 'need_lists+16', 'stream'], None), ('rn_amax', ['x0', 6144, 2,
+        'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2, 'x1._rn_amax', 'stream'], None), ('rn_wino_input_group_list', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4],
+        'src': ['x0', 'x1'], 'amax': ['x0._rn_amax', 'x1._rn_amax']}, 'ret[2]', 32, 0, 256, 'ret[3]', 'ret[4]', 'need', 'need_lists+24', 'need_lists+4', 'stream'], ('wino_input', 173056.0,
+        0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048, 0, None, None, None, None, 0, 0,
+        None, 'need_lists+16', 'need_lists+8'), 'ret[2]', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_list',
+        [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'dst': ['ret[0]', 'ret[1]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign'], 'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax']},
+        'other', 64, 0, 256, None, 'shift', 0, 1, 0, 'need_lists+88', 'need_lists', 'stream'], ('wino_output', 349440.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'),
+        ('torch.float32', (2, 4, 4, 64), 'ret[1]'), ('torch.float32', (294912,), 'ret[2]'), ('torch.int32', (256,), 'ret[3]'), ('torch.int32', (1,), 'ret[4]')],
+        'carried': {'x0': {'_rn_amax': 128}, 'x1': {'_rn_amax': 128}, 'ret[0]': {'_rn_sign': 768, '_rn_amax': 128}, 'ret[1]': {'_rn_sign': 64, '_rn_amax': 128}}},
+    'wino/conv_need_in_own': {'calls': [('rn_tile_lists', ['need', 256, 'need_lists', 'need_lists+88', 'need_lists+24', 'need_lists+16', 'stream'], None), ('rn_tile_lists', ['need_in', 256,
+        'need_in_lists', 'need_in_lists+88', 'need_in_lists+24', 'need_in_lists+16', 'stream'], None), ('rn_amax', ['x0', 6144, 2, 'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2,
+        'x1._rn_amax', 'stream'], None), ('rn_wino_input_group_list', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['x0', 'x1'], 'amax': ['x0._rn_amax', 'x1._rn_amax']},
+        'ret[2]', 32, 0, 256, 'ret[3]', 'ret[4]', 'need_in', 'need_in_lists+24', 'need_in_lists+4', 'stream'], ('wino_input', 173056.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1,
+        256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048, 0, None, None, None, None, 0, 0, None, 'need_lists+16', 'need_lists+8'), 'ret[2]',
+        'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_list', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4],
+        'dst': ['ret[0]', 'ret[1]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign'], 'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax']}, 'other', 64, 0, 256, None, 'shift', 0, 1, 0,
+        'need_lists+88', 'need_lists', 'stream'], ('wino_output', 349440.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]'),
+        ('torch.float32', (294912,), 'ret[2]'), ('torch.int32', (256,), 'ret[3]'), ('torch.int32', (1,), 'ret[4]')], 'carried': {'x0': {'_rn_amax': 128}, 'x1': {'_rn_amax': 128},
+        'ret[0]': {'_rn_sign': 768, '_rn_amax': 128}, 'ret[1]': {'_rn_sign': 64, '_rn_amax': 128}}},
+    'wino/conv_need_in_dense/native': {'calls': [('rn_tile_lists', ['need', 256, 'need_lists', 'need_lists+88', 'need_lists+24', 'need_lists+16', 'stream'], None), ('rn_wino_input_group',
+        [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['x0', 'x1']}, 'ret[2]', 32, 0, 256, 0, None, None, 'stream'], ('wino_input', 173056.0, 0.0)), ('rn_conv_igemm', [('D', 36,
+        1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048, 0, None, None, None, None, 0, 0, None, 'need_lists+16',
+        'need_lists+8'), 'ret[2]', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_list', [{'n': 2, 'N': [2, 2],
+        'H': [16, 4], 'W': [12, 4], 'dst': ['ret[0]', 'ret[1]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign']}, 'other', 64, 0, 256, None, 'shift', 0, 1, 0, 'need_lists+88', 'need_lists',
+        'stream'], ('wino_output', 349440.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]'), ('torch.float32', (294912,),
+        'ret[2]')], 'carried': {'ret[0]': {'_rn_sign': 768}, 'ret[1]': {'_rn_sign': 64}}},
+    'wino/conv_need_in_dense/split3': {'calls': [('rn_tile_lists', ['need', 256, 'need_lists', 'need_lists+88', 'need_lists+24', 'need_lists+16', 'stream'], None), ('rn_amax', ['x0', 6144,
+        2, 'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2, 'x1._rn_amax', 'stream'], None), ('rn_wino_input_group', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4],
+        'src': ['x0', 'x1'], 'amax': ['x0._rn_amax', 'x1._rn_amax']}, 'ret[2]', 32, 0, 256, 0, 'ret[3]', 'ret[4]', 'stream'], ('wino_input', 173056.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1,
+        256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048, 0, None, None, None, None, 0, 0, None, 'need_lists+16',
+        'need_lists+8'), 'ret[2]', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_list', [{'n': 2, 'N': [2, 2],
+        'H': [16, 4], 'W': [12, 4], 'dst': ['ret[0]', 'ret[1]'], 'sign': ['ret[0]._rn_sign', 'ret[1]._rn_sign'], 'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax']}, 'other', 64, 0, 256, None,
+        'shift', 0, 1, 0, 'need_lists+88', 'need_lists', 'stream'], ('wino_output', 349440.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4,
+        64), 'ret[1]'), ('torch.float32', (294912,), 'ret[2]'), ('torch.int32', (256,), 'ret[3]'), ('torch.int32', (1,), 'ret[4]')], 'carried': {'x0': {'_rn_amax': 128},
+        'x1': {'_rn_amax': 128}, 'ret[0]': {'_rn_sign': 768, '_rn_amax': 128}, 'ret[1]': {'_rn_sign': 64, '_rn_amax': 128}}},
+    'wino/conv_need_workspace_v': {'calls': [('rn_tile_lists', ['need', 256, 'need_lists', 'need_lists+88', 'need_lists+24', 'need_lists+16', 'stream'], None), ('rn_wino_input_group_list',
+        [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['x0', 'x1']}, 'other', 32, 0, 256, None, None, 'need', 'need_lists+24', 'need_lists+4', 'stream'], ('wino_input', 173056.0,
+        0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048, 0, None, None, None, None, 0, 0,
+        None, 'need_lists+16', 'need_lists+8'), 'other', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_list',
+        [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'dst': ['ret[0]', 'ret[1]']}, 'other', 64, 0, 256, None, None, 0, 0, 0, 'need_lists+88', 'need_lists', 'stream'], ('wino_output',
+        346112.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]')], 'carried': {}},
+    'wino/conv_flags_out/native': {'calls': [('rn_wino_input_group', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['x0', 'x1']}, 'other', 32, 0, 256, 0, None, None, 'stream'],
+        ('wino_input', 173056.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048),
+        'other', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4],
+        'W': [12, 4], 'dst': ['ret[0]', 'ret[1]'], 'add': ['add0', 'add1'], 'mask': ['mask0._rn_sign', 'mask1._rn_sign']}, 'other', 64, 0, 256, None, None, 6, 0, 0, None, 'flags_out',
+        'stream'], ('wino_output', 455936.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]')],
+        'carried': {'mask0': {'_rn_sign': 768}, 'mask1': {'_rn_sign': 64}}},
+    'wino/conv_flags_out/split3': {'calls': [('rn_amax', ['x0', 6144, 2, 'x0._rn_amax', 'stream'], None), ('rn_amax', ['x1', 512, 2, 'x1._rn_amax', 'stream'], None), ('rn_wino_input_group',
+        [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['x0', 'x1'], 'amax': ['x0._rn_amax', 'x1._rn_amax']}, 'other', 32, 0, 256, 0, 'other', None, 'stream'], ('wino_input',
+        173056.0, 0.0)), ('rn_conv_igemm', [('D', 36, 1, 256, 32, 1, 256, 64, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 8192, 16384, 0, 2048), 'other', 'U',
+        'other', None, None, None, None, None, 'stream'], ('conv_igemm_4x1', 3833856.0, 3833856.0)), ('rn_wino_output_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4],
+        'dst': ['ret[0]', 'ret[1]'], 'add': ['add0', 'add1'], 'mask': ['mask0._rn_sign', 'mask1._rn_sign'], 'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax']}, 'other', 64, 0, 256, None, None,
+        6, 0, 0, None, 'flags_out', 'stream'], ('wino_output', 455936.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 64), 'ret[0]'), ('torch.float32', (2, 4, 4, 64), 'ret[1]')],
+        'carried': {'x0': {'_rn_amax': 128}, 'x1': {'_rn_amax': 128}, 'mask0': {'_rn_sign': 768}, 'mask1': {'_rn_sign': 64}, 'ret[0]': {'_rn_amax': 128}, 'ret[1]': {'_rn_amax': 128}}},
+    'wino/conv_v_ready_flags': {'calls': [('rn_tile_lists', ['flags', 256, 'flags_lists', 'flags_lists+88', 'flags_lists+24', 'flags_lists+16', 'stream'], None), ('rn_conv_igemm', [('D', 36,
+        1, 256, 128, 1, 256, 96, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 32768, 24576, 0, 12288, 0, None, None, None, None, 0, 0, 'flags'), 'Vd', 'U', 'other',
+        None, None, None, None, None, 'stream'], ('conv_igemm_2x2', 23003136.0, 10027008.0)), ('rn_wino_output_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4],
+        'dst': ['ret[0]', 'ret[1]'], 'mask': ['mask0', 'mask1'], 'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax']}, 'other', 96, 0, 256, None, None, 2, 0, 0, 'flags', 'flags_out', 'stream'],
+        ('wino_output', 678912.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 96), 'ret[0]'), ('torch.float32', (2, 4, 4, 96), 'ret[1]')], 'carried': {'ret[0]': {'_rn_amax': 128},
+        'ret[1]': {'_rn_amax': 128}}},
+    'wino/conv_v_ready_lists': {'calls': [('rn_tile_lists', ['flags', 256, 'flags_lists', 'flags_lists+88', 'flags_lists+24', 'flags_lists+16', 'stream'], None), ('rn_conv_igemm', [('D', 36,
+        1, 256, 128, 1, 256, 96, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 256, 0, 0, 0, 0, 32768, 24576, 0, 12288, 0, None, None, None, None, 0, 0, 'flags', 'flags_lists+16',
+        'flags_lists+8'), 'Vd', 'U', 'other', None, None, None, None, None, 'stream'], ('conv_igemm_2x2', 23003136.0, 10027008.0)), ('rn_wino_output_group_flags', [{'n': 2, 'N': [2, 2],
+        'H': [16, 4], 'W': [12, 4], 'dst': ['ret[0]', 'ret[1]'], 'mask': ['mask0', 'mask1'], 'amax': ['ret[0]._rn_amax', 'ret[1]._rn_amax']}, 'other', 96, 0, 256, None, None, 2, 0, 0,
+        'flags', 'flags_out', 'stream'], ('wino_output', 678912.0, 0.0))], 'returned': [('torch.float32', (2, 16, 12, 96), 'ret[0]'), ('torch.float32', (2, 4, 4, 96), 'ret[1]')],
+        'carried': {'ret[0]': {'_rn_amax': 128}, 'ret[1]': {'_rn_amax': 128}}},
+    'wino/wgrad_fused_flags/split3': {'calls': [('rn_amax', ['g0', 24576, 2, 'g0._rn_amax', 'stream'], None), ('rn_amax', ['g1', 2048, 2, 'g1._rn_amax', 'stream'], None),
+        ('rn_wino_input_both_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['g0', 'g1'], 'amax': ['g0._rn_amax', 'g1._rn_amax']}, 'ret[0]', 'other', 128, 0, 256,
+        'ret[1]', 'other', 'flags', 'stream'], ('wino_input', 1171456.0, 0.0)), ('rn_conv_wgrad_batched_flags', ['other', 128, 'V', 'other', 'colsum', 36, 32768, 24576, 12288, 7, 1, 1, 26,
+        96, 1, 26, 128, 1, 1, 1, 0, 0, 'other', -1, 'v_word', -1, 'flags', None, 0, 'stream'], ('conv_wgrad', 23003136.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 128, 96, 'stream'], None)],
+        'returned': [('torch.float32', (1179648,), 'ret[0]'), ('torch.int32', (256,), 'ret[1]'), ('torch.uint8', (256,), 'flags')], 'carried': {'g0': {'_rn_amax': 128},
+        'g1': {'_rn_amax': 128}}},
+    'wino/wgrad_fused_flags/native_runs_dense': {'calls': [('rn_wino_input_both_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['g0', 'g1']}, 'ret', 'other', 128, 0,
+        256, None, None, None, 'stream'], ('wino_input', 1171456.0, 0.0)), ('rn_conv_wgrad_batched', ['other', 128, 'V', 'other', 'colsum', 36, 32768, 24576, 12288, 7, 1, 1, 26, 96, 1, 26,
+        128, 1, 1, 1, 0, 0, None, 0, None, 0, 'stream'], ('conv_wgrad', 23003136.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 128, 96, 'stream'], None)], 'returned': [('torch.float32',
+        (1179648,), 'ret')], 'carried': {}},
+    'wino/wgrad_fused_flags/no_once_runs_dense': {'calls': [('rn_amax', ['g0', 24576, 2, 'g0._rn_amax', 'stream'], None), ('rn_amax', ['g1', 2048, 2, 'g1._rn_amax', 'stream'], None),
+        ('rn_wino_input_both_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['g0', 'g1'], 'amax': ['g0._rn_amax', 'g1._rn_amax']}, 'ret[0]', 'other', 128, 0, 256,
+        'ret[1]', 'other', None, 'stream'], ('wino_input', 1171456.0, 0.0)), ('rn_conv_wgrad_batched', ['other', 128, 'V', 'other', 'colsum', 36, 32768, 24576, 12288, 7, 1, 1, 26, 96, 1, 26,
+        128, 1, 1, 1, 0, 0, 'other', -1, 'v_word', -1, 'stream'], ('conv_wgrad', 23003136.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 128, 96, 'stream'], None)], 'returned': [('torch.float32',
+        (1179648,), 'ret[0]'), ('torch.int32', (256,), 'ret[1]')], 'carried': {'g0': {'_rn_amax': 128}, 'g1': {'_rn_amax': 128}}},
+    'wino/wgrad_fused_lists/built_here': {'calls': [('rn_amax', ['g0', 24576, 2, 'g0._rn_amax', 'stream'], None), ('rn_amax', ['g1', 2048, 2, 'g1._rn_amax', 'stream'], None),
+        ('rn_tile_lists', ['flags', 256, 'ret[3]', 'ret[3]+88', 'ret[3]+24', 'ret[3]+16', 'stream'], None), ('rn_wino_input_both_group_lists', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12,
+        4], 'src': ['g0', 'g1'], 'amax': ['g0._rn_amax', 'g1._rn_amax']}, 'ret[0]', 'other', 128, 0, 256, 'ret[1]', 'other', 'flags', 'ret[3]+24', 'ret[3]+4', 'stream'], ('wino_input',
+        1171456.0, 0.0)), ('rn_conv_wgrad_batched_flags', ['other', 128, 'V', 'other', 'colsum', 36, 32768, 24576, 12288, 7, 1, 1, 26, 96, 1, 26, 128, 1, 1, 1, 0, 0, 'other', -1, 'v_word',
+        -1, 'flags', None, 0, 'stream'], ('conv_wgrad', 23003136.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 128, 96, 'stream'], None)], 'returned': [('torch.float32', (1179648,), 'ret[0]'),
+        ('torch.int32', (256,), 'ret[1]'), ('torch.uint8', (256,), 'flags'), ('torch.int32', (278,), 'ret[3]')], 'carried': {'g0': {'_rn_amax': 128}, 'g1': {'_rn_amax': 128}}},
+    'wino/wgrad_fused_lists/native_runs_dense': {'calls': [('rn_wino_input_both_group_flags', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4], 'src': ['g0', 'g1']}, 'ret', 'other', 128, 0,
+        256, None, None, None, 'stream'], ('wino_input', 1171456.0, 0.0)), ('rn_conv_wgrad_batched', ['other', 128, 'V', 'other', 'colsum', 36, 32768, 24576, 12288, 7, 1, 1, 26, 96, 1, 26,
+        128, 1, 1, 1, 0, 0, None, 0, None, 0, 'stream'], ('conv_wgrad', 23003136.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 128, 96, 'stream'], None)], 'returned': [('torch.float32',
+        (1179648,), 'ret')], 'carried': {}},
+    'wino/wgrad_fused_lists_buffer': {'calls': [('rn_amax', ['g0', 24576, 2, 'g0._rn_amax', 'stream'], None), ('rn_amax', ['g1', 2048, 2, 'g1._rn_amax', 'stream'], None), ('rn_tile_lists',
+        ['flags', 256, 'list_buf', 'list_buf+88', 'list_buf+24', 'list_buf+16', 'stream'], None), ('rn_wino_input_both_group_lists', [{'n': 2, 'N': [2, 2], 'H': [16, 4], 'W': [12, 4],
+        'src': ['g0', 'g1'], 'amax': ['g0._rn_amax', 'g1._rn_amax']}, 'ret[0]', 'other', 128, 0, 256, 'ret[1]', 'other', 'flags', 'list_buf+24', 'list_buf+4', 'stream'], ('wino_input',
+        1171456.0, 0.0)), ('rn_conv_wgrad_batched_flags', ['other', 128, 'V', 'other', 'colsum', 36, 32768, 24576, 12288, 7, 1, 1, 26, 96, 1, 26, 128, 1, 1, 1, 0, 0, 'other', -1, 'v_word',
+        -1, 'flags', None, 0, 'stream'], ('conv_wgrad', 23003136.0, 0.0)), ('rn_wino_dw', ['other', 'dw', 128, 96, 'stream'], None)], 'returned': [('torch.float32', (1179648,), 'ret[0]'),
+        ('torch.int32', (256,), 'ret[1]'), ('torch.uint8', (256,), 'flags'), ('torch.int32', (278,), 'list_buf')], 'carried': {'g0': {'_rn_amax': 128}, 'g1': {'_rn_amax': 128}}},
 }
