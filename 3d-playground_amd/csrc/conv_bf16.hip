@@ -1,5 +1,5 @@
-// bf16 implicit-GEMM convolution and weight gradient on the gfx950 matrix cores (v_mfma_f32_32x32x16_bf16, fp32
-// accumulation; dense peak ~2.5 PFLOP/s) -- the reduced-precision form of conv_igemm.hip / conv_wgrad.hip for BASELINE
+// bf16 implicit-GEMM convolution on the gfx950 matrix cores (v_mfma_f32_32x32x16_bf16, fp32
+// accumulation; dense peak ~2.5 PFLOP/s) -- the reduced-precision form of conv_igemm.hip for BASELINE
 // configs[2] ("bf16 MFMA").  Same convolutions of the reference (every nn.Conv2d of D/model.py with its fused frozen
 // batch-norm / bias / residual / ReLU / sigmoid / FPN upsample-add epilogue, D/model.py:59-205, D/utils.py:12-80), same
 // rn_conv_desc geometry (so the same call computes data gradients), different storage: activations and packed weights
@@ -16,26 +16,10 @@
 // staged the matrix cores are busy 1/8 as long, so this kernel lives on L2 / LDS / HBM bandwidth, not on MFMA issue
 // (128x128 tile: 64 FLOP per staged byte).
 //
-// Weight gradient: dW[co][k] = sum over pixels of dY[pixel][co] * X[pixel + tap][ci] has the REDUCTION index (pixels) as
-// the row of both NHWC operands, while a 32x32x16 operand wants 8 consecutive reduction elements per lane.  The tiles
-// are staged as they lie ([pixel][channel], direct-to-LDS like conv_wgrad.hip) and read through ds_read_b64_tr_b16,
-// gfx950's transposing LDS read: per 16 lanes a 4-pixel x 16-channel block comes back channel-major, two of them make
-// one operand.  fp32 atomics into the same packed fp32 [Cout][Kpad] gradient buffer the fp32 path uses.
+// The engine's weight gradient is conv_wgrad_bf16.hip.
 //
 // Roofline: MFMA by FLOPs (2.5 PF dense), in practice the staging bandwidth (see above) and, for the 1x1 layers, HBM.
 #include "conv_launch.h"
-#include "conv_wgrad_geom.h"
-
-#ifndef RN_WG_KO
-#define RN_WG_KO 0       // conv_wgrad.hip: 1 no tile atomics, 2 workgroup-scope atomics (RN_EXPERIMENT builds, timing only)
-#endif
-#if RN_WG_KO == 1
-#define RN_WG_ATOMIC(P, V) do { if ((V) == 1.2345e-30f) atomicAdd((P), (V)); } while (0)
-#elif RN_WG_KO == 2
-#define RN_WG_ATOMIC(P, V) __hip_atomic_fetch_add((P), (V), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#else
-#define RN_WG_ATOMIC(P, V) atomicAdd((P), (V))
-#endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -563,324 +547,3 @@ extern "C" int rn_conv_igemm_bf16(const rn_conv_desc *d, const void *x, const vo
     return RN_OK;
 }
 
-// ---------------------------------------------------------------------------------------------- weight gradient
-// dw[co][kk] += sum over pixels of dy[pixel][co] * x[pixel shifted by tap(kk)][ci(kk)], kk = packed-row index
-// (tap-major, channel-minor).  Tile 128 (co) x 128 (kk), 32 pixels per K-step, K split over the grid, fp32 atomics.
-struct WgradBf16Args {
-    const __bf16 *dy, *x;
-    float *dw;
-    float *colsum;               // [Cout] += sum over pixels of dy, or NULL
-    int ldy, N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad;
-    int Kflat, Kpad;             // kh*kw*Cin and its round-up to 32
-    int tiles_n, tiles, splits;
-    int xcd_map;                 // 1: whole K slices per XCD (the kernel)
-    int64_t pixels, per_split;   // K extent and K per slice (multiple of 32)
-};
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-#define WG_WK 32                 // pixels per K-step
-#define WG_ROWB 256              // bytes per staged row: 128 bf16
-
-// LDS image of a staged [32 pixels][128 columns] bf16 tile: 256-byte rows whose 16 chunks of 16 bytes are XOR-permuted
-// by wg_fx(row), the image that serves gfx950's transposing read without bank conflicts (cdna_hip_programming.md T10 (b);
-// operand addressing verified by tools/probes/tr_probe.hip).  The direct-to-LDS load fills rows linearly, so the
-// permutation is applied on the load's SOURCE: the lane filling position cp of row r fetches logical chunk cp ^ wg_fx(r).
-__device__ __forceinline__ int wg_fx(int row) { return WgradBf16Geom::fx(row); }
-
-// One 32x32x16 operand from such an image: lane l <- 8 consecutive rows (pixels) 16*kh + 8*(l>>5) + 0..7 of column
-// col0 + (l & 31), by two ds_read_b64_tr_b16 (each: a 4-row x 16-column block per 16 lanes, returned column-major).
-__device__ __forceinline__ bf16x8 wg_operand(const char *img, unsigned a_rd0, unsigned a_rd1, int kh) {
-    typedef __attribute__((address_space(3))) s16x4 *lp;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(__attribute__((address_space(3))) char *)(img + a_rd0 + kh * 16 * WG_ROWB));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(__attribute__((address_space(3))) char *)(img + a_rd1 + kh * 16 * WG_ROWB));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-// bid: the workgroup's id within ITS problem's range of the grid (a grouped launch holds several problems' ranges one after the other)
-__device__ __forceinline__ void conv_wgrad_bf16_body(const WgradBf16Args &p, const int bid) {
-    constexpr int BM = 128, BN = 128, WK = WG_WK;
-    constexpr int TB = 256 / WK;                             // K-steps per pixel-table batch: one entry per thread
-    constexpr int IA = WK / 4 / 4, IB = WK / 4 / 4;          // DMA instructions per wave per K-step: 4 rows each, 4 waves
-    __shared__ __attribute__((aligned(16))) char lds[2][WK * (BM + BN) * 2];   // per buffer: dY [32][128], then X [32][128]
-    __shared__ int4 pixtab[2][TB * WK];                      // (x byte offset of input pixel (ih0, iw0), ih0, iw0, -)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    // Workgroup id -> (tile, K slice).  Ids are dealt round-robin to the 8 XCDs; all tiles of a slice stream the same dY / X
-    // slabs, so a slice is kept on ONE XCD (slice s on XCD s % 8, its tiles consecutive there): the slabs come through that
-    // L2 once instead of through all eight.  Without it the PMC counters showed an L2 hit rate of 39 % and 5.5x the
-    // algorithmic bytes fetched (profiles/r02_pmc_conv_bf16.txt); conv_wgrad.hip does the same for its many-tile shapes.
-    int slice, tile;
-    if (p.xcd_map) {
-        const int xcd = bid & 7, wi = bid >> 3;                // a problem's range starts at a multiple of 8: bid & 7 is the XCD
-        slice = (wi / p.tiles) * 8 + xcd;
-        tile = wi % p.tiles;
-    } else {
-        slice = bid / p.tiles;
-        tile = bid % p.tiles;
-    }
-    if (slice >= p.splits) return;                           // padding of the last group of 8 slices
-    const int m0 = (tile / p.tiles_n) * BM, n0 = (tile % p.tiles_n) * BN;
-    const int64_t kbeg = (int64_t)slice * p.per_split;
-    const int64_t kend = (kbeg + p.per_split < p.pixels) ? kbeg + p.per_split : p.pixels;
-    const int nks = (int)((kend - kbeg + WK - 1) / WK);
-    if (nks <= 0) return;
-    const int HoWo = p.Ho * p.Wo;
-
-    // buffer descriptors: dY = this K slice only (pixels past kend are out of range by themselves); X from the first
-    // image the slice touches (the host keeps a slice's span of images below 2 GiB)
-    const int n_first = (int)(kbeg / HoWo);
-    const int rel0 = (int)(kbeg - (int64_t)n_first * HoWo);
-    const int64_t img = (int64_t)p.Hi * p.Wi * p.Cin;
-    int64_t xbytes = ((int64_t)p.N - n_first) * img * 2;
-    if (xbytes > 0x7FFFFFFF) xbytes = 0x7FFFFFFF;
-    const v4i32 rs_a = make_rsrc(p.dy + kbeg * p.ldy, (unsigned)((kend - kbeg) * p.ldy * 2));
-    const v4i32 rs_b = make_rsrc(p.x + (int64_t)n_first * img, (unsigned)xbytes);
-
-    // staging geometry: instruction j of wave w fills pixel rows (w*I + j)*4 + lane/16; the lane fills chunk position cp
-    const int cp = lane & 15, rq = lane >> 4;
-    unsigned a_voff[IA];
-    int b_fr[IB], b_fs[IB], b_tapoff[IB];
-#pragma unroll
-    for (int j = 0; j < IA; ++j) {
-        const int row = WgradBf16Geom::dma_row(wave, j) + rq;
-        const int col = m0 + 8 * (cp ^ wg_fx(row));
-        a_voff[j] = col < p.ldy ? (unsigned)((row * p.ldy + col) * 2) : 0x80000000u;
-    }
-#pragma unroll
-    for (int j = 0; j < IB; ++j) {
-        const int row = WgradBf16Geom::dma_row(wave, j) + rq;
-        const int jcol = n0 + 8 * (cp ^ wg_fx(row));         // the chunk fixes (tap, first input channel)
-        const int tap = jcol / p.Cin;
-        const int ci0 = jcol - tap * p.Cin;
-        const int fr = tap / p.kw;
-        b_fs[j] = tap - fr * p.kw;
-        b_fr[j] = jcol < p.Kflat ? fr : (1 << 24);           // a column past the matrix fails every row test
-        b_tapoff[j] = ((fr * p.Wi + b_fs[j]) * p.Cin + ci0) * 2;
-    }
-
-    auto fill_batch = [&](int j) {
-        const int rel = rel0 + j * (TB * WK) + tid;
-        int4 e = make_int4(0, -(1 << 28), 0, 0);             // past the slice: fails the row test
-        if (kbeg + (int64_t)j * (TB * WK) + tid < kend) {
-            const unsigned n = (unsigned)rel / (unsigned)HoWo;
-            const unsigned rem = (unsigned)rel - n * (unsigned)HoWo;
-            const unsigned oh = rem / (unsigned)p.Wo, ow = rem - oh * (unsigned)p.Wo;
-            const int ih0 = (int)oh * p.stride - p.pad, iw0 = (int)ow * p.stride - p.pad;
-            e = make_int4((((int)n * p.Hi + ih0) * p.Wi + iw0) * p.Cin * 2, ih0, iw0, 0);
-        }
-        pixtab[j & 1][tid] = e;
-    };
-    unsigned b_voff[IB];
-    auto make_offsets = [&](int ks) {
-        const int4 *tab = pixtab[(ks / TB) & 1];
-#pragma unroll
-        for (int j = 0; j < IB; ++j) {
-            const int4 e = tab[WgradBf16Geom::tab_index(ks, wave, lane, j)];
-            const bool ok = ((unsigned)(e.y + b_fr[j]) < (unsigned)p.Hi) & ((unsigned)(e.z + b_fs[j]) < (unsigned)p.Wi);
-            b_voff[j] = ok ? (unsigned)(e.x + b_tapoff[j]) : 0xFFFFFFFFu;
-        }
-    };
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const unsigned lds0 = lds_addr(&lds[0][0]);
-    constexpr unsigned BUFB = WK * (BM + BN) * 2;
-    auto dma_step = [&](int ks, int buf) {
-        const unsigned A = lds0 + (unsigned)(buf * BUFB + wave_u * IA * 4 * WG_ROWB);
-        const unsigned B = lds0 + (unsigned)(buf * BUFB + WK * WG_ROWB + wave_u * IB * 4 * WG_ROWB);
-        const unsigned so = (unsigned)ks * (unsigned)(WK * 2) * (unsigned)p.ldy;     // scalar: the K-step advance of dY
-#pragma unroll
-        for (int j = 0; j < IA; ++j) dma16(rs_a, A + j * (4 * WG_ROWB), a_voff[j], so);   // a_voff[j] holds instruction j's rows
-#pragma unroll
-        for (int j = 0; j < IB; ++j) dma16(rs_b, B + j * (4 * WG_ROWB), b_voff[j], 0u);
-    };
-
-    // fragment read addresses (bytes within a buffer): block row r0 + q, chunk c0 + (pp >> 1), half pp & 1 (conv_wgrad_geom.h)
-    unsigned fa[2][2], fb[2][2];                             // [32-column sub-tile][read 0/1]
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int rd = 0; rd < 2; ++rd) {
-            fa[t][rd] = (unsigned)WgradBf16Geom::tr_addr(wm, t, rd, 0, lane);
-            fb[t][rd] = (unsigned)(WgradBf16Geom::IMG + WgradBf16Geom::tr_addr(wn, t, rd, 0, lane));
-        }
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e_ = 0; e_ < 16; ++e_) acc[i][j][e_] = 0.f;
-    float cs[2] = {0.f, 0.f};
-    const bool do_cs = p.colsum != nullptr && (tile % p.tiles_n) == 0 && wn == 0;
-
-    fill_batch(0);
-    __syncthreads();
-    make_offsets(0);
-    dma_step(0, 0);
-    rn_wait_dma();
-    __syncthreads();
-    for (int ks = 0; ks < nks; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nks) {
-            // the table batch of step ks+1 was published by an earlier barrier: batch b is filled during step
-            // b*TB - 4 (below) or before the loop (batch 0)
-            make_offsets(ks + 1);
-            dma_step(ks + 1, buf ^ 1);
-        }
-        const char *S = &lds[buf][0];
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-            const bf16x8 a0 = wg_operand(S, fa[0][0], fa[0][1], kh), a1 = wg_operand(S, fa[1][0], fa[1][1], kh);
-            const bf16x8 b0 = wg_operand(S, fb[0][0], fb[0][1], kh), b1 = wg_operand(S, fb[1][0], fb[1][1], kh);
-            if (do_cs) {
-#pragma unroll
-                for (int e_ = 0; e_ < 8; ++e_) { cs[0] += (float)a0[e_]; cs[1] += (float)a1[e_]; }
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        // next table batch: needed from step (b+1)*TB - 1 on (make_offsets(ks + 1)); its slot held batch b-1, last read
-        // for step b*TB - 1, i.e. during iteration b*TB - 2
-        if ((ks % TB) == TB - 4 && (ks / TB + 1) * TB < nks) fill_batch(ks / TB + 1);
-        rn_wait_dma();
-        __syncthreads();
-    }
-    if (do_cs) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            cs[t] += __shfl_xor(cs[t], 32);                   // the two 8-pixel groups of the same channel
-            const int c = m0 + wm * 64 + t * 32 + (lane & 31);
-            if (lane < 32 && c < p.Cout) atomicAdd(p.colsum + c, cs[t]);
-        }
-    }
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn) {
-            const int col = n0 + wn * 64 + tn * 32 + (lane & 31);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = m0 + wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < p.Cout && col < p.Kflat) RN_WG_ATOMIC(p.dw + (int64_t)row * p.Kpad + col, acc[tm][tn][e]);
-            }
-        }
-}
-
-__global__ __launch_bounds__(256, 3) void conv_wgrad_bf16_kernel(const WgradBf16Args p) { conv_wgrad_bf16_body(p, (int)blockIdx.x); }
-
-// Grouped launch: the pyramid levels of a head layer (D/model.py:110-205: one weight tensor convolves all five levels, so its gradient
-// is the SUM over the levels) as ONE grid accumulating into one dw / colsum.  Alone, the small levels are launches of a few dozen
-// microseconds at 60-270 TFLOP/s (8 x 9 x 15 ... 8 x 34 x 60 pixels); here they ride along with the big ones.
-struct WgradBf16Group {
-    int n;
-    int block_end[RN_MAX_GROUP];         // running sum of the problems' workgroup counts (each a multiple of 8)
-    WgradBf16Args p[RN_MAX_GROUP];
-};
-__global__ __launch_bounds__(256, 3) void conv_wgrad_bf16_grouped_kernel(const WgradBf16Group g) {
-    int i = 0;
-#pragma unroll
-    for (int j = 0; j < RN_MAX_GROUP - 1; ++j) i += (j + 1 < g.n && (int)blockIdx.x >= g.block_end[j]) ? 1 : 0;
-    i = __builtin_amdgcn_readfirstlane(i);
-    conv_wgrad_bf16_body(g.p[i], (int)blockIdx.x - (i > 0 ? g.block_end[i - 1] : 0));
-}
-
-// Geometry, K slices and grid size of one weight-gradient problem; target_wgs: the workgroups it should bring to the grid.
-// Returns the number of workgroups (> 0) or -RN_EINVAL.
-static int64_t wgrad_bf16_fill(WgradBf16Args &a, const void *dy, int ldy, const void *x, float *dw, float *colsum, int N, int Hi, int Wi,
-                               int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int target_wgs, bool pad8) {
-    a.dy = reinterpret_cast<const __bf16 *>(dy); a.x = reinterpret_cast<const __bf16 *>(x); a.dw = dw; a.colsum = colsum; a.ldy = ldy;
-    a.N = N; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-    a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
-    a.Kflat = kh * kw * Cin;
-    a.Kpad = (a.Kflat + 31) / 32 * 32;
-    a.pixels = (int64_t)N * Ho * Wo;
-    const int tiles_m = (Cout + 127) / 128;
-    a.tiles_n = (a.Kflat + 127) / 128;
-    a.tiles = tiles_m * a.tiles_n;
-    int64_t splits = (target_wgs + a.tiles - 1) / a.tiles;
-    const int64_t max_splits = (a.pixels + 16 * WG_WK - 1) / (16 * WG_WK);
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    const int64_t HoWo = (int64_t)Ho * Wo, img_bytes = (int64_t)Hi * Wi * Cin * 2;
-    for (;;) {
-        a.per_split = ((a.pixels + splits - 1) / splits + WG_WK - 1) / WG_WK * WG_WK;
-        const int64_t span_imgs = (a.per_split + HoWo - 2) / HoWo + 1;
-        if ((a.per_split + WG_WK) * ldy * 2 <= 0x7FFFFFFF && span_imgs * img_bytes <= 0x7FFFFFFF) break;
-        if (a.per_split <= WG_WK || splits >= 65535) return -RN_EINVAL;
-        splits = splits * 2 > 65535 ? 65535 : splits * 2;
-    }
-    splits = (a.pixels + a.per_split - 1) / a.per_split;
-    a.splits = (int)splits;
-    static const int xcd_env = rn_env_int("RN_WGRAD_BF16_XCD", 1);
-    a.xcd_map = xcd_env != 0 && a.tiles >= 4 && splits >= 8;
-    int64_t blocks = a.tiles * (a.xcd_map ? (splits + 7) / 8 * 8 : splits);
-    if (pad8 && !a.xcd_map) blocks = (blocks + 7) / 8 * 8;      // grouped: every problem's range starts at a multiple of 8 (surplus ids: slice >= splits)
-    return blocks;
-}
-
-// Workgroups a weight-gradient launch aims for (see rn_conv_wgrad_bf16); RN_WGRAD_BF16_WGS overrides.
-static int wgrad_bf16_target_wgs() {
-    static const int v = rn_env_int("RN_WGRAD_BF16_WGS", 0);
-    return v > 0 ? v : 768;
-}
-
-extern "C" int rn_conv_wgrad_bf16(const void *dy, int ldy, const void *x, float *dw, float *colsum, int N, int Hi, int Wi,
-                                  int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, void *stream) {
-    if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin < 8 || (Cin & 7) || (ldy & 7) || ldy < Cout)
-        return RN_EINVAL;
-    if (((uintptr_t)dy & 15) || ((uintptr_t)x & 15)) return RN_EINVAL;
-    // (A 256 x 256 eight-wave form of this reduction was built in round 4, correct and slower -- 0.51 against 0.40 ms on the head tower
-    // layer, profiles/r04_wgrad_p8_knockouts.txt -- and now lives in tools/probes/quarantine_r05/.)
-    const int target_wgs = wgrad_bf16_target_wgs();
-    // K slices for ~768 workgroups = ONE resident round at three per CU.  Every slice ends in tile-sized fp32 atomics
-    // (Cout x Kflat x slices of them per launch, ~1.3 TB/s chip-wide), and with the MFMAs eight times shorter than in the
-    // fp32 kernel that tail weighs more: measured per training step (all weight gradients) 512: 11.6 ms, 768: 11.1,
-    // 1024: 13.5, 1536: 13.2, 2048: 14.6, 3072: 15.2 (the fp32 kernel's optimum is 2048).  RN_WGRAD_BF16_WGS overrides.
-    WgradBf16Args a;
-    const int64_t blocks = wgrad_bf16_fill(a, dy, ldy, x, dw, colsum, N, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, target_wgs, false);
-    if (blocks <= 0) return RN_EINVAL;
-    hipLaunchKernelGGL(conv_wgrad_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-}
-
-// The weight gradients of n <= RN_MAX_GROUP problems that share ONE weight tensor (the pyramid levels of a head layer) as one launch:
-// dw / colsum accumulate the sum over the problems.  Per problem i: dy[i] [N, H[i], W[i], ldy] and x[i] [N, H[i], W[i], Cin] (stride-1
-// same-size geometry is NOT required: Ho / Wo follow from H, W, k, stride, pad as in rn_conv_wgrad_bf16).
-extern "C" int rn_conv_wgrad_bf16_grouped(int n, const void *const *dy, int ldy, const void *const *x, float *dw, float *colsum, int N,
-                                          const int *Hi, const int *Wi, int Cin, int Cout, int kh, int kw, int stride, int pad, void *stream) {
-    if (n < 1 || n > RN_MAX_GROUP || N <= 0 || Cout <= 0 || Cin < 8 || (Cin & 7) || (ldy & 7) || ldy < Cout) return RN_EINVAL;
-    const int target_wgs = wgrad_bf16_target_wgs();
-    int Ho[RN_MAX_GROUP], Wo[RN_MAX_GROUP];
-    int64_t total_pixels = 0;
-    for (int i = 0; i < n; ++i) {
-        if (Hi[i] <= 0 || Wi[i] <= 0 || ((uintptr_t)dy[i] & 15) || ((uintptr_t)x[i] & 15)) return RN_EINVAL;
-        Ho[i] = (Hi[i] + 2 * pad - kh) / stride + 1;
-        Wo[i] = (Wi[i] + 2 * pad - kw) / stride + 1;
-        if (Ho[i] <= 0 || Wo[i] <= 0) return RN_EINVAL;
-        total_pixels += (int64_t)N * Ho[i] * Wo[i];
-    }
-    WgradBf16Group g;
-    g.n = n;
-    int64_t end = 0;
-    for (int i = 0; i < n; ++i) {
-        // the problem's share of one resident round, by its pixels (at least one slice per tile: wgrad_bf16_fill)
-        const int share = (int)((int64_t)target_wgs * ((int64_t)N * Ho[i] * Wo[i]) / total_pixels);
-        const int64_t blocks = wgrad_bf16_fill(g.p[i], dy[i], ldy, x[i], dw, colsum, N, Hi[i], Wi[i], Cin, Ho[i], Wo[i], Cout, kh, kw, stride, pad,
-                                               share, true);
-        if (blocks <= 0) return RN_EINVAL;
-        end += blocks;
-        if (end > 0x7fffffff) return RN_EINVAL;
-        g.block_end[i] = (int)end;
-    }
-    for (int i = n; i < RN_MAX_GROUP; ++i) g.block_end[i] = (int)end;
-    hipLaunchKernelGGL(conv_wgrad_bf16_grouped_kernel, dim3((unsigned)end), dim3(256), 0, (hipStream_t)stream, g);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-}

@@ -40,17 +40,7 @@
 #include "common.h"
 #include "conv_wgrad_geom.h"
 
-// RN_WG_KO (RN_EXPERIMENT builds; timing only, wrong results): 1 = the tile-sized atomic accumulation left out, 2 = workgroup-scope atomics
-#ifndef RN_WG_KO
-#define RN_WG_KO 0
-#endif
-#if RN_WG_KO == 1
-#define RN_WG_ATOMIC(P, V) do { if ((V) == 1.2345e-30f) atomicAdd((P), (V)); } while (0)
-#elif RN_WG_KO == 2
-#define RN_WG_ATOMIC(P, V) __hip_atomic_fetch_add((P), (V), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#else
-#define RN_WG_ATOMIC(P, V) atomicAdd((P), (V))
-#endif
+#include "conv_wgrad_plan.h"
 #include "mfma_split.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -112,21 +102,9 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_kernel(const WgradArgs p)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    // Workgroup id -> (tile, K slice).  Ids are dealt round-robin to the 8 XCDs; all tiles of one K slice read the same
-    // dY / X slabs, so a slice is kept on ONE XCD (slice s on XCD s % 8, its tiles consecutive there) and the slabs
-    // stream through that L2 once instead of through all eight.
-    // Measured: a win (+4..10 %) when a slice has many tiles to share the slabs (>= 16: the 256-channel 3x3 layers), a
-    // loss for the few-tile shapes, which keep the plain order (consecutive ids = the tiles of one slice).
-    int slice, tile;
-    if (p.xcd_map) {
-        const int xcd = blockIdx.x & 7, wi = blockIdx.x >> 3;
-        slice = (wi / p.tiles) * 8 + xcd;
-        tile = wi % p.tiles;
-    } else {
-        slice = blockIdx.x / p.tiles;
-        tile = blockIdx.x % p.tiles;
-    }
-    if (slice >= p.splits) return;                           // padding of the last group of 8 slices
+    const WgradPlace place = wgrad_place(blockIdx.x, p.tiles, p.splits, p.xcd_map);   // (K slice, tile): conv_wgrad_geom.h
+    if (!place.live) return;                                 // padding of the last group of 8 slices
+    int slice = place.slice, tile = place.tile;
     // Batched form (the 36 positions of the Winograd weight gradient): independent problems of identical shape, operands
     // and result p.*_bstride apart; a tile index enumerates (batch entry, tile).
     const int batch = tile / p.tiles_per_batch;
@@ -135,23 +113,16 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_kernel(const WgradArgs p)
     const float *x_b = p.x + (int64_t)batch * p.x_bstride;
     float *dw_b = p.dw + (int64_t)batch * p.dw_bstride;
     const int m0 = (tile / p.tiles_n) * BM, n0 = (tile % p.tiles_n) * BN;
-    const int64_t kbeg = (int64_t)slice * p.per_split;
-    const int64_t kend = (kbeg + p.per_split < p.pixels) ? kbeg + p.per_split : p.pixels;
-    const int nks = (int)((kend - kbeg + WK - 1) / WK);
+    WgradSlice<4, WK> sl(slice, p.per_split, p.pixels);      // conv_wgrad_geom.h
+    const int64_t kbeg = sl.kbeg, kend = sl.kend;
+    const int nks = sl.nks;
     if (nks <= 0) return;
     const int HoWo = p.Ho * p.Wo;
-
-    // Buffer descriptors (scalar registers).
-    //   dY: the K slice [kbeg, kend) only, so "pixel >= kend" is out of range by itself;
-    //   X : from the first image the slice touches; the host guarantees that the span of images of one slice stays
-    //       below 2 GiB, so byte offsets are plain int32 and -1 is always out of range.
-    const int n_first = (int)(kbeg / HoWo);
-    const int rel0 = (int)(kbeg - (int64_t)n_first * HoWo);  // index of pixel kbeg within image n_first
     const int64_t img = (int64_t)p.Hi * p.Wi * p.Cin;        // floats per input image
-    int64_t xbytes = ((int64_t)p.N - n_first) * img * 4;
-    if (xbytes > 0x7FFFFFFF) xbytes = 0x7FFFFFFF;
+    sl.locate(HoWo, p.N, img);
+    // Buffer descriptors (scalar registers): dY = the K slice [kbeg, kend) only, X from the first image the slice touches (WgradSlice)
     const v4i32 rs_a = make_rsrc(dy_b + kbeg * p.ldy, (unsigned)((kend - kbeg) * p.ldy * 4));
-    const v4i32 rs_b = make_rsrc(x_b + (int64_t)n_first * img, (unsigned)xbytes);
+    const v4i32 rs_b = make_rsrc(x_b + (int64_t)sl.n_first * img, (unsigned)sl.xbytes);
 
     // Lane -> (pixel within the instruction's group, 16-byte chunk).  Instruction j of wave w fills pixels
     // (w * I + j) * P + lane / C of the tile: 1 KiB of LDS starting at that pixel's row.
@@ -160,25 +131,14 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_kernel(const WgradArgs p)
     const bool a_col_ok = (m0 + 4 * ca) < p.ldy;
     const unsigned a_voff = a_col_ok ? (unsigned)(((wave * IA * PA + pa) * p.ldy + m0 + 4 * ca) * 4) : 0x80000000u;
     const unsigned a_step = (unsigned)(PA * 4) * (unsigned)p.ldy;          // bytes between consecutive instructions (scalar)
-    const int jcol = n0 + 4 * cb;                            // B: the chunk fixes (tap, first input channel)
-    const int tap = jcol / p.Cin;
-    const int ci0 = jcol - tap * p.Cin;
-    const int fr = tap / p.kw, fs = tap - fr * p.kw;
-    const int fr_t = jcol < p.Kflat ? fr : (1 << 24);        // a column past the matrix fails every row test below
-    const int tap_off = ((fr * p.Wi + fs) * p.Cin + ci0) * 4;
+    const WgradTap tap = wgrad_tap<4>(n0 + 4 * cb, p.Cin, p.kw, p.Wi, p.Kflat);   // B: the chunk fixes (tap, first input channel)
 
-    // Pixel table: one entry per pixel of the K range, (byte offset of input pixel (ih0, iw0) channel 0, ih0, iw0) with
-    // ih0 = oh*stride - pad: the two integer divisions of the (n, oh, ow) decomposition are done once per pixel for all
-    // lanes and all taps.  Filled TB K-steps at a time by the whole workgroup (one entry per thread).
+    // Pixel table: one entry per pixel of the K range (wgrad_pixel), filled TB K-steps at a time by the whole workgroup.
     auto fill_batch = [&](int j) {
-        const int rel = rel0 + j * (TB * WK) + tid;
-        int4 e = make_int4(0, -(1 << 28), 0, 0);              // past the slice: fails the row test (also with fr_t added)
+        int4 e = make_int4(0, WGRAD_PIXEL_DEAD, 0, 0);        // past the slice
         if (kbeg + (int64_t)j * (TB * WK) + tid < kend) {
-            const unsigned n = (unsigned)rel / (unsigned)HoWo;
-            const unsigned rem = (unsigned)rel - n * (unsigned)HoWo;
-            const unsigned oh = rem / (unsigned)p.Wo, ow = rem - oh * (unsigned)p.Wo;
-            const int ih0 = (int)oh * p.stride - p.pad, iw0 = (int)ow * p.stride - p.pad;
-            e = make_int4((((int)n * p.Hi + ih0) * p.Wi + iw0) * p.Cin * 4, ih0, iw0, 0);
+            const WgradPixel q = wgrad_pixel<4>(sl.rel0 + j * (TB * WK) + tid, HoWo, p.Wo, p.stride, p.pad, p.Hi, p.Wi, p.Cin);
+            e = make_int4(q.off, q.ih0, q.iw0, 0);
         }
         pixtab[j & 1][tid] = e;
     };
@@ -197,8 +157,8 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_kernel(const WgradArgs p)
     auto make_offsets = [&]() {
 #pragma unroll
         for (int j = 0; j < IB; ++j) {
-            const bool ok = ((unsigned)(e[j].y + fr_t) < (unsigned)p.Hi) & ((unsigned)(e[j].z + fs) < (unsigned)p.Wi);
-            b_voff[j] = ok ? (unsigned)(e[j].x + tap_off) : 0xFFFFFFFFu;
+            const bool ok = wgrad_tap_inside(e[j].y, e[j].z, tap.fr_t, tap.fs, p.Hi, p.Wi);
+            b_voff[j] = ok ? (unsigned)(e[j].x + tap.off) : 0xFFFFFFFFu;
         }
     };
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -215,13 +175,7 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_kernel(const WgradArgs p)
         for (int j = 0; j < IB; ++j) dma16(rs_b, B + j * (PB * BN * 4), b_voff[j], 0u);
     };
 
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e_ = 0; e_ < 16; ++e_) acc[i][j][e_] = 0.f;
+    f32x16 acc[2][2] = {};
     float2 cs = make_float2(0.f, 0.f);                       // column sums of this lane's two channels (its k parity)
     float s_a = 1.f, s_b = 1.f, us = 1.f;                    // HALF: operand scales and the product of their inverses
     if constexpr (HALF) {
@@ -361,16 +315,6 @@ __global__ __launch_bounds__(256, OCC) void conv_wgrad_kernel(const WgradArgs p)
 // (conv_wgrad_geom.h: WgradSplitGeom, the bf16 kernel's image); the MFMA phase reads ready operands through gfx950's transposing
 // LDS read (ds_read_b64_tr_b16: 8 consecutive pixels of one column per lane, two reads).  128 x 128 tile, 48 KB of LDS, three
 // workgroups per CU, same grid / K slices / atomics (or slabs) / column sums as the kernel above.
-typedef short s16x4w __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 wgs_operand(const char *img, unsigned a0, unsigned a1) {
-    typedef __attribute__((address_space(3))) s16x4w *lp;
-    const s16x4w lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(__attribute__((address_space(3))) char *)(img + a0));
-    const s16x4w hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(__attribute__((address_space(3))) char *)(img + a1));
-    typedef short s16x8w __attribute__((ext_vector_type(8)));
-    const s16x8w v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
-
 // HALF: the fp16 two-term form (RN_FP32_SPLIT3): two planes per operand (a buffer = dY hi, lo, X hi, lo: 16 KB instead of 24), the
 // operands scaled by their tensors' powers of two inside the split, three v_mfma_f32_32x32x16_f16 per block, the tile multiplied by the
 // two inverse scales before its atomics.
@@ -390,59 +334,41 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    int slice, tile;
-    if (p.xcd_map) {
-        const int xcd = blockIdx.x & 7, wi = blockIdx.x >> 3;
-        slice = (wi / p.tiles) * 8 + xcd;
-        tile = wi % p.tiles;
-    } else {
-        slice = blockIdx.x / p.tiles;
-        tile = blockIdx.x % p.tiles;
-    }
-    if (slice >= p.splits) return;
+    const WgradPlace place = wgrad_place(blockIdx.x, p.tiles, p.splits, p.xcd_map);
+    if (!place.live) return;
+    int slice = place.slice, tile = place.tile;
     const int batch = tile / p.tiles_per_batch;
     tile -= batch * p.tiles_per_batch;
     const float *dy_b = p.dy + (int64_t)batch * p.dy_bstride;
     const float *x_b = p.x + (int64_t)batch * p.x_bstride;
     float *dw_b = p.dw + (int64_t)batch * p.dw_bstride;
     const int m0 = (tile / p.tiles_n) * BM, n0 = (tile % p.tiles_n) * BN;
-    const int64_t kbeg = (int64_t)slice * p.per_split;
-    const int64_t kend = (kbeg + p.per_split < p.pixels) ? kbeg + p.per_split : p.pixels;
-    const int nks = (int)((kend - kbeg + WK - 1) / WK);
+    WgradSlice<4, WK> sl(slice, p.per_split, p.pixels);
+    const int64_t kbeg = sl.kbeg, kend = sl.kend;
+    const int nks = sl.nks;
     if (nks <= 0) return;
     const int HoWo = p.Ho * p.Wo;
-    const int n_first = (int)(kbeg / HoWo);
-    const int rel0 = (int)(kbeg - (int64_t)n_first * HoWo);
     const int64_t img = (int64_t)p.Hi * p.Wi * p.Cin;
-    int64_t xbytes = ((int64_t)p.N - n_first) * img * 4;
-    if (xbytes > 0x7FFFFFFF) xbytes = 0x7FFFFFFF;
+    sl.locate(HoWo, p.N, img);
     // buffer descriptors: dY = this K slice only (pixels past kend read as zero); X from the first image the slice touches
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(dy_b + kbeg * p.ldy), (short)0,
                                                                           (int)(unsigned)((kend - kbeg) * p.ldy * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x_b + (int64_t)n_first * img), (short)0,
-                                                                          (int)(unsigned)xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x_b + (int64_t)sl.n_first * img), (short)0,
+                                                                          (int)(unsigned)sl.xbytes, 0x00020000);
     // this thread: 4-channel chunk c of pixels px0 and px0 + 8 of every K-step, for both operands
     const int c = G::chunk(tid), px0 = G::pixel(tid, 0);
     const bool a_col_ok = (m0 + 4 * c) < p.ldy;
     const unsigned a_voff = a_col_ok ? (unsigned)((px0 * p.ldy + m0 + 4 * c) * 4) : 0x80000000u;
     const unsigned a_half = (unsigned)(8 * p.ldy * 4);       // bytes from pixel p to pixel p + 8 (scalar)
     const int jcol = n0 + 4 * c;                             // X: the chunk fixes (tap, first input channel)
-    const int tap = jcol / p.Cin;
-    const int ci0 = jcol - tap * p.Cin;
-    const int fr = tap / p.kw, fs = tap - fr * p.kw;
-    const int fr_t = jcol < p.Kflat ? fr : (1 << 24);        // a column past the matrix fails every row test
-    const int tap_off = ((fr * p.Wi + fs) * p.Cin + ci0) * 4;
+    const WgradTap tap = wgrad_tap<4>(jcol, p.Cin, p.kw, p.Wi, p.Kflat);
     const unsigned wr0 = (unsigned)G::wr_addr(tid, 0), wr1 = (unsigned)G::wr_addr(tid, 1);
 
     auto fill_batch = [&](int j) {
-        const int rel = rel0 + j * (TB * WK) + tid;
-        int2 e = make_int2(0, 0x8000);                       // past the slice: ih0 = -32768 fails the row test (also with fr_t added)
+        int2 e = make_int2(0, WGRAD_PACKED_DEAD);            // past the slice: ih0 = -32768 fails the row test (also with fr_t added)
         if (kbeg + (int64_t)j * (TB * WK) + tid < kend) {
-            const unsigned n = (unsigned)rel / (unsigned)HoWo;
-            const unsigned rem = (unsigned)rel - n * (unsigned)HoWo;
-            const unsigned oh = rem / (unsigned)p.Wo, ow = rem - oh * (unsigned)p.Wo;
-            const int ih0 = (int)oh * p.stride - p.pad, iw0 = (int)ow * p.stride - p.pad;      // both fit 16 bits (launcher)
-            e = make_int2((((int)n * p.Hi + ih0) * p.Wi + iw0) * p.Cin * 4, (ih0 & 0xffff) | (iw0 << 16));
+            const WgradPixel q = wgrad_pixel<4>(sl.rel0 + j * (TB * WK) + tid, HoWo, p.Wo, p.stride, p.pad, p.Hi, p.Wi, p.Cin);
+            e = make_int2(q.off, wgrad_pixel_pack(q.ih0, q.iw0));                            // both fit 16 bits (launcher)
         }
         pixtab[j & 1][tid] = e;
     };
@@ -489,7 +415,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
             for (int h = 0; h < 2; ++h) {
                 const int64_t px = kbeg + (int64_t)kq * WK + G::pixel(tid, h);       // n_first = 0: the pixel's index is its offset in x
                 const bool ok = px < kend && jcol < p.Kflat;
-                const unsigned v = ok ? (unsigned)((int)px * p.Cin * 4 + tap_off) : 0x80000000u;
+                const unsigned v = ok ? (unsigned)((int)px * p.Cin * 4 + tap.off) : 0x80000000u;
                 r.b[h] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_b, (int)v, 0, 0));
             }
             return;
@@ -501,9 +427,8 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int2 e = tab[G::tab_index(ks, tid, h)];
-            const int ih0 = (int)(short)(e.y & 0xffff), iw0 = e.y >> 16;
-            const unsigned ok = (((unsigned)(ih0 + fr_t) < (unsigned)p.Hi) & ((unsigned)(iw0 + fs) < (unsigned)p.Wi)) ? 0xFFFFFFFFu : 0u;
-            const unsigned v = ((unsigned)(e.x + tap_off) & ok) | (0x80000000u & ~ok);
+            const unsigned ok = wgrad_tap_inside(wgrad_packed_ih0(e.y), wgrad_packed_iw0(e.y), tap.fr_t, tap.fs, p.Hi, p.Wi) ? 0xFFFFFFFFu : 0u;
+            const unsigned v = ((unsigned)(e.x + tap.off) & ok) | (0x80000000u & ~ok);
             r.b[h] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs_b, (int)v, 0, 0));
         }
     };
@@ -565,13 +490,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
             fa[t][rd] = (unsigned)G::tr_addr(wm, t, rd, lane);
             fb[t][rd] = (unsigned)(NP * G::IMG + G::tr_addr(wn, t, rd, lane));
         }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e_ = 0; e_ < 16; ++e_) acc[i][j][e_] = 0.f;
+    f32x16 acc[2][2] = {};
 
     if constexpr (!SKIP) {
         fill_batch(0);
@@ -590,10 +509,10 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
             SplitH8 sa[2], sb[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                sa[t].h = __builtin_bit_cast(f16x8, wgs_operand(S, fa[t][0], fa[t][1]));
-                sa[t].l = __builtin_bit_cast(f16x8, wgs_operand(S + G::IMG, fa[t][0], fa[t][1]));
-                sb[t].h = __builtin_bit_cast(f16x8, wgs_operand(S, fb[t][0], fb[t][1]));
-                sb[t].l = __builtin_bit_cast(f16x8, wgs_operand(S + G::IMG, fb[t][0], fb[t][1]));
+                sa[t].h = __builtin_bit_cast(f16x8, wg_operand(S, fa[t][0], fa[t][1]));
+                sa[t].l = __builtin_bit_cast(f16x8, wg_operand(S + G::IMG, fa[t][0], fa[t][1]));
+                sb[t].h = __builtin_bit_cast(f16x8, wg_operand(S, fb[t][0], fb[t][1]));
+                sb[t].l = __builtin_bit_cast(f16x8, wg_operand(S + G::IMG, fb[t][0], fb[t][1]));
             }
             split_store(buf ^ 1, cur);
             load_step(ks + 2, nxt);
@@ -605,12 +524,12 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_once_kernel(const WgradArgs
         Split8 sa[2], sb[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            sa[t].h = wgs_operand(S, fa[t][0], fa[t][1]);
-            sa[t].m = wgs_operand(S + G::IMG, fa[t][0], fa[t][1]);
-            sa[t].l = wgs_operand(S + 2 * G::IMG, fa[t][0], fa[t][1]);
-            sb[t].h = wgs_operand(S, fb[t][0], fb[t][1]);
-            sb[t].m = wgs_operand(S + G::IMG, fb[t][0], fb[t][1]);
-            sb[t].l = wgs_operand(S + 2 * G::IMG, fb[t][0], fb[t][1]);
+            sa[t].h = wg_operand(S, fa[t][0], fa[t][1]);
+            sa[t].m = wg_operand(S + G::IMG, fa[t][0], fa[t][1]);
+            sa[t].l = wg_operand(S + 2 * G::IMG, fa[t][0], fa[t][1]);
+            sb[t].h = wg_operand(S, fb[t][0], fb[t][1]);
+            sb[t].m = wg_operand(S + G::IMG, fb[t][0], fb[t][1]);
+            sb[t].l = wg_operand(S + 2 * G::IMG, fb[t][0], fb[t][1]);
         }
         split_store(buf ^ 1, cur);
         load_step(ks + 2, nxt);
@@ -692,7 +611,90 @@ static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, flo
                         int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                         int in_relu, void *stream, bool det, void *workspace, int64_t workspace_bytes, int64_t *need_bytes,
                         const void *dy_amax = nullptr, int dy_amax_n = 0, const void *x_amax = nullptr, int x_amax_n = 0,
-                        const void *k_active = nullptr, int32_t *plan = nullptr);
+                        const void *k_active = nullptr, int32_t *plan = nullptr) {
+    if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin < 4 || (Cin & 3) || (ldy & 3) || ldy < Cout)
+        return RN_EINVAL;
+    if (nbatch < 1 || nbatch > 4096 || dy_bstride < 0 || x_bstride < 0 || dw_bstride < 0 || colsum_batch < 0 || colsum_batch >= nbatch)
+        return RN_EINVAL;
+    WgradArgs a;
+    a.dy_bstride = dy_bstride; a.x_bstride = x_bstride; a.dw_bstride = dw_bstride; a.colsum_batch = colsum_batch;
+    a.dy = dy; a.x = x; a.dw = dw; a.colsum = colsum; a.ldy = ldy;
+    a.N = N; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
+    a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad; a.in_relu = in_relu;
+    a.Kflat = kh * kw * Cin;
+    a.Kpad = (a.Kflat + 31) / 32 * 32;
+    a.pixels = (int64_t)N * Ho * Wo;
+    // tile shape: 64 x 256 for few output channels, 256 x 64 for a short packed row (1x1 from 64 channels), else 128 x 128
+    const int shape = Cout <= 64 ? 0 : (a.Kflat <= 64 ? 1 : 2);
+    const int BM = shape == 0 ? 64 : (shape == 1 ? 256 : 128), BN = shape == 0 ? 256 : (shape == 1 ? 64 : 128);
+    const int tiles_m = (Cout + BM - 1) / BM;
+    a.tiles_n = (a.Kflat + BN - 1) / BN;
+    a.tiles_per_batch = tiles_m * a.tiles_n;
+    const int tiles = a.tiles_per_batch * nbatch;
+    // enough K slices for ~2048 workgroups -- two rounds of what the chip holds (4 per CU at 40 KB of LDS); measured per
+    // training step: 512 -> 66.0 ms, 1024 -> 57.3, 1536 -> 55.2, 2048 -> 54.2, 4096 -> 54.9, 8192 -> 55.1 -- each at
+    // least 512 pixels long
+    static const int wgs_native = rn_env_int("RN_WGRAD_WGS", 2048);
+    static const int wgs_split = rn_env_int("RN_WGRAD_SPLIT_WGS", 1536);   // split kernels: three per CU -> two rounds of 768 (measured 768 / 1024 / 1536 / 2048 / 3072: 21.8 / 21.5 / 20.6 / 21.0 / 21.5 ms per step)
+    const int wg_target = rn_get_fp32_mfma() != RN_FP32_NATIVE ? wgs_split : wgs_native;
+    const WgradPlanIn in = {a.pixels, tiles, wg_target, WK_MAX, ldy, 4, (int64_t)Ho * Wo, (int64_t)Hi * Wi * Cin * 4, WGRAD_XCD_FP32, true, false};
+    WgradPlan pl;
+    if (!wgrad_plan(in, pl)) return RN_EINVAL;               // conv_wgrad_plan.h
+    const int64_t splits = pl.splits;
+    a.per_split = pl.per_split; a.xcd_map = pl.xcd_map; a.tiles = tiles; a.splits = pl.splits;
+    a.slab = a.cs_slab = nullptr;
+    a.slab_stride = 0;
+    // 16-pixel K-steps: 40-48 KiB of LDS, four / three workgroups per CU (measured: +2..4 % over 32-pixel steps at two per CU
+    // on the mid-size layers, equal on the largest; the 64 x 256 tile does not fit twice at 32).
+    const bool split = rn_get_fp32_mfma() != RN_FP32_NATIVE;
+    // RN_FP32_SPLIT3 with both amax words: the fp16 two-term kernels; without them (a caller of the plain entry point) the three-term ones
+    const bool half = rn_get_fp32_mfma() == RN_FP32_SPLIT3 && dy_amax != nullptr && x_amax != nullptr && dy_amax_n != 0 && x_amax_n != 0;
+    // RN_OPT_WGRAD_ONCE = 0: the per-wave split for the 128 x 128 tile too (A/B)
+    const bool once = split && shape == 2 && rn_get_option(RN_OPT_WGRAD_ONCE) != 0 && Hi + pad < 32000 && Wi + pad < 32000;
+    // only the once-split kernel lists and skips; no quiet dense run
+    if (k_active != nullptr && (!once || in_relu || (a.per_split + 15) / 16 > RN_WG_SKIP_MAX)) return RN_EINVAL;
+    if (plan != nullptr) {                                   // rn_conv_wgrad_plan: the numbers above, nothing launched
+        plan[0] = shape; plan[1] = tiles; plan[2] = a.splits; plan[3] = (int32_t)a.per_split; plan[4] = a.xcd_map;
+        plan[5] = (int32_t)pl.grid; plan[6] = once ? 1 : 0; plan[7] = half ? 2 : (split ? 1 : 0);
+        return RN_OK;
+    }
+    if (det) {
+        a.slab_stride = nbatch > 1 ? (int64_t)nbatch * dw_bstride : (int64_t)Cout * a.Kpad;
+        const int64_t need = splits * (a.slab_stride + Cout) * (int64_t)sizeof(float);
+        if (need_bytes != nullptr) { *need_bytes = need; return RN_OK; }
+        if (workspace_bytes < need) return RN_EINVAL;
+        a.slab = reinterpret_cast<float *>(workspace);
+        a.cs_slab = a.slab + splits * a.slab_stride;
+    }
+    const dim3 grid((unsigned)pl.grid);
+    a.dy_amax = dy_amax;
+    a.x_amax = x_amax;
+    a.dy_amax_n = dy_amax_n;
+    a.x_amax_n = x_amax_n;
+    a.k_active = reinterpret_cast<const unsigned char *>(k_active);
+    // [tile shape 0 .. 2 of conv_wgrad_kernel, 3 = conv_wgrad_once_kernel][0 fp32 / 1 three bf16 terms / 2 two fp16 terms][0 plain / 1 relu / 2 skip list]
+#define RN_WG_TILE(WM_, WN_, S_, H_) {conv_wgrad_kernel<WM_, WN_, false, 16, 3, S_, H_>, conv_wgrad_kernel<WM_, WN_, true, 16, 3, S_, H_>, nullptr}
+#define RN_WG_TILES(WM_, WN_) {RN_WG_TILE(WM_, WN_, false, false), RN_WG_TILE(WM_, WN_, true, false), RN_WG_TILE(WM_, WN_, true, true)}
+    static constexpr void (*instance[4][3][3])(const WgradArgs) = {
+        RN_WG_TILES(1, 4), RN_WG_TILES(4, 1), RN_WG_TILES(2, 2),
+        {{nullptr, nullptr, nullptr},
+         {conv_wgrad_once_kernel<false, false>, conv_wgrad_once_kernel<true, false>, conv_wgrad_once_kernel<false, false, true>},
+         {conv_wgrad_once_kernel<false, true>, conv_wgrad_once_kernel<true, true>, conv_wgrad_once_kernel<false, true, true>}}};
+#undef RN_WG_TILES
+#undef RN_WG_TILE
+    const auto kernel = instance[once ? 3 : shape][half ? 2 : (split ? 1 : 0)][k_active != nullptr ? 2 : (in_relu ? 1 : 0)];
+    if (kernel == nullptr) return RN_EINVAL;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    RN_LAUNCH_CHECK();
+    if (det) {
+        const int64_t total = (int64_t)nbatch * Cout * a.Kflat;
+        hipLaunchKernelGGL(wgrad_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dw,
+                           (const float *)a.slab, a.slab_stride, a.splits, nbatch, dw_bstride, Cout, a.Kflat, a.Kpad, colsum,
+                           (const float *)a.cs_slab);
+        RN_LAUNCH_CHECK();
+    }
+    return RN_OK;
+}
 
 extern "C" int rn_conv_wgrad_batched(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
                                      int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
@@ -747,123 +749,6 @@ extern "C" int rn_conv_wgrad_plan(int ldy, int nbatch, int64_t dy_bstride, int64
     return wgrad_launch(nullptr, ldy, nullptr, nullptr, nullptr, nbatch, dy_bstride, x_bstride, dw_bstride, colsum_batch, N, Hi, Wi, Cin, Ho,
                         Wo, Cout, kh, kw, stride, pad, in_relu, nullptr, det != 0, nullptr, 0, nullptr, am, have_amax ? 1 : 0, am,
                         have_amax ? 1 : 0, have_flags ? &word : nullptr, out);
-}
-
-static int wgrad_launch(const float *dy, int ldy, const float *x, float *dw, float *colsum, int nbatch,
-                        int64_t dy_bstride, int64_t x_bstride, int64_t dw_bstride, int colsum_batch, int N, int Hi,
-                        int Wi, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
-                        int in_relu, void *stream, bool det, void *workspace, int64_t workspace_bytes, int64_t *need_bytes,
-                        const void *dy_amax, int dy_amax_n, const void *x_amax, int x_amax_n, const void *k_active, int32_t *plan) {
-    if (N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin < 4 || (Cin & 3) || (ldy & 3) || ldy < Cout)
-        return RN_EINVAL;
-    if (nbatch < 1 || nbatch > 4096 || dy_bstride < 0 || x_bstride < 0 || dw_bstride < 0 || colsum_batch < 0 || colsum_batch >= nbatch)
-        return RN_EINVAL;
-    WgradArgs a;
-    a.dy_bstride = dy_bstride; a.x_bstride = x_bstride; a.dw_bstride = dw_bstride; a.colsum_batch = colsum_batch;
-    a.dy = dy; a.x = x; a.dw = dw; a.colsum = colsum; a.ldy = ldy;
-    a.N = N; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-    a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad; a.in_relu = in_relu;
-    a.Kflat = kh * kw * Cin;
-    a.Kpad = (a.Kflat + 31) / 32 * 32;
-    a.pixels = (int64_t)N * Ho * Wo;
-    // tile shape: 64 x 256 for few output channels, 256 x 64 for a short packed row (1x1 from 64 channels), else 128 x 128
-    const int shape = Cout <= 64 ? 0 : (a.Kflat <= 64 ? 1 : 2);
-    const int BM = shape == 0 ? 64 : (shape == 1 ? 256 : 128), BN = shape == 0 ? 256 : (shape == 1 ? 64 : 128);
-    const int tiles_m = (Cout + BM - 1) / BM;
-    a.tiles_n = (a.Kflat + BN - 1) / BN;
-    a.tiles_per_batch = tiles_m * a.tiles_n;
-    const int tiles = a.tiles_per_batch * nbatch;
-    // enough K slices for ~2048 workgroups -- two rounds of what the chip holds (4 per CU at 40 KB of LDS); measured per
-    // training step: 512 -> 66.0 ms, 1024 -> 57.3, 1536 -> 55.2, 2048 -> 54.2, 4096 -> 54.9, 8192 -> 55.1 -- each at
-    // least 512 pixels long
-    static const int wgs_native = rn_env_int("RN_WGRAD_WGS", 2048);
-    static const int wgs_split = rn_env_int("RN_WGRAD_SPLIT_WGS", 1536);   // split kernels: three per CU -> two rounds of 768 (measured 768 / 1024 / 1536 / 2048 / 3072: 21.8 / 21.5 / 20.6 / 21.0 / 21.5 ms per step)
-    const int wg_target = rn_get_fp32_mfma() != RN_FP32_NATIVE ? wgs_split : wgs_native;
-    int64_t splits = (wg_target + tiles - 1) / tiles;
-    const int64_t max_splits = (a.pixels + 16 * WK_MAX - 1) / (16 * WK_MAX);
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    a.xcd_map = tiles >= 16 && splits > 8 && splits + 7 <= max_splits;
-    if (a.xcd_map) splits = (splits + 7) / 8 * 8;            // whole slices per XCD: equal shares for the 8
-    // Buffer-load addressing (see the kernel): the dY bytes of one K slice and the span of input images a slice can
-    // touch must each stay below 2 GiB; more slices make both smaller.
-    const int64_t HoWo = (int64_t)Ho * Wo, img_bytes = (int64_t)Hi * Wi * Cin * 4;
-    for (;;) {
-        a.per_split = ((a.pixels + splits - 1) / splits + WK_MAX - 1) / WK_MAX * WK_MAX;
-        const int64_t span_imgs = (a.per_split + HoWo - 2) / HoWo + 1;
-        if ((a.per_split + WK_MAX) * ldy * 4 <= 0x7FFFFFFF && span_imgs * img_bytes <= 0x7FFFFFFF) break;
-        if (a.per_split <= WK_MAX || splits >= 65535) return RN_EINVAL;   // a single image of > 2 GiB
-        splits = splits * 2 > 65535 ? 65535 : splits * 2;
-        a.xcd_map = 0;
-    }
-    splits = (a.pixels + a.per_split - 1) / a.per_split;
-    a.tiles = tiles;
-    a.splits = (int)splits;
-    a.slab = a.cs_slab = nullptr;
-    a.slab_stride = 0;
-    // 16-pixel K-steps: 40-48 KiB of LDS, four / three workgroups per CU (measured: +2..4 % over 32-pixel steps at two per CU
-    // on the mid-size layers, equal on the largest; the 64 x 256 tile does not fit twice at 32).
-    const bool split = rn_get_fp32_mfma() != RN_FP32_NATIVE;
-    // RN_FP32_SPLIT3 with both amax words: the fp16 two-term kernels; without them (a caller of the plain entry point) the three-term ones
-    const bool half = rn_get_fp32_mfma() == RN_FP32_SPLIT3 && dy_amax != nullptr && x_amax != nullptr && dy_amax_n != 0 && x_amax_n != 0;
-    // RN_OPT_WGRAD_ONCE = 0: the per-wave split for the 128 x 128 tile too (A/B)
-    const bool once = split && shape == 2 && rn_get_option(RN_OPT_WGRAD_ONCE) != 0 && Hi + pad < 32000 && Wi + pad < 32000;
-    // only the once-split kernel lists and skips; no quiet dense run
-    if (k_active != nullptr && (!once || in_relu || (a.per_split + 15) / 16 > RN_WG_SKIP_MAX)) return RN_EINVAL;
-    const int64_t grid_wgs = (int64_t)tiles * (a.xcd_map ? (splits + 7) / 8 * 8 : splits);
-    if (plan != nullptr) {                                   // rn_conv_wgrad_plan: the numbers above, nothing launched
-        plan[0] = shape; plan[1] = tiles; plan[2] = a.splits; plan[3] = (int32_t)a.per_split; plan[4] = a.xcd_map;
-        plan[5] = (int32_t)grid_wgs; plan[6] = once ? 1 : 0; plan[7] = half ? 2 : (split ? 1 : 0);
-        return RN_OK;
-    }
-    if (det) {
-        a.slab_stride = nbatch > 1 ? (int64_t)nbatch * dw_bstride : (int64_t)Cout * a.Kpad;
-        const int64_t need = splits * (a.slab_stride + Cout) * (int64_t)sizeof(float);
-        if (need_bytes != nullptr) { *need_bytes = need; return RN_OK; }
-        if (workspace_bytes < need) return RN_EINVAL;
-        a.slab = reinterpret_cast<float *>(workspace);
-        a.cs_slab = a.slab + splits * a.slab_stride;
-    }
-    const dim3 grid((unsigned)grid_wgs);
-    a.dy_amax = dy_amax;
-    a.x_amax = x_amax;
-    a.dy_amax_n = dy_amax_n;
-    a.x_amax_n = x_amax_n;
-    a.k_active = reinterpret_cast<const unsigned char *>(k_active);
-#define RN_WGRAD_LAUNCH(WM_, WN_)                                                                                        \
-    do {                                                                                                                 \
-        if (half) {                                                                                                      \
-            if (in_relu) hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, true, 16, 3, true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
-            else hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, false, 16, 3, true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);         \
-        } else if (split) {                                                                                              \
-            if (in_relu) hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, true, 16, 3, true>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
-            else hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, false, 16, 3, true>), grid, dim3(256), 0, (hipStream_t)stream, a);         \
-        } else if (in_relu) hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, true, 16, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
-        else hipLaunchKernelGGL((conv_wgrad_kernel<WM_, WN_, false, 16, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);         \
-    } while (0)
-    if (k_active != nullptr) {
-        if (half) hipLaunchKernelGGL((conv_wgrad_once_kernel<false, true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((conv_wgrad_once_kernel<false, false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else if (once && half) {
-        if (in_relu) hipLaunchKernelGGL((conv_wgrad_once_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((conv_wgrad_once_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else if (once) {
-        if (in_relu) hipLaunchKernelGGL((conv_wgrad_once_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((conv_wgrad_once_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else if (shape == 0) RN_WGRAD_LAUNCH(1, 4);
-    else if (shape == 1) RN_WGRAD_LAUNCH(4, 1);
-    else RN_WGRAD_LAUNCH(2, 2);
-#undef RN_WGRAD_LAUNCH
-    RN_LAUNCH_CHECK();
-    if (det) {
-        const int64_t total = (int64_t)nbatch * Cout * a.Kflat;
-        hipLaunchKernelGGL(wgrad_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dw,
-                           (const float *)a.slab, a.slab_stride, a.splits, nbatch, dw_bstride, Cout, a.Kflat, a.Kpad, colsum,
-                           (const float *)a.cs_slab);
-        RN_LAUNCH_CHECK();
-    }
-    return RN_OK;
 }
 
 extern "C" int rn_conv_wgrad(const float *dy, int ldy, const float *x, float *dw, float *colsum, int N, int Hi, int Wi,

@@ -1,4 +1,4 @@
-// Probe for gfx950's transposing LDS read as the bf16 weight-gradient kernel uses it (conv_bf16.hip):
+// Probe for gfx950's transposing LDS read as the bf16 weight-gradient kernel uses it (conv_wgrad_bf16.hip):
 // image = [32 pixels][128 channels] of 16-bit values, 256-byte rows, 16-byte chunks XOR-permuted per row
 // (cdna_hip_programming.md T10, image (b)); operand(lane) = 8 consecutive pixels of one channel.
 // Prints the number of mismatching elements for every (channel sub-tile, pixel half) and the bank-conflict-relevant
