@@ -32,14 +32,12 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "anchor_match_dev.h"
 
 #ifndef FOCAL_NTHR
 #define FOCAL_NTHR 256
 #endif
 #define NTHR FOCAL_NTHR   // threads per workgroup
-#define APT 4             // anchors per thread of rn_assign
-#define TILE (NTHR * APT) // rn_assign: 1024 anchors per workgroup
 #define NWAVES (NTHR / 64)
 #define UAPT 2            // fused loss: anchors per lane per unit
 #define UNIT (64 * UAPT)  // fused loss: a wave's work item = 128 consecutive anchors of one image
@@ -47,7 +45,9 @@
 #ifndef RN_FOCAL_WAVES_PER_SIMD
 #define RN_FOCAL_WAVES_PER_SIMD 4
 #endif
-#define RN_FOCAL_WAVES_NOTE 4  // (HIP: second launch-bound = waves per SIMD) the register allocator must leave room for (128 VGPRs: no spills)
+// (HIP: the second launch bound = waves per SIMD the register allocator must leave room for.)  4 waves = 128 VGPRs, which the two
+// production instances do not quite fit: the compiler reports 128 VGPRs and 24 bytes of scratch for focal_kernel<true, false, 2> (forward),
+// 128 and 40 bytes for focal_kernel<true, true, 2> (backward); per instance in profiles/focal_refactor_isa.txt.
 #define RN_FOCAL_RESIDENT 768   // workgroups of the persistent grid (3 per CU).  Measured at B=8, A=389 205: 512..768 is
                                 // the optimum; more workgroups lengthen the same-address completion-counter queue
                                 // (~8 ns each) faster than they add memory-level parallelism
@@ -66,20 +66,6 @@ static inline int focal_groups(int B, int64_t A) {
     const int64_t need = (units + NWAVES - 1) / NWAVES;          // more workgroups than units/4 would idle
     if (G > need) G = need >= 8 ? ((need + 7) & ~7LL) : need;
     return (int)(G < 1 ? 1 : G);
-}
-
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float uniform_f(float v) {      // tell the compiler the value is wave-uniform (scalar branch)
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
 struct ImageStats {       // one per image, written by finalize, read by backward
@@ -107,114 +93,6 @@ extern "C" int64_t rn_focal_workspace_bytes(int B, int64_t A) {
 }
 
 // ----------------------------------------------------------------------------------------------------------
-struct LabelLds {
-    float x1[RN_MAX_GT], y1[RN_MAX_GT], x2[RN_MAX_GT], y2[RN_MAX_GT], area[RN_MAX_GT];
-    int row[RN_MAX_GT];     // original row index in ann[j]
-    int count;
-};
-
-// One label row reduced to its matching box: valid iff the class column != -1 (D/losses.py:54, R/losses.py:47);
-// the directional box is the min/max envelope of the 8 corners (D/losses.py:93-107).
-template <bool DIR>
-__device__ __forceinline__ void load_label_row(const float *__restrict__ ann_j, int N, int r, float &bx1, float &by1,
-                                               float &bx2, float &by2, bool &valid) {
-    constexpr int COLS = DIR ? 27 : 5;
-    constexpr int CLS_COL = DIR ? 20 : 4;
-    valid = false;
-    bx1 = by1 = bx2 = by2 = 0.f;
-    if (r < N) {
-        const float *p = ann_j + (int64_t)r * COLS;
-        valid = p[CLS_COL] != -1.0f;
-        if (DIR) {
-            bx1 = bx2 = p[0];
-            by1 = by2 = p[1];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) {
-                bx1 = fminf(bx1, p[2 * k]);
-                bx2 = fmaxf(bx2, p[2 * k]);
-                by1 = fminf(by1, p[2 * k + 1]);
-                by2 = fmaxf(by2, p[2 * k + 1]);
-            }
-        } else {
-            bx1 = p[0]; by1 = p[1]; bx2 = p[2]; by2 = p[3];
-        }
-    }
-}
-
-// The same from a raw row staged in LDS (row stride COLS words is odd: conflict-free across lanes).
-template <bool DIR>
-__device__ __forceinline__ void label_row_from_lds(const float *__restrict__ raw, int n_rows, int r, float &bx1, float &by1,
-                                                   float &bx2, float &by2, bool &valid) {
-    constexpr int COLS = DIR ? 27 : 5;
-    constexpr int CLS_COL = DIR ? 20 : 4;
-    valid = false;
-    bx1 = by1 = bx2 = by2 = 0.f;
-    if (r < n_rows) {
-        const float *p = raw + r * COLS;
-        valid = p[CLS_COL] != -1.0f;
-        if (DIR) {
-            bx1 = bx2 = p[0];
-            by1 = by2 = p[1];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) {
-                bx1 = fminf(bx1, p[2 * k]);
-                bx2 = fmaxf(bx2, p[2 * k]);
-                by1 = fminf(by1, p[2 * k + 1]);
-                by2 = fmaxf(by2, p[2 * k + 1]);
-            }
-        } else {
-            bx1 = p[0]; by1 = p[1]; bx2 = p[2]; by2 = p[3];
-        }
-    }
-}
-
-// Collect valid rows in their original order into LDS (rn_assign): wave 0 scans rows in chunks of 64, ordered
-// compaction by ballot.
-template <bool DIR>
-__device__ __forceinline__ void load_labels(const float *__restrict__ ann_j, int N, LabelLds &L) {
-    if (threadIdx.x < 64) {
-        int base = 0;
-        for (int r0 = 0; r0 < N; r0 += 64) {
-            const int r = r0 + threadIdx.x;
-            bool valid;
-            float bx1, by1, bx2, by2;
-            load_label_row<DIR>(ann_j, N, r, bx1, by1, bx2, by2, valid);
-            const unsigned long long m = __ballot(valid);
-            if (valid) {
-                const int pos = base + __popcll(m & ((1ull << threadIdx.x) - 1ull));
-                L.x1[pos] = bx1; L.y1[pos] = by1; L.x2[pos] = bx2; L.y2[pos] = by2;
-                L.area[pos] = (bx2 - bx1) * (by2 - by1);                       // D/losses.py:6
-                L.row[pos] = r;
-            }
-            base += __popcll(m);
-        }
-        if (threadIdx.x == 0) L.count = base;
-    }
-    __syncthreads();
-}
-
-// IoU max / first argmax of one anchor against the LDS label set.  Exactly calc_iou's operation order
-// (D/losses.py:5-22) followed by torch.max(dim=1) (first maximum wins).
-__device__ __forceinline__ void match_anchor(const float4 a, const LabelLds &L, float &best, int &arg) {
-    const float area_a = (a.z - a.x) * (a.w - a.y);
-    best = -1.0f;
-    arg = 0;
-    for (int n = 0; n < L.count; ++n) {
-        float iw = fminf(a.z, L.x2[n]) - fmaxf(a.x, L.x1[n]);
-        float ih = fminf(a.w, L.y2[n]) - fmaxf(a.y, L.y1[n]);
-        iw = fmaxf(iw, 0.f);
-        ih = fmaxf(ih, 0.f);
-        const float inter = iw * ih;
-        float iou = 0.f;                                     // 0 / max(ua, 1e-8) == 0 exactly: ~99 % of pairs skip the divide
-        if (inter > 0.f) {
-            float ua = (area_a + L.area[n]) - inter;
-            ua = fmaxf(ua, 1e-8f);
-            iou = inter / ua;
-        }
-        if (iou > best) { best = iou; arg = n; }
-    }
-}
-
 // sign tables of the corner synthesis (D/losses.py:310-327): corner j = c + sl*l + sw*w + sh*h
 __device__ __constant__ float kSL[8] = {-1, -1, +1, +1, -1, -1, +1, +1};
 __device__ __constant__ float kSW[8] = {-1, +1, -1, +1, -1, +1, -1, +1};
@@ -354,6 +232,15 @@ __device__ __forceinline__ float focal_elem(float x, bool pos, float wl) {
     return (x < 1e-4f || x > 1.0f - 1e-4f) ? 0.f : g;                         // clamp passes no gradient outside
 }
 
+// Weight of one classification value of an anchor in state st (-1 ignored, 0 negative, 1 + class): negatives 0.75, the positive class
+// 0.25, nothing for an ignored anchor -- with focal_elem's factor folded in (forward ln 2, backward +-the gradient scale).
+template <bool BWD>
+__device__ __forceinline__ float focal_weight(int st, bool isp, float cls_scale) {
+    const float wn = st < 0 ? 0.f : (BWD ? -0.75f * cls_scale : 0.75f * RN_LN2);
+    const float wp = BWD ? 0.25f * cls_scale : 0.25f * RN_LN2;
+    return isp ? wp : wn;
+}
+
 // Epilogue of the forward, two levels so that nothing waits in one long same-address queue and the per-image work runs
 // in parallel (profiles/r01_loss_analysis.txt: 768 arrivals at one counter ~6 us, then a serial epilogue ~7 us):
 //   level 1  the LAST workgroup of image j to finish (per-image counter: G arrivals) adds that image's G partials -- all
@@ -361,20 +248,12 @@ __device__ __forceinline__ float focal_elem(float x, bool pos, float wl) {
 //            label row, and publishes the per-image loss terms;
 //   level 2  the last of those B workgroups (batch counter: B arrivals) forms the batch means and writes the per-image
 //            gradient scales the backward kernel reads (D/losses.py:152, 350, 304, 359-362).
-__device__ __forceinline__ double shfl_xor_f64(double v, int off) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, off, 64);
-    hi = __shfl_xor(hi, off, 64);
-    return __hiloint2double(hi, lo);
-}
 // Sum of v[0..NV) over the 256 threads of the workgroup in a fixed order; valid in thread 0.  red: 4*NV doubles of LDS.
 template <int NV>
 __device__ __forceinline__ void block_sum_f64(double (&v)[NV], double *red) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[i] += shfl_xor_f64(v[i], off);
+    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) red[w * NV + i] = v[i];
@@ -399,12 +278,17 @@ __device__ __forceinline__ double fetch_f64(const double *p) {
                                                              __HIP_MEMORY_SCOPE_AGENT));
 }
 
+// What an image's three sums are divided by.  focal_finalize_image divides by them, focal_finalize_batch takes their reciprocals.
+__device__ __forceinline__ double cls_denom(double npos) { return npos > 1.0 ? npos : 1.0; }      // clamp(min=1), D/losses.py:152
+template <bool DIR>
+__device__ __forceinline__ double reg_denom(double npos) { return npos * LabelLayout<DIR>::NVALS; }   // mean over [P,20] / [P,4]
+__device__ __forceinline__ double vp_denom(double npos) { return 3.0 * npos; }                    // mean over P of (sum_k)/3
+
 template <bool DIR>
 __device__ __forceinline__ void focal_finalize_image(const float4 *__restrict__ partials, int G, int j,
                                                      const float *__restrict__ ann, int N, double *__restrict__ terms,
                                                      double *s_red) {
-    constexpr int COLS = DIR ? 27 : 5;
-    constexpr int CLS_COL = DIR ? 20 : 4;
+    typedef LabelLayout<DIR> LL;
     double v[4] = {0, 0, 0, 0};
     for (int t0 = 0; t0 < G; t0 += NTHR * 2) {                                // 2 independent partials in flight per thread
         float4 p[2];
@@ -423,21 +307,19 @@ __device__ __forceinline__ void focal_finalize_image(const float4 *__restrict__ 
             if (t0 + k * NTHR + threadIdx.x < G) { v[0] += p[k].x; v[1] += p[k].y; v[2] += p[k].z; v[3] += p[k].w; }
     }
     bool any = false;
-    for (int r = threadIdx.x; r < N; r += NTHR) any |= ann[((int64_t)j * N + r) * COLS + CLS_COL] != -1.0f;
+    for (int r = threadIdx.x; r < N; r += NTHR) any |= ann[((int64_t)j * N + r) * LL::COLS + LL::CLS_COL] != -1.0f;
     const bool has = __syncthreads_or(any) != 0;
     block_sum_f64<4>(v, s_red);
     if (threadIdx.x == 0) {
         const double npos = v[3];
-        const double nvals = DIR ? 20.0 : 4.0;
         double lc, lr = 0.0, lv = 0.0;
         if (!has) {
             lc = v[0];                                                        // raw sum, not normalised (D/losses.py:58-87)
         } else {
-            const double dn = npos > 1.0 ? npos : 1.0;                        // clamp(min=1), D/losses.py:152
-            lc = v[0] / dn;
+            lc = v[0] / cls_denom(npos);
             if (npos > 0.0) {
-                lr = v[1] / (npos * nvals);                                   // mean over [P,20] / [P,4]
-                lv = v[2] / (3.0 * npos);                                     // mean over P of (sum_k)/3
+                lr = v[1] / reg_denom<DIR>(npos);
+                lv = v[2] / vp_denom(npos);
             }
         }
         double *t = terms + (int64_t)j * RN_TERMS;
@@ -466,7 +348,6 @@ __device__ __forceinline__ void focal_finalize_batch(int B, const double *__rest
     }
     __syncthreads();
     const int vp_images = (int)s_bc[0];
-    const double nvals = DIR ? 20.0 : 4.0;
     for (int j = threadIdx.x; j < B; j += NTHR) {                              // per-image scales with the batch means folded in
         const double *t = terms + (int64_t)j * RN_TERMS;
         const bool has = fetch_f64(t + 3) != 0.0;
@@ -477,11 +358,10 @@ __device__ __forceinline__ void focal_finalize_batch(int B, const double *__rest
         st.pad[0] = st.pad[1] = st.pad[2] = 0.f;
         st.cls_scale = 1.0f; st.reg_scale = 0.f; st.vp_scale = 0.f;
         if (has) {
-            const double dn = npos > 1.0 ? npos : 1.0;
-            st.cls_scale = (float)(1.0 / dn);
+            st.cls_scale = (float)(1.0 / cls_denom(npos));
             if (npos > 0.0) {
-                st.reg_scale = (float)(1.0 / (npos * nvals));
-                st.vp_scale = (float)(1.0 / (3.0 * npos));
+                st.reg_scale = (float)(1.0 / reg_denom<DIR>(npos));
+                st.vp_scale = (float)(1.0 / vp_denom(npos));
             }
         }
         st.cls_scale = st.cls_scale / (float)B;
@@ -513,9 +393,7 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
                                                      float *__restrict__ dreg, int G, int units,
                                                      unsigned *__restrict__ counter, double *__restrict__ terms,
                                                      float *__restrict__ losses, const float *__restrict__ grad_losses) {
-    constexpr int COLS = DIR ? 27 : 5;
-    constexpr int CLS_COL = DIR ? 20 : 4;
-    constexpr int NREG = DIR ? 12 : 4;
+    constexpr int COLS = LabelLayout<DIR>::COLS, CLS_COL = LabelLayout<DIR>::CLS_COL, NREG = LabelLayout<DIR>::NREG;
     constexpr int NX = CQ > 0 ? UAPT * CQ : 1;               // float4 per lane per unit held in registers
     extern __shared__ float s_raw[];                         // the image's label rows, raw: N*COLS floats (dynamic)
     __shared__ int s_wstate[NWAVES][UNIT];                   // per wave: -1 ignore, 0 negative, 1 + class for a positive
@@ -573,7 +451,7 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
     const int n0 = N < 64 ? N : 64;
     float bx1, by1, bx2, by2;
     bool bvalid;
-    label_row_from_lds<DIR>(s_raw, n0, lane, bx1, by1, bx2, by2, bvalid);
+    load_label_row<DIR>(s_raw, n0, lane, bx1, by1, bx2, by2, bvalid);
     const float bcls = lane < n0 ? s_raw[lane * COLS + CLS_COL] : 0.f;
     const float barea = (bx2 - bx1) * (by2 - by1);                             // D/losses.py:6
     bool any_valid = __ballot(bvalid) != 0ull;
@@ -587,15 +465,9 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
 #pragma unroll
         for (int uu = 0; uu < UAPT; ++uu) {
             const float4 a = av[uu];
-            float iw = fminf(a.z, gx2) - fmaxf(a.x, gx1);                          // calc_iou's order (D/losses.py:5-22)
-            float ih = fminf(a.w, gy2) - fmaxf(a.y, gy1);
-            iw = fmaxf(iw, 0.f);
-            ih = fmaxf(ih, 0.f);
-            const float inter = iw * ih;
-            if (inter > 0.f) {                                                     // else 0 / max(ua, 1e-8) == 0
-                float ua = ((a.z - a.x) * (a.w - a.y) + garea) - inter;
-                ua = fmaxf(ua, 1e-8f);
-                const float iou = inter / ua;
+            const float inter = box_inter(a, gx1, gy1, gx2, gy2);
+            if (inter > 0.f) {
+                const float iou = inter / box_union((a.z - a.x) * (a.w - a.y), garea, inter);
                 if (iou > best[uu]) { best[uu] = iou; arg[uu] = row; cbest[uu] = gcls; }
             }
         }
@@ -633,7 +505,7 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
             const int nrow = N - c0 < 64 ? N - c0 : 64;
             float cx1, cy1, cx2, cy2;
             bool cvalid;
-            label_row_from_lds<DIR>(s_raw + c0 * COLS, nrow, lane, cx1, cy1, cx2, cy2, cvalid);
+            load_label_row<DIR>(s_raw + c0 * COLS, nrow, lane, cx1, cy1, cx2, cy2, cvalid);
             const float ccls = lane < nrow ? s_raw[(c0 + lane) * COLS + CLS_COL] : 0.f;
             const float carea = (cx2 - cx1) * (cy2 - cy1);
             unsigned long long mc = __ballot(cvalid && wx2 > cx1 && cx2 > wx1 && wy2 > cy1 && cy2 > wy1);
@@ -656,8 +528,8 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
                 if (!any_valid) {
                     state[uu] = 0;                                            // empty image: all negative (D/losses.py:58-87)
                 } else {
-                    if (best[uu] < 0.4f) state[uu] = 0;                       // D/losses.py:121
-                    if (best[uu] >= 0.5f) {                                   // D/losses.py:124
+                    if (best[uu] < RN_IOU_NEG) state[uu] = 0;                 // D/losses.py:121
+                    if (best[uu] >= RN_IOU_POS) {                             // D/losses.py:124
                         state[uu] = 1 + (int)cbest[uu];                       // .long() truncation, D/losses.py:131
                         pos[uu] = true;
                     }
@@ -726,15 +598,12 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
                         const int c0 = CQ == 2 ? ((v & 1) << 2) : 0;
                         const int st = s_wstate[wv][al];
                         const int tc = st - 1 - c0;                           // lane-local index of the positive class, if any
-                        // per-anchor weights: negatives 0.75, the positive class 0.25, nothing for an ignored anchor
-                        const float wn = st < 0 ? 0.f : (BWD ? -0.75f * cls_scale : 0.75f * RN_LN2);
-                        const float wp = BWD ? 0.25f * cls_scale : 0.25f * RN_LN2;
                         const float xs[4] = {x.x, x.y, x.z, x.w};
                         float o[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const bool isp = q == tc;                         // st <= 0 makes tc negative
-                            o[q] = focal_elem<BWD>(xs[q], isp, isp ? wp : wn);
+                            o[q] = focal_elem<BWD>(xs[q], isp, focal_weight<BWD>(st, isp, cls_scale));
                         }
                         if (BWD) dst4[v] = make_float4(o[0], o[1], o[2], o[3]);
                         else sums[0] += (o[0] + o[1]) + (o[2] + o[3]);
@@ -746,9 +615,7 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
                     const int c = e - al * C;
                     const int st = s_wstate[wv][al];
                     const bool isp = st > 0 && c == st - 1;
-                    const float wn = st < 0 ? 0.f : (BWD ? -0.75f * cls_scale : 0.75f * RN_LN2);
-                    const float wp = BWD ? 0.25f * cls_scale : 0.25f * RN_LN2;
-                    const float o = focal_elem<BWD>(src[e], isp, isp ? wp : wn);
+                    const float o = focal_elem<BWD>(src[e], isp, focal_weight<BWD>(st, isp, cls_scale));
                     if (BWD) dst[e] = o;
                     else sums[0] += o;
                 }
@@ -833,14 +700,6 @@ __global__ __launch_bounds__(NTHR, RN_FOCAL_WAVES_PER_SIMD) void focal_kernel(co
     }
 }
 
-static int check_args(int B, int64_t A, int C, int N) {
-    if (B <= 0 || A <= 0 || C <= 0 || N < 0) return RN_EINVAL;
-    if (N > RN_MAX_GT) return RN_ETOOMANY;
-    if (B > 1024) return RN_EINVAL;
-    if (A > 0x7fffffffLL) return RN_EINVAL;                                      // anchor / unit ids are ints; grid = B*G <= 1024*160
-    return RN_OK;
-}
-
 struct FocalWs {
     unsigned *counter;
     ImageStats *stats;
@@ -858,224 +717,42 @@ static inline FocalWs focal_ws(void *workspace, int B) {
     return r;
 }
 
-extern "C" int rn_focal_loss_fwd(const float *cls, const float *reg, const float *anchors, const float *ann, int B,
-                                 int64_t A, int C, int N, int directional, void *workspace, float *losses,
-                                 void *stream) {
+// One launch, forward or backward: the instance comes from a table indexed by (directional, backward, CQ).  An instance reads only its own
+// direction's arguments, so the forward passes no gradients and the backward no losses.
+static int focal_launch(bool bwd, const float *cls, const float *reg, const float *anchors, const float *ann, int B, int64_t A, int C,
+                        int N, int directional, void *workspace, float *losses, const float *grad_losses, float *dcls, float *dreg,
+                        void *stream) {
     const int rc = check_args(B, A, C, N);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
+    typedef void (*Kernel)(const float *, const float *, const float4 *, const float *, int64_t, int, int, float *, ImageStats *, float *,
+                           float *, int, int, unsigned *, double *, float *, const float *);
+#define RN_FOCAL_ROW(DIR_, BWD_) {focal_kernel<DIR_, BWD_, 0>, focal_kernel<DIR_, BWD_, 1>, focal_kernel<DIR_, BWD_, 2>}
+    static const Kernel table[2][2][3] = {{RN_FOCAL_ROW(false, false), RN_FOCAL_ROW(false, true)},
+                                          {RN_FOCAL_ROW(true, false), RN_FOCAL_ROW(true, true)}};
+#undef RN_FOCAL_ROW
     const int G = focal_groups(B, A);
     const int units = (int)((A + UNIT - 1) / UNIT);
     const FocalWs ws = focal_ws(workspace, B);
-    const dim3 grid((unsigned)(B * G)), block(NTHR);
-    const float4 *anc = reinterpret_cast<const float4 *>(anchors);
     const int cq = C == 4 ? 1 : (C == 8 ? 2 : 0);
-    const size_t raw_bytes = (size_t)(N > 0 ? N : 1) * (directional ? 27 : 5) * sizeof(float);   // label rows in LDS
-#define RN_FOCAL_FWD(DIR_, CQ_)                                                                                        \
-    hipLaunchKernelGGL((focal_kernel<DIR_, false, CQ_>), grid, block, raw_bytes, s, cls, reg, anc, ann, A, C, N,        \
-                       ws.partials, ws.stats, (float *)nullptr, (float *)nullptr, G, units, ws.counter, ws.terms, losses, \
-                       (const float *)nullptr)
-    if (directional) {
-        if (cq == 2) RN_FOCAL_FWD(true, 2); else if (cq == 1) RN_FOCAL_FWD(true, 1); else RN_FOCAL_FWD(true, 0);
-    } else {
-        if (cq == 2) RN_FOCAL_FWD(false, 2); else if (cq == 1) RN_FOCAL_FWD(false, 1); else RN_FOCAL_FWD(false, 0);
-    }
-#undef RN_FOCAL_FWD
+    const int cols = directional ? LabelLayout<true>::COLS : LabelLayout<false>::COLS;
+    const size_t raw_bytes = (size_t)(N > 0 ? N : 1) * cols * sizeof(float);                     // label rows in LDS
+    hipLaunchKernelGGL(table[directional != 0][bwd][cq], dim3((unsigned)(B * G)), dim3(NTHR), raw_bytes, (hipStream_t)stream, cls, reg,
+                       reinterpret_cast<const float4 *>(anchors), ann, A, C, N, bwd ? nullptr : ws.partials, ws.stats, dcls, dreg, G,
+                       units, bwd ? nullptr : ws.counter, bwd ? nullptr : ws.terms, losses, grad_losses);
     RN_LAUNCH_CHECK();
     return RN_OK;
+}
+
+extern "C" int rn_focal_loss_fwd(const float *cls, const float *reg, const float *anchors, const float *ann, int B,
+                                 int64_t A, int C, int N, int directional, void *workspace, float *losses,
+                                 void *stream) {
+    return focal_launch(false, cls, reg, anchors, ann, B, A, C, N, directional, workspace, losses, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int rn_focal_loss_bwd(const float *cls, const float *reg, const float *anchors, const float *ann, int B,
                                  int64_t A, int C, int N, int directional, const void *workspace,
                                  const float *grad_losses, float *dcls, float *dreg, void *stream) {
-    const int rc = check_args(B, A, C, N);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int G = focal_groups(B, A);
-    const int units = (int)((A + UNIT - 1) / UNIT);
-    const FocalWs ws = focal_ws(const_cast<void *>(workspace), B);
-    const dim3 grid((unsigned)(B * G)), block(NTHR);
-    const float4 *anc = reinterpret_cast<const float4 *>(anchors);
-    const int cq = C == 4 ? 1 : (C == 8 ? 2 : 0);
-    const size_t raw_bytes = (size_t)(N > 0 ? N : 1) * (directional ? 27 : 5) * sizeof(float);   // label rows in LDS
-#define RN_FOCAL_BWD(DIR_, CQ_)                                                                                      \
-    hipLaunchKernelGGL((focal_kernel<DIR_, true, CQ_>), grid, block, raw_bytes, s, cls, reg, anc, ann, A, C, N,       \
-                       (float *)nullptr, ws.stats, dcls, dreg, G, units, (unsigned *)nullptr, (double *)nullptr,      \
-                       (float *)nullptr, grad_losses)
-    if (directional) {
-        if (cq == 2) RN_FOCAL_BWD(true, 2); else if (cq == 1) RN_FOCAL_BWD(true, 1); else RN_FOCAL_BWD(true, 0);
-    } else {
-        if (cq == 2) RN_FOCAL_BWD(false, 2); else if (cq == 1) RN_FOCAL_BWD(false, 1); else RN_FOCAL_BWD(false, 0);
-    }
-#undef RN_FOCAL_BWD
-    RN_LAUNCH_CHECK();
-    return RN_OK;
+    return focal_launch(true, cls, reg, anchors, ann, B, A, C, N, directional, const_cast<void *>(workspace), nullptr, grad_losses, dcls,
+                        dreg, stream);
 }
 
-// ----------------------------------------------------------------------------------------------------------
-template <bool DIR>
-__global__ __launch_bounds__(NTHR) void assign_kernel(const float4 *__restrict__ anchors, const float *__restrict__ ann,
-                                                      int64_t A, int N, float *__restrict__ iou_max,
-                                                      int32_t *__restrict__ argmax, int32_t *__restrict__ state) {
-    constexpr int COLS = DIR ? 27 : 5;
-    __shared__ LabelLds L;
-    const int j = blockIdx.y;
-    load_labels<DIR>(ann + (int64_t)j * N * COLS, N, L);
-    const int64_t ai = (int64_t)blockIdx.x * NTHR + threadIdx.x;
-    if (ai >= A) return;
-    float best = 0.f; int arg = -1; int st = 0;
-    if (L.count > 0) {
-        match_anchor(anchors[ai], L, best, arg);
-        st = -1;
-        if (best < 0.4f) st = 0;
-        if (best >= 0.5f) st = 1;
-    }
-    iou_max[(int64_t)j * A + ai] = best;
-    argmax[(int64_t)j * A + ai] = arg;
-    state[(int64_t)j * A + ai] = st;
-}
-
-extern "C" int rn_assign(const float *anchors, const float *ann, int B, int64_t A, int N, int directional,
-                         float *iou_max, int32_t *argmax, int32_t *state, void *stream) {
-    const int rc = check_args(B, A, 1, N);
-    if (rc) return rc;
-    const dim3 grid((unsigned)((A + NTHR - 1) / NTHR), B), block(NTHR);
-    const float4 *anc = reinterpret_cast<const float4 *>(anchors);
-    if (directional)
-        hipLaunchKernelGGL(assign_kernel<true>, grid, block, 0, (hipStream_t)stream, anc, ann, A, N, iou_max, argmax, state);
-    else
-        hipLaunchKernelGGL(assign_kernel<false>, grid, block, 0, (hipStream_t)stream, anc, ann, A, N, iou_max, argmax, state);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------------
-// Need sets of the regression tower's forward.  The loss reads the regression output at the positive anchors only (the
-// queue of focal_kernel: best IoU >= 0.5 against the image's valid labels -- rn_assign's rule, match_anchor's arithmetic), so the labels
-// say BEFORE the forward which 4x4 output tiles of which pyramid level anybody will read: P0 = the tiles that hold a pixel with a positive
-// anchor.  A 3x3 layer computed on a set S of tiles reads its input inside D(S), the 3x3 dilation of S on the tile grid of one image of
-// one level, so the layers below need D^k(P0).  Flag arrays, RN_REG_NEED_ARRAYS of Tpad bytes each, in the tile order of the Winograd
-// transforms (levels concatenated; image, tile row, tile column): [0] P0, [1] D^2(P0), [2] D^3, [3] D^4, [4] D^5, [5] D(P0).
-struct NeedGeom {
-    int n;
-    int W[RN_MAX_GROUP], TH[RN_MAX_GROUP], TW[RN_MAX_GROUP];
-    int64_t a_end[RN_MAX_GROUP];                 // inclusive prefix sums of the levels' anchors per image
-    int64_t t_end[RN_MAX_GROUP];                 // ... and of their tiles over the whole batch
-};
-
-template <bool DIR>
-__global__ __launch_bounds__(NTHR) void need_p0_kernel(const float4 *__restrict__ anchors, const float *__restrict__ ann, int64_t A, int N,
-                                                       int per_pixel, const NeedGeom g, unsigned char *__restrict__ p0) {
-    constexpr int COLS = DIR ? 27 : 5;
-    __shared__ LabelLds L;
-    const int j = blockIdx.y;
-    load_labels<DIR>(ann + (int64_t)j * N * COLS, N, L);
-    const int64_t ai = (int64_t)blockIdx.x * NTHR + threadIdx.x;
-    if (ai >= A || L.count == 0) return;
-    float best; int arg;
-    match_anchor(anchors[ai], L, best, arg);
-    if (!(best >= 0.5f)) return;
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) q += (i + 1 < g.n && ai >= g.a_end[i]) ? 1 : 0;
-    const int64_t a_first = q ? g.a_end[q - 1] : 0, t_first = q ? g.t_end[q - 1] : 0;
-    const int64_t pix = (ai - a_first) / per_pixel;
-    const int h = (int)(pix / g.W[q]), w = (int)(pix - (int64_t)h * g.W[q]);
-    p0[t_first + ((int64_t)j * g.TH[q] + (h >> 2)) * g.TW[q] + (w >> 2)] = 1;      // (plain byte stores of 1: no atomics)
-}
-
-// One thread per tile: its Chebyshev distance to the nearest tile of P0 on its own image's grid, up to 5, decides the five dilations.
-__global__ __launch_bounds__(256) void need_dilate_kernel(const NeedGeom g, int64_t T, int64_t Tpad, unsigned char *__restrict__ flags) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= T) return;
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < RN_MAX_GROUP - 1; ++i) q += (i + 1 < g.n && t >= g.t_end[i]) ? 1 : 0;
-    const int64_t t_first = q ? g.t_end[q - 1] : 0;
-    const int TH = g.TH[q], TW = g.TW[q];
-    const int64_t local = t - t_first;
-    const int64_t n = local / ((int64_t)TH * TW);
-    const int r = (int)(local - n * TH * TW);
-    const int th = r / TW, tw = r - th * TW;
-    const unsigned char *img = flags + t_first + n * TH * TW;     // array 0: P0 of this tile's image
-    int dmin = 6;
-    for (int dh = -5; dh <= 5; ++dh) {
-        const int th2 = th + dh;
-        if ((unsigned)th2 >= (unsigned)TH) continue;
-        for (int dw = -5; dw <= 5; ++dw) {
-            const int tw2 = tw + dw;
-            if ((unsigned)tw2 >= (unsigned)TW) continue;
-            if (img[th2 * TW + tw2] != 0) {
-                const int a = dh < 0 ? -dh : dh, b = dw < 0 ? -dw : dw, d = a > b ? a : b;
-                dmin = d < dmin ? d : dmin;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 1; k <= 4; ++k)
-        if (dmin <= k + 1) flags[k * Tpad + t] = 1;
-    if (dmin <= 1) flags[5 * Tpad + t] = 1;
-}
-
-__global__ __launch_bounds__(256) void need_zero_kernel(uint4 *__restrict__ p, int64_t n16) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n16) p[i] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-extern "C" int rn_reg_need_tiles(const float *anchors, const float *ann, int B, int64_t A, int N, int directional, int n_levels,
-                                 const int *H, const int *W, int per_pixel, void *flags, int64_t Tpad, void *stream) {
-    const int rc = check_args(B, A, 1, N);
-    if (rc) return rc;
-    if (!anchors || (N > 0 && !ann) || !H || !W || !flags || n_levels < 1 || n_levels > RN_MAX_GROUP || per_pixel < 1) return RN_EINVAL;
-    if (Tpad <= 0 || (Tpad & 15) || ((uintptr_t)flags & 15)) return RN_EINVAL;
-    NeedGeom g = {};
-    g.n = n_levels;
-    int64_t a = 0, t = 0;
-    for (int i = 0; i < RN_MAX_GROUP; ++i) {
-        const int k = i < n_levels ? i : n_levels - 1;           // unused slots repeat the last level (never selected)
-        if (H[k] <= 0 || W[k] <= 0) return RN_EINVAL;
-        g.W[i] = W[k]; g.TH[i] = (H[k] + 3) / 4; g.TW[i] = (W[k] + 3) / 4;
-        if (i < n_levels) { a += (int64_t)H[k] * W[k] * per_pixel; t += (int64_t)B * g.TH[i] * g.TW[i]; }
-        g.a_end[i] = a; g.t_end[i] = t;
-    }
-    if (a != A || t > Tpad) return RN_EINVAL;                    // every anchor lies in a level, every tile in the arrays
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n16 = (int64_t)RN_REG_NEED_ARRAYS * Tpad / 16;       // (a kernel, not a memset node: part of a captured step like the rest)
-    hipLaunchKernelGGL(need_zero_kernel, dim3(rn_blocks(n16, 256)), dim3(256), 0, s, reinterpret_cast<uint4 *>(flags), n16);
-    RN_LAUNCH_CHECK();
-    const dim3 grid((unsigned)((A + NTHR - 1) / NTHR), B), block(NTHR);
-    const float4 *anc = reinterpret_cast<const float4 *>(anchors);
-    unsigned char *f = reinterpret_cast<unsigned char *>(flags);
-    if (directional) hipLaunchKernelGGL(need_p0_kernel<true>, grid, block, 0, s, anc, ann, A, N, per_pixel, g, f);
-    else hipLaunchKernelGGL(need_p0_kernel<false>, grid, block, 0, s, anc, ann, A, N, per_pixel, g, f);
-    RN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(need_dilate_kernel, dim3(rn_blocks(t, 256)), dim3(256), 0, s, g, t, Tpad, f);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-}
-
-// calc_iou as a standalone op (D/losses.py:5-22): one lane per (anchor, label) pair, label index fastest.
-__global__ void pairwise_iou_kernel(const float4 *__restrict__ a, const float4 *__restrict__ b, float *__restrict__ out,
-                                    int64_t A, int N) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= A * N) return;
-    const int64_t ai = i / N;
-    const int n = (int)(i - ai * N);
-    const float4 p = a[ai], q = b[n];
-    const float area_b = (q.z - q.x) * (q.w - q.y);
-    float iw = fminf(p.z, q.z) - fmaxf(p.x, q.x);
-    float ih = fminf(p.w, q.w) - fmaxf(p.y, q.y);
-    iw = fmaxf(iw, 0.f);
-    ih = fmaxf(ih, 0.f);
-    float ua = ((p.z - p.x) * (p.w - p.y) + area_b) - iw * ih;
-    ua = fmaxf(ua, 1e-8f);
-    out[i] = (iw * ih) / ua;
-}
-
-extern "C" int rn_pairwise_iou(const float *a, const float *b, float *iou, int64_t A, int N, void *stream) {
-    if (A <= 0 || N <= 0) return RN_EINVAL;
-    hipLaunchKernelGGL(pairwise_iou_kernel, dim3(rn_blocks(A * N, 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4 *>(a), reinterpret_cast<const float4 *>(b), iou, A, N);
-    RN_LAUNCH_CHECK();
-    return RN_OK;
-}

@@ -1,7 +1,8 @@
 """Edge cases, a float64 reference and derived error envelopes for the fused loss (focal_kernel and its epilogue in
-csrc/focal_loss.hip, reached through ops.focal_loss / ops.assign).  tests/test_loss_cases_host.py proves that the cases
-reach the code paths they are named after and pins the reference to oracle/losses.py; tests/test_gpu_loss_edges.py runs
-the kernels on them.  Nothing here touches a GPU; every input comes from retinanet_mi355x.synth and numpy.
+csrc/focal_loss.hip, reached through ops.focal_loss) and for the matching rule it shares with ops.assign and the need sets
+(csrc/anchor_match_dev.h, csrc/anchor_match.hip).  tests/test_loss_cases_host.py proves that the cases reach the code paths
+they are named after and pins the reference to oracle/losses.py; tests/test_gpu_loss_edges.py runs the kernels on them,
+tests/test_gpu_need_rule.py the need sets.  Nothing here touches a GPU; every input comes from retinanet_mi355x.synth and numpy.
 
 Reference (``reference``): the loss of D/losses.py / R/losses.py with every continuous operation in float64 (torch
 autograd on doubles) and every integer decision -- valid rows, IoU bands, first-maximum argmax, ``.long()`` of the class
