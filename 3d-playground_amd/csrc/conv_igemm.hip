@@ -61,15 +61,16 @@ __global__ __launch_bounds__(256, 4) void conv_igemm_grouped_kernel(const rn_con
     conv_igemm_tile<WM, WN, true, BK>(d, x, w, y, scale, shift, add, mask, nullptr, tile - first);
 }
 
-// conv_igemm_split.hip: the same instances with split-operand products
+// conv_igemm_split.hip: the same instances with split-operand products.  plan != NULL (here and below): the launcher fills the
+// rn_conv_igemm_plan report at the point where it would launch and launches nothing (conv_launch.h: rn_plan_fill).
 int rn_igemm_split_launch(int variant, unsigned tiles, const rn_conv_desc *d, const float *x, const float *w, float *y,
                           const float *scale, const float *shift, const float *add, const float *mask, const float *add2,
-                          hipStream_t s);
+                          hipStream_t s, int32_t *plan);
 int rn_igemm_split_grouped_launch(bool narrow, unsigned tiles, const rn_conv_group *g, const float *w, const float *scale,
-                                  const float *shift, hipStream_t s);
+                                  const float *shift, hipStream_t s, int32_t *plan);
 
-extern "C" int rn_conv_igemm_grouped(const rn_conv_group *g, const float *w_packed, const float *scale, const float *shift,
-                                     void *stream) {
+static int igemm_grouped_launch(const rn_conv_group *g, const float *w_packed, const float *scale, const float *shift, void *stream,
+                                int32_t *plan) {
     const rn_conv_desc &d0 = g->d[0];
     const bool narrow = d0.Cout <= 64;
     int prev = 0;
@@ -88,15 +89,32 @@ extern "C" int rn_conv_igemm_grouped(const rn_conv_group *g, const float *w_pack
     const bool split_mode = rn_get_fp32_mfma() != RN_FP32_NATIVE;                    // RN_FP32_SPLIT or RN_FP32_SPLIT3
     if (d0.w_format != 0 && !split_mode) return RN_EINVAL;                           // the pre-split forms are operands of the split kernels only
     if (split_mode && (d0.w_format != 0 || d0.kh * d0.kw * d0.Cin >= rn_fp32_split_min_k()))
-        return rn_igemm_split_grouped_launch(narrow, (unsigned)prev, g, w_packed, scale, shift, s);
-    if (narrow) hipLaunchKernelGGL((conv_igemm_grouped_kernel<4, 1, 16>), grid, block, 0, s, *g, w_packed, scale, shift);
-    else hipLaunchKernelGGL((conv_igemm_grouped_kernel<2, 2, 16>), grid, block, 0, s, *g, w_packed, scale, shift);
+        return rn_igemm_split_grouped_launch(narrow, (unsigned)prev, g, w_packed, scale, shift, s, plan);
+#define RN_LAUNCH_GROUPED(WM, WN)                                                                                                       \
+    do {                                                                                                                                \
+        if (plan != nullptr) return rn_plan_fill(plan, RN_PLAN_FAMILY_TILE, 64 * WM, 64 * WN, 4, true, false, false, 0, 0, false, grid.x, RN_PLAN_FORM_GROUPED); \
+        hipLaunchKernelGGL((conv_igemm_grouped_kernel<WM, WN, 16>), grid, block, 0, s, *g, w_packed, scale, shift);                     \
+    } while (0)
+    if (narrow) RN_LAUNCH_GROUPED(4, 1);
+    else RN_LAUNCH_GROUPED(2, 2);
+#undef RN_LAUNCH_GROUPED
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
 
-extern "C" int rn_conv_igemm(const rn_conv_desc *d, const float *x, const float *w_packed, float *y, const float *scale,
-                             const float *shift, const float *add, const float *mask, const float *add2, void *stream) {
+extern "C" int rn_conv_igemm_grouped(const rn_conv_group *g, const float *w_packed, const float *scale, const float *shift,
+                                     void *stream) {
+    return igemm_grouped_launch(g, w_packed, scale, shift, stream, nullptr);
+}
+
+// The path rn_conv_igemm_grouped takes for this group in the current product mode and options, nothing launched (include/retinanet_mi355x.h).
+extern "C" int rn_conv_igemm_grouped_plan(const rn_conv_group *g, int32_t *out) {
+    if (g == nullptr || out == nullptr) return RN_EINVAL;
+    return igemm_grouped_launch(g, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+static int igemm_launch(const rn_conv_desc *d, const float *x, const float *w_packed, float *y, const float *scale,
+                        const float *shift, const float *add, const float *mask, const float *add2, void *stream, int32_t *plan) {
     const int rc = check_desc(d);
     if (rc) return rc;
     if ((d->add_mode != 0) != (add != nullptr)) return RN_EINVAL;
@@ -108,8 +126,11 @@ extern "C" int rn_conv_igemm(const rn_conv_desc *d, const float *x, const float 
     const int64_t tiles = igemm_tiles(d, narrow);
     if (tiles > 0x7fffffff) return RN_EINVAL;
     const dim3 grid((unsigned)tiles), block(256);
-#define RN_LAUNCH_IGEMM(WM, WN, G, K) \
-    hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, G, K>), grid, block, 0, s, *d, x, w_packed, y, scale, shift, add, mask, add2)
+#define RN_LAUNCH_IGEMM(WM, WN, G, K, R, RAW)                                                                                           \
+    do {                                                                                                                                \
+        if (plan != nullptr) return rn_plan_fill(plan, RN_PLAN_FAMILY_TILE, 64 * WM, 64 * WN, 4, G, R, RAW, 0, 0, false, grid.x, RN_PLAN_FORM_SINGLE); \
+        hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, G, K, R, RAW>), grid, block, 0, s, *d, x, w_packed, y, scale, shift, add, mask, add2); \
+    } while (0)
     // K-step 16 (34-41 KB of LDS, four workgroups per CU) everywhere: with the operands arriving by direct-to-LDS loads it
     // ties or beats K-step 32 at two workgroups per CU on every layer shape (measured).
     const bool raw = dense && !narrow && !d->in_relu && !scale && !shift && d->add_mode == 0 && d->mask_mode == 0 && d->act == 0 &&
@@ -118,23 +139,44 @@ extern "C" int rn_conv_igemm(const rn_conv_desc *d, const float *x, const float 
         // pre-split weights, products from the first bf16 terms only: whatever the fp32 product mode (it is not fp32 arithmetic),
         // narrow instances only, no input ReLU (rn_igemm_split_launch)
         if (!narrow || d->in_relu) return RN_EINVAL;
-        return rn_igemm_split_launch(dense ? 2 : 3, (unsigned)tiles, d, x, w_packed, y, scale, shift, add, mask, add2, s);
+        return rn_igemm_split_launch(dense ? 2 : 3, (unsigned)tiles, d, x, w_packed, y, scale, shift, add, mask, add2, s, plan);
     }
     const bool split_mode = rn_get_fp32_mfma() != RN_FP32_NATIVE;                    // RN_FP32_SPLIT or RN_FP32_SPLIT3
     if (d->w_format != 0 && !split_mode) return RN_EINVAL;
     if (split_mode && (d->w_format != 0 || d->kh * d->kw * d->Cin >= rn_fp32_split_min_k()))
         return rn_igemm_split_launch(raw ? 0 : (d->in_relu ? 1 : (narrow ? (dense ? 2 : 3) : (dense ? 4 : 5))), (unsigned)tiles, d, x,
-                                     w_packed, y, scale, shift, add, mask, add2, s);
+                                     w_packed, y, scale, shift, add, mask, add2, s, plan);
     if (raw) {                                                           // a plain GEMM: the Winograd stage
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, false, 16, false, true>), grid, block, 0, s, *d, x, w_packed, y, scale, shift, add, mask, add2);
+        RN_LAUNCH_IGEMM(2, 2, false, 16, false, true);
     } else if (d->in_relu) {
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, true, 16, true>), grid, block, 0, s, *d, x, w_packed, y, scale, shift, add, mask, add2);
+        RN_LAUNCH_IGEMM(2, 2, true, 16, true, false);
     } else if (narrow) {
-        if (dense) RN_LAUNCH_IGEMM(4, 1, false, 16); else RN_LAUNCH_IGEMM(4, 1, true, 16);
+        if (dense) RN_LAUNCH_IGEMM(4, 1, false, 16, false, false); else RN_LAUNCH_IGEMM(4, 1, true, 16, false, false);
     } else {
-        if (dense) RN_LAUNCH_IGEMM(2, 2, false, 16); else RN_LAUNCH_IGEMM(2, 2, true, 16);
+        if (dense) RN_LAUNCH_IGEMM(2, 2, false, 16, false, false); else RN_LAUNCH_IGEMM(2, 2, true, 16, false, false);
     }
 #undef RN_LAUNCH_IGEMM
     RN_LAUNCH_CHECK();
     return RN_OK;
+}
+
+extern "C" int rn_conv_igemm(const rn_conv_desc *d, const float *x, const float *w_packed, float *y, const float *scale,
+                             const float *shift, const float *add, const float *mask, const float *add2, void *stream) {
+    return igemm_launch(d, x, w_packed, y, scale, shift, add, mask, add2, stream, nullptr);
+}
+
+// conv_igemm_splitk.hip: the plan of rn_conv_igemm_splitk's launch
+int rn_igemm_splitk_plan(const rn_conv_desc *d, const float *add, const float *mask, const float *add2, int32_t *plan);
+
+// The path the launch of this descriptor takes in the current product mode and options, nothing launched (include/retinanet_mi355x.h).  The
+// operands a launch is only asked about -- present or NULL -- are stood for by one word: those the descriptor names (add, mask, add2) as
+// it names them, scale as out[0] & RN_PLAN_ASK_AFFINE says.
+extern "C" int rn_conv_igemm_plan(const rn_conv_desc *d, int32_t *out) {
+    if (d == nullptr || out == nullptr) return RN_EINVAL;
+    static const float word = 0.f;
+    const int ask = out[0];
+    if (ask & ~(RN_PLAN_ASK_AFFINE | RN_PLAN_ASK_SPLITK)) return RN_EINVAL;
+    const float *add = d->add_mode != 0 ? &word : nullptr, *mask = d->mask_mode != 0 ? &word : nullptr, *add2 = d->add2_mode != 0 ? &word : nullptr;
+    if (ask & RN_PLAN_ASK_SPLITK) return rn_igemm_splitk_plan(d, add, mask, add2, out);
+    return igemm_launch(d, nullptr, nullptr, nullptr, (ask & RN_PLAN_ASK_AFFINE) ? &word : nullptr, nullptr, add, mask, add2, nullptr, out);
 }

@@ -512,9 +512,12 @@ extern "C" int rn_conv_igemm_wants_f16(const rn_conv_desc *d) {
     return rn_get_fp32_mfma() == RN_FP32_SPLIT3 && d->w_batch_stride >= 0;
 }
 
-// -> true if launched.  variant as rn_igemm_split_launch: 0 raw, 4 / 5 wide dense / general.
+// -> true if launched.  variant as rn_igemm_split_launch: 0 raw, 4 / 5 wide dense / general.  plan (conv_igemm.hip): filled where the
+// launch would be, *rc = RN_OK, true.
+#define RN_MF16_PLAN(WV, G, RAW, T, S, GRID, FORM) \
+    if (plan != nullptr) { *rc = rn_plan_fill(plan, RN_PLAN_FAMILY_MF16, 32 * WV, 128, WV, G, false, RAW, 0, T, S, GRID, FORM); return true; }
 bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, const float *w, float *y, const float *scale,
-                          const float *shift, const float *add, const float *mask, const float *add2, hipStream_t s, int *rc) {
+                          const float *shift, const float *add, const float *mask, const float *add2, hipStream_t s, int *rc, int32_t *plan) {
     if (!mf16_ok(d) || (variant != 0 && variant != 4 && variant != 5)) return false;
     const int64_t tiles = mf16_tiles(d);
     if (tiles < mf16_min_tiles() || tiles > 0x7fffffff) return false;
@@ -527,15 +530,17 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
         if (lst > 0) {
             const dim3 gl(rn_row_list_grid(d, 3));
             static const int stg_min_k_l = rn_env_int("RN_MF16_STG_MIN_K", 256);
-            if (d->w_format != 3) hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<3, false>), gl, block, 0, s, *d, x, w, y);
-            else if (RN_MF16_STG != 0 && d->kh * d->kw * d->Cin >= stg_min_k_l) hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<2, true>), gl, block, 0, s, *d, x, w, y);
-            else hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<2, false>), gl, block, 0, s, *d, x, w, y);
+#define RN_MF16_LIST(T, S) do { RN_MF16_PLAN(4, false, true, T, S, gl.x, RN_PLAN_FORM_LIST) hipLaunchKernelGGL((conv_igemm_mf16_list_kernel<T, S>), gl, block, 0, s, *d, x, w, y); } while (0)
+            if (d->w_format != 3) RN_MF16_LIST(3, false);
+            else if (RN_MF16_STG != 0 && d->kh * d->kw * d->Cin >= stg_min_k_l) RN_MF16_LIST(2, true);
+            else RN_MF16_LIST(2, false);
+#undef RN_MF16_LIST
             const hipError_t e = hipGetLastError();
             *rc = e == hipSuccess ? RN_OK : (int)e;
             return true;
         }
     }
-#define RN_MF16_LAUNCH(G, R, T, S) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, T, S>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
+#define RN_MF16_LAUNCH(G, R, T, S) do { RN_MF16_PLAN(4, G, R, T, S, grid.x, RN_PLAN_FORM_SINGLE) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, T, S>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2); } while (0)
     if (d->w_format == 3) {
         // staged activations (row-coalesced direct-to-LDS loads) where the K loop is long enough to pay for the longer prologue: measured
         // -4 % on the Winograd GEMMs (K = 256) and K >= 1024, +8 % on K = 64 / 128 (profiles/r05_mf16_bounds.txt, 4)
@@ -550,7 +555,7 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
         const int64_t tiles8 = rn_conv_tiles(d, 256, 128);
         if (stg && wv8_min > 0 && d->w_batch_stride == 0 && tiles8 >= wv8_min && tiles8 <= 0x7fffffff) {
             const dim3 grid8((unsigned)tiles8), block8(512);
-#define RN_MF16_LAUNCH8(G, R) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, 2, true, 8>), grid8, block8, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
+#define RN_MF16_LAUNCH8(G, R) do { RN_MF16_PLAN(8, G, R, 2, true, grid8.x, RN_PLAN_FORM_SINGLE) hipLaunchKernelGGL((conv_igemm_mf16_kernel<G, R, 2, true, 8>), grid8, block8, 0, s, *d, x, w, y, scale, shift, add, mask, add2); } while (0)
             if (variant == 0) RN_MF16_LAUNCH8(false, true);
             else if (variant == 4) RN_MF16_LAUNCH8(false, false);
             else RN_MF16_LAUNCH8(true, false);
@@ -570,7 +575,8 @@ bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, co
     return true;
 }
 
-bool rn_igemm_mf16_grouped_launch(const rn_conv_group *g, const float *w, const float *scale, const float *shift, hipStream_t s, int *rc) {
+bool rn_igemm_mf16_grouped_launch(const rn_conv_group *g, const float *w, const float *scale, const float *shift, hipStream_t s, int *rc,
+                                  int32_t *plan) {
     for (int i = 0; i < g->n; ++i)
         if (!mf16_ok(&g->d[i]) || g->d[i].w_format != g->d[0].w_format) return false;
     rn_conv_group gb = *g;                                  // the caller's tile table counts 128 x 128 tiles: recount
@@ -581,9 +587,12 @@ bool rn_igemm_mf16_grouped_launch(const rn_conv_group *g, const float *w, const 
     }
     for (int i = g->n; i < RN_MAX_GROUP; ++i) gb.tile_end[i] = (int)total;
     if (total < mf16_min_tiles() || total > 0x7fffffff) return false;
-    if (g->d[0].w_format == 3) hipLaunchKernelGGL(conv_igemm_mf16_grouped_kernel<2>, dim3((unsigned)total), dim3(256), 0, s, gb, w, scale, shift);
-    else hipLaunchKernelGGL(conv_igemm_mf16_grouped_kernel<3>, dim3((unsigned)total), dim3(256), 0, s, gb, w, scale, shift);
+#define RN_MF16_GROUPED(T) do { RN_MF16_PLAN(4, true, false, T, (T == 2 && RN_MF16_STG != 0), (unsigned)total, RN_PLAN_FORM_GROUPED) hipLaunchKernelGGL(conv_igemm_mf16_grouped_kernel<T>, dim3((unsigned)total), dim3(256), 0, s, gb, w, scale, shift); } while (0)
+    if (g->d[0].w_format == 3) RN_MF16_GROUPED(2);
+    else RN_MF16_GROUPED(3);
+#undef RN_MF16_GROUPED
     const hipError_t e = hipGetLastError();
     *rc = e == hipSuccess ? RN_OK : (int)e;
     return true;
 }
+#undef RN_MF16_PLAN

@@ -60,8 +60,9 @@ static bool split_a_once(const rn_conv_desc *d) {
 
 // conv_igemm_mf16.hip: 128 x 128 tiles on v_mfma_f32_16x16x32_bf16 (RN_FP32_SPLIT) / v_mfma_f32_16x16x32_f16 (RN_FP32_SPLIT3)
 bool rn_igemm_mf16_launch(int variant, const rn_conv_desc *d, const float *x, const float *w, float *y, const float *scale,
-                          const float *shift, const float *add, const float *mask, const float *add2, hipStream_t s, int *rc);
-bool rn_igemm_mf16_grouped_launch(const rn_conv_group *g, const float *w, const float *scale, const float *shift, hipStream_t s, int *rc);
+                          const float *shift, const float *add, const float *mask, const float *add2, hipStream_t s, int *rc, int32_t *plan);
+bool rn_igemm_mf16_grouped_launch(const rn_conv_group *g, const float *w, const float *scale, const float *shift, hipStream_t s, int *rc,
+                                  int32_t *plan);
 
 static int dbg_dyn_lds(const void *fn) {                  // occupancy experiment: RN_DBG_DYN_LDS bytes of unused dynamic LDS per workgroup
     static const int v = rn_env_int("RN_DBG_DYN_LDS", 0);
@@ -70,22 +71,32 @@ static int dbg_dyn_lds(const void *fn) {                  // occupancy experimen
 }
 
 // variant: the instance conv_igemm.hip's launcher chose -- 0 raw GEMM, 1 input ReLU, 2 / 3 narrow dense / general,
-// 4 / 5 wide dense / general.  d->w_format 1: w is the pre-split form (rn_split_weights).
+// 4 / 5 wide dense / general.  d->w_format 1: w is the pre-split form (rn_split_weights).  plan: conv_igemm.hip.
+#define RN_SPLIT_GO(GRID, DYN, WM, WN, G, R, RAW, SPLIT, TERMS)                                                                         \
+    do {                                                                                                                                \
+        if (plan != nullptr) return rn_plan_fill(plan, RN_PLAN_FAMILY_SPLIT, 64 * WM, 64 * WN, 4, G, R, RAW, SPLIT, TERMS, false, (GRID).x, RN_PLAN_FORM_SINGLE); \
+        hipLaunchKernelGGL((conv_igemm_split_kernel<WM, WN, G, R, RAW, SPLIT, 16, TERMS>), GRID, dim3(256), DYN, s, *d, x, w, y, scale, shift, add, mask, add2); \
+    } while (0)
+#define RN_SPLIT_GROUPED_GO(WM, WN, SPLIT, TERMS)                                                                                       \
+    do {                                                                                                                                \
+        if (plan != nullptr) return rn_plan_fill(plan, RN_PLAN_FAMILY_SPLIT, 64 * WM, 64 * WN, 4, true, false, false, SPLIT, TERMS, false, tiles, RN_PLAN_FORM_GROUPED); \
+        hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<WM, WN, SPLIT, 16, TERMS>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift); \
+    } while (0)
 int rn_igemm_split_launch(int variant, unsigned tiles, const rn_conv_desc *d, const float *x, const float *w, float *y,
                           const float *scale, const float *shift, const float *add, const float *mask, const float *add2,
-                          hipStream_t s) {
+                          hipStream_t s, int32_t *plan) {
     if (d->w_format == 2) {
         // pre-split weights, products from the first bf16 terms only (the fp32 stem of the bf16 / fp8 engines): the narrow instances
-        const dim3 grid1(tiles), block1(256);
-        if (variant == 2) hipLaunchKernelGGL((conv_igemm_split_kernel<4, 1, false, false, false, 2, 16, 1>), grid1, block1, 0, s, *d, x, w, y, scale, shift, add, mask, add2);
-        else if (variant == 3) hipLaunchKernelGGL((conv_igemm_split_kernel<4, 1, true, false, false, 2, 16, 1>), grid1, block1, 0, s, *d, x, w, y, scale, shift, add, mask, add2);
+        const dim3 grid1(tiles);
+        if (variant == 2) RN_SPLIT_GO(grid1, 0, 4, 1, false, false, false, 2, 1);
+        else if (variant == 3) RN_SPLIT_GO(grid1, 0, 4, 1, true, false, false, 2, 1);
         else return RN_EINVAL;
         RN_LAUNCH_CHECK();
         return RN_OK;
     }
     {
         int rc = RN_OK;
-        if (rn_igemm_mf16_launch(variant, d, x, w, y, scale, shift, add, mask, add2, s, &rc)) return rc;
+        if (rn_igemm_mf16_launch(variant, d, x, w, y, scale, shift, add, mask, add2, s, &rc, plan)) return rc;
     }
     if (d->w_format == 3) {
         // RN_FP32_SPLIT3 for what the 16x16x32 kernel does not take (<= 64 output channels, the 4-channel stem, channel counts that are
@@ -96,13 +107,13 @@ int rn_igemm_split_launch(int variant, unsigned tiles, const rn_conv_desc *d, co
             const int lst = rn_row_list_ok(d);
             if (lst < 0) return RN_EINVAL;
             if (lst > 0) {
+                if (plan != nullptr) return rn_plan_fill(plan, RN_PLAN_FAMILY_SPLIT, 128, 128, 4, false, false, true, 2, 2, false, rn_row_list_grid(d, 3), RN_PLAN_FORM_LIST);
                 hipLaunchKernelGGL(conv_igemm_split_list_kernel, dim3(rn_row_list_grid(d, 3)), block2, 0, s, *d, x, w, y);
                 RN_LAUNCH_CHECK();
                 return RN_OK;
             }
         }
-#define RN_HALF_LAUNCH(WM, WN, G, R, RAW) \
-        hipLaunchKernelGGL((conv_igemm_split_kernel<WM, WN, G, R, RAW, 2, 16, 2>), grid2, block2, 0, s, *d, x, w, y, scale, shift, add, mask, add2)
+#define RN_HALF_LAUNCH(WM, WN, G, R, RAW) RN_SPLIT_GO(grid2, 0, WM, WN, G, R, RAW, 2, 2)
         switch (variant) {
             case 0: RN_HALF_LAUNCH(2, 2, false, false, true); break;
             case 1: RN_HALF_LAUNCH(2, 2, true, true, false); break;
@@ -116,12 +127,12 @@ int rn_igemm_split_launch(int variant, unsigned tiles, const rn_conv_desc *d, co
         RN_LAUNCH_CHECK();
         return RN_OK;
     }
-    const dim3 grid(tiles), block(256);
+    const dim3 grid(tiles);
 #define RN_SPLIT_LAUNCH(WM, WN, G, R, RAW)                                                                                              \
     do {                                                                                                                                \
-        if (WM == 2 && split_a_once(d)) hipLaunchKernelGGL((conv_igemm_split_kernel<WM, WN, G, R, RAW, (WM == 2 ? 3 : 2)>), grid, block, dbg_dyn_lds((const void *)conv_igemm_split_kernel<WM, WN, G, R, RAW, (WM == 2 ? 3 : 2)>), s, *d, x, w, y, scale, shift, add, mask, add2); \
-        else if (d->w_format == 1) hipLaunchKernelGGL((conv_igemm_split_kernel<WM, WN, G, R, RAW, 2>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2); \
-        else hipLaunchKernelGGL((conv_igemm_split_kernel<WM, WN, G, R, RAW, 1>), grid, block, 0, s, *d, x, w, y, scale, shift, add, mask, add2);                 \
+        if (WM == 2 && split_a_once(d)) RN_SPLIT_GO(grid, dbg_dyn_lds((const void *)conv_igemm_split_kernel<WM, WN, G, R, RAW, (WM == 2 ? 3 : 2)>), WM, WN, G, R, RAW, (WM == 2 ? 3 : 2), 3); \
+        else if (d->w_format == 1) RN_SPLIT_GO(grid, 0, WM, WN, G, R, RAW, 2, 3);                                                       \
+        else RN_SPLIT_GO(grid, 0, WM, WN, G, R, RAW, 1, 3);                                                                             \
     } while (0)
     switch (variant) {
         case 0: RN_SPLIT_LAUNCH(2, 2, false, false, true); break;
@@ -138,28 +149,30 @@ int rn_igemm_split_launch(int variant, unsigned tiles, const rn_conv_desc *d, co
 }
 
 int rn_igemm_split_grouped_launch(bool narrow, unsigned tiles, const rn_conv_group *g, const float *w, const float *scale,
-                                  const float *shift, hipStream_t s) {
+                                  const float *shift, hipStream_t s, int32_t *plan) {
     const bool pre = g->d[0].w_format == 1;
     if (!narrow) {
         int rc = RN_OK;
-        if (rn_igemm_mf16_grouped_launch(g, w, scale, shift, s, &rc)) return rc;
+        if (rn_igemm_mf16_grouped_launch(g, w, scale, shift, s, &rc, plan)) return rc;
     }
     if (g->d[0].w_format == 3) {                             // the fp16 two-term tile (see rn_igemm_split_launch)
         for (int i = 0; i < g->n; ++i)
             if (g->d[i].w_format != 3 || g->d[i].x_amax == nullptr || g->d[i].w_unscale == nullptr) return RN_EINVAL;
-        if (narrow) hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<4, 1, 2, 16, 2>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
-        else hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<2, 2, 2, 16, 2>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
+        if (narrow) RN_SPLIT_GROUPED_GO(4, 1, 2, 2);
+        else RN_SPLIT_GROUPED_GO(2, 2, 2, 2);
         RN_LAUNCH_CHECK();
         return RN_OK;
     }
-    if (!narrow && split_a_once(&g->d[0])) hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<2, 2, 3>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
-    else if (narrow && pre) hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<4, 1, 2>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
-    else if (narrow) hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<4, 1, 1>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
-    else if (pre) hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<2, 2, 2>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
-    else hipLaunchKernelGGL((conv_igemm_split_grouped_kernel<2, 2, 1>), dim3(tiles), dim3(256), 0, s, *g, w, scale, shift);
+    if (!narrow && split_a_once(&g->d[0])) RN_SPLIT_GROUPED_GO(2, 2, 3, 3);
+    else if (narrow && pre) RN_SPLIT_GROUPED_GO(4, 1, 2, 3);
+    else if (narrow) RN_SPLIT_GROUPED_GO(4, 1, 1, 3);
+    else if (pre) RN_SPLIT_GROUPED_GO(2, 2, 2, 3);
+    else RN_SPLIT_GROUPED_GO(2, 2, 1, 3);
     RN_LAUNCH_CHECK();
     return RN_OK;
 }
+#undef RN_SPLIT_GO
+#undef RN_SPLIT_GROUPED_GO
 
 // ---- the pre-split form of a packed weight tensor
 __global__ __launch_bounds__(256) void split_weights_kernel(const float *__restrict__ src, void *__restrict__ dst, int64_t chunks) {

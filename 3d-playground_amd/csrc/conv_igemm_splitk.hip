@@ -77,9 +77,11 @@ extern "C" int64_t rn_conv_splitk_workspace_bytes(const rn_conv_desc *d) {
     return s <= 1 ? 0 : (int64_t)s * d->N * d->Ho * d->Wo * d->Cout * (int64_t)sizeof(float);
 }
 
-extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const float *w_packed, float *y, const float *scale,
-                                    const float *shift, const float *add, const float *mask, const float *add2,
-                                    void *workspace, void *stream) {
+// plan != NULL (rn_conv_igemm_plan, conv_igemm.hip): the report of this launch -- the partial kernel's tile, the slices asked for and used, the
+// K-steps per slice, the finish kernel -- is filled once everything is decided, and nothing is launched.
+static int splitk_launch(const rn_conv_desc *d, const float *x, const float *w_packed, float *y, const float *scale,
+                         const float *shift, const float *add, const float *mask, const float *add2,
+                         void *workspace, void *stream, int32_t *plan) {
     const int rc = check_desc(d);
     if (rc) return rc;
     if (d->w_format != 0) return RN_EINVAL;                  // the pre-split weight form: rn_conv_igemm only
@@ -87,7 +89,7 @@ extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const
     if ((d->mask_mode != 0) != (mask != nullptr)) return RN_EINVAL;
     if ((d->add2_mode != 0) != (add2 != nullptr)) return RN_EINVAL;
     const int slices = splitk_slices(d);
-    if (slices <= 1 || !workspace) return RN_EINVAL;         // ask rn_conv_splitk_workspace_bytes first
+    if (slices <= 1 || (!workspace && plan == nullptr)) return RN_EINVAL;      // ask rn_conv_splitk_workspace_bytes first
     const int64_t M = (int64_t)d->N * d->Ho * d->Wo;
     hipStream_t s = (hipStream_t)stream;
     const bool narrow = igemm_narrow(d);
@@ -99,11 +101,16 @@ extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const
     const int used = (nks + per - 1) / per;                  // slices that actually get K-steps
     const dim3 grid((unsigned)tiles, (unsigned)used), block(256);
     float *ws = reinterpret_cast<float *>(workspace);
+    const bool dense = rn_conv_dense(d) && d->add2_mode == 0;
+    if (plan != nullptr) {
+        rn_plan_fill(plan, RN_PLAN_FAMILY_SPLITK, narrow ? 256 : 128, narrow ? 64 : 128, 4, !dense, d->in_relu != 0, false, 0, 0, false, grid.x, RN_PLAN_FORM_SINGLE);
+        plan[RN_PLAN_SLICES] = slices; plan[RN_PLAN_USED] = used; plan[RN_PLAN_STEPS] = per; plan[RN_PLAN_FINISH] = dense ? 0 : 1;
+        return RN_OK;
+    }
     if (d->in_relu) hipLaunchKernelGGL((conv_igemm_splitk_kernel<2, 2, 16, true>), grid, block, 0, s, *d, x, w_packed, ws, per, nks);
     else if (narrow) hipLaunchKernelGGL((conv_igemm_splitk_kernel<4, 1, 16>), grid, block, 0, s, *d, x, w_packed, ws, per, nks);
     else hipLaunchKernelGGL((conv_igemm_splitk_kernel<2, 2, 16>), grid, block, 0, s, *d, x, w_packed, ws, per, nks);
     RN_LAUNCH_CHECK();
-    const bool dense = rn_conv_dense(d) && d->add2_mode == 0;
     const int64_t chunks = M * ((d->Cout + 3) / 4);
     const dim3 fgrid((unsigned)((chunks + 255) / 256));
     if (dense) hipLaunchKernelGGL((conv_splitk_finish_kernel<false>), fgrid, block, 0, s, *d, (const float *)ws, used, y, scale, shift, add, mask, add2);
@@ -112,3 +119,12 @@ extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const
     return RN_OK;
 }
 
+extern "C" int rn_conv_igemm_splitk(const rn_conv_desc *d, const float *x, const float *w_packed, float *y, const float *scale,
+                                    const float *shift, const float *add, const float *mask, const float *add2,
+                                    void *workspace, void *stream) {
+    return splitk_launch(d, x, w_packed, y, scale, shift, add, mask, add2, workspace, stream, nullptr);
+}
+
+int rn_igemm_splitk_plan(const rn_conv_desc *d, const float *add, const float *mask, const float *add2, int32_t *plan) {
+    return splitk_launch(d, nullptr, nullptr, nullptr, nullptr, nullptr, add, mask, add2, nullptr, nullptr, plan);
+}

@@ -59,6 +59,23 @@ static inline int rn_check_desc_mask(const rn_conv_desc *d) {
     return RN_OK;
 }
 
+// The report of rn_conv_igemm_plan / rn_conv_igemm_grouped_plan (include/retinanet_mi355x.h has the words' meaning).  The fp32 launchers
+// carry an `int32_t *plan` down to the statement that launches: with a plan they fill it there, from the very template arguments the launch
+// would instantiate, and return before the launch -- one set of rules, asked or run.
+enum { RN_PLAN_FAMILY, RN_PLAN_ROWS, RN_PLAN_COLS, RN_PLAN_WAVES, RN_PLAN_GENERAL, RN_PLAN_RELU, RN_PLAN_RAW, RN_PLAN_SPLIT, RN_PLAN_TERMS,
+       RN_PLAN_STAGED, RN_PLAN_GRID, RN_PLAN_SLICES, RN_PLAN_USED, RN_PLAN_STEPS, RN_PLAN_FINISH, RN_PLAN_FORM };
+enum { RN_PLAN_FAMILY_TILE, RN_PLAN_FAMILY_SPLIT, RN_PLAN_FAMILY_MF16, RN_PLAN_FAMILY_SPLITK };
+enum { RN_PLAN_FORM_SINGLE, RN_PLAN_FORM_GROUPED, RN_PLAN_FORM_LIST };
+static inline int rn_plan_fill(int32_t *plan, int family, int rows, int cols, int waves, bool general, bool relu, bool raw, int split,
+                               int terms, bool staged, unsigned grid, int form) {
+    for (int i = 0; i < RN_IGEMM_PLAN_WORDS; ++i) plan[i] = 0;
+    plan[RN_PLAN_FAMILY] = family; plan[RN_PLAN_ROWS] = rows; plan[RN_PLAN_COLS] = cols; plan[RN_PLAN_WAVES] = waves;
+    plan[RN_PLAN_GENERAL] = general; plan[RN_PLAN_RELU] = relu; plan[RN_PLAN_RAW] = raw; plan[RN_PLAN_SPLIT] = split;
+    plan[RN_PLAN_TERMS] = terms; plan[RN_PLAN_STAGED] = staged; plan[RN_PLAN_GRID] = (int32_t)grid; plan[RN_PLAN_FINISH] = -1;
+    plan[RN_PLAN_FORM] = form;
+    return RN_OK;
+}
+
 // A grouped launch: 1 .. RN_MAX_GROUP problems, each passing the form's own check(desc, index) (RN_OK or an error), all with the first
 // one's channels and filter, and the caller's tile_end = the running count of rows x cols tiles.  *tiles receives the grid size.
 template <class Check>

@@ -174,6 +174,8 @@ class ConvDesc(ctypes.Structure):
 
 RN_MAX_GROUP = 5
 RN_REG_NEED_ARRAYS = 6                                 # flag arrays rn_reg_need_tiles fills
+RN_IGEMM_PLAN_WORDS = 16                               # int32 words of rn_conv_igemm_plan's report
+RN_PLAN_ASK_AFFINE, RN_PLAN_ASK_SPLITK = 1, 2          # ... and what its out[0] says on entry
 
 
 class ConvGroup(ctypes.Structure):
@@ -222,6 +224,8 @@ SIGNATURES.update({
     "rn_conv_splitk_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "rn_conv_igemm_wants_f16": (c_i32, [ctypes.POINTER(ConvDesc)]),
     "rn_conv_igemm_splitk": (c_i32, [ctypes.POINTER(ConvDesc)] + [c_vp] * 10),
+    "rn_conv_igemm_plan": (c_i32, [ctypes.POINTER(ConvDesc), c_vp]),
+    "rn_conv_igemm_grouped_plan": (c_i32, [ctypes.POINTER(ConvGroup), c_vp]),
     "rn_conv_wgrad": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp] + [c_i32] * 12 + [c_vp]),
     "rn_pack_weights": (c_i32, [c_vp, c_vp] + [c_i32] * 7 + [c_vp] + [c_i32] * 4 + [c_vp]),
     "rn_unpack_wgrad": (c_i32, [c_vp, c_vp, c_vp] + [c_i32] * 6 + [c_vp] * 7),

@@ -81,14 +81,15 @@ def _mask_operand(mask, mask_mode):
 def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=0, add_hw=(0, 0), mask=None,
                mask_mode=2, act=ACT_NONE, y_batch_stride=None, add_batch_stride=None, in_relu=False, flops=0.0,
                out_map=None, add2=None, w_batch_stride=0, kind=None, sign=False, bf16_products=False, x_amax=None, x_amax_rows=False,
-               amax=None, row_active=None, row_list=None):
+               amax=None, row_active=None, row_list=None, plans=None):
     """Launch rn_conv_igemm.  x [N,Hi,Wi,Cin]; y a tensor whose storage receives [N,Ho,Wo,Cout] at batch stride
     y_batch_stride; geom = (Ho, Wo, Cout, kh, kw, a, b, p, div_shift) with p an int or (p_rows, p_cols).
     out_map = (os, oo_h, oo_w, Hy, Wy) stores output pixel (oh,ow) at (oh*os+oo_h, ow*os+oo_w) of a [N,Hy,Wy,Cout]
     tensor.  add2: [N,Ha2,Wa2,Cout] added at even stored positions (1x1 stride-2 shortcut gradient).
     split3 mode: x_amax = the amax words of x when the caller holds them (default: amax_words(x), one per image; x_amax_rows: one per GEMM
     row instead -- the Winograd stage); a dense result gets words of its own (y._rn_amax), `amax` = the words several launches that fill
-    ONE tensor share (the parity classes of a stride-2 data gradient)."""
+    ONE tensor share (the parity classes of a stride-2 data gradient).  plans: a list that receives igemm_plan's report of the very
+    descriptor this call launches (tests assert the kernel they ran)."""
     lib = _hip.load()
     mask_ptr, mask_mode = _mask_operand(mask, mask_mode)
     d = _make_desc(x, geom, act, add_mode, add_hw, mask_mode, in_relu, out_map, y_batch_stride, add_batch_stride, add2, w_batch_stride)
@@ -104,8 +105,11 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
         yam = amax if amax is not None else amax_slot(y.device, d.N)
         d.y_amax = yam.data_ptr()
     kind = _kind(kind or ("conv_igemm_4x1" if d.Cout <= 64 else "conv_igemm_2x2"), d)
-    ws_bytes = 0 if w_batch_stride else lib.rn_conv_splitk_workspace_bytes(ctypes.byref(d))   # > 0: few output tiles, long K -> split-K
+    affine = scale is not None or shift is not None
+    ws_bytes = _splitk_bytes(lib, d)                     # > 0: few output tiles, long K -> split-K
     if ws_bytes > 0:
+        if plans is not None:
+            plans.append(igemm_plan(d, affine, splitk=True))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
         rc = prof.timed(kind, flops, lambda: lib.rn_conv_igemm_splitk(
             ctypes.byref(d), x.data_ptr(), w_packed.data_ptr(), y.data_ptr(), _hip.ptr(scale), _hip.ptr(shift),
@@ -123,6 +127,8 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
         if ws is None:
             ws = split_weights(w_packed)._rn_split
         wptr, d.w_format = ws.data_ptr(), 2
+    if plans is not None:
+        plans.append(igemm_plan(d, affine, splitk=False))
     nb = 0.0
     if prof.ACTIVE is not None:            # algorithmic bytes: every operand once (the split kernels read weights as 6-byte terms)
         out_el = d.N * d.Ho * d.Wo * d.Cout
@@ -136,6 +142,34 @@ def conv_igemm(x, w_packed, y, geom, scale=None, shift=None, add=None, add_mode=
     if yam is not None and amax is None:
         amax_attach(y, yam)
     return y
+
+
+def _splitk_bytes(lib, d):
+    """Workspace bytes of the split-K form when conv_igemm takes it for d (0: it does not; never for a batch of GEMMs)."""
+    return 0 if d.w_batch_stride else lib.rn_conv_splitk_workspace_bytes(ctypes.byref(d))
+
+
+IGEMM_PLAN_FIELDS = ("family", "rows", "cols", "waves", "general", "relu", "raw", "split", "terms", "staged", "grid", "slices", "used",
+                     "steps", "finish", "form")
+PLAN_TILE, PLAN_SPLIT, PLAN_MF16, PLAN_SPLITK = range(4)         # "family" (include/retinanet_mi355x.h: rn_conv_igemm_plan)
+PLAN_SINGLE, PLAN_GROUPED, PLAN_LIST = range(3)                  # "form"
+
+
+def igemm_plan(d, affine=False, splitk=None):
+    """rn_conv_igemm_plan: the kernel conv_igemm's launch of the ConvDesc d takes, as a dict of IGEMM_PLAN_FIELDS (None: refused).  affine:
+    the launch passes a scale or a shift.  splitk: report rn_conv_igemm_splitk's launch; None = where conv_igemm would choose it."""
+    lib = _hip.load()
+    if splitk is None:
+        splitk = d.w_format == 0 and _splitk_bytes(lib, d) > 0
+    out = (ctypes.c_int32 * _hip.RN_IGEMM_PLAN_WORDS)()
+    out[0] = (_hip.RN_PLAN_ASK_AFFINE if affine else 0) | (_hip.RN_PLAN_ASK_SPLITK if splitk else 0)
+    return dict(zip(IGEMM_PLAN_FIELDS, out)) if lib.rn_conv_igemm_plan(ctypes.byref(d), out) == 0 else None
+
+
+def igemm_grouped_plan(g):
+    """rn_conv_igemm_grouped_plan: the kernel conv_igemm_grouped's launch of the ConvGroup g takes (None: refused)."""
+    out = (ctypes.c_int32 * _hip.RN_IGEMM_PLAN_WORDS)()
+    return dict(zip(IGEMM_PLAN_FIELDS, out)) if _hip.load().rn_conv_igemm_grouped_plan(ctypes.byref(g), out) == 0 else None
 
 
 def _make_desc(x, geom, act, add_mode, add_hw, mask_mode, in_relu, out_map, y_batch_stride, add_batch_stride, add2, w_batch_stride=0):
@@ -857,7 +891,7 @@ def wino_wgrad_group(gs, xs, dw, colsum, flops=0.0, V=None, dU=None, fuse_dgrad_
     return v_dy                                      # (B^T dy B, shapes) for the data gradient that follows, or None when not fused
 
 
-def conv_igemm_grouped(problems, w_packed, scale=None, shift=None, act=ACT_NONE, flops=0.0):
+def conv_igemm_grouped(problems, w_packed, scale=None, shift=None, act=ACT_NONE, flops=0.0, plans=None):
     """One launch for up to 5 problems sharing weights / epilogue scalars (the pyramid levels of a head tower).
     problems: list of dicts with x, y, geom and optional add, mask, mask_mode, y_batch_stride, sign (write y's sign bits)."""
     lib = _hip.load()
@@ -874,6 +908,8 @@ def conv_igemm_grouped(problems, w_packed, scale=None, shift=None, act=ACT_NONE,
     narrow = g.d[0].Cout <= 64                           # at most 64 output channels: 256-row strips, else 128 x 128 tiles
     _tile_ends(g, *((256, 64) if narrow else (128, 128)))
     kind = _kind("conv_igemm_4x1" if narrow else "conv_igemm_2x2", g.d[0], grouped=True)
+    if plans is not None:                                # the report of this very group (igemm_grouped_plan)
+        plans.append(igemm_grouped_plan(g))
     nb = 0.0
     if prof.ACTIVE is not None:
         nb = {0: 4.0, 1: 6.0, 3: 4.0}[wfmt] * w_packed.numel()

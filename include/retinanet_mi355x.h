@@ -731,6 +731,28 @@ typedef struct rn_conv_group {
 int rn_conv_igemm_grouped(const rn_conv_group *g, const float *w_packed, const float *scale, const float *shift,
                           void *stream);
 
+/* Which kernel a launch takes, without launching it: the launchers' own decision code run up to the launch statement, in the current
+ * product mode and options (tests name their cases by it; DESIGN.md 4.2 has the table of paths).  RN_EINVAL for every descriptor /
+ * group the launcher refuses.  rn_conv_igemm_plan: d as the launch would pass it (w_format, x_amax, w_unscale, sign_out, y_amax and
+ * row_list matter: only NULL or not is looked at, nothing is dereferenced); add, mask and add2 count as present exactly when add_mode,
+ * mask_mode and add2_mode name them.  ON ENTRY out[0] holds the RN_PLAN_ASK_ bits: AFFINE = the launch passes a scale or a shift (only
+ * the raw GEMM instance asks), SPLITK = report rn_conv_igemm_splitk's launch instead of rn_conv_igemm's (RN_EINVAL where
+ * rn_conv_splitk_workspace_bytes is 0).  rn_conv_igemm_grouped_plan: g as rn_conv_igemm_grouped takes it (add / mask pointers NULL or not).
+ * out[RN_IGEMM_PLAN_WORDS] =
+ *    0 family: 0 csrc/conv_igemm.hip (fp32 MFMA), 1 conv_igemm_split.hip, 2 conv_igemm_mf16.hip, 3 conv_igemm_splitk.hip
+ *    1 tile rows   2 tile columns   3 waves per workgroup
+ *    4 GENERAL (the output map is honoured; split-K: of the finish kernel)   5 RELU (on load)   6 RAW (no epilogue)
+ *    7 SPLIT (family 1: 1 both operands split in the loop, 2 weights pre-split, 3 activations split once per workgroup; else 0)
+ *    8 TERMS (3 bf16 terms, 2 fp16 terms, 1 first bf16 term only; 0: fp32 MFMA)
+ *    9 activations staged through the LDS (family 2)   10 workgroups (split-K: grid.x, the tiles)
+ *   11 split-K: slices asked for   12 slices used = grid.y   13 K-steps per slice   14 finish kernel 0 dense / 1 general (-1: no split-K)
+ *   15 form: 0 single launch, 1 grouped, 2 work list (rn_conv_desc.row_list) */
+#define RN_IGEMM_PLAN_WORDS 16
+#define RN_PLAN_ASK_AFFINE 1
+#define RN_PLAN_ASK_SPLITK 2
+int rn_conv_igemm_plan(const rn_conv_desc *d, int32_t *out);
+int rn_conv_igemm_grouped_plan(const rn_conv_group *g, int32_t *out);
+
 /* Weight gradient: dw[co][r][s][ci] += sum_{n,oh,ow} dy[n,oh,ow,co] * x[n, oh*st + r - pd, ow*st + s - pd, ci]
  * (fp32 atomics into a zeroed or previously accumulated [Cout][Kpad] buffer, same layout as the packed forward
  * weights; heads accumulate their five pyramid levels into one buffer).  dy: [N,Ho,Wo,Cout] with channel
