@@ -1,7 +1,7 @@
 """GPU: the forms of the Winograd transforms (csrc/conv_wino.hip) against each other, bit for bit, at the entry-point level.
 
-The dense input transform is checked against fp64 elsewhere (test_gpu_conv.py); here every list / flag / fused / offset form must give
-exactly what the dense form gives where it writes, and leave everything else as it was.  Shapes (the smallest at which each piece can
+The dense forms of both transforms are checked against fp64 elsewhere (test_gpu_wino_transforms.py); here every list / flag / fused /
+offset form must give exactly what the dense form gives where it writes, and leave everything else as it was.  Shapes (the smallest at which each piece can
 go wrong): two problems in one group, N=3 H=13 W=10 (4 x 3 tiles per image, ragged right and bottom edges) and N=1 H=4 W=4: T = 37 tiles,
 Tpad = 256; C = 4 (one thread per tile) and 8; Cout = 32 (sign words are legal).  Flags: tiles 3 and 36, so units 0 and 2 are listed and
 unit 1 holds tiles but is not.  Every output, V and Z starts as NaN, row words and sign words as all-ones (what conv.NEED_POISON does).
